@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 256x256 images/sec for one full G+D training step (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one iteration of scripts/train.py:353-393 (graph encoder + AttSPADE generator forward,
 generator losses through two PatchGAN passes, backward + Adam; discriminator losses through two more
@@ -52,7 +52,13 @@ def parse():
     p.add_argument("--no_gen_metric", action="store_true",
                    help="skip the generator-only fwd+bwd passes (use under rocprofv3 so that its per-kernel "
                         "averages cover the same launch mix as the timed region)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (losses, bbox predictions, generated "
+                        "images, a fixed sample of the updated weights) as DIR/<name>.npy, rank 0 only (step_outputs)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def _physical_cores():
@@ -133,6 +139,50 @@ def _parity(gpu_step, Go, Do, img_o, note, rel_l2_limit=2e-5, img_atol=1e-4, img
     return {"ok": bool(ok and keys_ok and img_ok and bb_ok and oracle_sane), "hip_ok": bool(ok and keys_ok and img_ok and bb_ok),
             "oracle_sane": bool(oracle_sane), "rtol": RTOL, "max_rel": float("%.3g" % max_rel),
             "losses": rows, "imgs_pred": img, "bbox_pred_all_ok": bb_ok, "note": note}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_WEIGHT_SAMPLE = 1 << 18       # elements of each network's weight sample
+DUMP_SEED = 0
+
+
+def step_outputs(trainer, G, D, sample=DUMP_WEIGHT_SAMPLE, seed=DUMP_SEED):
+    """What one `trainer.step` hands its caller, as host arrays: the generator / discriminator loss dictionaries it returns
+    (`G_*`, `D_*`), the generated images and predicted boxes it leaves in `last_model_out`, and the parameters its optimiser
+    steps updated in place — those as a fixed sample (`seed`) of `sample` elements of each network's parameters, flattened
+    in `named_parameters` order (the generator's alone are ~375 MB).  Call it before any further step overwrites them."""
+    import numpy as np
+    import torch
+    out = {}
+    for prefix, d in (("G_", G), ("D_", D)):
+        out.update({prefix + k: v for k, v in d.items()})
+    imgs, boxes = trainer.last_model_out[:2]
+    out["imgs_pred"] = imgs
+    if boxes is not None:
+        out["boxes_pred"] = boxes
+    for name, module in (("generator", trainer.model), ("discriminator", trainer.discriminator)):
+        flat = torch.cat([p.detach().reshape(-1) for _, p in module.named_parameters()])
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), min(sample, flat.numel()), replace=False))
+        out["weights_%s_sample" % name] = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().cpu().numpy()
+        arrays[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    return arrays
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """`arrays` ({name: float32 / float64 ndarray}) as path/<name>.npy; refuses (writing nothing) above `limit` bytes in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, limit))
+    if any(a.dtype not in (np.float32, np.float64) for a in arrays.values()):
+        raise SystemExit("bench.py: --dump-outputs writes float32 / float64 arrays only")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return total
 
 
 def _overlap(on):
@@ -430,6 +480,11 @@ def main():
         G, Dl = trainer.step(batches[i % nb])
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the untimed steps below (eager event legs, generator passes) update the same weights: copy the outputs first
+        nbytes = write_outputs(args.dump_outputs, step_outputs(trainer, G, Dl))
+        print("[bench] last timed step's outputs: %.1f MB in %s" % (nbytes / 2**20, args.dump_outputs), file=sys.stderr,
+              flush=True)
     graph_stats = eager_ms = None
     if graphs_on:
         # kernels inside a replayed graph carry no per-dispatch events: the dominant kernel's event timing (mode 2) is

@@ -612,6 +612,38 @@ def fx_model_and_step():
                         "shapes": {"sg": shapes_of(sg), "g": shapes_of(G, unused), "d": shapes_of(D, unused)}}, **arrays)
 
 
+def fx_step_images64():
+    """The generated image of the train_step and train_step_masks fixtures evaluated again by the reference's generator
+    in float64 (same weights, same batch, the same training-mode forward).  Their fp32 `imgs_pred` carry the rounding of
+    the host that made them, 1e-5..2e-4 from the exact image and CPU-dependent; this is the host-independent yardstick.
+    Reads the two fixtures (argv, batch) and first checks that the fp32 evaluation reproduces their `imgs_pred`."""
+    import copy
+    vocab = make_vocab("tiny")
+    arrays = {}
+    for name, seed in (("train_step", 12), ("train_step_masks", 42)):       # G's deterministic_state seed in each
+        z = np.load(os.path.join(HERE, name + ".npz"))
+        opt = ref_opt(vocab, json.loads(bytes(z["__meta__"]).decode())["argv"])
+        G = SPADEGenerator(opt)
+        G.load_state_dict(deterministic_state(G.state_dict(), seed=seed))
+        G.train()
+        G64 = copy.deepcopy(G).double()                  # before the fp32 forward moves the spectral-norm vectors
+        objs, boxes = torch.from_numpy(z["objs"]), torch.from_numpy(z["boxes"])
+        masks = torch.from_numpy(z["masks"]) if "masks" in z.files else None
+        img32 = G(objs, boxes, masks, test_mode=False)
+        if not torch.equal(img32, torch.from_numpy(z["imgs_pred"])):
+            raise SystemExit("%s: the fp32 generator does not reproduce the fixture's imgs_pred" % name)
+        torch.set_default_dtype(torch.float64)          # tensors the reference creates inside its forward
+        try:
+            img64 = G64(objs, boxes.double(), None if masks is None else masks.double(), test_mode=False)
+        finally:
+            torch.set_default_dtype(torch.float32)
+        assert img64.dtype == torch.float64
+        arrays[name] = npy(img64)
+    save("step_images_fp64", {"ref": "spade/models/networks/generator.py (SPADEGenerator.forward), float64",
+                              "note": "imgs_pred of the named fixture, same weights and batch, evaluated in float64"},
+         **arrays)
+
+
 def _tv_vgg19(pretrained=False):
     """Stand-in for torchvision.models.vgg19 (absent here): the public configuration 'E' feature stack
     with default-initialised weights — the fixture overwrites them by name afterwards."""
@@ -859,6 +891,7 @@ if __name__ == "__main__":
     fx_step_objdisc()
     fx_vgg()
     fx_step_masks()
+    fx_step_images64()
     fx_canon_graph()
     fx_canon_converse()
     fx_converse()

@@ -129,3 +129,90 @@ def test_world_size_must_equal_gpus(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "--gpus 4 but WORLD_SIZE=1" in str(e.value.code)
+
+
+# ------------------------------------------------------------------ --dump-outputs
+class _StandInTrainer:
+    """The attributes step_outputs reads, on CPU modules."""
+    def __init__(self):
+        torch.manual_seed(0)
+        self.model = torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.Linear(30, 5))
+        self.discriminator = torch.nn.Conv2d(3, 2, 3)            # 56 parameters: fewer than the sample
+        self.last_model_out = (torch.rand(2, 3, 8, 8), torch.rand(2, 4, 4), None)
+
+
+def test_step_outputs_are_what_the_step_returns_as_float_arrays():
+    import numpy as np
+    tr = _StandInTrainer()
+    G = {"total_loss": torch.tensor(3.25), "bbox_pred_all": torch.linspace(0.1, 0.9, 8)}
+    D = {"total_img_loss": torch.tensor(1.5), "count": torch.tensor(7)}
+    a = bench.step_outputs(tr, G, D, sample=100)
+    assert set(a) == {"G_total_loss", "G_bbox_pred_all", "D_total_img_loss", "D_count", "imgs_pred", "boxes_pred",
+                      "weights_generator_sample", "weights_discriminator_sample"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["D_count"].dtype == np.float64 and float(a["D_count"]) == 7.0
+    assert float(a["G_total_loss"]) == 3.25 and np.array_equal(a["G_bbox_pred_all"], G["bbox_pred_all"].numpy())
+    assert np.array_equal(a["imgs_pred"], tr.last_model_out[0].numpy())
+    # the weight sample: `sample` distinct entries of the flattened parameters, the same ones every time
+    flat = torch.cat([p.detach().reshape(-1) for p in tr.model.parameters()]).numpy()
+    s = a["weights_generator_sample"]
+    assert s.shape == (100,) and np.isin(s, flat).all() and len(np.unique(s)) == 100
+    assert np.array_equal(s, bench.step_outputs(tr, G, D, sample=100)["weights_generator_sample"])
+    # a network smaller than the sample is written whole
+    assert a["weights_discriminator_sample"].size == sum(p.numel() for p in tr.discriminator.parameters())
+    # an optimiser step shows in the sample
+    with torch.no_grad():
+        for p in tr.model.parameters():
+            p.add_(1e-3)
+    assert not np.array_equal(s, bench.step_outputs(tr, G, D, sample=100)["weights_generator_sample"])
+
+
+def test_write_outputs_round_trip_and_limits(tmp_path):
+    import numpy as np
+    arrays = {"x": np.arange(6, dtype=np.float32).reshape(2, 3), "y": np.float64(2.5) * np.ones(4)}
+    assert bench.write_outputs(str(tmp_path / "d"), arrays) == 6 * 4 + 4 * 8
+    for k, v in arrays.items():
+        r = np.load(str(tmp_path / "d" / (k + ".npy")))
+        assert r.dtype == v.dtype and np.array_equal(r, v)
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), arrays, limit=50)
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "int"), {"i": np.arange(3)})
+    assert not (tmp_path / "big").exists() and not (tmp_path / "int").exists()
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+
+
+def test_steps_must_be_positive(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.steps == 3 and a.dump_outputs == "out"
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_dump_outputs_repeat_run_to_run_and_follow_steps(tmp_path):
+    """Two runs with the same arguments write the same arrays, bit for bit; one more timed step changes the weights."""
+    import json
+    import subprocess
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1", "--batch", "2", "--image_size", "64",
+            "--ngf", "8", "--ndf", "8", "--no_cpu_baseline", "--no_vgg_variant", "--no_prof", "--no_gen_metric"]
+    dumps = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 3)):
+        out = subprocess.run(base + ["--steps", str(steps), "--dump-outputs", str(tmp_path / tag)], cwd=ROOT,
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == steps
+        dumps[tag] = {f[:-4]: np.load(str(tmp_path / tag / f)) for f in sorted(os.listdir(str(tmp_path / tag)))}
+    a, b, c = dumps["a"], dumps["b"], dumps["c"]
+    assert {"G_total_loss", "D_total_img_loss", "G_bbox_pred_all", "imgs_pred", "weights_generator_sample",
+            "weights_discriminator_sample"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a["imgs_pred"].shape == (2, 3, 64, 64)
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a), [k for k in a if not np.array_equal(a[k], b[k])]
+    assert set(a) == set(c) and not np.array_equal(a["weights_generator_sample"], c["weights_generator_sample"])

@@ -3,6 +3,7 @@
 import torch
 
 import oracle
+from oracle.fp64 import generated_image64
 from canonicalsg2im_amd.scripts.args import make_opt
 from canonicalsg2im_amd.synth import make_vocab
 from conftest import assert_close, load_golden, state_from_shapes, sub_state
@@ -113,11 +114,30 @@ def _train_fixture():
     return meta, a, opt, sg, g, d, batch
 
 
+def _check_image(imgs_pred, fresh_ts, batch, a, fixture, msg):
+    """The generated image of a train-step fixture against the reference's.
+
+    Two fp32 evaluations of the generator agree to ~1e-5 only when they round alike: the fixture's fp32 image was made on
+    one CPU, and the same oracle on another instruction set or thread count lands 4-6e-5 from it (train_step_masks: both
+    fp32 images sit 1.8e-4 from the exact one).  So the algorithm is judged in float64, against the reference's own
+    generator evaluated in float64 on the fixture's weights and batch (step_images_fp64.npz, measured 4e-14 apart), and
+    the oracle's fp32 arithmetic against that exact image: at most 3x the reference's own fp32 distance from it, in
+    relative L2 and in max norm (the factor of tests/fp64_band.py; measured <= 1.44 over oneDNN ISAs and thread counts).
+    `fresh_ts`: the fixture's state before the step, rebuilt (the fp64 forward advances its integer BatchNorm counters)."""
+    from fp64_band import errors
+    img64 = generated_image64(fresh_ts, batch)
+    ref64 = load_golden("step_images_fp64")[1][fixture]
+    assert_close(img64, ref64, 1e-9, 1e-11, msg + " (fp64 oracle vs fp64 reference)")
+    (o_l2, o_max), (r_l2, r_max) = errors(imgs_pred, ref64), errors(a["imgs_pred"], ref64)
+    assert o_l2 <= 3 * r_l2 and o_max <= 3 * r_max, "%s: fp32 oracle l2 %.2e max %.2e from fp64, fp32 reference %.2e %.2e" % (
+        msg, o_l2, o_max, r_l2, r_max)
+
+
 def test_full_train_step_matches_reference():
     meta, a, opt, sg, g, d, batch = _train_fixture()
     ts = oracle.TrainState(opt, sg, g, d)
     G, D, imgs_pred = oracle.train_step(ts, batch)
-    assert_close(imgs_pred, a["imgs_pred"], RTOL, 1e-5, "imgs_pred")
+    _check_image(imgs_pred, oracle.TrainState(opt, *_train_fixture()[3:6]), batch, a, "train_step", "imgs_pred")
     for k in ("bbox_pred_all", "bbox_pred", "GAN_Img", "GAN_Feat", "total_loss"):
         assert_close(G[k].reshape(a["G:" + k].shape), a["G:" + k], RTOL, 1e-5, "G " + k)
     for k in ("D_img_fake", "D_img_real", "total_img_loss"):
@@ -348,7 +368,9 @@ def test_train_step_with_masks():
     assert_close(masks_pred, a["masks_pred"], RTOL, 1e-6, "masks_pred")
     ts = oracle.TrainState(opt, sg, g, d, dobj, None, dmask, a["mask_noise"])
     G, D, imgs_pred = oracle.train_step(ts, batch)
-    assert_close(imgs_pred, a["imgs_pred"], RTOL, 1e-5, "imgs_pred (masks layout)")
+    sg0, g0, d0, dobj0, dmask0 = _masks_fixture()[3:8]
+    _check_image(imgs_pred, oracle.TrainState(opt, sg0, g0, d0, dobj0, None, dmask0, a["mask_noise"]), batch, a,
+                 "train_step_masks", "imgs_pred (masks layout)")
     assert {k[2:] for k in a if k.startswith("G:")} == set(G.keys())
     assert {k[2:] for k in a if k.startswith("D:")} == set(D.keys())
     for k in G:
