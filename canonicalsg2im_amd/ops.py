@@ -5,6 +5,7 @@ PyTorch supplies device memory, the current HIP stream and the autograd graph on
 activations are logical (B,C,H,W) tensors whose MEMORY is NHWC (channel stride 1) — build them
 with `empty_nhwc` / `nhwc`.  Nothing here runs on CPU tensors.
 """
+import collections
 import ctypes
 import os
 
@@ -20,7 +21,7 @@ from ._lib import ACT_LEAKY, ACT_NONE, ACT_TANH, ConvDesc, FewDesc, GemmDesc, Hi
 __all__ = [
     "nhwc", "empty_nhwc", "conv2d", "linear", "norm_act", "upsample2x", "nearest_resize", "avgpool3s2", "embed", "real_object_mask",
     "norm_act_pair", "graph_csr", "gather_concat", "segment_avg", "layout_pyramid", "layout_paint", "disc_input", "crop_objects", "maxpool2", "avgpool2", "l1_mean",
-    "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "spectral_weight", "spectral_weights", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
+    "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
 ]
 
 
@@ -372,17 +373,6 @@ def prepack_weights(root):
         mine.append(key)
 
 
-def _take_bwd_operand(weight, B, IH, IW, Cin, Cout, KH, KW, stride, pad):
-    """At FORWARD time: (variant, parked backward-data operand or None) of a convolution whose backward-data pass will run
-    Winograd — kept in the Function's ctx, so that the backward uses the operand of the weights its forward saw.  (That
-    pass counts as plain for `wino_variant`: its only epilogue is the producer's activation derivative, which a launch split
-    over the input channels leaves to a separate pass — _wino_launch.)"""
-    if not _PREPACKED or not wino_eligible(B, IH, IW, Cout, Cin, KH, KW, stride, pad):
-        return None
-    var = wino_variant(B, IH, IW, Cout, Cin, plain=True)
-    return (var, take_prepacked(_f32(weight.detach()), True, var))
-
-
 WINO4_AUDIT = None     # developer audit (tools/wino4_traffic_model.py): a dict collects the ALGORITHMIC HBM bytes of the
 #                        F(4x4,3x3) convolution launches (every operand once, the packed weights included) and their count
 
@@ -490,6 +480,277 @@ def _few_desc(B, IH, IW, Cin, KH, KW, stride, pad, cout_real, act, slope):
     return d if lib.csg_conv_few_supported(d) == 1 else None
 
 
+# The kernels of one convolution, chosen once (plan_conv) and run by _conv_fwd / _conv_bwd.  fwd: few | wino | wino34 | gemm |
+# direct; dx (backward-data): few | few_direct | range | wino | wino34 | gemm | direct, or None; wgrad: few | gemm_tn | wino4w |
+# wino | direct | colsum (bias gradient only), or None.  *_var: the Winograd variant (wino_variant) of a "wino" pass.
+# geom = (B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW, act, slope) with Cout the kernels' output width; few: the
+# csrc/fewn.hip descriptor; wgrad_ws: the workspace bytes of a Winograd weight gradient.
+ConvPlan = collections.namedtuple("ConvPlan", "fwd fwd_var dx dx_var wgrad geom few wgrad_ws has_bias dx_range in_act pre_slope")
+
+
+def plan_conv(B, IH, IW, Cin, Cout, KH, KW, stride, pad, act=ACT_NONE, slope=0.0, has_bias=False, has_res=False, packs=None,
+              dx_range=None, in_act=None, cout_real=None, pre_slope=None, need=(False, False, False)):
+    """The kernels that serve y = act(conv(x, w) + b) [+ res] in each direction: the one place a convolution's kernels are
+    chosen (host only; the module flags are read per call).  `need`: the `needs_input_grad` of (x, w, b) — only the
+    directions asked for are planned.  Options as conv2d's; `packs`: pack_conv_weight's frozen layouts."""
+    few = None
+    if ((Cout == 4 or (cout_real is not None and Cout == cout_real and Cout < 4)) and not has_res and dx_range is None
+            and packs is None and in_act is None):
+        few = _few_desc(B, IH, IW, Cin, KH, KW, stride, pad, cout_real, act, slope)
+    if pre_slope is not None:
+        # `pre_slope`: the convolution sees leaky(x, pre_slope) — applied in the few-output kernels' loaders (conv_img)
+        if few is None:
+            raise RuntimeError("conv2d: pre_slope is served by the few-output kernels only (the caller applies the "
+                               "activation itself otherwise)")
+        few.in_act, few.in_slope = 1, float(pre_slope)
+    if few is None and Cout % 4:
+        raise RuntimeError("conv2d: an output-channel count that is not a multiple of 4 reached the kernels")
+    OH, OW = (IH + 2 * pad - KH) // stride + 1, (IW + 2 * pad - KW) // stride + 1
+    fwd_var = None
+    if few is not None:
+        fwd, Cout = "few", 4                    # the kernels' padded output width
+    elif dx_range is None and wino_eligible(B, IH, IW, Cin, Cout, KH, KW, stride, pad):
+        fwd, fwd_var = "wino", wino_variant(B, IH, IW, Cin, Cout, plain=not has_bias and not has_res and act == ACT_NONE)
+    elif dx_range is None and packs is None and wino34_eligible(B, IH, IW, Cin, Cout, KH, KW, stride, pad,
+                                                                backward=not (need[0] or need[1])):
+        # (a forward pass nothing is differentiated through — the discriminator on the real images in the generator
+        # step, inference — counts as a backward-class pass: its error meets no gate of a backward pass)
+        fwd = "wino34"
+    elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and not has_res and packs is None and dx_range is None
+          and act in (ACT_NONE, ACT_LEAKY) and gemm_eligible(B * IH * IW, Cout, Cin)):
+        fwd = "gemm"
+    else:
+        fwd = "direct"
+    dx = dx_var = None
+    if need[0]:
+        if few is not None:
+            if Cin >= 256 and pre_slope is not None:
+                raise RuntimeError("conv2d: pre_slope with >= 256 input channels is not served")
+            dx = "few" if Cin >= 256 else "few_direct"
+        elif dx_range is not None:
+            dx = "range"
+        elif wino_eligible(B, IH, IW, Cout, Cin, KH, KW, stride, pad):
+            # the same Winograd kernel with the roles of the channel counts swapped; the pass counts as plain: its only
+            # epilogue is the producer's activation derivative, which a launch split over the input channels leaves to a
+            # separate pass (_wino_launch)
+            dx, dx_var = "wino", wino_variant(B, IH, IW, Cout, Cin, plain=True)
+        elif packs is None and wino34_eligible(B, OH, OW, Cout, Cin, KH, KW, stride, 3 - pad, backward=True):
+            dx = "wino34"
+        elif fwd == "gemm":
+            dx = "gemm"
+        else:
+            dx = "direct"
+    wgrad, wgrad_ws = None, 0
+    if few is not None:
+        if need[1] or (has_bias and need[2]):
+            wgrad = "few"
+    elif need[1]:
+        wino_ws = wino4_ws = -1
+        if WINO_WGRAD and wino_eligible(B, IH, IW, Cin, Cout, KH, KW, stride, pad):
+            d = _wino_desc(B, IH, IW, Cin, Cout)
+            wino_ws = lib.csg_wino_bwd_weight_workspace(d)      # < 0: the 16-tile stages do not tile this image exactly
+            if WINO4_WGRAD and Cin >= 64 and Cout >= 64 and IH % 8 == 0 and IW % 8 == 0 and IH * IW >= WINO4_WGRAD_MIN_PIXELS:
+                wino4_ws = lib.csg_wino4_bwd_weight_workspace(d)
+        if fwd == "gemm":
+            wgrad = "gemm_tn"
+        elif wino4_ws >= 0:
+            wgrad, wgrad_ws = "wino4w", wino4_ws
+        elif wino_ws >= 0:
+            wgrad, wgrad_ws = "wino", wino_ws
+        else:
+            wgrad = "direct"
+    elif has_bias and need[2]:
+        wgrad = "colsum"
+    return ConvPlan(fwd, fwd_var, dx, dx_var, wgrad, (B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW, act, slope), few,
+                    wgrad_ws, has_bias, dx_range, in_act, pre_slope)
+
+
+def _take_dx_operand(plan, w):
+    """At FORWARD time: the parked backward-data operand of `w` when the plan's backward-data pass runs Winograd, else None
+    — kept in the Function's ctx, so that the backward uses the operand of the weights its forward saw."""
+    return take_prepacked(_f32(w.detach()), True, plan.dx_var) if plan.dx == "wino" else None
+
+
+def _conv_fwd(plan, x, w, b, res, packs):
+    """The forward of `plan` on NHWC x: returns y and the parked backward-data operand taken for the backward (or None)."""
+    B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW, act, slope = plan.geom
+    cin_w = packs.fwd.shape[3] if packs is not None else w.shape[1]       # packed weights carry their own channel padding
+    if cin_w != Cin:
+        raise RuntimeError("conv2d: weight expects %d input channels, x has %d" % (cin_w, Cin))
+    b = b.detach() if b is not None else None
+    y = empty_nhwc(B, Cout, OH, OW, x.device)
+    ut_pre = None
+    if plan.fwd == "few":
+        wp = w.detach().permute(0, 2, 3, 1).contiguous()
+        nws = lib.csg_conv_few_fwd_workspace(plan.few)
+        ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32) if nws > 0 else None
+        check(lib.csg_conv_few_fwd(plan.few, ptr(x), ptr(wp), ptr(b), ptr(y), ptr(ws), nws, stream()), "conv_few_fwd")
+    elif plan.fwd == "wino":
+        var = plan.fwd_var
+        up = _frozen_pack(packs, False, var) if (packs is not None and packs.wino_fwd is not None) else \
+            wino_pack(w, False, None, var)
+        if packs is None:
+            ut_pre = _take_dx_operand(plan, w)
+        _wino_launch(x, up, b, res, y, B, IH, IW, Cin, Cout, act, slope, "wino_conv_fwd", variant=var)
+    elif plan.fwd == "wino34":
+        check(lib.csg_wino34_conv(_wino_desc(B, IH, IW, Cin, Cout, act, slope), pad, ptr(x), ptr(wino_pack(w, False, None, 34)),
+                                  ptr(b), ptr(res), None, 0.0, ptr(y), None, 0, stream()), "wino34_conv_fwd")
+    elif plan.fwd == "gemm":
+        # a matrix product: rows = pixels (or the rows of a Linear), csrc/gemm.hip
+        w2 = w.detach().reshape(Cout, Cin)
+        _gemm_nt(x, B * IH * IW, Cin, w2 if w2.is_contiguous() else w2.contiguous(), Cout, b, act, slope, None, 0.0, y)
+    else:
+        # [Cout][KH][KW][Cin]: free for channels-last parameters (sg2im.layers.Conv2d keeps them that way)
+        wp = packs.fwd if packs is not None else w.detach().permute(0, 2, 3, 1).contiguous()
+        d, _, _ = _desc_forward(B, IH, IW, Cin, Cout, KH, KW, stride, pad, act, slope)
+        _conv_launch(d, x, wp, b, res, y, "conv_fwd")
+    return y, ut_pre
+
+
+def _weight_grad_dest(w, Cout, KH, KW, Cin, want_db, dev):
+    """dW [Cout][KH][KW][Cin] (the bucket slot of `w` if registered and its memory has that order) and db if wanted."""
+    dwp = _grad_dest(w, (Cout, KH, KW, Cin)) if _ohwi_dense(w) else None
+    if dwp is None:
+        dwp = torch.empty((Cout, KH, KW, Cin), device=dev, dtype=torch.float32)
+    return dwp, (torch.empty(Cout, device=dev, dtype=torch.float32) if want_db else None)
+
+
+def _conv_bwd(plan, dy, x, w, y, need, packs, ut_pre):
+    """dx, dw, db of the convolution `plan` describes, from its NHWC incoming gradient dy.  `y`: the saved output when dy
+    still has to pass the layer's activation derivative, else None; `need`: (x, w, b) — a subset of what the plan was made
+    for; `ut_pre`: the operand _conv_fwd took."""
+    B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW, act, slope = plan.geom
+    in_act, dev = plan.in_act, dy.device
+    gate, gate_slope = (x, in_act[1]) if in_act is not None else (None, 0.0)      # the producer's activation derivative
+    dpre = dy
+    if y is not None:
+        dpre = torch.empty_like(dy)
+        check(lib.csg_act_bwd(ptr(dy), ptr(y), dy.numel(), act, slope, ptr(dpre), stream()), "act_bwd")
+    dx = dw = db = None
+    gated = in_act is None
+    fam = plan.dx if need[0] else None
+    if fam == "few":
+        wp = w.detach().permute(0, 2, 3, 1).contiguous()
+        dx = empty_nhwc(B, Cin, IH, IW, dev)
+        check(lib.csg_conv_few_bwd_data(plan.few, ptr(dpre), ptr(wp), ptr(dx), stream()), "conv_few_bwd_data")
+    elif fam == "few_direct":
+        # few input channels as well (conv_img: 64): a (pixels x 36) x (36 x 64) product, fine on the matrix cores
+        # (w: the 1..3 rows as given when the few-output path takes the weight raw)
+        w4 = w.detach() if w.shape[0] == 4 else F.pad(w.detach(), (0, 0, 0, 0, 0, 0, 0, 4 - w.shape[0]))
+        wt = w4.permute(1, 2, 3, 0).contiguous()                    # [Cin][KH][KW][Cout]
+        dx = empty_nhwc(B, Cin, IH, IW, dev)
+        for d in _descs_backward_data(B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW):
+            if plan.pre_slope is not None:         # d leaky(x) / dx in the epilogue: x gates through the residual slot
+                d.res_gate, d.slope = 1, plan.pre_slope
+                _conv_launch(d, dpre, wt, None, x, dx, "conv_bwd_data")
+            else:
+                _conv_launch(d, dpre, wt, None, None, dx, "conv_bwd_data")
+    elif fam == "range":
+        # only input channels [lo, hi) are wanted by the consumer of dx (the discriminator's packed
+        # [layout | img | pad] input: the image part in the generator pass, the layout part in the
+        # discriminator passes): the transposed convolution runs over that slice of the weight only
+        lo, hi = plan.dx_range
+        wt = w.detach()[:, lo:hi].permute(1, 2, 3, 0).contiguous()      # [hi-lo][KH][KW][Cout]
+        dx = empty_nhwc(B, Cin, IH, IW, dev, zero=True)
+        descs = _descs_backward_data(B, IH, IW, hi - lo, Cout, KH, KW, stride, pad, OH, OW)
+        for d in descs:
+            d.y_cs = Cin
+        _conv_launch_classes(descs, dpre, wt, ctypes_ptr_off(dx, lo), dev, "conv_bwd_data")
+    elif fam == "wino":
+        # dX = conv3x3(dY, flipped W^T): the same Winograd kernel with the roles of the channel counts swapped
+        var = plan.dx_var
+        if packs is not None and packs.wino_bwd is not None:
+            ut = _frozen_pack(packs, True, var)
+        elif ut_pre is not None:
+            ut = ut_pre
+        else:
+            ut = wino_pack(w, True, None, var)
+        dx = empty_nhwc(B, Cin, IH, IW, dev)
+        gated = _wino_launch(dpre, ut, None, None, dx, B, IH, IW, Cout, Cin, ACT_NONE, 0.0, "wino_conv_bwd_data", gate=gate,
+                             gate_slope=gate_slope, variant=var) or in_act is None
+    elif fam == "wino34":
+        # dX = conv4x4(dY, flipped W^T) with padding 3 - pad: the same F(3x3,4x4) kernel, channel counts swapped
+        dx = empty_nhwc(B, Cin, IH, IW, dev)
+        d34 = _wino_desc(B, OH, OW, Cout, Cin)
+        ws, nws = None, 0
+        if in_act is None:                      # a small tile grid is split over the input channels (slabs + ordered sum)
+            nws = lib.csg_wino34_conv_workspace(d34, 3 - pad)
+            if nws > 0:
+                ws = torch.empty(nws // 4, device=dev, dtype=torch.float32)
+        check(lib.csg_wino34_conv(d34, 3 - pad, ptr(dpre), ptr(wino_pack(w, True, None, 34)), None, None, ptr(gate), gate_slope,
+                                  ptr(dx), ptr(ws), nws, stream()), "wino34_conv_bwd_data")
+        gated = True
+    elif fam == "gemm":
+        # dX (M, Cin) = dY (M, Cout) . W^T stored [Cin][Cout] (the reduction index contiguous), the producer's
+        # activation derivative as the epilogue's gate
+        wt = w.detach().reshape(Cout, Cin).t().contiguous()
+        dx = empty_nhwc(B, Cin, IH, IW, dev)
+        _gemm_nt(dpre, B * IH * IW, Cout, wt, Cin, None, ACT_NONE, 0.0, gate, gate_slope, dx)
+        gated = True
+    elif fam == "direct":
+        wt = packs.bwd if packs is not None else w.detach().permute(1, 2, 3, 0).contiguous()       # [Cin][KH][KW][Cout]
+        dx = empty_nhwc(B, Cin, IH, IW, dev)
+        descs = _descs_backward_data(B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW)
+        if in_act is not None and len(descs) == 1:
+            # the producer's (Leaky)ReLU derivative in the epilogue: x (its output) rides in the residual slot as a gate
+            d = descs[0]
+            d.res_gate, d.slope = 1, gate_slope
+            _conv_launch(d, dpre, wt, None, x, dx, "conv_bwd_data")
+            gated = True
+        else:
+            _conv_launch_classes(descs, dpre, wt, ptr(dx), dev, "conv_bwd_data")
+    if dx is not None and not gated:              # the producer's activation derivative as a separate pass
+        check(lib.csg_act_bwd(ptr(dx), ptr(x), dx.numel(), in_act[0], in_act[1], ptr(dx), stream()), "act_bwd")
+    want_db = plan.has_bias and need[2]
+    wg = plan.wgrad
+    if not need[1] and wg != "few":             # a plan made for more than this call needs (_SpadeJoined)
+        wg = "colsum" if want_db else None
+    if wg == "few":
+        nbytes = lib.csg_conv_few_bwd_weight_workspace(plan.few)
+        ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+        dwp = torch.empty((Cout, KH, KW, Cin), device=dev, dtype=torch.float32)
+        db = torch.empty(Cout, device=dev, dtype=torch.float32) if plan.has_bias else None
+        check(lib.csg_conv_few_bwd_weight(plan.few, ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
+              "conv_few_bwd_weight")
+        dw = dwp[:w.shape[0]].permute(0, 3, 1, 2)
+        db = db[:w.shape[0]] if db is not None else None
+    elif wg == "gemm_tn":
+        # dW (Cout, Cin) = dY^T . X over the rows, the bias gradient from the same staged tiles (csg_gemm_tn)
+        M = B * IH * IW
+        nbytes = lib.csg_gemm_tn_workspace(M, Cout, Cin)
+        if nbytes < 0:
+            raise RuntimeError("gemm_tn_workspace: (%d, %d, %d) not served" % (M, Cout, Cin))
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        dwp, db = _weight_grad_dest(w, Cout, KH, KW, Cin, want_db, dev)
+        check(lib.csg_gemm_tn(M, Cout, Cin, ptr(dpre), Cout, ptr(x), Cin, ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
+              "gemm_tn")
+        _GEMM_CALLS[0] += 1
+        dw = dwp.permute(0, 3, 1, 2)
+    elif wg in ("wino4w", "wino"):
+        # Winograd F(3x3,4x4) (csrc/wino4w.hip) / F(3x3,2x2) (csrc/wino.hip) weight gradient, the direct kernel's layout
+        ws = torch.empty(plan.wgrad_ws // 4, device=dev, dtype=torch.float32)
+        dwp, db = _weight_grad_dest(w, Cout, KH, KW, Cin, want_db, dev)
+        fn, what = (lib.csg_wino4_bwd_weight, "wino4_bwd_weight") if wg == "wino4w" else (lib.csg_wino_bwd_weight, "wino_bwd_weight")
+        check(fn(_wino_desc(B, IH, IW, Cin, Cout), ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), plan.wgrad_ws, stream()), what)
+        dw = dwp.permute(0, 3, 1, 2)
+    elif wg == "direct":
+        d, _, _ = _desc_forward(B, IH, IW, Cin, Cout, KH, KW, stride, pad)
+        nbytes = lib.csg_conv_bwd_weight_workspace(d)
+        if nbytes < 0:
+            raise RuntimeError("conv_bwd_weight_workspace: " + _lib.last_error())
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        dwp, db = _weight_grad_dest(w, Cout, KH, KW, Cin, want_db, dev)     # column sums of dY ride along in the same kernel
+        check(lib.csg_conv_bwd_weight(d, ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), nbytes, stream()), "conv_bwd_weight")
+        dw = dwp.permute(0, 3, 1, 2)
+    elif wg == "colsum":
+        rows = B * OH * OW
+        nch = _chunks(rows)
+        part = torch.empty(nch * 2 * Cout, device=dev, dtype=torch.float64)
+        db = torch.empty(Cout, device=dev, dtype=torch.float32)
+        check(lib.csg_colsum(ptr(dpre), rows, Cout, Cout, ptr(db), ptr(part), nch, stream()), "colsum")
+    return dx, dw, db
+
+
 class _Conv2d(torch.autograd.Function):
     """y = act(conv2d(x, w) + b) [+ residual] — reference nn.Conv2d call sites listed in
     include/csg_hip.h (K8/K11)."""
@@ -503,251 +764,28 @@ class _Conv2d(torch.autograd.Function):
         gradient needs no activation derivative any more."""
         x = nhwc(_f32(x))
         B, Cin, IH, IW = x.shape
-        Cout, Cin_w, KH, KW = weight.shape
-        if packs is not None:
-            Cin_w = packs[0].shape[3]              # packed weights carry their own channel padding
-        if Cin_w != Cin:
-            raise RuntimeError("conv2d: weight expects %d input channels, x has %d" % (Cin_w, Cin))
-        ctx.packs, ctx.dx_range, ctx.in_act, ctx.grad_is_pre = packs, dx_range, in_act, grad_is_pre
+        Cout, _, KH, KW = weight.shape
         res = nhwc(residual) if residual is not None else None
-        ctx.few = None
-        ctx.gemm = False
-        ctx.cout_w = Cout                       # rows of the weight as given (1..3 when the few-output path takes it raw)
-        if (Cout == 4 or (cout_real is not None and Cout == cout_real and Cout < 4)) and res is None and dx_range is None \
-                and packs is None and in_act is None:
-            ctx.few = _few_desc(B, IH, IW, Cin, KH, KW, stride, pad, cout_real, act, slope)
-        ctx.pre_slope = pre_slope
-        if pre_slope is not None:
-            # `pre_slope`: the convolution sees leaky(x, pre_slope) — applied in the few-output kernels' loaders (conv_img)
-            if ctx.few is None:
-                raise RuntimeError("conv2d: pre_slope is served by the few-output kernels only (the caller applies the "
-                                   "activation itself otherwise)")
-            ctx.few.in_act, ctx.few.in_slope = 1, float(pre_slope)
-        if ctx.few is None and Cout % 4:
-            raise RuntimeError("conv2d: an output-channel count that is not a multiple of 4 reached the kernels")
-        if ctx.few is not None:
-            Cout = 4                            # the kernels' padded output width
-            OH, OW = IH + 2 * pad - KH + 1, IW + 2 * pad - KW + 1
-            y = empty_nhwc(B, Cout, OH, OW, x.device)
-            wp = weight.detach().permute(0, 2, 3, 1).contiguous()
-            nws = lib.csg_conv_few_fwd_workspace(ctx.few)
-            ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32) if nws > 0 else None
-            check(lib.csg_conv_few_fwd(ctx.few, ptr(x), ptr(wp), ptr(bias.detach() if bias is not None else None), ptr(y),
-                                       ptr(ws), nws, stream()), "conv_few_fwd")
-        elif dx_range is None and wino_eligible(B, IH, IW, Cin, Cout, KH, KW, stride, pad):
-            OH, OW = IH, IW
-            y = empty_nhwc(B, Cout, OH, OW, x.device)
-            var = wino_variant(B, IH, IW, Cin, Cout, plain=bias is None and res is None and act == ACT_NONE)
-            up = _frozen_pack(packs, False, var) if (packs is not None and len(packs) > 2) else wino_pack(weight, False, None, var)
-            if packs is None and ctx.needs_input_grad[0]:
-                ctx.ut_pre = _take_bwd_operand(weight, B, IH, IW, Cin, Cout, KH, KW, stride, pad)
-            _wino_launch(x, up, bias.detach() if bias is not None else None, res, y, B, IH, IW, Cin, Cout, act, slope,
-                         "wino_conv_fwd", variant=var)
-        elif dx_range is None and packs is None and wino34_eligible(
-                B, IH, IW, Cin, Cout, KH, KW, stride, pad, backward=not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])):
-            # (a forward pass nothing is differentiated through — the discriminator on the real images in the generator
-            # step, inference — counts as a backward-class pass: its error meets no gate of a backward pass)
-            OH, OW = IH + 2 * pad - 3, IW + 2 * pad - 3
-            y = empty_nhwc(B, Cout, OH, OW, x.device)
-            check(lib.csg_wino34_conv(_wino_desc(B, IH, IW, Cin, Cout, act, slope), pad, ptr(x),
-                                      ptr(wino_pack(weight, False, None, 34)), ptr(bias.detach() if bias is not None else None),
-                                      ptr(res), None, 0.0, ptr(y), None, 0, stream()), "wino34_conv_fwd")
-        elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and res is None and packs is None and dx_range is None
-              and act in (ACT_NONE, ACT_LEAKY) and gemm_eligible(B * IH * IW, Cout, Cin)):
-            # a matrix product: rows = pixels (or the rows of a Linear), csrc/gemm.hip
-            OH, OW = IH, IW
-            y = empty_nhwc(B, Cout, OH, OW, x.device)
-            w2 = weight.detach().reshape(Cout, Cin)
-            _gemm_nt(x, B * IH * IW, Cin, w2 if w2.is_contiguous() else w2.contiguous(), Cout,
-                     bias.detach() if bias is not None else None, act, slope, None, 0.0, y)
-            ctx.gemm = True
-        else:
-            # [Cout][KH][KW][Cin]: free for channels-last parameters (sg2im.layers.Conv2d keeps them that way)
-            wp = packs[0] if packs is not None else weight.detach().permute(0, 2, 3, 1).contiguous()
-            d, OH, OW = _desc_forward(B, IH, IW, Cin, Cout, KH, KW, stride, pad, act, slope)
-            y = empty_nhwc(B, Cout, OH, OW, x.device)
-            _conv_launch(d, x, wp, bias.detach() if bias is not None else None, res, y, "conv_fwd")
-        ctx.geom = (B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW, act, slope)
-        ctx.has_bias, ctx.has_res = bias is not None, residual is not None
+        ctx.plan = plan_conv(B, IH, IW, Cin, Cout, KH, KW, stride, pad, act, slope, bias is not None, res is not None, packs,
+                             dx_range, in_act, cout_real, pre_slope, ctx.needs_input_grad[:3])
+        y, ctx.ut_pre = _conv_fwd(ctx.plan, x, weight, bias, res, packs)
+        ctx.packs, ctx.grad_is_pre, ctx.has_res = packs, grad_is_pre, res is not None
         ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight, y = ctx.saved_tensors
-        B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW, act, slope = ctx.geom
         dy = nhwc(dy)
-        gated = ctx.in_act is None
-        if act != ACT_NONE and not ctx.grad_is_pre:
-            dpre = torch.empty_like(dy)
-            check(lib.csg_act_bwd(ptr(dy), ptr(y), dy.numel(), act, slope, ptr(dpre), stream()), "act_bwd")
-        else:
-            dpre = dy
-        dx = dw = db = dres = None
-        if ctx.few is not None:
-            if ctx.needs_input_grad[0] and Cin >= 256:
-                if ctx.pre_slope is not None:
-                    raise RuntimeError("conv2d: pre_slope with >= 256 input channels is not served")
-                wp = weight.detach().permute(0, 2, 3, 1).contiguous()
-                dx = empty_nhwc(B, Cin, IH, IW, dy.device)
-                check(lib.csg_conv_few_bwd_data(ctx.few, ptr(dpre), ptr(wp), ptr(dx), stream()), "conv_few_bwd_data")
-            elif ctx.needs_input_grad[0]:
-                # few input channels as well (conv_img: 64): a (pixels x 36) x (36 x 64) product, fine on the matrix cores
-                w4 = weight.detach() if ctx.cout_w == 4 else F.pad(weight.detach(), (0, 0, 0, 0, 0, 0, 0, 4 - ctx.cout_w))
-                wt = w4.permute(1, 2, 3, 0).contiguous()                    # [Cin][KH][KW][Cout]
-                dx = empty_nhwc(B, Cin, IH, IW, dy.device)
-                for d in _descs_backward_data(B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW):
-                    if ctx.pre_slope is not None:            # d leaky(x) / dx in the epilogue: x gates through the residual slot
-                        d.res_gate, d.slope = 1, ctx.pre_slope
-                        _conv_launch(d, dpre, wt, None, x, dx, "conv_bwd_data")
-                    else:
-                        _conv_launch(d, dpre, wt, None, None, dx, "conv_bwd_data")
-            if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-                nbytes = lib.csg_conv_few_bwd_weight_workspace(ctx.few)
-                ws = torch.empty(nbytes // 4, device=dy.device, dtype=torch.float32)
-                dwp = torch.empty((Cout, KH, KW, Cin), device=dy.device, dtype=torch.float32)
-                db = torch.empty(Cout, device=dy.device, dtype=torch.float32) if ctx.has_bias else None
-                check(lib.csg_conv_few_bwd_weight(ctx.few, ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
-                      "conv_few_bwd_weight")
-                dw = dwp[:ctx.cout_w].permute(0, 3, 1, 2)
-                db = db[:ctx.cout_w] if db is not None else None
-            return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None
-        if ctx.needs_input_grad[0] and ctx.dx_range is not None:
-            # only input channels [lo, hi) are wanted by the consumer of dx (the discriminator's packed
-            # [layout | img | pad] input: the image part in the generator pass, the layout part in the
-            # discriminator passes): the transposed convolution runs over that slice of the weight only
-            lo, hi = ctx.dx_range
-            wt = weight.detach()[:, lo:hi].permute(1, 2, 3, 0).contiguous()      # [hi-lo][KH][KW][Cout]
-            dx = empty_nhwc(B, Cin, IH, IW, dy.device, zero=True)
-            descs = _descs_backward_data(B, IH, IW, hi - lo, Cout, KH, KW, stride, pad, OH, OW)
-            for d in descs:
-                d.y_cs = Cin
-            _conv_launch_classes(descs, dpre, wt, ctypes_ptr_off(dx, lo), dy.device, "conv_bwd_data")
-        elif ctx.needs_input_grad[0] and wino_eligible(B, IH, IW, Cout, Cin, KH, KW, stride, pad):
-            # dX = conv3x3(dY, flipped W^T): the same Winograd kernel with the roles of the channel counts swapped
-            var = wino_variant(B, IH, IW, Cout, Cin, plain=True)
-            pre = getattr(ctx, "ut_pre", None)           # parked at forward time (prepack_weights)
-            if ctx.packs is not None and len(ctx.packs) > 3:
-                ut = _frozen_pack(ctx.packs, True, var)
-            elif pre is not None and pre[1] is not None and pre[0] == var:
-                ut = pre[1]
-            else:
-                ut = wino_pack(weight, True, None, var)
-            dx = empty_nhwc(B, Cin, IH, IW, dy.device)
-            gated = _wino_launch(dpre, ut, None, None, dx, B, IH, IW, Cout, Cin, ACT_NONE, 0.0, "wino_conv_bwd_data",
-                                 gate=x if ctx.in_act is not None else None,
-                                 gate_slope=ctx.in_act[1] if ctx.in_act is not None else 0.0, variant=var) or ctx.in_act is None
-        elif ctx.needs_input_grad[0] and ctx.packs is None and wino34_eligible(B, OH, OW, Cout, Cin, KH, KW, stride, 3 - pad,
-                                                                                    backward=True):
-            # dX = conv4x4(dY, flipped W^T) with padding 3 - pad: the same F(3x3,4x4) kernel, channel counts swapped
-            dx = empty_nhwc(B, Cin, IH, IW, dy.device)
-            has_gate = ctx.in_act is not None
-            d34 = _wino_desc(B, OH, OW, Cout, Cin)
-            ws, nws = None, 0
-            if not has_gate:                     # a small tile grid is split over the input channels (slabs + ordered sum)
-                nws = lib.csg_wino34_conv_workspace(d34, 3 - pad)
-                if nws > 0:
-                    ws = torch.empty(nws // 4, device=dy.device, dtype=torch.float32)
-            check(lib.csg_wino34_conv(d34, 3 - pad, ptr(dpre), ptr(wino_pack(weight, True, None, 34)), None, None,
-                                      ptr(x) if has_gate else None, ctx.in_act[1] if has_gate else 0.0, ptr(dx), ptr(ws), nws,
-                                      stream()), "wino34_conv_bwd_data")
-            gated = True
-        elif ctx.needs_input_grad[0] and getattr(ctx, "gemm", False):
-            # dX (M, Cin) = dY (M, Cout) . W^T stored [Cin][Cout] (the reduction index contiguous), the producer's
-            # activation derivative as the epilogue's gate
-            wt = weight.detach().reshape(Cout, Cin).t().contiguous()
-            dx = empty_nhwc(B, Cin, IH, IW, dy.device)
-            has_gate = ctx.in_act is not None
-            _gemm_nt(dpre, B * IH * IW, Cout, wt, Cin, None, ACT_NONE, 0.0, x if has_gate else None,
-                     ctx.in_act[1] if has_gate else 0.0, dx)
-            gated = True
-        elif ctx.needs_input_grad[0]:
-            wt = ctx.packs[1] if ctx.packs is not None else \
-                weight.detach().permute(1, 2, 3, 0).contiguous()       # [Cin][KH][KW][Cout]
-            dx = empty_nhwc(B, Cin, IH, IW, dy.device)
-            descs = _descs_backward_data(B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW)
-            if ctx.in_act is not None and len(descs) == 1:
-                # the producer's (Leaky)ReLU derivative in the epilogue: x (its output) rides in the residual slot as a gate
-                d = descs[0]
-                d.res_gate, d.slope = 1, ctx.in_act[1]
-                _conv_launch(d, dpre, wt, None, x, dx, "conv_bwd_data")
-                gated = True
-            else:
-                _conv_launch_classes(descs, dpre, wt, ptr(dx), dy.device, "conv_bwd_data")
-        if dx is not None and not gated:              # the producer's activation derivative as a separate pass
-            check(lib.csg_act_bwd(ptr(dx), ptr(x), dx.numel(), ctx.in_act[0], ctx.in_act[1], ptr(dx), stream()), "act_bwd")
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        wino_wg = wino4_wg = -1
-        if ctx.needs_input_grad[1] and WINO_WGRAD and wino_eligible(B, IH, IW, Cin, Cout, KH, KW, stride, pad):
-            d = WinoDesc()
-            d.B, d.H, d.W, d.Cin, d.x_cs, d.Cout, d.y_cs, d.act, d.slope = B, IH, IW, Cin, Cin, Cout, Cout, ACT_NONE, 0.0
-            wino_wg = lib.csg_wino_bwd_weight_workspace(d)      # < 0: the 16-tile stages do not tile this image exactly
-            if (WINO4_WGRAD and Cin >= 64 and Cout >= 64 and IH % 8 == 0 and IW % 8 == 0
-                    and IH * IW >= WINO4_WGRAD_MIN_PIXELS):
-                wino4_wg = lib.csg_wino4_bwd_weight_workspace(d)
-        if ctx.needs_input_grad[1] and getattr(ctx, "gemm", False):
-            # dW (Cout, Cin) = dY^T . X over the rows, the bias gradient from the same staged tiles (csg_gemm_tn)
-            M = B * IH * IW
-            nbytes = lib.csg_gemm_tn_workspace(M, Cout, Cin)
-            if nbytes < 0:
-                raise RuntimeError("gemm_tn_workspace: (%d, %d, %d) not served" % (M, Cout, Cin))
-            ws = torch.empty(max(nbytes // 4, 4), device=dy.device, dtype=torch.float32)
-            dwp = _grad_dest(weight, (Cout, KH, KW, Cin)) if _ohwi_dense(weight) else None
-            if dwp is None:
-                dwp = torch.empty((Cout, KH, KW, Cin), device=dy.device, dtype=torch.float32)
-            if want_db:
-                db = torch.empty(Cout, device=dy.device, dtype=torch.float32)
-            check(lib.csg_gemm_tn(M, Cout, Cin, ptr(dpre), Cout, ptr(x), Cin, ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
-                  "gemm_tn")
-            _GEMM_CALLS[0] += 1
-            dw = dwp.permute(0, 3, 1, 2)
-        elif wino4_wg >= 0:
-            # Winograd F(3x3,4x4) weight gradient (csrc/wino4w.hip), same output layout as the direct kernel
-            nbytes = wino4_wg
-            ws = torch.empty(nbytes // 4, device=dy.device, dtype=torch.float32)
-            dwp = _grad_dest(weight, (Cout, KH, KW, Cin)) if _ohwi_dense(weight) else None
-            if dwp is None:
-                dwp = torch.empty((Cout, KH, KW, Cin), device=dy.device, dtype=torch.float32)
-            if want_db:
-                db = torch.empty(Cout, device=dy.device, dtype=torch.float32)
-            check(lib.csg_wino4_bwd_weight(d, ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
-                  "wino4_bwd_weight")
-            dw = dwp.permute(0, 3, 1, 2)
-        elif wino_wg >= 0:
-            # Winograd F(3x3,2x2) weight gradient (csrc/wino.hip), same output layout as the direct kernel
-            nbytes = wino_wg
-            ws = torch.empty(nbytes // 4, device=dy.device, dtype=torch.float32)
-            dwp = _grad_dest(weight, (Cout, KH, KW, Cin)) if _ohwi_dense(weight) else None
-            if dwp is None:
-                dwp = torch.empty((Cout, KH, KW, Cin), device=dy.device, dtype=torch.float32)
-            if want_db:
-                db = torch.empty(Cout, device=dy.device, dtype=torch.float32)
-            check(lib.csg_wino_bwd_weight(d, ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
-                  "wino_bwd_weight")
-            dw = dwp.permute(0, 3, 1, 2)
-        elif ctx.needs_input_grad[1]:
-            d, _, _ = _desc_forward(B, IH, IW, Cin, Cout, KH, KW, stride, pad)
-            nbytes = lib.csg_conv_bwd_weight_workspace(d)
-            if nbytes < 0:
-                raise RuntimeError("conv_bwd_weight_workspace: " + _lib.last_error())
-            ws = torch.empty(max(nbytes // 4, 4), device=dy.device, dtype=torch.float32)
-            dwp = _grad_dest(weight, (Cout, KH, KW, Cin)) if _ohwi_dense(weight) else None
-            if dwp is None:
-                dwp = torch.empty((Cout, KH, KW, Cin), device=dy.device, dtype=torch.float32)
-            if want_db:                                   # column sums of dY ride along in the same kernel
-                db = torch.empty(Cout, device=dy.device, dtype=torch.float32)
-            check(lib.csg_conv_bwd_weight(d, ptr(x), ptr(dpre), ptr(dwp), ptr(db), ptr(ws), nbytes, stream()),
-                  "conv_bwd_weight")
-            dw = dwp.permute(0, 3, 1, 2)
-        elif want_db:
-            rows = B * OH * OW
-            nch = _chunks(rows)
-            part = torch.empty(nch * 2 * Cout, device=dy.device, dtype=torch.float64)
-            db = torch.empty(Cout, device=dy.device, dtype=torch.float32)
-            check(lib.csg_colsum(ptr(dpre), rows, Cout, Cout, ptr(db), ptr(part), nch, stream()), "colsum")
-        if ctx.has_res and ctx.needs_input_grad[3]:
-            dres = dy                            # the residual is added AFTER the activation (igemm.hip epilogue)
+        dx, dw, db = _conv_bwd(ctx.plan, dy, x, weight, None if ctx.grad_is_pre else y, ctx.needs_input_grad[:3], ctx.packs,
+                               ctx.ut_pre)
+        dres = dy if (ctx.has_res and ctx.needs_input_grad[3]) else None     # added AFTER the activation (igemm.hip epilogue)
         return dx, dw, db, dres, None, None, None, None, None, None, None, None, None, None
+
+
+# The kernel-side layouts of a frozen weight (pack_conv_weight): fwd [Cout][KH][KW][Cin], bwd [Cin][KH][KW][Cout]; for 3x3
+# weights also the F(2x2,3x3) operands wino_fwd / wino_bwd and `cache` (the padded weight "w" and the other variants' operands)
+FrozenPacks = collections.namedtuple("FrozenPacks", "fwd bwd wino_fwd wino_bwd cache", defaults=(None, None, None))
 
 
 def pack_conv_weight(weight):
@@ -757,22 +795,21 @@ def pack_conv_weight(weight):
     Trainable weights are repacked per call instead."""
     pc = (-weight.shape[1]) % 4
     w = F.pad(weight.detach(), (0, 0, 0, 0, 0, pc)) if pc else weight.detach()
-    out = (w.permute(0, 2, 3, 1).contiguous(), w.permute(1, 2, 3, 0).contiguous())
+    fwd, bwd = w.permute(0, 2, 3, 1).contiguous(), w.permute(1, 2, 3, 0).contiguous()
     if WINO_ENABLED and w.shape[2] == 3 and w.shape[3] == 3 and w.shape[0] % 4 == 0:
         # F(2x2,3x3) operands now; the F(4x4,3x3) ones (maps >= 32 wide) are added on first use (_frozen_pack)
-        out = out + (wino_pack(w, False), wino_pack(w, True), {"w": w})
-    return out
+        return FrozenPacks(fwd, bwd, wino_pack(w, False), wino_pack(w, True), {"w": w})
+    return FrozenPacks(fwd, bwd)
 
 
 def _frozen_pack(packs, backward_data, variant):
     """The Winograd operand of a frozen weight for the kernel variant a call site runs (packs from pack_conv_weight)."""
     if variant == 2:
-        return packs[3 if backward_data else 2]
-    cache = packs[4]
+        return packs.wino_bwd if backward_data else packs.wino_fwd
     key = ("bwd" if backward_data else "fwd", variant)
-    if key not in cache:
-        cache[key] = wino_pack(cache["w"], backward_data, None, variant)
-    return cache[key]
+    if key not in packs.cache:
+        packs.cache[key] = wino_pack(packs.cache["w"], backward_data, None, variant)
+    return packs.cache[key]
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, residual=None, packs=None,
@@ -796,8 +833,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, r
     if (po and Cout + po == 4 and not pc and residual is None and packs is None and dx_range is None and in_act is None
             and x.dim() == 4 and x.is_cuda):
         # csrc/fewn.hip takes the 1..3 real output channels as they are (no zero-padded copies of weight and bias)
-        few_raw = _few_desc(x.shape[0], x.shape[2], x.shape[3], Cin, weight.shape[2], weight.shape[3], int(stride),
-                            int(padding), Cout, int(act), float(slope)) is not None
+        few_raw = plan_conv(x.shape[0], x.shape[2], x.shape[3], Cin, 4, weight.shape[2], weight.shape[3], int(stride),
+                            int(padding), int(act), float(slope), cout_real=Cout).fwd == "few"
     if pre_slope is not None and not (few_raw and x.shape[1] < 256):
         x, pre_slope = F.leaky_relu(x, float(pre_slope)), None      # no loader to fold it into: a pass of its own
     if po and not few_raw:
@@ -1177,7 +1214,9 @@ class _SpadeFused(torch.autograd.Function):
             check(lib.csg_norm_stats(ptr(x), 1, P, C, ptr(sums), ptr(part), nch, stream()), "norm_stats")
             # N > 1: the statistics travel while the gamma halves (which do not need them) are computed
             pending = csg_dist.all_reduce_stats_async(sums)
-        saved, outs, cfg, launches, pres = [x, mean, invstd], [], [], [], []
+        # per modulation, by index k: its output and saved (actv, w, gamma, y) — the joint launches finish inside the loop,
+        # the launch pairs after it
+        outs, groups, launches, plans, pres = [None] * K, [None] * K, [], [], []
         # One rank, C a multiple of 32: ONE launch per modulation (csg_wino4_conv_spade: blocks own a gamma tile and its beta
         # tile; gamma is written for the backward but never read back, the 128-channel input is staged once).  N > 1 ranks keep
         # the launch pair: the gamma halves, which need no statistics, run while the SyncBN message travels.
@@ -1190,7 +1229,11 @@ class _SpadeFused(torch.autograd.Function):
                 raise RuntimeError("spade_fused: weight %s / actv %s do not fit x %s" % (tuple(w.shape), tuple(actv.shape),
                                                                                          tuple(x.shape)))
             up = wino_pack(w, False, None, 4)
-            pres.append(_take_bwd_operand(w, B, H, W, nh, 2 * C, 3, 3, 1, 1) if ctx.needs_input_grad[4 + k * 7] else None)
+            # the joined gamma || beta convolution's backward passes (_conv_bwd on d(gamma || beta))
+            plans.append(plan_conv(B, H, W, nh, 2 * C, 3, 3, 1, 1, has_bias=True,
+                                   in_act=(ACT_LEAKY, in_slope) if in_slope is not None else None,
+                                   need=ctx.needs_input_grad[4 + 7 * k:7 + 7 * k]))
+            pres.append(_take_dx_operand(plans[k], w))
             bd = b.detach().contiguous()
             gbuf = empty_nhwc(B, C, H, W, dev)                # gamma only: beta is consumed in the epilogue that forms it
             d = _wino_desc(B, H, W, nh, C)
@@ -1200,39 +1243,34 @@ class _SpadeFused(torch.autograd.Function):
                 _wino4_audit("spade_joint", B * H * W, nh + 3 * C, up)          # actv, x read; gamma, y written
                 check(lib.csg_wino4_conv_spade(d, ptr(actv), ptr(up), ptr(bd), ptr(x), ptr(gbuf), C, ptr(mean), ptr(invstd),
                                                slope, ptr(y), stream()), "wino4_conv_spade")
-                saved += [actv, w, gbuf, y]
-                outs.append(y)
-                cfg.append((slope, in_slope, nh))
+                outs[k], groups[k] = y, [actv, w, gbuf, y]
                 continue
             _wino4_audit("spade_gamma", B * H * W, nh + C, up)
             _wino4_audit("spade_beta", B * H * W, nh + 3 * C, up)
             check(lib.csg_wino4_conv_part(d, ptr(actv), ptr(up), 0, 2 * C // 32, ptr(bd), None, None, 0, None, None, 1.0,
                                           ptr(gbuf), stream()), "wino4_conv_part(gamma)")
-            launches.append((actv, w, up, bd, gbuf, nh, slope, in_slope))
+            launches.append((k, actv, w, up, bd, gbuf, nh, slope))
         if pending is not None:
             pending.wait()
         for k in range(K if multi else 0):
             rm, rv = mods[k * 7 + 3], mods[k * 7 + 4]
             check(lib.csg_norm_finalize(ptr(sums), 1, C, count, eps, 1, ptr(mean), ptr(invstd), ptr(rm),
                                         ptr(rv if rm is not None else None), momentum, stream()), "norm_finalize")
-        for (actv, w, up, bd, gbuf, nh, slope, in_slope) in launches:
+        for (k, actv, w, up, bd, gbuf, nh, slope) in launches:
             y = torch.empty_like(x)
             d = _wino_desc(B, H, W, nh, C)
             d.y_cs = C
             check(lib.csg_wino4_conv_part(d, ptr(actv), ptr(up), C // 32, 2 * C // 32, ptr(bd[C:]), ptr(x), ptr(gbuf), C,
                                           ptr(mean), ptr(invstd), slope, ptr(y), stream()), "wino4_conv_part(beta)")
-            saved += [actv, w, gbuf, y]
-            outs.append(y)
-            cfg.append((slope, in_slope, nh))
-        ctx.save_for_backward(*saved)
-        ctx.cfg = (K, P, C, B, H, W, multi, count, tuple(cfg))
-        ctx.ut_pres = pres
+            outs[k], groups[k] = y, [actv, w, gbuf, y]
+        ctx.save_for_backward(x, mean, invstd, *[t for g in groups for t in g])
+        ctx.cfg = (K, P, C, B, H, W, multi, count, tuple(mods[k * 7 + 5] for k in range(K)))
+        ctx.plans, ctx.ut_pres = plans, pres
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dys):
-        import types
-        K, P, C, B, H, W, multi, count, cfg = ctx.cfg
+        K, P, C, B, H, W, multi, count, slopes = ctx.cfg
         sv = ctx.saved_tensors
         x, mean, invstd = sv[0], sv[1], sv[2]
         dev = x.device
@@ -1244,7 +1282,7 @@ class _SpadeFused(torch.autograd.Function):
         for k in range(K):
             actv, w, gbuf, y = sv[3 + 4 * k:7 + 4 * k]
             dgb = empty_nhwc(B, 2 * C, H, W, dev)             # d(gamma || beta): the joined convolution's incoming gradient
-            check(lib.csg_norm_apply_bwd_reduce(ptr(dys[k]), ptr(x), ptr(mean), ptr(invstd), ptr(gbuf), ptr(y), cfg[k][0], 1, P,
+            check(lib.csg_norm_apply_bwd_reduce(ptr(dys[k]), ptr(x), ptr(mean), ptr(invstd), ptr(gbuf), ptr(y), slopes[k], 1, P,
                                                 C, ptr(dgb), ptr(dsums[k]), ptr(part), nch, C, stream()), "norm_bwd_reduce")
             dgbs.append(dgb)
         dx, both, pending = None, None, None
@@ -1255,25 +1293,16 @@ class _SpadeFused(torch.autograd.Function):
         grads = [None, None, None, None]
         for k in range(K):
             actv, w, gbuf, y = sv[3 + 4 * k:7 + 4 * k]
-            slope, in_slope, nh = cfg[k]
-            base = 4 + 7 * k
-            need = ctx.needs_input_grad[base:base + 3]
-            # the joined gamma || beta convolution's backward on d(gamma || beta): _Conv2d.backward on a stand-in context
-            fake = types.SimpleNamespace(
-                saved_tensors=(actv, w, None), geom=(B, H, W, nh, 2 * C, 3, 3, 1, 1, H, W, ACT_NONE, 0.0),
-                in_act=(ACT_LEAKY, in_slope) if in_slope is not None else None, grad_is_pre=False, few=None, dx_range=None,
-                packs=None, needs_input_grad=(need[0], need[1], need[2], False), has_bias=True, has_res=False, cout_w=2 * C,
-                pre_slope=None, ut_pre=ctx.ut_pres[k])
-            r = _Conv2d.backward(fake, dgbs[k])
-            grads += [r[0], r[1], r[2], None, None, None, None]
+            need = ctx.needs_input_grad[4 + 7 * k:7 + 7 * k]
+            grads += list(_conv_bwd(ctx.plans[k], dgbs[k], actv, w, None, need, None, ctx.ut_pres[k])) + [None] * 4
         if ctx.needs_input_grad[0]:
             if pending is not None:
                 pending.wait()
             dx = torch.empty_like(x)
             two = K == 2
-            check(lib.csg_norm_apply_bwd_dx(ptr(dys[0]), ptr(x), ptr(mean), ptr(invstd), ptr(sv[5]), cfg[0][0], ptr(both), count,
+            check(lib.csg_norm_apply_bwd_dx(ptr(dys[0]), ptr(x), ptr(mean), ptr(invstd), ptr(sv[5]), slopes[0], ptr(both), count,
                                             1, P, C, ptr(dx), ptr(dys[1]) if two else None, ptr(sv[9]) if two else None,
-                                            cfg[1][0] if two else 1.0, ptr(dgbs[0]), ptr(dgbs[1]) if two else None, C, stream()),
+                                            slopes[1] if two else 1.0, ptr(dgbs[0]), ptr(dgbs[1]) if two else None, C, stream()),
                   "norm_bwd_dx")
             grads[0] = dx
         return tuple(grads)
@@ -1289,7 +1318,6 @@ class _SpadeJoined(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, actv, w, b, running_mean, running_var, pad, slope, in_slope, eps, momentum, sync):
-        import types
         x = nhwc(_f32(x))
         B, C, H, W = x.shape
         P = B * H * W
@@ -1310,12 +1338,12 @@ class _SpadeJoined(torch.autograd.Function):
             sums = torch.empty(2 * C, device=dev, dtype=torch.float64)
             check(lib.csg_norm_stats(ptr(x), 1, P, C, ptr(sums), ptr(part), nch, stream()), "norm_stats")
             pending = csg_dist.all_reduce_stats_async(sums)
-        # the joined convolution through _Conv2d's own forward on a stand-in context (its saved tensors are kept for the
-        # backward below)
-        fake = types.SimpleNamespace(needs_input_grad=(True, True, True, False))
-        fake.save_for_backward = lambda *t: setattr(fake, "saved_tensors", t)
-        in_act = (ACT_LEAKY, float(in_slope)) if in_slope is not None else None
-        gb = _Conv2d.forward(fake, actv, w, b, None, 1, int(pad), ACT_NONE, 0.0, None, None, in_act, False, None, None)
+        # the joined convolution, planned for all three gradients whatever this call needs (the backward-data operand is
+        # taken now, as for any convolution whose input needs a gradient)
+        actv = nhwc(_f32(actv))
+        ctx.plan = plan_conv(B, H, W, actv.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, int(pad), has_bias=b is not None,
+                             in_act=(ACT_LEAKY, float(in_slope)) if in_slope is not None else None, need=(True, True, True))
+        gb, ctx.ut_pre = _conv_fwd(ctx.plan, actv, w, b, None, None)
         if pending is not None:
             pending.wait()
         if multi:
@@ -1325,11 +1353,7 @@ class _SpadeJoined(torch.autograd.Function):
         y = torch.empty_like(x)
         check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb), slope, 1, P, C, ptr(y), None, 1.0, None, stream()),
               "norm_apply_fwd")
-        cx, cw, cy = fake.saved_tensors
-        ctx.save_for_backward(x, gb, mean, invstd, cx, cw)
-        fake.save_for_backward = None
-        fake.saved_tensors = None
-        ctx.conv = fake
+        ctx.save_for_backward(x, gb, mean, invstd, actv, w)
         ctx.cfg = (P, C, slope, multi, count)
         return y
 
@@ -1346,10 +1370,7 @@ class _SpadeJoined(torch.autograd.Function):
         check(lib.csg_norm_apply_bwd_reduce(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), None, slope, 1, P, C, ptr(dgb),
                                             ptr(dsums), ptr(part), nch, 2 * C, stream()), "norm_bwd_reduce")
         pending = csg_dist.all_reduce_stats_async(dsums) if (multi and ctx.needs_input_grad[0]) else None
-        fake = ctx.conv
-        fake.saved_tensors = (cx, cw, None)
-        fake.needs_input_grad = (ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3], False)
-        r = _Conv2d.backward(fake, dgb)
+        r = _conv_bwd(ctx.plan, dgb, cx, cw, None, ctx.needs_input_grad[1:4], None, ctx.ut_pre)
         dx = None
         if ctx.needs_input_grad[0]:
             if pending is not None:

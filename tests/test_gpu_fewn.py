@@ -70,18 +70,6 @@ def test_few_output_conv_vs_torch(ops, case):
     assert torch.equal(again[1], outs[True][1][1]) and torch.equal(again[2], outs[True][1][2])
 
 
-def test_unsupported_shapes_are_declined(ops):
-    from canonicalsg2im_amd._lib import FewDesc, lib
-    d = FewDesc()
-    d.B, d.IH, d.IW, d.Cin, d.x_cs, d.KH, d.KW, d.pad, d.cout_real, d.act, d.slope = 1, 8, 8, 64, 64, 5, 5, 2, 1, 0, 0.0
-    assert lib.csg_conv_few_supported(d) == 0                       # 5x5
-    d.KH = d.KW = 4
-    d.cout_real = 3
-    assert lib.csg_conv_few_supported(d) == 0                       # 16 taps x 3 outputs: registers
-    d.cout_real, d.Cin, d.x_cs = 1, 48, 48
-    assert lib.csg_conv_few_supported(d) == 0                       # Cin not a power-of-two multiple of 32
-
-
 def test_conv_img_with_the_leaky_relu_in_its_loaders():
     """`conv_img(leaky_relu(x, 0.2))` of the generator (reference generator.py:123-124) with the activation folded into
     the few-output kernels' forward / weight-gradient loaders and its derivative into the backward-data epilogue

@@ -163,15 +163,3 @@ def test_conv1x1_on_the_gemm_kernels_vs_torch(ops):
     for name, a, b in zip(("dx", "dw"), got, ref_g):
         err = (a.double().cpu() - b).abs().max().item()
         assert err <= 2e-5 * b.abs().max().item() + 1e-6, "%s: %g at scale %g" % (name, err, b.abs().max().item())
-
-
-def test_default_rule_sends_the_narrow_shortcuts_to_the_gemm_kernels(ops):
-    """Mode "auto" (the default): N <= 256 <= K with at least 256 tiles — conv_s of the 64 x 64 and 128 x 128 residual blocks
-    at batch 16; the graph encoder's wide linears and everything small stay on the implicit-GEMM kernel."""
-    old, ops.GEMM_MODE = ops.GEMM_MODE, "auto"
-    try:
-        assert ops.gemm_eligible(16 * 128 * 128, 128, 256) and ops.gemm_eligible(16 * 64 * 64, 256, 512)
-        assert not ops.gemm_eligible(96000, 512, 384) and not ops.gemm_eligible(96000, 1152, 512)
-        assert not ops.gemm_eligible(768, 128, 512) and not ops.gemm_eligible(16 * 256 * 256, 64, 128)
-    finally:
-        ops.GEMM_MODE = old
