@@ -824,6 +824,10 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=ACT_NONE, slope=0.0, r
         raise NotImplementedError("conv2d: a fused residual needs act == ACT_NONE")
     if packs is not None and po:
         raise RuntimeError("conv2d: packed weights need an output-channel count that is a multiple of 4")
+    if packs is not None and pc and weight.requires_grad and torch.is_grad_enabled():
+        # the packed layouts carry the input channels zero-padded to a multiple of 4: the weight gradient would come
+        # back with that padded width, not the weight's
+        raise RuntimeError("conv2d: packs= needs a frozen weight when the input channels (%d) are padded" % Cin)
     if pc:
         if x.shape[1] == Cin:                  # an already padded input (e.g. the 4-channel object crops) is used as is
             x = F.pad(x, (0, 0, 0, 0, 0, pc))
