@@ -8,9 +8,9 @@
 //   k_gemm_tn   dW[N][K] = sum_m dY[m][N]^T . X[m][K]      weight gradient (+ column sums of dY = bias gradient)
 //
 // Both: 128 x 128 output tiles, four waves of 64 x 64 (2 x 2 v_mfma_f32_32x32x2_f32 accumulators = 64 registers), two
-// blocks per CU, two 32 KB LDS stages filled by LDS-DMA (buffer_load_dwordx4 ... lds: no VGPRs, no ds_write, no VALU
-// beside the fp32 MFMAs, which share their issue slot with it on this chip — DESIGN 4.1b).
-// * nt: both operands have the reduction index contiguous.  A stage is 32 k = eight 16-byte slots per row; the DMA
+// 16 KB LDS stages filled by LDS-DMA (buffer_load_dwordx4 ... lds: no VGPRs, no ds_write, no VALU beside the fp32 MFMAs,
+// which share their issue slot with it on this chip — DESIGN 4.1b), four blocks per CU.
+// * nt: both operands have the reduction index contiguous.  A stage of 32 k is eight 16-byte slots per row; the DMA
 //   writes 1 KB per wave-instruction linearly (8 rows), so the XOR swizzle that makes the ds_read_b128 of the MFMA
 //   operands conflict-free is applied to the SOURCE address of each lane: LDS slot s of row r holds the row's k-slot
 //   s ^ ((r >> 1) & 7) (rows are 128 B, a ds_read_b128 is served in groups of 16 lanes whose rows differ in exactly
@@ -19,8 +19,6 @@
 // * tn: the reduction index (rows m) is the strided one; tiles are staged row by row ([32 m][128 n], [32 m][128 k]) and
 //   read with ds_read_b32 (32 consecutive floats per half-wave: conflict-free), one read per MFMA.  The rows are cut
 //   into slices, one slab per slice, summed in a fixed order (bit-reproducible, csg_reduce.h).
-#include <stdlib.h>
-
 #include "csg_buffer.h"
 #include "csg_common.h"
 #include "csg_reduce.h"
@@ -63,7 +61,7 @@ __device__ __forceinline__ int gm_xcd_remap(int bid, int nblk) {   // consecutiv
 // NTW = 32-column accumulators per wave: 2 -> 128 x 128 tiles, 1 -> 128 x 64 (layers with at most 64 outputs: conv_s of
 // the last residual block; a half-empty 128-wide tile would double their matrix work).
 // BK = reduction depth of a stage (32 or 16), NBUF = LDS stages in the ring: the DMA of stage s + NBUF - 1 is issued at the top
-// of stage s.  (BK, NBUF) = (32, 2): 64 KB, two blocks per CU; (16, 2): 32 KB, four blocks; (16, 3): 48 KB, three; (16, 4): 64 KB, two.
+// of stage s.  Launched: (BK, NBUF) = (16, 2) on 128-wide tiles (32 KB, four blocks per CU), (32, 2) on 64-wide ones (48 KB).
 // Every stage issues the same number of DMAs (past the end of K all their lanes are out of range and write zeros into a
 // buffer nobody reads), so the wait for "stage s + 1 has landed" is a constant vmcnt.
 template <int NTW, int BK, int NBUF, bool GATED>
@@ -256,11 +254,13 @@ __global__ __launch_bounds__(256, GATED ? 2 : (BK == 16 ? 8 : 4) / NBUF) void k_
 }
 
 // ------------------------------------------------------------------------------------------------ dW = dY^T . X
-// RS = rows (reduction steps) per stage: 32 (64 KB of LDS, two blocks per CU) or 16 (32 KB, four blocks per CU)
+// RS = rows (reduction steps) per stage: 16 (32 KB of LDS, four blocks per CU) measured 2-4 % ahead of 32 (64 KB, two
+// blocks per CU)
 template <int RS>
-__global__ __launch_bounds__(256, RS == 16 ? 4 : 2) void k_gemm_tn(GemmTnParams p, const float* __restrict__ dY,
-                                                                   const float* __restrict__ X, float* __restrict__ out,
-                                                                   float* __restrict__ dbout) {
+__global__ __launch_bounds__(256, 4) void k_gemm_tn(GemmTnParams p, const float* __restrict__ dY,
+                                                    const float* __restrict__ X, float* __restrict__ out,
+                                                    float* __restrict__ dbout) {
+  static_assert(RS == 16, "16 rows per stage");
   constexpr int ND = RS / 8;                          // DMA instructions per thread, operand and stage
   constexpr int HALF = RS * 128, STG = 2 * HALF;      // floats: one operand's tile, a stage
   constexpr int G = RS / 8;                           // groups of four k2-steps (eight rows) per stage
@@ -454,25 +454,12 @@ int csg_gemm_nt(const csg_gemm_desc* d, const float* a, const float* bw, const f
   p.act = d->act, p.slope = d->slope, p.gate_slope = d->gate_slope;
   const bool narrow = d->N <= 64;                      // 128 x 64 tiles
   p.nnb = (int)cdiv(d->N, narrow ? 64 : 128);
-  p.nstage = (int)cdiv(d->K, 32);
   const unsigned grid = (unsigned)(cdiv(d->M, 128) * p.nnb);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_gemm_nt<2, 32, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)k_gemm_nt<2, 32, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)k_gemm_tn<32>, hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES);
-    attr = true;
-  }
   ProfScope ps(K_GEMM_NT, 2.0 * (double)d->M * (double)d->N * (double)d->K, s);
-  // (BK, NBUF) by CSG_GEMM_CFG = 322 | 162 — developer knob, see the kernel's header
-  static const int cfg_env = getenv("CSG_GEMM_CFG") ? atoi(getenv("CSG_GEMM_CFG")) : 0;
-  // measured (tools/gemm_probe.py, M = 96 000): four 32 KB blocks per CU beat two 64 KB ones by 2-4 % on 128-wide tiles; a
-  // deeper ring — (16, 3) three blocks, (16, 4) two blocks — equals the two-buffer form at the same occupancy: the DMA latency
-  // is not what is exposed.  The 64-wide tiles of N <= 64 prefer the long stages (84 vs 72 TFLOP/s at K = 128).
-  const int cfg = cfg_env ? cfg_env : (narrow ? 322 : 162);
-  // only these two (BK, NBUF) pairs are instantiated; any other value would size the LDS for a kernel that is not launched
-  CSG_REQUIRE(cfg == 162 || cfg == 322, CSG_E_UNSUPPORTED, "csg_gemm_nt: CSG_GEMM_CFG=%d (only 162 and 322 are built)", cfg);
-  const int bk = cfg / 10, nbuf = cfg % 10;
+  // (BK, NBUF), measured (tools/gemm_probe.py, M = 96 000): four 32 KB blocks per CU beat two 64 KB ones by 2-4 % on 128-wide
+  // tiles; a deeper ring — (16, 3) three blocks, (16, 4) two blocks — equals the two-buffer form at the same occupancy: the DMA
+  // latency is not what is exposed.  The 64-wide tiles of N <= 64 prefer the long stages (84 vs 72 TFLOP/s at K = 128).
+  const int bk = narrow ? 32 : 16, nbuf = 2;
   p.nstage = (int)cdiv(d->K, bk);
   const size_t shm = (size_t)nbuf * (128 + (narrow ? 64 : 128)) * bk * 4;
 #define GM_NT(NTW, BK, NBUF)                                                                                     \
@@ -482,11 +469,7 @@ int csg_gemm_nt(const csg_gemm_desc* d, const float* a, const float* bw, const f
     else                                                                                                         \
       CSG_LAUNCH((k_gemm_nt<NTW, BK, NBUF, false>), dim3(grid), dim3(256), shm, s, p, a, bw, bias, gate, y);     \
   } while (0)
-  if (cfg == 162) {
-    if (narrow) GM_NT(1, 16, 2); else GM_NT(2, 16, 2);
-  } else {
-    if (narrow) GM_NT(1, 32, 2); else GM_NT(2, 32, 2);
-  }
+  if (narrow) GM_NT(1, 32, 2); else GM_NT(2, 16, 2);
 #undef GM_NT
   return check_launch("k_gemm_nt");
 }
@@ -520,23 +503,10 @@ int csg_gemm_tn(int64_t M, int64_t N, int64_t K, const float* dy, int64_t ldy, c
   p.M = (int)M, p.N = (int)N, p.K = (int)K, p.ldy = (int)ldy, p.ldx = (int)ldx;
   p.nnb = (int)cdiv(N, 128), p.nkb = (int)cdiv(K, 128);
   p.nsplit = ns, p.rows_per = per, p.direct = ns == 1 ? 1 : 0;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_gemm_nt<2, 32, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)k_gemm_nt<2, 32, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)k_gemm_tn<32>, hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES);
-    attr = true;
-  }
   float* slabs = ns > 1 ? workspace : dw;
   float* dbs = db == nullptr ? nullptr : (ns > 1 ? workspace + (int64_t)ns * N * K : db);
   ProfScope ps(K_GEMM_TN, 2.0 * (double)M * (double)N * (double)K, s);
-  // rows per stage: 16 (four 32 KB blocks per CU) measured 2-4 % ahead of 32 (two 64 KB blocks); developer knob
-  static const int rs = getenv("CSG_GEMM_TN_ROWS") ? atoi(getenv("CSG_GEMM_TN_ROWS")) : 16;
-  CSG_REQUIRE(rs == 16 || rs == 32, CSG_E_UNSUPPORTED, "csg_gemm_tn: CSG_GEMM_TN_ROWS=%d (only 16 and 32 are built)", rs);
-  if (rs == 16)
-    CSG_LAUNCH(k_gemm_tn<16>, dim3((unsigned)(p.nnb * p.nkb * ns)), dim3(256), GM_LDS_BYTES / 2, s, p, dy, x, slabs, dbs);
-  else
-    CSG_LAUNCH(k_gemm_tn<32>, dim3((unsigned)(p.nnb * p.nkb * ns)), dim3(256), GM_LDS_BYTES, s, p, dy, x, slabs, dbs);
+  CSG_LAUNCH(k_gemm_tn<16>, dim3((unsigned)(p.nnb * p.nkb * ns)), dim3(256), GM_LDS_BYTES / 2, s, p, dy, x, slabs, dbs);
   if (ns > 1) launch_slab_reduce(slabs, N * K, dw, dbs, db != nullptr ? N : 0, db, ns, s);
   return check_launch("k_gemm_tn");
 }

@@ -257,8 +257,8 @@ __global__ __launch_bounds__(256) void k_gather_concat_fwd(const float* __restri
 // inside a workgroup 256/LPE edge groups of LPE lanes work on different edges, a lane owns one float4
 // of the D columns, 4 edges are in flight per lane.  Group partials are combined through LDS and
 // segment partials by k_rowsum_finish, both in a fixed order: results are bit-reproducible run to run.
-#define ROWSUM_SEG_DEFAULT 128       // edges per segment in edge-balanced mode (CSG_ROWSUM_SEG: developer knob; 64 / 128 / 256
-                                     // measured 112 / 102 / 135 us per forward launch on config C5)
+#define ROWSUM_SEG_EDGES 128         // edges per segment in edge-balanced mode (64 / 128 / 256 measured 112 / 102 / 135 us
+                                     // per forward launch on config C5)
 template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_csr_rowsum(const float* __restrict__ src, const float* __restrict__ conf,
                                                      const uint8_t* __restrict__ valid,
@@ -461,14 +461,10 @@ static inline int rowsum_lpe(int64_t D) {
 }
 // segments per image in edge-balanced mode (0 = sparse graph: one workgroup per row).  Dense mode is chosen
 // from the PADDED triplet count, so a batch whose longest sample is dense uses it for every sample.
-static inline int rowsum_seg() {
-  static const int seg = getenv("CSG_ROWSUM_SEG") ? atoi(getenv("CSG_ROWSUM_SEG")) : ROWSUM_SEG_DEFAULT;
-  return seg >= 16 ? seg : ROWSUM_SEG_DEFAULT;
-}
 static inline int64_t rowsum_nseg(int64_t O, int64_t T) {
   const int64_t deg = O > 0 ? (2 * T + O - 1) / O : 0;
   if (deg <= 48 || O > 1024) return 0;
-  return cdiv(2 * T, rowsum_seg()) + O;
+  return cdiv(2 * T, ROWSUM_SEG_EDGES) + O;
 }
 // workspace: partial rows (+ counts when weighted) and the (first segment, segments) pair of every row
 static inline int64_t rowsum_ws_bytes(int64_t B, int64_t O, int64_t T, int64_t D, bool weighted) {
@@ -711,8 +707,8 @@ int csg_gather_concat_bwd(const float* dcat, const int32_t* row_ptr, const int32
     int32_t* seg_info = ns ? (int32_t*)(part + B * ns * Din) : nullptr;
     CSG_LAUNCH(k_csr_rowsum<false>, dim3((unsigned)(ns ? ns : O), (unsigned)B), dim3(256), 0, s, dcat,
                        (const float*)nullptr, (const uint8_t*)nullptr, row_ptr, col, (int)O, (int)T, (int)Din,
-                       (int)(2 * Din + Dp), 0, (int)(Din + Dp), rowsum_lpe(Din), (int)ns, rowsum_seg(), dobj, (float*)nullptr, part,
-                       (float*)nullptr, seg_info);
+                       (int)(2 * Din + Dp), 0, (int)(Din + Dp), rowsum_lpe(Din), (int)ns, ROWSUM_SEG_EDGES, dobj, (float*)nullptr,
+                       part, (float*)nullptr, seg_info);
     if (ns)
       CSG_LAUNCH(k_rowsum_finish<false>, dim3((unsigned)(B * O)), dim3(1024), 0, s, (const float*)part,
                          (const float*)nullptr, (const int32_t*)seg_info, (int)O, (int)Din, rowsum_lpe(Din), (int)ns, dobj,
@@ -749,7 +745,7 @@ int csg_segment_avg_fwd(const float* h, const float* conf, const uint8_t* valid,
   int32_t* seg_info = ns ? (int32_t*)(part_cnt + B * ns) : nullptr;
   CSG_LAUNCH(k_csr_rowsum<true>, dim3((unsigned)(ns ? ns : O), (unsigned)B), dim3(256), 0, s, h, conf, valid,
                      row_ptr, col, (int)O, (int)T, (int)H, (int)(2 * H + Dp), 0, (int)(H + Dp), rowsum_lpe(H), (int)ns,
-                     rowsum_seg(), pooled, cnt, part, part_cnt, seg_info);
+                     ROWSUM_SEG_EDGES, pooled, cnt, part, part_cnt, seg_info);
   if (ns)
     CSG_LAUNCH(k_rowsum_finish<true>, dim3((unsigned)(B * O)), dim3(1024), 0, s, (const float*)part,
                        (const float*)part_cnt, (const int32_t*)seg_info, (int)O, (int)H, rowsum_lpe(H), (int)ns, pooled,

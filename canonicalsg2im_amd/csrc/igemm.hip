@@ -811,15 +811,12 @@ static void fwd_plan(IgemmParams& p) {
   const int blocks = p.mtiles * p.ntiles;
   int ks = 1;
   if (blocks < 1024 && nkt >= 16 && p.d.Cout % 4 == 0) ks = pick_split(blocks, nkt, 8, 64);
-  static const int force = getenv("CSG_IGEMM_KSPLIT") ? atoi(getenv("CSG_IGEMM_KSPLIT")) : 0;   // experiments only
-  if (force > 0 && p.d.Cout % 4 == 0) ks = force < nkt ? force : nkt;
   p.kt_per_split = (nkt + ks - 1) / ks;
   p.ksplit = (nkt + p.kt_per_split - 1) / p.kt_per_split;
   // Grids a little above a multiple of the 512 resident blocks (PatchGAN: 580 and 529 tiles): splitting EVERY tile
   // along K pays slab traffic for all of them.  Instead the whole rounds run unsplit and only the m-tiles of the last,
-  // partly filled round are split, finely enough to fill that round.
-  static const int tail_on = getenv("CSG_IGEMM_TAIL_SPLIT") ? atoi(getenv("CSG_IGEMM_TAIL_SPLIT")) : 1;
-  if (tail_on && force == 0 && blocks > 512 && blocks < 4096 && nkt >= 16 && p.d.Cout % 4 == 0) {
+  // partly filled round are split, finely enough to fill that round (the uniform split measured 0.7 ms/step slower).
+  if (blocks > 512 && blocks < 4096 && nkt >= 16 && p.d.Cout % 4 == 0) {
     const int rounds = blocks / 512;                                  // whole rounds
     int full_mt = (rounds * 512) / p.ntiles;                          // m-tiles that fit in them
     const int tail_tiles = (p.mtiles - full_mt) * p.ntiles;

@@ -12,10 +12,9 @@
 //     M_p = sum_cin V_p U_p  for the 16 positions p = (xi, nu)   <- 16 independent GEMMs on v_mfma_f32_32x32x2_f32
 //     Y = A^T M A   (2x2 outputs; bias / activation / residual fused behind it)
 //
-// Work decomposition.  A block owns 64 tiles (TW x TH, 128..256 output pixels of one image) x 64 output channels
-// x all 16 positions.  Wave w owns the four positions of row xi = w: 4 nu x 2 tile-groups x 2 channel-groups =
-// 16 accumulators of 32x32 (256 VGPRs; one wave per SIMD, one block per CU — the fp32 MFMA issues back to back
-// from a single wave, it needs no second wave to hide latency).
+// Work decomposition.  A block owns 32 tiles (TW x TH, 64..128 output pixels of one image) x 64 output channels
+// x all 16 positions.  Wave w owns the four positions of row xi = w: 4 nu x 2 channel-groups = 8 accumulators of
+// 32x32 (128 VGPRs), so two blocks are resident per CU (two waves per SIMD).
 //   * B operand (U): every (position, channel-group) is read by exactly ONE wave, so it never goes through LDS:
 //     k_wino_pack stores U in the MFMA operand order [xi][nu][cout/32][cin/8][lane][4] and a lane fetches its
 //     operands of four consecutive MFMAs with one coalesced 16-byte load (L2 resident: 16*Cin*Cout*4 B per layer).
@@ -23,8 +22,8 @@
 //     even/odd columns de-interleaved and 18-word pixel rows, so that the eight ds_read_b64 a lane needs for its
 //     tile (two rows x four columns — row xi of B^T d touches two input rows) are bank-conflict free; the
 //     transform is 8 VALU adds per 4 MFMA operands.
-//   * K loop: 16 channels per LDS stage (128 MFMAs per wave), double-buffered, global loads of stage s+1 issued
-//     before the MFMAs of stage s and written to LDS after them: one barrier per 8192 matrix-pipe cycles.
+//   * K loop: 16 channels per LDS stage (64 MFMAs per wave), double-buffered, global loads of stage s+1 issued
+//     before the MFMAs of stage s and written to LDS after them: one barrier per stage.
 //   * Epilogue: each wave reduces its row over nu (M A), the four rows meet in LDS (A^T .), 16-byte stores.
 #include <stddef.h>
 #include <stdlib.h>
@@ -47,7 +46,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 struct WinoParams {
   int B, H, W, Cin, x_cs, Cout, y_cs;
-  int TW, TH;          // tiles per block region (TW * TH == 64)
+  int TW, TH;          // tiles per block region (TW * TH == 32)
   int tbx, tby;        // block regions per image
   int nblocks;         // ceil(Cout / 64)
   int RS;              // LDS row stride in words
@@ -56,9 +55,8 @@ struct WinoParams {
   float slope;
   float gate_slope;    // epilogue gate: y *= (gate > 0 ? 1 : gate_slope)
   int nstage;          // ceil(Cin / 16)
-  int variant;         // 1: 64 tiles per block (k_wino_conv), 2: 32 tiles per block, two blocks per CU (k_wino_conv2)
-  int ntb;             // k_wino_conv2: 32-channel groups per block (2, or 1 when Cout <= 32)
-  int ksplit, sps;     // k_wino_conv2: input-channel stages cut into ksplit ranges of sps stages, one output slab each
+  int ntb;             // 32-channel groups per block (2, or 1 when Cout <= 32)
+  int ksplit, sps;     // input-channel stages cut into ksplit ranges of sps stages, one output slab each
   long long slab;      // floats per slab (B*H*W*y_cs)
 };
 
@@ -169,35 +167,39 @@ constexpr int wn_row_stride(int TW) {
   return C * WN_PS;
 }
 
-// Every VALU instruction of the single wave per SIMD takes issue time away from the fp32 MFMAs (measured: 57 % matrix
-// pipe busy with 2 VALU per MFMA in the loop, profiles/archive/r02_pmc_wino.md), so the loop body carries none that is not
-// arithmetic of the transform: the tile geometry is a template parameter (LDS offsets become instruction immediates),
-// the per-stage advance of the global loads rides in the SCALAR offset of the buffer instructions, and the stage loop
-// is unrolled by two so that the LDS buffer is a compile-time constant.
-template <int TW>
-__global__ __launch_bounds__(256, 1) void k_wino_conv(WinoParams p, const float* __restrict__ x,
-                                                       const float4* __restrict__ up, const float* __restrict__ bias,
-                                                       const float* __restrict__ res, const float* __restrict__ gate,
-                                                       float* __restrict__ y) {
-  constexpr int TH = 64 / TW;
+// Two blocks per CU: the partner wave's MFMAs run underneath every VMEM / LDS / VALU issue of a wave, and one block's
+// epilogue under the other block's main loop.  (The first form, 64 tiles per block with one wave per SIMD, kept the
+// matrix pipe 55 % busy and lost: 202 vs 236 TFLOP/s on the dominant shape, profiles/HISTORY.md.)  Every VALU
+// instruction beside the MFMAs takes issue time from them (57 % matrix pipe busy with 2 VALU per MFMA), so the loop
+// body carries none that is not arithmetic of the transform: the tile geometry is a template parameter (LDS offsets become
+// instruction immediates), the per-stage advance of the global loads rides in the SCALAR offset of the buffer
+// instructions, and the stage loop is unrolled by two so that the LDS buffer is a compile-time constant.  To fit 256
+// registers the weights are single-buffered: the eight operands of one channel group are reloaded (for the next
+// k-oct) right after their last MFMA, while the other group's 16 MFMAs run.
+template <int TW, int NTB = 2>     // NTB: 32-channel groups per block (1 for layers with <= 32 output channels)
+__global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float* __restrict__ x,
+                                                        const float4* __restrict__ up, const float* __restrict__ bias,
+                                                        const float* __restrict__ res, const float* __restrict__ gate,
+                                                        float* __restrict__ y) {
+  constexpr int TH = 32 / TW;
   constexpr int R = 2 * TH + 2, C = 2 * TW + 2;
   constexpr int RS = wn_row_stride(TW);
-  constexpr int BUFW = R * RS + 16;              // words per input buffer (+ a 16-word dump slot)
-  constexpr int HALF = (C / 2) * WN_PS;          // odd columns live HALF words after the even ones
-  constexpr int NLD = (R * C * 4 + 255) / 256;   // float4 global loads per thread and stage
-  constexpr int RPG = 32 / TW;                   // tile rows per tile group
+  constexpr int BUFW = R * RS + 16;
+  constexpr int HALF = (C / 2) * WN_PS;
+  constexpr int NLD = (R * C * 4 + 255) / 256;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-  // ---- block -> (image, region, channel block); channel blocks of one region are adjacent (same XCD: input reuse)
   int bid = wn_xcd_remap(blockIdx.x, gridDim.x);
+  const int split = bid % p.ksplit;              // splits of one tile are neighbours: they share the input in L2
+  bid /= p.ksplit;
   const int nb = bid % p.nblocks;
   bid /= p.nblocks;
   const int bx = bid % p.tbx;
   bid /= p.tbx;
   const int by = bid % p.tby;
   const int img = bid / p.tby;
-  const int X0 = bx * 2 * TW, Y0 = by * 2 * TH;              // first output pixel of the region
+  const int X0 = bx * 2 * TW, Y0 = by * 2 * TH;
 
   // ---- staging plan of this thread (k-invariant): byte offset of channel 0 in x (CSG_OOB_OFF: zero padding or no
   // work) and LDS word offset (threads beyond the region write a dump slot at the end of the buffer).  All loads go
@@ -236,311 +238,17 @@ __global__ __launch_bounds__(256, 1) void k_wino_conv(WinoParams p, const float*
     }
   };
 
-  // ---- this lane's tile inside each of the two tile groups, and the two input rows its wave combines
+  // ---- this lane's tile, and the two input rows its wave combines
   const int j = lane & 31, h = lane >> 5;
   const int tx = j % TW, tyl = j / TW;
   // row xi of B^T d:  xi=0: d0 - d2;  1: d1 + d2;  2: d2 - d1;  3: d1 - d3
   const int ia = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
   const int ib = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
   const float sgn = wave == 1 ? 1.0f : -1.0f;
-  // word offsets of (row a / row b, column 0, channel pair h) for tile group 0; group 1 is 2*RPG rows further down
   const float* pa0 = smem + (2 * tyl + ia) * RS + tx * WN_PS + 2 * h;
   const float* pb0 = smem + (2 * tyl + ib) * RS + tx * WN_PS + 2 * h;
 
   // ---- packed weights of this wave: [xi = wave][nu][nt32][q][lane], byte offsets; q rides in the scalar offset
-  unsigned uoff[4][2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int nt32 = nb * 2 + nt;
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu)
-      uoff[nu][nt] = nt32 < p.NT32 ? (unsigned)((((wave * 4 + nu) * p.NT32 + nt32) * p.Q8) * 64 + lane) * 16u : CSG_OOB_OFF;
-  }
-  csg_f32x4 ua[4][2], ub[4][2];
-  auto load_u = [&](csg_f32x4 (&u)[4][2], int q) {
-    const int qq = min(q, p.Q8 - 1);             // the prefetch past the end re-reads the last block (scalar op)
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) u[nu][nt] = csg_buf_load_x4(rsU, (int)uoff[nu][nt], qq * 1024, 0);
-  };
-
-  f32x16 acc[4][2][2];
-#pragma unroll
-  for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[nu][mt][nt][e] = 0.f;
-
-  // One "group" = one k-oct (8 channels) of one tile group: 16 ds_read_b64 -> 32 VALU (B^T d B) -> 32 MFMAs.
-  // The loop below is software-pipelined by hand over groups: while the MFMAs of group g run, the LDS reads of
-  // group g+1 are already issued and its transform is slotted between the last MFMAs (sched_group_barrier), so the
-  // single wave per SIMD keeps the matrix pipe fed.
-  struct RawG {
-    float2 a[2][4], b[2][4];                     // [channel pair][column] of input rows ia / ib
-  };
-  auto read_group = [&](int bufsel, int o, int mt, RawG& r) {     // every offset below is an immediate
-    const float* pa = pa0 + bufsel * BUFW + mt * (2 * RPG * RS) + 8 * o;
-    const float* pb = pb0 + bufsel * BUFW + mt * (2 * RPG * RS) + 8 * o;
-#pragma unroll
-    for (int cp = 0; cp < 2; ++cp)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {              // column c of the 4x4 patch: even/odd halves, then + c>>1 pixels
-        const int co = (c & 1) * HALF + (c >> 1) * WN_PS + 4 * cp;
-        r.a[cp][c] = *(const float2*)(pa + co);
-        r.b[cp][c] = *(const float2*)(pb + co);
-      }
-  };
-  auto transform = [&](const RawG& r, float2 (&v)[4][2]) {
-#pragma unroll
-    for (int cp = 0; cp < 2; ++cp) {
-      float2 q[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) q[c] = make_float2(r.a[cp][c].x + sgn * r.b[cp][c].x, r.a[cp][c].y + sgn * r.b[cp][c].y);
-      v[0][cp] = make_float2(q[0].x - q[2].x, q[0].y - q[2].y);
-      v[1][cp] = make_float2(q[1].x + q[2].x, q[1].y + q[2].y);
-      v[2][cp] = make_float2(q[2].x - q[1].x, q[2].y - q[1].y);
-      v[3][cp] = make_float2(q[1].x - q[3].x, q[1].y - q[3].y);
-    }
-  };
-  auto mfma_group = [&](int mt, const csg_f32x4 (&u)[4][2], const float2 (&v)[4][2]) {
-    // k-step outermost: consecutive MFMAs go to 8 different accumulators
-    // weights as the first operand: D[i = channel][j = tile] -> a lane holds one tile and runs of 4 channels
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-        acc[nu][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[nu][nt].x, v[nu][0].x, acc[nu][mt][nt], 0, 0, 0);
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-        acc[nu][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[nu][nt].y, v[nu][0].y, acc[nu][mt][nt], 0, 0, 0);
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-        acc[nu][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[nu][nt].z, v[nu][1].x, acc[nu][mt][nt], 0, 0, 0);
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-        acc[nu][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[nu][nt].w, v[nu][1].y, acc[nu][mt][nt], 0, 0, 0);
-  };
-  // issue order of one pipeline step: the 16 LDS reads, 16 MFMAs back to back, then MFMA / 2 VALU alternating
-#define WN_STEP_SCHED()                                   \
-  __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);     \
-  __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);     \
-  _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) {     \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    \
-    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);    \
-  }
-
-  // one stage = 16 channels out of buffer `bufsel` (compile-time), entered with v0 = transform of (s, oct 0, group 0)
-  RawG raw;
-  float2 v0[4][2], v1[4][2];
-  auto stage = [&](int s, auto bufsel_tag) {
-    constexpr int bufsel = decltype(bufsel_tag)::value;
-    load_stage(s + 1);
-    load_u(ub, 2 * s + 1);
-    __builtin_amdgcn_sched_barrier(0);           // the global loads of the next stage lead the trip
-
-    read_group(bufsel, 0, 1, raw);
-    mfma_group(0, ua, v0);
-    transform(raw, v1);
-    WN_STEP_SCHED();
-    __builtin_amdgcn_sched_barrier(0);
-
-    read_group(bufsel, 1, 0, raw);
-    mfma_group(1, ua, v1);
-    transform(raw, v0);
-    WN_STEP_SCHED();
-    __builtin_amdgcn_sched_barrier(0);
-
-    load_u(ua, 2 * s + 2);
-    read_group(bufsel, 1, 1, raw);
-    mfma_group(0, ub, v0);
-    transform(raw, v1);
-    __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);
-    WN_STEP_SCHED();
-    __builtin_amdgcn_sched_barrier(0);
-
-    store_stage(smem + (bufsel ^ 1) * BUFW);     // the buffer every wave finished reading one trip ago
-    __syncthreads();
-    read_group(bufsel ^ 1, 0, 0, raw);           // first group of the next stage, under the last MFMAs of this one
-    mfma_group(1, ub, v1);
-    transform(raw, v0);
-    WN_STEP_SCHED();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  // ---- K loop
-  load_stage(0);
-  load_u(ua, 0);
-  store_stage(smem);
-  __syncthreads();
-  read_group(0, 0, 0, raw);
-  transform(raw, v0);
-  int s = 0;
-  for (; s + 1 < p.nstage; s += 2) {
-    stage(s, std::integral_constant<int, 0>());
-    stage(s + 1, std::integral_constant<int, 1>());
-  }
-  if (s < p.nstage) stage(s, std::integral_constant<int, 0>());
-  __syncthreads();                               // every wave is done reading before the epilogue reuses the LDS
-  const int rows_per_group = RPG;
-
-  // ---- epilogue: M A per wave (row xi), A^T . across the four waves through LDS, one channel group at a time
-  //   R[0] = M0 + M1 + M2,  R[1] = M1 - M2 - M3;   Y[0][b] = R0b + R1b + R2b,  Y[1][b] = R1b - R2b - R3b
-  float* rbuf = smem;                            // [xi][b][64 tiles][WN_RSE]
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float r0[4], r1[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float m0 = acc[0][mt][nt][4 * g + e], m1 = acc[1][mt][nt][4 * g + e], m2 = acc[2][mt][nt][4 * g + e],
-                      m3 = acc[3][mt][nt][4 * g + e];
-          r0[e] = m0 + m1 + m2;
-          r1[e] = m1 - m2 - m3;
-        }
-        const int tile = mt * 32 + j, ch = 8 * g + 4 * h;
-        *(float4*)(rbuf + ((wave * 2 + 0) * 64 + tile) * WN_RSE + ch) = make_float4(r0[0], r0[1], r0[2], r0[3]);
-        *(float4*)(rbuf + ((wave * 2 + 1) * 64 + tile) * WN_RSE + ch) = make_float4(r1[0], r1[1], r1[2], r1[3]);
-      }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int item = tid + 256 * it;           // 64 tiles x 8 channel quads
-      const int tile = item >> 3, cq = item & 7;
-      const int n = nb * 64 + nt * 32 + cq * 4;
-      const int mt = tile >> 5, jj = tile & 31;
-      const int ttx = jj % TW, tty = mt * rows_per_group + jj / TW;
-      const int oy = Y0 + 2 * tty, ox = X0 + 2 * ttx;
-      if (n < p.Cout && oy < p.H && ox < p.W) {
-        float4 rr[4][2];
-#pragma unroll
-        for (int xi = 0; xi < 4; ++xi)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) rr[xi][b] = *(const float4*)(rbuf + ((xi * 2 + b) * 64 + tile) * WN_RSE + cq * 4);
-        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bias != nullptr) bv = *(const float4*)(bias + n);
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            float v[4];
-            const float4 q0 = rr[0][b], q1 = rr[1][b], q2 = rr[2][b], q3 = rr[3][b];
-            if (a == 0) {
-              v[0] = q0.x + q1.x + q2.x; v[1] = q0.y + q1.y + q2.y; v[2] = q0.z + q1.z + q2.z; v[3] = q0.w + q1.w + q2.w;
-            } else {
-              v[0] = q1.x - q2.x - q3.x; v[1] = q1.y - q2.y - q3.y; v[2] = q1.z - q2.z - q3.z; v[3] = q1.w - q2.w - q3.w;
-            }
-            v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (p.act == CSG_ACT_LEAKY)
-                v[e] = v[e] > 0.f ? v[e] : v[e] * p.slope;
-              else if (p.act == CSG_ACT_TANH)
-                v[e] = tanhf(v[e]);
-            }
-            // H and W are even: a tile is either wholly inside the image or wholly outside
-            const int64_t pix = ((int64_t)img * p.H + (oy + a)) * p.W + (ox + b);
-            if (res != nullptr) {
-              const float4 rv = *(const float4*)(res + pix * p.y_cs + n);
-              v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
-            }
-            if (gate != nullptr) {
-              const float4 gv = *(const float4*)(gate + pix * p.y_cs + n);
-              v[0] *= gv.x > 0.f ? 1.f : p.gate_slope; v[1] *= gv.y > 0.f ? 1.f : p.gate_slope;
-              v[2] *= gv.z > 0.f ? 1.f : p.gate_slope; v[3] *= gv.w > 0.f ? 1.f : p.gate_slope;
-            }
-            *(float4*)(y + pix * p.y_cs + n) = make_float4(v[0], v[1], v[2], v[3]);
-          }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ------------------------------------------------------------------------------------ convolution, 2 blocks per CU
-// Same algorithm with HALF the tile set per block: 32 tiles (TW x TH) x 64 output channels, accumulators 4 nu x 2
-// channel groups = 128 registers, so TWO blocks are resident per CU (two waves per SIMD).  A lone wave pays for every
-// VMEM / LDS / VALU issue and for its prologue and epilogue with idle matrix-pipe time (k_wino_conv: 55 % busy); here
-// the partner wave's MFMAs run underneath, and one block's epilogue under the other block's main loop.  To fit 256
-// registers the weights are single-buffered: the eight operands of one channel group are reloaded (for the next
-// k-oct) right after their last MFMA, while the other group's 16 MFMAs run.
-template <int TW, int NTB = 2>     // NTB: 32-channel groups per block (1 for layers with <= 32 output channels)
-__global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float* __restrict__ x,
-                                                        const float4* __restrict__ up, const float* __restrict__ bias,
-                                                        const float* __restrict__ res, const float* __restrict__ gate,
-                                                        float* __restrict__ y) {
-  constexpr int TH = 32 / TW;
-  constexpr int R = 2 * TH + 2, C = 2 * TW + 2;
-  constexpr int RS = wn_row_stride(TW);
-  constexpr int BUFW = R * RS + 16;
-  constexpr int HALF = (C / 2) * WN_PS;
-  constexpr int NLD = (R * C * 4 + 255) / 256;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-  int bid = wn_xcd_remap(blockIdx.x, gridDim.x);
-  const int split = bid % p.ksplit;              // splits of one tile are neighbours: they share the input in L2
-  bid /= p.ksplit;
-  const int nb = bid % p.nblocks;
-  bid /= p.nblocks;
-  const int bx = bid % p.tbx;
-  bid /= p.tbx;
-  const int by = bid % p.tby;
-  const int img = bid / p.tby;
-  const int X0 = bx * 2 * TW, Y0 = by * 2 * TH;
-
-  const csg_i32x4 rsX = csg_make_srd(x, (long long)p.B * p.H * p.W * p.x_cs * 4);
-  const csg_i32x4 rsU = csg_make_srd(up, (long long)16 * p.NT32 * p.Q8 * 64 * 16);
-  unsigned goff[NLD];
-  int loff[NLD];
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int e = tid + 256 * i;
-    goff[i] = CSG_OOB_OFF;
-    loff[i] = BUFW - 16 + (tid & 3) * 4;
-    if (e < R * C * 4) {
-      const int pix = e >> 2, c4 = e & 3;
-      const int row = pix / C, col = pix - row * C;
-      const int iy = Y0 + row - 1, ix = X0 + col - 1;
-      loff[i] = row * RS + ((col & 1) * (C >> 1) + (col >> 1)) * WN_PS + c4 * 4;
-      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-        goff[i] = (unsigned)(((img * p.H + iy) * p.W + ix) * p.x_cs + c4 * 4) * 4u;
-    }
-  }
-  csg_f32x4 st[NLD];
-  auto load_stage = [&](int s) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) st[i] = csg_buf_load_x4(rsX, (int)goff[i], s * (WN_BK * 4), 0);
-  };
-  auto store_stage = [&](float* base) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      float* dst = base + loff[i];
-      *(float2*)(dst) = make_float2(st[i].x, st[i].y);
-      *(float2*)(dst + 2) = make_float2(st[i].z, st[i].w);
-    }
-  };
-
-  const int j = lane & 31, h = lane >> 5;
-  const int tx = j % TW, tyl = j / TW;
-  const int ia = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
-  const int ib = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
-  const float sgn = wave == 1 ? 1.0f : -1.0f;
-  const float* pa0 = smem + (2 * tyl + ia) * RS + tx * WN_PS + 2 * h;
-  const float* pb0 = smem + (2 * tyl + ib) * RS + tx * WN_PS + 2 * h;
-
   unsigned uoff[4][NTB];
 #pragma unroll
   for (int nt = 0; nt < NTB; ++nt) {
@@ -550,8 +258,8 @@ __global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float
       uoff[nu][nt] = nt32 < p.NT32 ? (unsigned)((((wave * 4 + nu) * p.NT32 + nt32) * p.Q8) * 64 + lane) * 16u : CSG_OOB_OFF;
   }
   csg_f32x4 u[4][NTB];
-  auto load_u_half = [&](int nt, int q) {        // operands of channel group nt for k-oct q (clamped: see k_wino_conv)
-    const int qq = min(q, p.Q8 - 1);
+  auto load_u_half = [&](int nt, int q) {        // operands of channel group nt for k-oct q
+    const int qq = min(q, p.Q8 - 1);             // the prefetch past the end re-reads the last block (scalar op)
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) u[nu][nt] = csg_buf_load_x4(rsU, (int)uoff[nu][nt], qq * 1024, 0);
   };
@@ -583,6 +291,7 @@ __global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float
       v[3][cp] = make_float2(q[1].x - q[3].x, q[1].y - q[3].y);
     }
   };
+  // weights as the first operand: D[i = channel][j = tile] -> a lane holds one tile and runs of 4 channels
   auto mfma_half = [&](int nt) {                 // 16 MFMAs: k-step outermost, 4 accumulators in rotation
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) acc[nu][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[nu][nt].x, v[nu][0].x, acc[nu][nt], 0, 0, 0);
@@ -626,7 +335,8 @@ __global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float
   }
   if (s < s_end) stage(s, std::integral_constant<int, 0>());
 
-  // ---- epilogue (as k_wino_conv, 32 tiles): R[0] = M0+M1+M2, R[1] = M1-M2-M3 per wave, A^T . through LDS
+  // ---- epilogue: M A per wave (row xi), A^T . across the four waves through LDS, one channel group at a time
+  //   R[0] = M0 + M1 + M2,  R[1] = M1 - M2 - M3;   Y[0][b] = R0b + R1b + R2b,  Y[1][b] = R1b - R2b - R3b
   float* rbuf = smem;                            // [xi][b][32 tiles][WN_RSE]
 #pragma unroll
   for (int nt = 0; nt < NTB; ++nt) {
@@ -676,6 +386,7 @@ __global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float
               else if (p.act == CSG_ACT_TANH)
                 vv[e] = tanhf(vv[e]);
             }
+            // H and W are even: a tile is either wholly inside the image or wholly outside
             const int64_t pix = ((int64_t)img * p.H + (oy + a)) * p.W + (ox + b);
             if (res != nullptr) {
               const float4 rv = *(const float4*)(res + pix * p.y_cs + n);
@@ -708,18 +419,11 @@ static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const cha
   CSG_REQUIRE((int64_t)16 * ((d->Cout + 31) / 32) * ((d->Cin + 7) / 8) * 1024 < CSG_MAX_RECORDS, CSG_E_UNSUPPORTED,
               "%s: packed weights too large for 32-bit byte offsets", who);
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_cs = d->x_cs; p.Cout = d->Cout; p.y_cs = d->y_cs;
-  static const int variant = getenv("CSG_WINO_VARIANT") ? atoi(getenv("CSG_WINO_VARIANT")) : 2;
-  p.variant = variant;
-  if (variant == 2) {            // 32 tiles per block, two blocks per CU
-    p.TW = d->W >= 32 ? 16 : (d->W >= 16 ? 8 : 4);
-    p.TH = 32 / p.TW;
-  } else {                       // 64 tiles per block, one block per CU
-    p.TW = d->W >= 64 ? 32 : (d->W >= 32 ? 16 : (d->W >= 16 ? 8 : 4));
-    p.TH = 64 / p.TW;
-  }
+  p.TW = d->W >= 32 ? 16 : (d->W >= 16 ? 8 : 4);
+  p.TH = 32 / p.TW;
   p.tbx = (d->W / 2 + p.TW - 1) / p.TW;
   p.tby = (d->H / 2 + p.TH - 1) / p.TH;
-  p.ntb = (variant == 2 && d->Cout <= 32) ? 1 : 2;     // 32-wide blocks for layers with <= 32 output channels
+  p.ntb = d->Cout <= 32 ? 1 : 2;                 // 32-wide blocks for layers with <= 32 output channels
   p.nblocks = (d->Cout + 32 * p.ntb - 1) / (32 * p.ntb);
   p.RS = wn_row_stride(p.TW);
   CSG_REQUIRE(d->Cin % 16 == 0, CSG_E_UNSUPPORTED, "%s: Cin must be a multiple of 16 (one LDS stage)", who);
@@ -731,7 +435,7 @@ static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const cha
   p.sps = p.nstage;
   p.slab = (long long)d->B * d->H * d->W * d->y_cs;
   const size_t in_bytes = (size_t)2 * ((2 * p.TH + 2) * p.RS + 16) * 4;        // + the dump slots of idle staging lanes
-  const size_t ep_bytes = (size_t)4 * 2 * (p.variant == 2 ? 32 : 64) * WN_RSE * 4;
+  const size_t ep_bytes = (size_t)4 * 2 * 32 * WN_RSE * 4;
   shm = in_bytes > ep_bytes ? in_bytes : ep_bytes;
   return CSG_OK;
 }
@@ -770,7 +474,7 @@ int csg_wino2_pack_multi_launch(const PackMulti* pm, int blocks, double bytes, h
 // convolutions: 128 output channels, 2048 input channels): only without an epilogue (bias / activation / residual)
 // and with a dense output, the slabs are summed in a fixed order by k_slab_reduce.
 static void wn_split_plan(WinoParams& p, bool plain) {
-  if (p.variant != 2 || !plain || p.y_cs != p.Cout) return;
+  if (!plain || p.y_cs != p.Cout) return;
   const int64_t blocks = (int64_t)p.B * p.tby * p.tbx * p.nblocks;
   if (blocks >= 384 || p.nstage < 16) return;
   int ks = (int)((512 + blocks - 1) / blocks);
@@ -812,10 +516,8 @@ int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, c
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (attr_once.pending(dev)) {
-    const void* fns[10] = {(const void*)k_wino_conv<32>, (const void*)k_wino_conv<16>, (const void*)k_wino_conv<8>,
-                          (const void*)k_wino_conv<4>, (const void*)k_wino_conv2<16, 2>, (const void*)k_wino_conv2<8, 2>,
-                          (const void*)k_wino_conv2<4, 2>, (const void*)k_wino_conv2<16, 1>, (const void*)k_wino_conv2<8, 1>,
-                          (const void*)k_wino_conv2<4, 1>};
+    const void* fns[6] = {(const void*)k_wino_conv2<16, 2>, (const void*)k_wino_conv2<8, 2>, (const void*)k_wino_conv2<4, 2>,
+                          (const void*)k_wino_conv2<16, 1>, (const void*)k_wino_conv2<8, 1>, (const void*)k_wino_conv2<4, 1>};
     for (const void* fn : fns) {
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
       CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_wino_conv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
@@ -829,36 +531,25 @@ int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, c
   // algorithmic FLOPs of the DIRECT convolution this replaces (2 * M * 9*Cin * Cout): what FlopCounterMode counts
   ProfScope ps(K_WINO_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
   const float4* up = (const float4*)packed;
-  if (p.variant == 2) {
-    if (p.ntb == 1) {
-      if (p.TW == 16)
-        CSG_LAUNCH((k_wino_conv2<16, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-      else if (p.TW == 8)
-        CSG_LAUNCH((k_wino_conv2<8, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-      else
-        CSG_LAUNCH((k_wino_conv2<4, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-    } else if (p.TW == 16)
-      CSG_LAUNCH((k_wino_conv2<16, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+  if (p.ntb == 1) {
+    if (p.TW == 16)
+      CSG_LAUNCH((k_wino_conv2<16, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
     else if (p.TW == 8)
-      CSG_LAUNCH((k_wino_conv2<8, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+      CSG_LAUNCH((k_wino_conv2<8, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
     else
-      CSG_LAUNCH((k_wino_conv2<4, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-    rc = check_launch("csg_wino_conv");
-    if (rc == CSG_OK && p.ksplit > 1) {
-      launch_slab_reduce(workspace, p.slab, y_final, nullptr, 0, nullptr, p.ksplit, s);
-      rc = check_launch("csg_wino_conv(slab sum)");
-    }
-    return rc;
-  }
-  if (p.TW == 32)
-    CSG_LAUNCH(k_wino_conv<32>, dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-  else if (p.TW == 16)
-    CSG_LAUNCH(k_wino_conv<16>, dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+      CSG_LAUNCH((k_wino_conv2<4, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+  } else if (p.TW == 16)
+    CSG_LAUNCH((k_wino_conv2<16, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
   else if (p.TW == 8)
-    CSG_LAUNCH(k_wino_conv<8>, dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+    CSG_LAUNCH((k_wino_conv2<8, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
   else
-    CSG_LAUNCH(k_wino_conv<4>, dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-  return check_launch("csg_wino_conv");
+    CSG_LAUNCH((k_wino_conv2<4, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+  rc = check_launch("csg_wino_conv");
+  if (rc == CSG_OK && p.ksplit > 1) {
+    launch_slab_reduce(workspace, p.slab, y_final, nullptr, 0, nullptr, p.ksplit, s);
+    rc = check_launch("csg_wino_conv(slab sum)");
+  }
+  return rc;
 }
 
 }  // extern "C"
@@ -870,9 +561,9 @@ int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, c
 // with A^T = [[1,1,1,0],[0,1,-1,0],[0,1,1,1]], G = [[1,0],[1/2,1/2],[1/2,-1/2],[0,1]] and
 // B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,-1,0,1]].  The sum over tiles is taken INSIDE the brackets: 16 GEMMs
 //     Acc_p[cout][cin] = sum_tiles E_p[tile][cout] * V_p[tile][cin]
-// whose reduction index is the tile.  A block owns 64 cout x 64 cin x 16 positions over a slice of the tiles; wave w
-// owns row xi = w.  Both operands are formed in registers from plain coalesced global loads (32 consecutive channels
-// per half-wave; the two half-waves work on two consecutive tiles = the k-pair of v_mfma_f32_32x32x2_f32): no LDS and
+// whose reduction index is the tile.  A block owns 64 cout x 32 cin x 16 positions over a slice of the tiles (two
+// blocks per CU; the 64-cin form with one block per CU spilled to scratch); wave w owns row xi = w.  Both operands
+// are formed in registers from plain coalesced global loads (32 consecutive channels per half-wave; the two half-waves work on two consecutive tiles = the k-pair of v_mfma_f32_32x32x2_f32): no LDS and
 // no barrier in the main loop.  Slabs per tile slice + the ordered reduction of igemm.hip (k_wgrad_reduce) give a
 // bit-reproducible result; the bias gradient rides along in wave 1, which loads all four pixels of every dY tile.
 struct WinoWgParams {
@@ -880,7 +571,6 @@ struct WinoWgParams {
   int RXn, RYn, nregions;        // stage regions per tile row / column of an image, in all
   int cblocks, kblocks;
   int nsplit, rps;               // regions per split
-  int nt;                        // input-channel groups of 32 per block (2: one block per CU, 1: two)
 };
 
 #define WG_EPS 33                // words per row of the epilogue exchange buffer
@@ -894,10 +584,11 @@ struct WinoWgParams {
 // s+1 issued before the MFMAs of stage s, one barrier per stage.  Regions tile the image exactly (host-checked), so
 // only the one-pixel halo needs masking: per-thread flags x uniform edge conditions, one v_cndmask per load; the
 // region's position rides in the scalar offset of the buffer loads.
-template <int TSX, int NT>
-__global__ __launch_bounds__(256, NT == 2 ? 1 : 2) void k_wino_wgrad(WinoWgParams p, const float* __restrict__ x,
+template <int TSX, int NT>     // NT: input-channel groups of 32 per block
+__global__ __launch_bounds__(256, 2) void k_wino_wgrad(WinoWgParams p, const float* __restrict__ x,
                                                         const float* __restrict__ dy, float* __restrict__ slabs,
                                                         float* __restrict__ dbslabs) {
+  static_assert(NT == 1, "one 32-channel input group per block");
   constexpr int TSY = 16 / TSX;
   constexpr int XR = 2 * TSY + 2, XC = 2 * TSX + 2, YR = 2 * TSY, YC = 2 * TSX;
   constexpr int XCH = 32 * NT, XF4 = XCH / 4;    // input channels per block and pixel, as floats / as 16-byte pieces
@@ -1146,13 +837,11 @@ static int wn_wg_plan(const csg_wino_desc* d, WinoWgParams& p, const char* who) 
   const int64_t nr = (int64_t)d->B * p.RXn * p.RYn;
   CSG_REQUIRE(nr < (1ll << 30), CSG_E_UNSUPPORTED, "%s: too many regions", who);
   p.nregions = (int)nr;
-  static const int variant = getenv("CSG_WINO_WGRAD_VARIANT") ? atoi(getenv("CSG_WINO_WGRAD_VARIANT")) : 2;
-  p.nt = variant == 2 ? 1 : 2;                   // 32 (two blocks per CU) or 64 input channels per block
   p.cblocks = (d->Cout + 63) / 64;
-  p.kblocks = (d->Cin + 32 * p.nt - 1) / (32 * p.nt);
-  // 1 or 2 blocks per CU are resident: aim at ~2 waves of blocks, at least 8 stages per block, at most 512 slabs
+  p.kblocks = (d->Cin + 31) / 32;
+  // 2 blocks per CU are resident: aim at ~2 waves of blocks, at least 8 stages per block, at most 512 slabs
   const int tiles2d = p.cblocks * p.kblocks;
-  int ns = (512 * (3 - p.nt) + tiles2d - 1) / tiles2d;
+  int ns = (1024 + tiles2d - 1) / tiles2d;
   const int max_ns = (int)((nr + 7) / 8);
   if (ns > max_ns) ns = max_ns;
   if (ns > 512) ns = 512;
@@ -1183,14 +872,13 @@ int csg_wino_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy,
   int dev = 0;
   (void)hipGetDevice(&dev);
   const int tsx = wn_wg_tsx(d->W), tsy = 16 / tsx;
-  // per buffer: the X patch (32*nt channels) padded to whole 256-lane DMAs + the dY pixels (64 channels)
-  const size_t x_f4 = (size_t)(((2 * tsy + 2) * (2 * tsx + 2) * 8 * p.nt + 255) / 256) * 256;
+  // per buffer: the X patch (32 channels) padded to whole 256-lane DMAs + the dY pixels (64 channels)
+  const size_t x_f4 = (size_t)(((2 * tsy + 2) * (2 * tsx + 2) * 8 + 255) / 256) * 256;
   const size_t stage_bytes = 2 * (x_f4 * 16 + (size_t)(2 * tsy) * (2 * tsx) * 64 * 4);
   const size_t ep_bytes = (size_t)4 * 3 * 32 * WG_EPS * 4;
   const size_t shm = stage_bytes > ep_bytes ? stage_bytes : ep_bytes;
   if (attr_once.pending(dev)) {
-    const void* fns[6] = {(const void*)k_wino_wgrad<16, 2>, (const void*)k_wino_wgrad<8, 2>, (const void*)k_wino_wgrad<4, 2>,
-                          (const void*)k_wino_wgrad<16, 1>, (const void*)k_wino_wgrad<8, 1>, (const void*)k_wino_wgrad<4, 1>};
+    const void* fns[3] = {(const void*)k_wino_wgrad<16, 1>, (const void*)k_wino_wgrad<8, 1>, (const void*)k_wino_wgrad<4, 1>};
     for (const void* fn : fns) {
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
       CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_wino_bwd_weight: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
@@ -1207,21 +895,12 @@ int csg_wino_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy,
   {
     ProfScope ps(K_WINO_WGRAD, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
     const dim3 grid((unsigned)(p.cblocks * p.kblocks * p.nsplit));
-    if (p.nt == 2) {
-      if (tsx == 16)
-        CSG_LAUNCH((k_wino_wgrad<16, 2>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-      else if (tsx == 8)
-        CSG_LAUNCH((k_wino_wgrad<8, 2>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-      else
-        CSG_LAUNCH((k_wino_wgrad<4, 2>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-    } else {
-      if (tsx == 16)
-        CSG_LAUNCH((k_wino_wgrad<16, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-      else if (tsx == 8)
-        CSG_LAUNCH((k_wino_wgrad<8, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-      else
-        CSG_LAUNCH((k_wino_wgrad<4, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-    }
+    if (tsx == 16)
+      CSG_LAUNCH((k_wino_wgrad<16, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
+    else if (tsx == 8)
+      CSG_LAUNCH((k_wino_wgrad<8, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
+    else
+      CSG_LAUNCH((k_wino_wgrad<4, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
     rc = check_launch("csg_wino_bwd_weight");
     if (rc) return rc;
   }

@@ -81,22 +81,6 @@ typedef const volatile __attribute__((address_space(3))) csg_f32x2* w4_lds_cv2;
 #define W4_THREADS 768             // twelve waves: two channel groups x six rows xi
 #define W4_RBUF (6 * 2 * 32 * W4_RSE)       // words of one channel group's epilogue exchange buffer
 
-// Developer build (-DW4_TRACE, tools/wino4_trace.py): thread 0 of the first 8192 blocks leaves shader-clock timestamps
-// at the phase boundaries of the kernel; csg_wino4_trace_read copies them out.
-#ifdef W4_TRACE
-__device__ unsigned long long w4_trace[8192 * 8];
-__device__ unsigned long long w4_trace2[8192 * 8];   // per item (persistent) / per block: stage-level markers
-#define W4_T(i)                                                                                   \
-  if (threadIdx.x == 0 && blockIdx.x < 8192) w4_trace[blockIdx.x * 8 + (i)] = __builtin_readcyclecounter();
-// persistent form: the same table indexed by ITEM (markers 0 item start | 3 main loop done | 6 epilogue done | 7 V[0] of the next item)
-#define W4_TI(i)                                                                                   \
-  if (threadIdx.x == 0 && (P ? v : (int)blockIdx.x) < 8192)                                        \
-    w4_trace2[(P ? v : (int)blockIdx.x) * 8 + (i)] = __builtin_readcyclecounter();
-#else
-#define W4_T(i)
-#define W4_TI(i)
-#endif
-
 struct Wino4Params {
   int B, H, W, Cin, x_cs, Cout, y_cs;
   int Ho, Wo, pad;     // output size and zero padding (F(4x4,3x3): Ho = H, Wo = W, pad = 1)
@@ -432,10 +416,7 @@ __device__ __forceinline__ void w4_epilogue(f32x16 (&acc)[6], const Wino4Params&
   float* rbuf = rbase + grp * (W4_RBUF / 2 * NB);   // this channel group's exchange buffer
   const int tig = tid - grp * (W4_THREADS / 2);  // thread index inside the channel group
   const bool plain = p.act == CSG_ACT_NONE && res == nullptr && gate == nullptr;
-  if (NB == 2) {
-    __syncthreads();                             // every wave is done reading the staging buffers
-    W4_T(3)
-  }
+  if (NB == 2) __syncthreads();                  // every wave is done reading the staging buffers
   // NB = 1: all four columns are reduced over nu FIRST (64 registers in place of the 96 accumulators), so that the three
   // store phases that follow a not-yet-written column do not have to carry the accumulators next to their own operands
   csg_f32x2 rr[NB == 1 ? 4 : 1][8];
@@ -482,7 +463,6 @@ __device__ __forceinline__ void w4_epilogue(f32x16 (&acc)[6], const Wino4Params&
         *(float4*)(rbuf + ((wave * NB + 1) * 32 + j) * W4_RSE + ch) = make_float4(r1[0].x, r1[0].y, r1[1].x, r1[1].y);
     }
     __syncthreads();
-    if (NB == 2 && round == 0) { W4_T(4) }
     if (NB == 1 && p.mod == 2)            // (the persistent form only: the one-item form carries its accumulators through the rounds)
       w4_store_joint<NB>(p, rbase, tid, round, nt32 - grp * p.gb_off, img, X0, Y0, bias, res, const_cast<float*>(gate), y);
     else if (p.mod)
@@ -491,12 +471,8 @@ __device__ __forceinline__ void w4_epilogue(f32x16 (&acc)[6], const Wino4Params&
       w4_store_columns<0, NB>(p, rbuf, tig, round, nt32, img, X0, Y0, bias, res, gate, y);
     else
       w4_store_columns<1, NB>(p, rbuf, tig, round, nt32, img, X0, Y0, bias, res, gate, y);
-    if (round + 1 < 4 / NB) {
-      __syncthreads();                           // the exchange buffer is rewritten by the next round
-      if (NB == 2) { W4_T(5) }
-    }
+    if (round + 1 < 4 / NB) __syncthreads();     // the exchange buffer is rewritten by the next round
   }
-  if (NB == 2) { W4_T(6) }
 }
 
 // ---- epilogue of F(3x3,4x4): A^T = [[1,1,1,1,1,0],[0,1,-1,1/2,-2,0],[0,1,1,1/4,4,1]] (the first three rows of the
@@ -509,7 +485,6 @@ __device__ __forceinline__ void w3_epilogue(f32x16 (&acc)[6], const Wino4Params&
   float* rbuf = smem + grp * W4_RBUF;
   const int tig = tid - grp * (W4_THREADS / 2);
   __syncthreads();                               // every wave is done reading the staging buffers
-  W4_T(3)
 #pragma unroll
   for (int round = 0; round < 2; ++round) {
 #pragma unroll
@@ -533,7 +508,6 @@ __device__ __forceinline__ void w3_epilogue(f32x16 (&acc)[6], const Wino4Params&
         *(float4*)(rbuf + ((wave * 2 + 1) * 32 + j) * W4_RSE + ch) = make_float4(r1[0].x, r1[0].y, r1[1].x, r1[1].y);
     }
     __syncthreads();
-    if (round == 0) { W4_T(4) }
     const int nitem = round == 0 ? 512 : 256;      // 32 tiles x 8 channel quads x (2 | 1) columns
     for (int item = tig; item < nitem; item += W4_THREADS / 2) {
       const int cq = item & 7, tile = (item >> 3) & 31, bb = item >> 8;
@@ -593,12 +567,8 @@ __device__ __forceinline__ void w3_epilogue(f32x16 (&acc)[6], const Wino4Params&
         }
       }
     }
-    if (round == 0) {
-      __syncthreads();                           // the exchange buffer is rewritten by round 1
-      W4_T(5)
-    }
+    if (round == 0) __syncthreads();             // the exchange buffer is rewritten by round 1
   }
-  W4_T(6)
 }
 
 // ------------------------------------------------------------------------------------ convolution
@@ -656,7 +626,6 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
   static_assert(!P || T == 4, "the persistent form serves F(4x4,3x3)");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
-  W4_T(0)
   const int wave12 = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave12 >= 6 ? 1 : 0;           // consumer: channel group; producer: channel pairs 2 grp + {0, 1}
   const int wave = wave12 - 6 * grp;             // row xi of the transformed domain (both roles)
@@ -794,19 +763,10 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
       const int co = rbufsel * W4_BUFW + ((c % T) * W4_CQ + (c / T)) * W4_PS;
       const csg_f32x2 e0 = *(w4_lds_cv2)(p0 + co);
       const csg_f32x2 e1 = *(w4_lds_cv2)(p0 + co + W4_RS);
-#ifdef W4_HALF_READS   // ablation (wrong results): half the raw LDS reads of the transform at the same VALU count
-      const csg_f32x2 e2 = e0 * 1.5f;
-      const csg_f32x2 e3 = e1 * 0.75f;
-#else
       const csg_f32x2 e2 = *(w4_lds_cv2)(p0 + co + O2);
       const csg_f32x2 e3 = *(w4_lds_cv2)(p0 + co + O3);
-#endif
       if (XI == 0 || XI == 5) {
-#ifdef W4_HALF_READS
-        const csg_f32x2 e4 = e0 * 0.5f;
-#else
         const csg_f32x2 e4 = *(w4_lds_cv2)(p0 + co + 4 * W4_RS + 2);
-#endif
         t[c] = w4_pfma(1.5f, e3 - e1, w4_pfma(-2.0f, e2, e0 + e4));
       } else if (XI == 1) {
         t[c] = w4_pfma(2.5f, e2, w4_pfma(0.5f, e1, e3 - e0));
@@ -861,51 +821,28 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
       acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[slot].y, v.y, acc[nu], 0, 0, 0);
       acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[slot].z, v.z, acc[nu], 0, 0, 0);
       acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[slot].w, v.w, acc[nu], 0, 0, 0);
-#ifndef W4_NO_ULOAD
       if (nu < 3) load_ur(slot, nu + 3, s); else load_ur(slot, nu - 3, s + 1);
-#endif
     }
   };
-  // One stage.  The transform of stage k+1 sits BETWEEN the MFMAs of stage k (W4_SPLIT positions in front of it): after
+  // One stage.  The transform of stage k+1 sits BETWEEN the MFMAs of stage k (SPLIT positions in front of it): after
   // the barrier every wave has matrix work at once (V[k] is complete) and again after its transform, instead of all
-  // twelve waves issuing their 166 KB of transform reads together while the matrix pipes wait.
-#ifndef W4_SPLIT
-#define W4_SPLIT 3
-#endif
-  // (-DW4_HALF_PRODUCE, -DW4_HALF_READS, -DW4_NO_BARRIER, -DW4_NO_ULOAD, -DW4_NO_STAGING: ablations for
-  // tools/wino4_variants.py — wrong results, loop timing only.
-  // Round 6 measured two more placements with that tool and dropped them: s_setprio 1 / 3 around the matrix clusters
-  // -3 % on every shape; different split points on the three waves of a SIMD needed the stage body as a callable the
-  // compiler no longer inlined — 1 KB of scratch, 30x slower.  profiles/r06b_wino4_variants.txt.)
+  // twelve waves issuing their 166 KB of transform reads together while the matrix pipes wait.  (Two other placements
+  // lost: s_setprio around the matrix clusters, -3 % on every shape; per-wave split points, which made the compiler stop
+  // inlining the stage body — profiles/r06b_wino4_variants.txt, tool since removed.)
+  constexpr int SPLIT = 3;
   auto stage = [&](int s, auto par_tag) {        // par = (s - s_begin) & 1
     constexpr int par = decltype(par_tag)::value;
     typedef std::integral_constant<int, 0> I0;
-    typedef std::integral_constant<int, W4_SPLIT> IS;
+    typedef std::integral_constant<int, SPLIT> IS;
     typedef std::integral_constant<int, 6> I6;
-#ifndef W4_NO_MFMA
     consume(I0(), IS(), par, s);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef W4_NO_PRODUCE
-#ifdef W4_HALF_PRODUCE
-    if (s + 1 < s_end && par == 0) produce(par ^ 1, par ^ 1);
-#else
     if (s + 1 < s_end) produce(par ^ 1, par ^ 1);   // V[k+1] from raw[k+1]
-#endif
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef W4_NO_MFMA
     consume(IS(), I6(), par, s);
-#endif
-#if !defined(W4_NO_STAGING) && !defined(W4_NO_STAGING_STORE)
     store_stage(smem + W4V_RAW0 + par * W4_BUFW);   // raw[k+2] takes the buffer raw[k] left
-#endif
-#ifndef W4_NO_BARRIER
     __syncthreads();
-#endif
-#if !defined(W4_NO_STAGING) && !defined(W4_NO_STAGING_LOAD)
     load_stage(s + 3);
-#endif
   };
 
   y += (long long)split * p.slab;
@@ -922,7 +859,6 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
     st[1] = a1;
     store_stage(smem + W4V_RAW0);
     __syncthreads();
-    W4_T(1)
     st[0] = b0;
     st[1] = b1;
     produce(0, 0);                               // V[0] from raw[0]
@@ -930,7 +866,6 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
     __syncthreads();
     load_stage(s_begin + 2);
   }
-  W4_T(2)
   for (;;) {
 #pragma unroll
     for (int nu = 0; nu < 6; ++nu)
@@ -938,7 +873,6 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
       for (int e = 0; e < 16; ++e) acc[nu][e] = 0.f;
     bool more = false;
     int item_n = 0;
-    W4_TI(0)
     int nb_n = nb, img_n = img, X0_n = X0, Y0_n = Y0;
     if (P) {
       // the next item's plan: its first two stages enter the pipeline three stages before this item ends
@@ -954,17 +888,11 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
       nt32 = p.gb_off ? nb + grp * p.gb_off : nb * 2 + grp;
     }
     int s = s_begin;
-    W4_TI(1)
     for (; s + 1 < s_end; s += 2) {
       stage(s, std::integral_constant<int, 0>());
       stage(s + 1, std::integral_constant<int, 1>());
-#ifdef W4_TRACE
-      if (s == s_begin) { W4_TI(2) }
-      if (s + 4 == s_end) { W4_TI(4) }
-#endif
     }
     if (s < s_end) stage(s, std::integral_constant<int, 0>());
-    W4_TI(3)
     if (T == 4 && P) {
       // the epilogue's addresses and parameters are formed HERE, not kept across the main loop: the thread index goes
       // through an opaque copy and the parameters are read back from the kernel-argument segment (scalar loads)
@@ -984,7 +912,6 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
     } else {
       w3_epilogue(acc, p, smem, tid, wave, grp, j, h, nt32, img, X0, Y0, bias, res, gate, y);
     }
-    W4_TI(6)
     if (!P || !more) break;
     // the next item: raw[0] and raw[1] are in place, its U ring is loaded and its stage 2 in flight (the last stage's loads)
     v = item_n;
@@ -995,21 +922,9 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
     __syncthreads();                             // the exchange buffer sat in the V buffers
     produce(0, 0);
     __syncthreads();
-#ifdef W4_TRACE
-    if (P && threadIdx.x == 0 && v - v_step < 8192 && v - v_step >= 0) w4_trace2[(v - v_step) * 8 + 7] = __builtin_readcyclecounter();
-#endif
   }
 #undef W4_TAB
 }
-
-#ifdef W4_TRACE
-extern "C" int csg_wino4_trace_read(unsigned long long* out, int n) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(w4_trace), (size_t)n * 8);
-}
-extern "C" int csg_wino4_trace2_read(unsigned long long* out, int n) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(w4_trace2), (size_t)n * 8);
-}
-#endif
 
 // ------------------------------------------------------------------------------------ host side
 // T = 4: F(4x4,3x3), pad 1, output = input size.  T = 3: F(3x3,4x4), pad 1 or 2, output = input + 2 pad - 3.
@@ -1085,9 +1000,6 @@ static int w4_persistent_blocks(const Wino4Params& p, int64_t items) {
   }
   const int g = ncu > 0 ? (ncu & ~7) : 0;
   if (g == 0 || p.ksplit != 1 || (p.nstage & 1) || p.nstage < 4 || (p.gb_off == 0 && (p.Cout & 63)) || items < 2 * (int64_t)g) return 0;
-#ifdef W4_TRACE
-  if (on == 2 && (items & 7) == 0) return (int)items;   // experiment: the persistent code, one item per block
-#endif
   return g;
 }
 

@@ -28,8 +28,8 @@
 //   * one stage later every wave runs its 18 MFMAs out of the operand buffer (one ds_read_b64 per operand: both tile
 //     pairs; a three-deep register ring fetched two positions ahead), one barrier per stage.  The two roles are template
 //     parameters of the loop (their own register allocations: 208 VGPRs, no scratch); a launch is ONE wave of blocks (256).
-//   * measured (tools/wgrad_bench.py, tools/wgrad_ablate.py): 1.2-1.4x over F(3x3,2x2) from 8 x 8 maps up; MFMA-only +
-//     transform-only = everything (the fp32 MFMA and the VALU of a SIMD share their lanes), matrix pipe 52 % busy.
+//   * measured (tools/wgrad_bench.py; ablations with a tool since removed): 1.2-1.4x over F(3x3,2x2) from 8 x 8 maps
+//     up; MFMA-only + transform-only = everything (the fp32 MFMA and the VALU of a SIMD share their lanes), matrix pipe 52 % busy.
 //   * the bias gradient is free: G' row 1 is (1,1,1,1), so E'[1][1] IS the sum of the dY tile.
 //   * epilogue: accumulators through LDS (two rounds of 36), every thread applies A^T (.) A with the scales of G folded in
 //     to its (cout, cin) pairs and writes the 3 x 3 taps of its slab; slabs are summed in order by k_slab_reduce
@@ -62,7 +62,6 @@ struct Wino4WgParams {
   int RXn, RYn, nregions;        // 8 x 8-pixel stage regions per row / column of an image, in all
   int cblocks, kblocks;          // 64-channel blocks of cout / cin
   int nsplit, rps;               // slices of the regions, regions per slice
-  int dbg;                       // developer ablations (CSG_WW_DBG bit mask): 1 no MFMAs, 2 no transform, 4 no DMA in the loop, 8 staggered E' waves
 };
 
 __device__ __forceinline__ int ww_xcd_remap(int bid, int nblk) {
@@ -124,7 +123,7 @@ typedef __attribute__((address_space(3))) void* ww_lds_ptr;
 
 // PH: the block's half of the positions; ISV: the wave's transform role (a template parameter: each role gets its own loop
 // and its own register allocation — under a runtime branch the two roles' live ranges were merged and spilled)
-template <int PH, bool ISV, bool STAG>
+template <int PH, bool ISV>
 __device__ __forceinline__ void ww_body(const Wino4WgParams& p, const float* __restrict__ x, const float* __restrict__ dy,
                                         float* __restrict__ slabs, float* __restrict__ dbslabs, float* smem, int cb, int kb,
                                         int sp) {
@@ -325,31 +324,20 @@ __device__ __forceinline__ void ww_body(const Wino4WgParams& p, const float* __r
     load_raw(0);
     transform(0, true);
     __syncthreads();
-    // stage s: DMA of stage s + 2 into the raw buffer stage s left; transform of stage s + 1; MFMAs of stage s
+    // stage s: DMA of stage s + 2 into the raw buffer stage s left; transform of stage s + 1; MFMAs of stage s.  (A
+    // stagger, the E' waves running the two halves in the other order so that one partner of a SIMD has matrix work while
+    // the other transforms, measured equal: 0.912 vs 0.901 ms — on this chip the fp32 MFMA and the VALU of a SIMD share
+    // their lanes.)
     auto stage = [&](int s, auto par_tag) {
       constexpr int par = decltype(par_tag)::value;
-      if (!(p.dbg & 4)) dma_stage(par);
-      if (ISV || !STAG) {
-        if (!(p.dbg & 1)) ops_prefill(par);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 2)) load_raw(par ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 1)) mfmas(par);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 2)) transform(par ^ 1, s + 1 < nst);
-      } else {
-        // STAG: the E' waves run the two halves of a stage in the OTHER order (a stagger: MI355X_MICROARCH.md, two waves per
-        // SIMD, item 9), so that one partner of a SIMD has matrix work while the other transforms.  Measured equal to the
-        // plain order (0.912 vs 0.901 ms, same box): MFMA-only + transform-only = everything either way — on this chip the
-        // fp32 MFMA and the VALU of a SIMD share their lanes.  Off by default.
-        if (!(p.dbg & 2)) load_raw(par ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 2)) transform(par ^ 1, s + 1 < nst);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 1)) ops_prefill(par);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 1)) mfmas(par);
-      }
+      dma_stage(par);
+      ops_prefill(par);
+      __builtin_amdgcn_sched_barrier(0);
+      load_raw(par ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas(par);
+      __builtin_amdgcn_sched_barrier(0);
+      transform(par ^ 1, s + 1 < nst);
       __builtin_amdgcn_sched_barrier(0);
       __syncthreads();
     };
@@ -435,10 +423,11 @@ __device__ __forceinline__ void ww_body(const Wino4WgParams& p, const float* __r
   }
 }
 
-template <bool STAG>
+template <bool STAG>     // STAG: staggered stage order of the E' waves (measured equal, removed)
 __global__ __launch_bounds__(WW_THREADS, 2) void k_wino4_wgrad(Wino4WgParams p, const float* __restrict__ x,
                                                                const float* __restrict__ dy, float* __restrict__ slabs,
                                                                float* __restrict__ dbslabs) {
+  static_assert(!STAG, "the plain stage order only");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int bid = ww_xcd_remap(blockIdx.x, gridDim.x);
   // the two position halves and all (cout block, cin block) pairs of one slice are adjacent: the slice's dY and X stay in
@@ -452,14 +441,14 @@ __global__ __launch_bounds__(WW_THREADS, 2) void k_wino4_wgrad(Wino4WgParams p, 
   const bool is_v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4;
   if (ph == 0) {
     if (is_v)
-      ww_body<0, true, STAG>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
+      ww_body<0, true>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
     else
-      ww_body<0, false, STAG>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
+      ww_body<0, false>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
   } else {
     if (is_v)
-      ww_body<1, true, STAG>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
+      ww_body<1, true>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
     else
-      ww_body<1, false, STAG>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
+      ww_body<1, false>(p, x, dy, slabs, dbslabs, smem, cb, kb, sp);
   }
 }
 
@@ -484,16 +473,15 @@ static int ww_plan(const csg_wino_desc* d, Wino4WgParams& p, const char* who) {
   // one block per CU is resident: aim at ONE wave of blocks (256: every CU gets one block of equal length — measured 256 / 512 /
   // 768 / 1024: 4.92 / 5.00 / 5.13 / 5.24 ms over eight generator shapes, fewer slabs to sum and fewer epilogues), at least 16
   // stages per block, at most 256 slices
-  static const int target = getenv("CSG_WINO4_WGRAD_BLOCKS") ? atoi(getenv("CSG_WINO4_WGRAD_BLOCKS")) : 256;
+  constexpr int target_blocks = 256;
   const int tiles2d = p.cblocks * p.kblocks * 2;
-  int ns = (target + tiles2d - 1) / tiles2d;
+  int ns = (target_blocks + tiles2d - 1) / tiles2d;
   const int max_ns = (int)((nr + 15) / 16);
   if (ns > max_ns) ns = max_ns;
   if (ns > 256) ns = 256;
   if (ns < 1) ns = 1;
   p.rps = (int)((nr + ns - 1) / ns);
   p.nsplit = (int)((nr + p.rps - 1) / p.rps);
-  p.dbg = getenv("CSG_WW_DBG") ? atoi(getenv("CSG_WW_DBG")) : 0;      // (read per call: tools/wgrad_ablate.py flips it)
   return CSG_OK;
 }
 
@@ -521,10 +509,8 @@ int csg_wino4_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy
   const size_t ep_bytes = (size_t)2 * 18 * 32 * WW_EXR * 4;
   const size_t shm = (size_t)WW_LDS_FLOATS * 4 > ep_bytes ? (size_t)WW_LDS_FLOATS * 4 : ep_bytes;
   if (attr_once.pending(dev)) {
-    for (const void* fn : {(const void*)k_wino4_wgrad<true>, (const void*)k_wino4_wgrad<false>}) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_wino4_bwd_weight: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    }
+    hipError_t e = hipFuncSetAttribute((const void*)k_wino4_wgrad<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_wino4_bwd_weight: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
     attr_once.mark(dev);
   }
   hipStream_t s = (hipStream_t)stream;
@@ -532,10 +518,7 @@ int csg_wino4_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy
   {
     ProfScope ps(K_WINO4_WGRAD, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
     const dim3 grid((unsigned)(p.cblocks * p.kblocks * 2 * p.nsplit));
-    if (p.dbg & 8)                               // the staggered form (measured equal: DESIGN.md 8) stays selectable
-      CSG_LAUNCH(k_wino4_wgrad<true>, grid, dim3(WW_THREADS), shm, s, p, x, dy, workspace, dbslabs);
-    else
-      CSG_LAUNCH(k_wino4_wgrad<false>, grid, dim3(WW_THREADS), shm, s, p, x, dy, workspace, dbslabs);
+    CSG_LAUNCH(k_wino4_wgrad<false>, grid, dim3(WW_THREADS), shm, s, p, x, dy, workspace, dbslabs);
     rc = check_launch("csg_wino4_bwd_weight");
     if (rc) return rc;
   }

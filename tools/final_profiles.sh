@@ -55,7 +55,6 @@ python3 bench.py --config C5 --batch 6 --no_cpu_baseline --no_vgg_variant \
 python3 tools/conv_shapes.py > "$O/${TAG}_conv_shapes.txt" 2> /dev/null
 python3 tools/wgrad_bench.py > "$O/${TAG}_wgrad_bench.txt" 2> /dev/null
 python3 tools/wino4_ab.py 2> /dev/null | grep -v amdgpu > "$O/${TAG}_wino4_ab.txt" || true
-python3 tools/wgrad_ablate.py 2> /dev/null | grep -v amdgpu > "$O/${TAG}_wgrad_ablate.txt" || true
 python3 tools/graph_timing.py C4 2> /dev/null | grep '^C4' > "$O/${TAG}_graph_timing_C4.txt" || true
 
 tail -c 400 "$O/${TAG}_bench_under_rocprof.json"; head -c 600 "$O/${TAG}_pmc_traffic.json"; head -20 "$O/${TAG}_pmc_mfma.txt"

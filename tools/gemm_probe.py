@@ -1,4 +1,4 @@
-"""Developer aid: csg_gemm_nt alone on the graph encoder's shapes (raw C ABI), TFLOP/s.  CSG_GEMM_CFG=322|162 and CSG_GEMM_TN_ROWS=32|16 select the variants."""
+"""Developer aid: csg_gemm_nt and csg_gemm_tn alone on the graph encoder's shapes (raw C ABI), TFLOP/s."""
 import ctypes
 import os
 import sys
@@ -27,7 +27,7 @@ for M, K, N in [(96000, 384, 512), (96000, 512, 1152), (96000, 1408, 512), (9600
     e1.record()
     torch.cuda.synchronize()
     t = e0.elapsed_time(e1) / 20
-    print("nt cfg %s  M %7d K %4d N %4d  %.3f ms  %.1f TFLOP/s" % (os.environ.get("CSG_GEMM_CFG", "default"), M, K, N, t, 2.0 * M * K * N / t / 1e9))
+    print("nt  M %7d K %4d N %4d  %.3f ms  %.1f TFLOP/s" % (M, K, N, t, 2.0 * M * K * N / t / 1e9))
 
 for M, N, K in [(96000, 512, 384), (96000, 1152, 512), (96000, 512, 1408), (96000, 512, 512), (96000, 128, 512), (1048576, 64, 128)]:
     dy = torch.randn(M, N, device=dev)
@@ -49,5 +49,4 @@ for M, N, K in [(96000, 512, 384), (96000, 1152, 512), (96000, 512, 1408), (9600
     e1.record()
     torch.cuda.synchronize()
     t = e0.elapsed_time(e1) / 20
-    print("tn rows %s  M %7d N %4d K %4d  %.3f ms  %.1f TFLOP/s  (workspace %d MB)" % (os.environ.get("CSG_GEMM_TN_ROWS", "16"), M, N, K, t,
-                                                                                 2.0 * M * K * N / t / 1e9, nbytes >> 20))
+    print("tn  M %7d N %4d K %4d  %.3f ms  %.1f TFLOP/s  (workspace %d MB)" % (M, N, K, t, 2.0 * M * K * N / t / 1e9, nbytes >> 20))

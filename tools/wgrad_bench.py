@@ -2,7 +2,7 @@
 raw C-ABI calls at the bench's shapes (B = 16): ms, algorithmic TFLOP/s (2*M*9*Cin*Cout / time), executed fraction of the
 fp32 MFMA peak (36/144 resp. 64/144 of the algorithmic FLOPs), error of both against each other.
 
-    python tools/wgrad_bench.py [shape indices...] [--blocks N]      (CSG_WINO4_WGRAD_BLOCKS=N: target blocks per launch)
+    python tools/wgrad_bench.py [shape indices...]
 """
 import os
 import sys
