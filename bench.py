@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 256x256 images/sec for one full G+D training step (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one iteration of scripts/train.py:353-393 (graph encoder + AttSPADE generator forward,
 generator losses through two PatchGAN passes, backward + Adam; discriminator losses through two more
@@ -12,6 +12,12 @@ not available offline).
 For N > 1 the driver launches this file under torch.distributed.run: one rank per GPU, RCCL
 gradient all-reduce + SyncBN statistics, per-GPU batch fixed (weak scaling).  Rank 0 prints ONE
 JSON line.  Inputs are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line.  --full adds
+everything else, each after the timed region: the eager replay of the timed steps, per-kernel tables and rooflines,
+the generator-only passes, the VGG-on variant, the config-C5 leg, and the CPU baseline with the oracle parity
+checks (parity_b16, parity_step4), whose failure makes the exit status non-zero.  Both modes run the same
+steps up to the end of the timed region.
 """
 import argparse
 import json
@@ -38,7 +44,9 @@ def parse():
     p.add_argument("--ndf", type=int, default=64)
     p.add_argument("--use_img_disc", type=int, default=0,
                    help="0 = the reference's default COCO/VG recipe (image + object discriminators); 1 = image only")
-    p.add_argument("--no_cpu_baseline", action="store_true")
+    p.add_argument("--no_cpu_baseline", action="store_true",
+                   help="skip the two untimed parity steps on batch 0 (the timed steps then start from other weights) and, "
+                        "with --full, the CPU baseline and the oracle parity checks")
     p.add_argument("--vgg_loss", type=int, default=0,
                    help="1 = keep the VGG perceptual term (reference default; random-feature VGG19 here, the "
                         "pretrained weights cannot be downloaded); 0 = --no_vgg_loss, the configuration "
@@ -55,6 +63,11 @@ def parse():
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last timed step computed (losses, bbox predictions, generated "
                         "images, a fixed sample of the updated weights) as DIR/<name>.npy, rank 0 only (step_outputs)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run the eager replay, per-kernel tables and rooflines, generator-only "
+                        "passes, VGG-on variant, C5 leg and CPU baseline with the oracle parity checks (--no_prof, "
+                        "--no_gen_metric, --no_vgg_variant, --no_c5_leg and --no_cpu_baseline skip single legs of it); "
+                        "without it the line holds the headline figure only")
     args = p.parse_args()
     if args.steps < 1:
         p.error("--steps must be at least 1")
@@ -411,16 +424,21 @@ def main():
         torch.cuda.synchronize()
 
     # parity of the benchmarked workload (N = 1): step 0 on batch 0 is kept (losses + generated image) together with a
-    # CPU snapshot of the weights it started from; the cpu_baseline leg replays exactly that step on the oracle
+    # CPU snapshot of the weights it started from; the cpu_baseline leg replays exactly that step on the oracle.
+    # The parity steps (this one and the later one below) are taken in plain runs too, where nothing of them is kept:
+    # they are part of the trainer's step sequence, so the timed steps start from the same weights with or without --full.
     check = world == 1 and not args.no_cpu_baseline
+    keep = check and args.full
     snapshot = batch0_cpu = gpu_step0 = None
     if check:
-        snapshot = T.state_snapshot(trainer)
-        batch0_cpu = make_batch(vocab, bc, seed=0)
+        if keep:
+            snapshot = T.state_snapshot(trainer)
+            batch0_cpu = make_batch(vocab, bc, seed=0)
         G0, D0 = trainer.step(batches[0])
         torch.cuda.synchronize()
-        gpu_step0 = ({k: (v.detach().cpu() if k == "bbox_pred_all" else float(v.detach())) for k, v in G0.items()},
-                     {k: float(v.detach()) for k, v in D0.items()}, trainer.last_model_out[0].detach().float().cpu())
+        if keep:
+            gpu_step0 = ({k: (v.detach().cpu() if k == "bbox_pred_all" else float(v.detach())) for k, v in G0.items()},
+                         {k: float(v.detach()) for k, v in D0.items()}, trainer.last_model_out[0].detach().float().cpu())
         del G0, D0
 
     # parity after PARITY_LATER_STEP optimiser steps: a CPU snapshot of the LIVE weights, then one more (untimed) step on batch 0
@@ -434,16 +452,18 @@ def main():
         g = trainer.graphs
         before = g.replays if g is not None else 0
         later["index"] = done[0]
-        later["snapshot"] = T.state_snapshot(trainer)
+        if keep:
+            later["snapshot"] = T.state_snapshot(trainer)
         Gk, Dk = trainer.step(batches[0])
         torch.cuda.synchronize()
-        later["step"] = ({k: (v.detach().cpu() if k == "bbox_pred_all" else float(v.detach())) for k, v in Gk.items()},
-                         {k: float(v.detach()) for k, v in Dk.items()}, trainer.last_model_out[0].detach().float().cpu())
+        if keep:
+            later["step"] = ({k: (v.detach().cpu() if k == "bbox_pred_all" else float(v.detach())) for k, v in Gk.items()},
+                             {k: float(v.detach()) for k, v in Dk.items()}, trainer.last_model_out[0].detach().float().cpu())
         later["replayed"] = bool(g is not None and g.replays > before)
         done[0] += 1
 
     def untimed_step(b):
-        if check and later["step"] is None and done[0] == PARITY_LATER_STEP:
+        if check and later["index"] is None and done[0] == PARITY_LATER_STEP:
             take_later_parity()
         trainer.step(b)
         done[0] += 1
@@ -462,15 +482,16 @@ def main():
                 break
             untimed_step(batches[(args.warmup + i) % nb])
     if check:
-        while later["step"] is None and done[0] < PARITY_LATER_STEP:
+        while later["index"] is None and done[0] < PARITY_LATER_STEP:
             untimed_step(batches[done[0] % nb])
-        if later["step"] is None:
+        if later["index"] is None:
             take_later_parity()
     sync()
     snapshot_k, gpu_stepk, k_index = later["snapshot"], later["step"], later["index"]
     if not args.no_prof and not graphs_on:
         # events only around the dominant kernel inside the timed region (mode 2): a pair on every one of the
-        # ~1100 launches of a step would cost ~10 ms/step of queue time and distort `value`
+        # ~1100 launches of a step would cost ~10 ms/step of queue time and distort `value`.  On in plain runs too (only
+        # --full reads them), so that the timed region is the same in both
         _lib.prof_reset()
         _lib.prof_enable(2)
     D.comm_reset()
@@ -487,11 +508,12 @@ def main():
               flush=True)
     graph_stats = eager_ms = None
     if graphs_on:
-        # kernels inside a replayed graph carry no per-dispatch events: the dominant kernel's event timing (mode 2) is
-        # taken over the SAME number of steps of the same batches run eagerly right after the timed region
         graph_stats = {"captures": trainer.graphs.captures, "replays": trainer.graphs.replays,
                        "eager_steps": trainer.graphs.eager_steps, "encoder_captures": trainer.graphs.sg_captures,
                        "encoder_replays": trainer.graphs.sg_replays}
+    if graphs_on and args.full:
+        # kernels inside a replayed graph carry no per-dispatch events: the dominant kernel's event timing (mode 2) is
+        # taken over the SAME number of steps of the same batches run eagerly right after the timed region
         trainer.use_graphs = False
         trainer.step(batches[0])
         sync()
@@ -509,7 +531,7 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
     prof, prof_all, prof_all_steps = {}, {}, 2
-    if not args.no_prof:
+    if not args.no_prof and args.full:
         prof = _lib.prof_read()
         # untimed: two more steps with an event pair on EVERY launch, for the per-kernel table (one stream: _overlap)
         _overlap(False)
@@ -527,10 +549,10 @@ def main():
 
     # BASELINE.json's second metric: the SPADE generator alone, forward + backward (no optimiser step)
     gen_ms = gen_exec_ratio = None
-    # (the auxiliary legs below — generator-only passes, the VGG-on variant, the C5 leg — run on ONE rank only: the N > 1 line
-    # is the scaling measurement, and every extra trainer construction there is more collectives between the timed region
-    # and the JSON line it has to deliver)
-    if H in (64, 128, 256) and args.ngf == 64 and not args.no_gen_metric and world == 1:
+    # (the auxiliary legs below — generator-only passes, the VGG-on variant, the C5 leg — run with --full, on ONE rank only:
+    # the N > 1 line is the scaling measurement, and every extra trainer construction there is more collectives between the
+    # timed region and the JSON line it has to deliver)
+    if args.full and H in (64, 128, 256) and args.ngf == 64 and not args.no_gen_metric and world == 1:
         gen = trainer.model.layout_to_image_model
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 3
@@ -563,7 +585,7 @@ def main():
     # SURVEY.md 8(d)'s --no_vgg_loss configuration.  A short second measurement with the term on (random-feature
     # VGG19: the pretrained weights cannot be downloaded) makes that number visible to the driver as well.
     vgg_variant = None
-    if not args.vgg_loss and not args.no_vgg_variant and world == 1:
+    if args.full and not args.vgg_loss and not args.no_vgg_variant and world == 1:
         os.environ.setdefault("CSG_VGG19_RANDOM", "1")
         argv_v = [a for a in opt_argv if a != "--no_vgg_loss"]
         opt_v = T.make_opt(vocab, argv_v + ["--batch_size", str(args.batch * world), "--gpu_ids",
@@ -592,7 +614,7 @@ def main():
         del tv
 
     c5 = None
-    if world == 1 and args.config == "C3" and H == 256 and not args.no_c5_leg and not args.no_prof:
+    if args.full and world == 1 and args.config == "C3" and H == 256 and not args.no_c5_leg and not args.no_prof:
         trainer = None
         import gc
         gc.collect()
@@ -620,12 +642,13 @@ def main():
         "losses_finite": loss_ok,
     }
     if graph_stats is not None:
-        out["hip_graphs"] = dict(graph_stats, eager_ms_per_step=round(eager_ms, 2),
-                                 note="timed region: generator + PatchGAN forward/backward/Adam replayed from 4 captured HIP "
-                                      "graphs per step and the scene-graph encoder from its own (encoder_*: one per bucket of "
-                                      "the batch's triplet count), object-crop discriminator enqueued eagerly "
-                                      "(canonicalsg2im_amd/graphs.py); eager_ms_per_step = the same steps without replay "
-                                      "(with the dominant kernel's events on)")
+        note = ("timed region: generator + PatchGAN forward/backward/Adam replayed from 4 captured HIP graphs per step and the "
+                "scene-graph encoder from its own (encoder_*: one per bucket of the batch's triplet count), object-crop "
+                "discriminator enqueued eagerly (canonicalsg2im_amd/graphs.py)")
+        if eager_ms is not None:
+            graph_stats["eager_ms_per_step"] = round(eager_ms, 2)
+            note += "; eager_ms_per_step = the same steps without replay (with the dominant kernel's events on)"
+        out["hip_graphs"] = dict(graph_stats, note=note)
     # Winograd F(2x2,3x3) / F(3x3,2x2) issue 16 multiplications where the direct convolution needs 36: the kernels' `work`
     # is the ALGORITHMIC FLOP count (2*M*9*Cin*Cout, what FlopCounterMode counts for the layer); the matrix pipe EXECUTES
     # 4/9 of it.  Every `frac` below is executed FLOPs / time / peak (a hardware utilisation, <= 1 by construction);
@@ -757,7 +780,7 @@ def main():
     if c5 is not None:
         out["c5"] = c5
     parity_ok = True
-    if check:                                             # the CPU leg runs at N = 1 only
+    if keep:                                              # the CPU leg runs with --full at N = 1 only
         out["cpu_baseline"], out["parity_b16"], pk = cpu_baseline(snapshot, batch0_cpu, gpu_step0, H, snapshot_k, gpu_stepk,
                                                                     k_index, dense=cfg.graph == "closure")
         parity_ok = out["parity_b16"]["ok"]

@@ -191,6 +191,13 @@ def test_steps_must_be_positive(monkeypatch):
     assert a.steps == 3 and a.dump_outputs == "out"
 
 
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full"])
+    assert bench.parse().full is True
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_dump_outputs_repeat_run_to_run_and_follow_steps(tmp_path):
@@ -216,3 +223,39 @@ def test_dump_outputs_repeat_run_to_run_and_follow_steps(tmp_path):
     assert a["imgs_pred"].shape == (2, 3, 64, 64)
     assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a), [k for k in a if not np.array_equal(a[k], b[k])]
     assert set(a) == set(c) and not np.array_equal(a["weights_generator_sample"], c["weights_generator_sample"])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_run_times_the_same_steps_as_a_full_run(tmp_path):
+    """Without --full the line holds the headline only; --full adds the legs after the timed region (tables, CPU baseline,
+    oracle parity), and both runs time the same steps: their dumped outputs are identical, bit for bit."""
+    import json
+    import subprocess
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+            "--image_size", "64", "--ngf", "8", "--ndf", "8", "--no_vgg_variant"]
+    lines, dumps = {}, {}
+    for tag, extra in (("plain", []), ("full", ["--full"])):
+        out = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], cwd=ROOT, capture_output=True, text=True,
+                             timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        found = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1
+        lines[tag] = json.loads(found[0])
+        dumps[tag] = {f[:-4]: np.load(str(tmp_path / tag / f)) for f in sorted(os.listdir(str(tmp_path / tag)))}
+    plain, full = lines["plain"], lines["full"]
+    headline = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "losses_finite"}
+    assert headline <= set(plain) and headline <= set(full)
+    assert plain["metric"] == full["metric"] and plain["unit"] == full["unit"] == "img/s" and plain["dtype"] == "f32"
+    legs = {"cpu_baseline", "parity_b16", "parity_later_step", "kernels", "hbm_kernels", "roofline", "roofline_step"}
+    assert not legs & set(plain), legs & set(plain)
+    assert {"cpu_baseline", "parity_b16", "parity_later_step", "kernels"} <= set(full)
+    assert full["parity_b16"]["ok"] and full[full["parity_later_step"]]["ok"]
+    assert ("hip_graphs" in plain) == ("hip_graphs" in full)
+    if "hip_graphs" in plain:
+        assert "eager_ms_per_step" in full["hip_graphs"] and "eager_ms_per_step" not in plain["hip_graphs"]
+        assert {k: v for k, v in plain["hip_graphs"].items() if k != "note"} == \
+               {k: v for k, v in full["hip_graphs"].items() if k not in ("note", "eager_ms_per_step")}
+    a, b = dumps["plain"], dumps["full"]
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a), [k for k in a if not np.array_equal(a[k], b[k])]

@@ -10,7 +10,7 @@ O=gpurun_out
 mkdir -p "$O"
 # the counter passes see C3 training steps ONLY (no CPU leg, no VGG variant, no generator-only passes, no C5 leg): their
 # per-launch averages cover exactly the launch mix of the timed region
-PMC_FLAGS="--steps 3 --warmup 1 --no_c5_leg --no_vgg_variant --no_cpu_baseline --no_gen_metric"
+PMC_FLAGS="--full --steps 3 --warmup 1 --no_c5_leg --no_vgg_variant --no_cpu_baseline --no_gen_metric"
 export PMC_FLAGS_NOTE="bench.py $PMC_FLAGS"
 
 first_csv() {   # first file matching a pattern under a directory, or fail loudly
@@ -20,11 +20,11 @@ first_csv() {   # first file matching a pattern under a directory, or fail loudl
   echo "$f"
 }
 
-# the driver's exact command (BENCH_r*.json "cmd"): the parity gate is validated at THESE flags
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/${TAG}_bench.json.tmp" 2> "$O/${TAG}_bench.err"
+# the headline command (BENCH_r*.json "cmd") with --full: the parity gate is validated at THESE flags
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/${TAG}_bench.json.tmp" 2> "$O/${TAG}_bench.err"
 mv "$O/${TAG}_bench.json.tmp" "$O/${TAG}_bench.json"
 
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/p_stats" -- python3 bench.py --steps 10 --warmup 2 --no_c5_leg \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/p_stats" -- python3 bench.py --full --steps 10 --warmup 2 --no_c5_leg \
   > "$O/${TAG}_bench_under_rocprof.json.tmp" 2> "$O/p_err1.txt"
 cp "$(first_csv "$O/p_stats" '*kernel_stats.csv')" "$O/${TAG}_kernel_stats.csv"
 mv "$O/${TAG}_bench_under_rocprof.json.tmp" "$O/${TAG}_bench_under_rocprof.json"
@@ -48,9 +48,9 @@ python3 tools/pmc_summarize.py "$O/pmc_mfma" > "$O/${TAG}_pmc_mfma.txt.tmp"
 mv "$O/${TAG}_pmc_mfma.txt.tmp" "$O/${TAG}_pmc_mfma.txt"
 rm -rf "$O/pmc_mfma"
 
-python3 bench.py --config C2 --image_size 128 --no_cpu_baseline --no_vgg_variant > "$O/${TAG}_bench_C2.json" 2> /dev/null
-python3 bench.py --config C4 --batch 4 --no_cpu_baseline --no_vgg_variant > "$O/${TAG}_bench_C4.json" 2> /dev/null
-python3 bench.py --config C5 --batch 6 --no_cpu_baseline --no_vgg_variant \
+python3 bench.py --full --config C2 --image_size 128 --no_cpu_baseline --no_vgg_variant > "$O/${TAG}_bench_C2.json" 2> /dev/null
+python3 bench.py --full --config C4 --batch 4 --no_cpu_baseline --no_vgg_variant > "$O/${TAG}_bench_C4.json" 2> /dev/null
+python3 bench.py --full --config C5 --batch 6 --no_cpu_baseline --no_vgg_variant \
   > "$O/${TAG}_bench_C5_dense_graphs.json" 2> /dev/null
 python3 tools/conv_shapes.py > "$O/${TAG}_conv_shapes.txt" 2> /dev/null
 python3 tools/wgrad_bench.py > "$O/${TAG}_wgrad_bench.txt" 2> /dev/null

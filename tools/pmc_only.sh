@@ -6,7 +6,7 @@ TAG="${1:?usage: pmc_only.sh <tag>}"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
 mkdir -p "$O"
-PMC_FLAGS="--steps 3 --warmup 1 --no_c5_leg --no_vgg_variant --no_cpu_baseline --no_gen_metric"
+PMC_FLAGS="--full --steps 3 --warmup 1 --no_c5_leg --no_vgg_variant --no_cpu_baseline --no_gen_metric"
 export PMC_FLAGS_NOTE="bench.py $PMC_FLAGS"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -- python3 bench.py $PMC_FLAGS > /dev/null 2> "$O/p_err2.txt"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write" -- python3 bench.py $PMC_FLAGS > /dev/null 2> "$O/p_err3.txt"

@@ -5,7 +5,7 @@ run() { # label, env..., -- args
   label=$1; shift
   envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  out=$(env "${envs[@]}" python bench.py --no_cpu_baseline --no_vgg_variant --no_gen_metric --steps 12 --warmup 3 "$@" 2>/dev/null | python -c "
+  out=$(env "${envs[@]}" python bench.py --full --no_cpu_baseline --no_vgg_variant --no_gen_metric --steps 12 --warmup 3 "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); k=d.get('kernels',{})
 def g(n): return k.get(n,{}).get('ms_per_step',0)
