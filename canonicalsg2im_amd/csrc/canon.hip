@@ -17,6 +17,8 @@
 // in (ascending predicate id, s, o) order.
 #include "csg_common.h"
 
+#include <vector>
+
 using namespace csg;
 
 namespace {
@@ -450,6 +452,388 @@ int fill_params(CanonParams* P, int64_t O, const int32_t* pred_ids, int64_t imag
   return 1;
 }
 
+
+// ==== annotated relationships and any vocabulary (packed_vg.py:127-142) ==========================================
+// The graph of a sample is cut per (sample, predicate): one 256x256 bit matrix of a predicate fits LDS, the 44+ of a
+// Visual Genome vocabulary do not.  Phases that need another block's results are separate launches:
+//   geometry   k_canon_build (above) on the six location relations alone: their per-relation minimal graphs
+//   scatter    (sample, predicate): U = annotated rows | geometric minimal graph | __in_image__ dummies  (np.unique)
+//   draws      (sample): the prefix count of original rows over the non-meta predicates by ascending id
+//   converse   (sample, predicate): one uniform per row of U, in (s, o) order; converse edges OR-ed into V of the chosen
+//              predicate (integer atomics)
+//   close      (sample, predicate): U <- U | V; Warshall on U; V <- closure - U; per-row counts
+//   offsets    (sample): per-row counts -> output positions, (s, p, o) for the originals, (p, s, o) for the extras
+//   emit       (sample, predicate): the rows of U and V at those positions, then the collate's padding
+constexpr int GMAXP = 256;       // predicates of a vocabulary
+
+struct GenParams {
+  int B, P, O;
+  int K;                         // non-meta predicates; a draw chooses among K - 1 candidates and "none"
+  int image_id;
+  int pid_padding, pid_in_image;
+  int include_dummies, learned_transitivity;
+  signed char role[GMAXP];       // CSG_CANON_ROLE_*, or the location slot 0..5
+  unsigned char nm[GMAXP];       // the non-meta predicate ids, ascending
+  unsigned char rank[GMAXP];     // position of a non-meta predicate in nm
+};
+
+struct GenWs {
+  uint64_t* U;                   // [B][P][MAXN][W] original rows of a predicate
+  uint64_t* V;                   // [B][P][MAXN][W] converse edges drawn into it, then its transitive extras
+  int* rc;                       // [B][P][MAXN] originals per row -> their first output position
+  int* xc;                       // [B][P][MAXN] extras per row -> their first output position
+  int* tot;                      // [B][P][2] originals (after scatter, then after close), extras
+  int* flag;                     // [B][P] converse edges were drawn into the predicate
+  int* doff;                     // [B][P] first draw of the predicate's rows within the sample
+  int64_t* geo_counts;           // [B][2] k_canon_build's counts (unused)
+  int64_t* nob;                  // [B] objects per sample
+  int* rbeg;                     // [B + 1] first annotated row of a sample
+  uint32_t* rows;                // annotated rows: s | o << 8 | p << 16
+};
+
+__host__ __device__ inline int64_t gen_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+// byte offsets of the regions; the annotated rows come last, so every region but them depends on (B, P) only
+inline int64_t gen_layout(int64_t B, int64_t P, int64_t R, void* base, GenWs* w) {
+  char* b = (char*)base;
+  int64_t at = gen_align(B * kWsBytesPerSample);
+  const int64_t mat = B * P * MAXN * W * 8, row = B * P * MAXN * 4;
+  if (w) {
+    w->U = (uint64_t*)(b + at);
+    w->V = (uint64_t*)(b + at + mat);
+  }
+  at += 2 * mat;
+  if (w) {
+    w->rc = (int*)(b + at);
+    w->xc = (int*)(b + at + row);
+  }
+  at += 2 * row;
+  if (w) w->tot = (int*)(b + at);
+  at += gen_align(B * P * 2 * 4);
+  if (w) w->flag = (int*)(b + at);
+  at += gen_align(B * P * 4);
+  if (w) w->doff = (int*)(b + at);
+  at += gen_align(B * P * 4);
+  if (w) w->geo_counts = (int64_t*)(b + at);
+  at += gen_align(B * 2 * 8);
+  if (w) w->nob = (int64_t*)(b + at);
+  at += gen_align(B * 8);
+  if (w) w->rbeg = (int*)(b + at);
+  at += gen_align((B + 1) * 4);
+  if (w) w->rows = (uint32_t*)(b + at);
+  at += gen_align(B * R * 4);
+  return at;
+}
+
+__device__ __forceinline__ int gen_n(const GenWs& w, const GenParams& P, int b) {
+  int n = (int)w.nob[b];
+  return n > MAXN ? MAXN : n;
+}
+
+__device__ __forceinline__ int block_sum(int v, int* sm) {
+  int total = 0;
+  (void)block_exscan(v, sm, &total);
+  return total;
+}
+
+// ---- scatter: U[b][p] = annotated rows of p | the geometric minimal graph (location slots) | the dummies (__in_image__)
+__global__ __launch_bounds__(256) void k_gen_scatter(GenParams P, const int64_t* __restrict__ objs0, GenWs w, void* geo) {
+  __shared__ uint64_t adj[MAXN][W];
+  __shared__ int scan[256];
+  const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int n = gen_n(w, P, b), nw = (n + 63) >> 6;
+  const int role = P.role[p];
+  for (int i = tid; i < n * W; i += 256) (&adj[0][0])[i] = 0;
+  int img = -1;
+  if (role == CSG_CANON_ROLE_IN_IMAGE && P.include_dummies) {      // base_dataset.py:141-151
+    scan[tid] = (tid < n && objs0[(int64_t)b * P.O + tid] == (int64_t)P.image_id) ? tid : MAXN;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) scan[tid] = min(scan[tid], scan[tid + o]);
+      __syncthreads();
+    }
+    img = scan[0] < MAXN ? scan[0] : -1;
+  }
+  __syncthreads();
+  if (tid < n) {
+    if (role >= 0) {                                                  // base_dataset.py:83-87
+      const uint64_t* Rg = ws_R(geo, b) + ((int64_t)role * MAXN + tid) * W;
+      for (int k = 0; k < nw; ++k) adj[tid][k] = Rg[k];
+    }
+    if (img >= 0 && tid != img) adj[tid][img >> 6] |= 1ull << (img & 63);
+  }
+  __syncthreads();
+  const int r0 = w.rbeg[b], r1 = w.rbeg[b + 1];
+  for (int r = r0 + tid; r < r1; r += 256) {                          // packed_vg.py:127-138
+    const uint32_t v = w.rows[r];
+    if ((int)(v >> 16) != p) continue;
+    const int s = v & 255, o = (v >> 8) & 255;
+    atomicOr((unsigned long long*)&adj[s][o >> 6], 1ull << (o & 63));
+  }
+  __syncthreads();
+  int c = 0;
+  if (tid < n) {
+    const int64_t at = (((int64_t)b * P.P + p) * MAXN + tid) * W;
+    for (int k = 0; k < nw; ++k) {
+      const uint64_t m = adj[tid][k];
+      w.U[at + k] = m;
+      w.V[at + k] = 0;
+      c += __popcll(m);
+    }
+  }
+  const int total = block_sum(c, scan);
+  if (tid == 0) {
+    w.tot[((int64_t)b * P.P + p) * 2 + 0] = total;
+    w.tot[((int64_t)b * P.P + p) * 2 + 1] = 0;
+    w.flag[(int64_t)b * P.P + p] = 0;
+  }
+}
+
+// ---- draws: the first draw of each non-meta predicate's rows (predicates by ascending id); counts[b] = {draws, 0}
+__global__ __launch_bounds__(256) void k_gen_draws(GenParams P, GenWs w, int64_t* __restrict__ counts) {
+  __shared__ int scan[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int c = (tid < P.P && P.role[tid] != CSG_CANON_ROLE_PADDING && P.role[tid] != CSG_CANON_ROLE_IN_IMAGE)
+                    ? w.tot[((int64_t)b * P.P + tid) * 2] : 0;
+  int total = 0;
+  const int ex = block_exscan(c, scan, &total);
+  if (tid < P.P) w.doff[(int64_t)b * P.P + tid] = ex;
+  if (tid == 0) {
+    counts[b * 2 + 0] = total;
+    counts[b * 2 + 1] = 0;
+  }
+}
+
+// ---- converse (base_dataset.py:104-107, graphs_utils.py:126-152): block (rel, b) draws for the rows of U[b][rel]
+__global__ __launch_bounds__(256) void k_gen_converse(GenParams P, GenWs w, const double* __restrict__ cdf,
+                                                      const double* __restrict__ uniforms, const int64_t* __restrict__ u_off,
+                                                      float* __restrict__ conv_counts) {
+  __shared__ int scan[256];
+  __shared__ int hist[GMAXP];                  // choice 0..K-2 = candidate, K-1 = none
+  const int rel = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int role = P.role[rel];
+  if (role == CSG_CANON_ROLE_PADDING || role == CSG_CANON_ROLE_IN_IMAGE) return;
+  if (w.tot[((int64_t)b * P.P + rel) * 2] == 0) return;
+  const int n = gen_n(w, P, b), nw = (n + 63) >> 6, K = P.K, q = P.rank[rel];
+  if (tid < K) hist[tid] = 0;
+  const uint64_t* U = w.U + (((int64_t)b * P.P + rel) * MAXN) * W;
+  int c = 0;
+  if (tid < n)
+    for (int k = 0; k < nw; ++k) c += __popcll(U[tid * W + k]);
+  int total = 0;
+  int64_t k0 = u_off[b] + w.doff[(int64_t)b * P.P + rel] + block_exscan(c, scan, &total);   // syncs: hist is zero
+  const double* cd = cdf + (int64_t)rel * K;
+  if (tid < n) {
+    const int s = tid;
+    for (int k = 0; k < nw; ++k) {
+      uint64_t m = U[s * W + k];
+      while (m) {
+        const int o = k * 64 + (__ffsll((long long)m) - 1);
+        m &= m - 1;
+        const double u = uniforms[k0++];
+        int lo = 0, hi = K - 1;                                // searchsorted(cdf, u, side='right'), at most K - 1
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (cd[mid] <= u) lo = mid + 1; else hi = mid;
+        }
+        atomicAdd(&hist[lo], 1);
+        if (lo < K - 1) {                                      // converse edge (o, cand, s)
+          const int cand = P.nm[lo + (lo >= q)];
+          atomicOr((unsigned long long*)&w.V[(((int64_t)b * P.P + cand) * MAXN + o) * W + (s >> 6)], 1ull << (s & 63));
+          w.flag[(int64_t)b * P.P + cand] = 1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < K) {                                               // conv_counts[b][rel][r] (base_dataset.py:93), r = P: none
+    const int col = tid < K - 1 ? P.nm[tid + (tid >= q)] : P.P;
+    conv_counts[((int64_t)b * P.P + rel) * (P.P + 1) + col] = (float)hist[tid];
+  }
+}
+
+// ---- close (base_dataset.py:109-120, graphs_utils.py:15-27,96-100): block (p, b)
+__global__ __launch_bounds__(256) void k_gen_close(GenParams P, GenWs w) {
+  __shared__ uint64_t adj[MAXN][W];
+  __shared__ int scan[256];
+  const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int64_t bp = (int64_t)b * P.P + p;
+  const int conv = w.flag[bp];
+  if (w.tot[bp * 2] == 0 && !conv) return;                     // empty predicate: tot stays {0, 0}
+  const int role = P.role[p];
+  const bool meta = role == CSG_CANON_ROLE_PADDING || role == CSG_CANON_ROLE_IN_IMAGE;
+  const int n = gen_n(w, P, b), nw = (n + 63) >> 6;
+  uint64_t* U = w.U + bp * MAXN * W;
+  uint64_t* V = w.V + bp * MAXN * W;
+  uint64_t cur[W] = {0, 0, 0, 0};             // the current graph's row, kept for closure - current
+  int c = 0;
+  if (tid < n) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      if (k < nw) {
+        cur[k] = U[tid * W + k] | V[tid * W + k];
+        if (conv) U[tid * W + k] = cur[k];
+        adj[tid][k] = cur[k];
+        c += __popcll(cur[k]);
+      }
+    }
+    w.rc[bp * MAXN + tid] = c;
+  }
+  const int n_orig = block_sum(c, scan);
+  int n_x = 0;
+  if (P.learned_transitivity && !meta) {
+    for (int i = 0; i < n; ++i) {
+      __syncthreads();
+      uint64_t any = 0;
+      for (int k = 0; k < nw; ++k) any |= adj[i][k];
+      if (!any) continue;                                      // an empty row i adds nothing (uniform: LDS read after a barrier)
+      if (tid < n && tid != i && ((adj[tid][i >> 6] >> (i & 63)) & 1ull))
+        for (int k = 0; k < nw; ++k) adj[tid][k] |= adj[i][k];
+    }
+    __syncthreads();
+    int cx = 0;
+    if (tid < n) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        if (k < nw) {
+          const uint64_t x = adj[tid][k] & ~cur[k];
+          V[tid * W + k] = x;
+          cx += __popcll(x);
+        }
+      }
+      w.xc[bp * MAXN + tid] = cx;
+    }
+    n_x = block_sum(cx, scan);
+  }
+  if (tid == 0) {
+    w.tot[bp * 2 + 0] = n_orig;
+    w.tot[bp * 2 + 1] = n_x;
+  }
+}
+
+// ---- offsets: block b, thread s.  rc / xc become output positions in place.
+__global__ __launch_bounds__(256) void k_gen_offsets(GenParams P, GenWs w, int64_t* __restrict__ counts) {
+  __shared__ int scan[256];
+  __shared__ int tot[GMAXP][2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = gen_n(w, P, b);
+  if (tid < P.P) {
+    tot[tid][0] = w.tot[((int64_t)b * P.P + tid) * 2 + 0];
+    tot[tid][1] = w.tot[((int64_t)b * P.P + tid) * 2 + 1];
+  }
+  __syncthreads();
+  int c = 0;
+  if (tid < n)
+    for (int p = 0; p < P.P; ++p)
+      if (tot[p][0]) c += w.rc[((int64_t)b * P.P + p) * MAXN + tid];
+  int n_orig = 0;
+  int at = block_exscan(c, scan, &n_orig);                     // (s, p, o): rows first, predicates by ascending id
+  if (tid < n)
+    for (int p = 0; p < P.P; ++p) {
+      if (!tot[p][0]) continue;
+      int* rc = w.rc + ((int64_t)b * P.P + p) * MAXN + tid;
+      const int v = *rc;
+      *rc = at;
+      at += v;
+    }
+  int run = n_orig;                                            // (p, s, o): the extras after every original
+  for (int p = 0; p < P.P; ++p) {
+    if (!tot[p][1]) continue;                                  // uniform: tot is in LDS
+    int* xc = w.xc + ((int64_t)b * P.P + p) * MAXN + tid;
+    const int v = tid < n ? *xc : 0;
+    int t = 0;
+    const int e = block_exscan(v, scan, &t);
+    if (tid < n) *xc = run + e;
+    run += t;
+  }
+  if (tid == 0) {
+    counts[b * 2 + 0] = n_orig;
+    counts[b * 2 + 1] = run - n_orig;
+  }
+}
+
+// ---- emit: block (p, b) writes the originals and the extras of predicate p, and a share of the padding
+__global__ __launch_bounds__(256) void k_gen_emit(GenParams P, GenWs w, const int64_t* __restrict__ counts, int64_t T,
+                                                  int64_t* __restrict__ triplets, int64_t* __restrict__ ttype) {
+  const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int64_t bp = (int64_t)b * P.P + p;
+  int64_t* trip = triplets + (int64_t)b * T * 3;
+  int64_t* tt = ttype + (int64_t)b * T;
+  const int n = gen_n(w, P, b), nw = (n + 63) >> 6;
+  const int n_orig = w.tot[bp * 2 + 0], n_x = w.tot[bp * 2 + 1];
+  if (tid < n && n_orig) {
+    int64_t at = w.rc[bp * MAXN + tid];
+    const uint64_t* U = w.U + (bp * MAXN + tid) * W;
+    for (int k = 0; k < nw; ++k) {
+      uint64_t m = U[k];
+      while (m) {
+        const int o = k * 64 + (__ffsll((long long)m) - 1);
+        m &= m - 1;
+        if (at < T) put(trip, tt, at, tid, p, o, 0);
+        ++at;
+      }
+    }
+  }
+  if (tid < n && n_x) {
+    int64_t at = w.xc[bp * MAXN + tid];
+    const uint64_t* X = w.V + (bp * MAXN + tid) * W;
+    for (int k = 0; k < nw; ++k) {
+      uint64_t m = X[k];
+      while (m) {
+        const int o = k * 64 + (__ffsll((long long)m) - 1);
+        m &= m - 1;
+        if (at < T) put(trip, tt, at, tid, p, o, 1);
+        ++at;
+      }
+    }
+  }
+  const int64_t used = counts[b * 2 + 0] + counts[b * 2 + 1];
+  for (int64_t t = used + (int64_t)p * 256 + tid; t < T; t += (int64_t)P.P * 256)    // vg_collate_fn: packed_vg.py:207-212
+    put(trip, tt, t, 0, P.pid_padding, 0, 0);
+}
+
+// roles -> GenParams and the eight ids of k_canon_build; 0 if the table is not a vocabulary's
+int gen_params(GenParams* G, int32_t* pred_ids, const int32_t* roles, int64_t B, int64_t P, int64_t O, int64_t image_id,
+               int include_dummies, int learned_transitivity) {
+  int seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  G->B = (int)B;
+  G->P = (int)P;
+  G->O = (int)O;
+  G->image_id = (int)image_id;
+  G->include_dummies = include_dummies;
+  G->learned_transitivity = learned_transitivity;
+  G->K = 0;
+  for (int p = 0; p < P; ++p) {
+    const int r = roles[p];
+    int slot;
+    if (r == CSG_CANON_ROLE_PADDING) slot = 0;
+    else if (r == CSG_CANON_ROLE_IN_IMAGE) slot = 1;
+    else if (r >= 0 && r < NREL) slot = 2 + r;
+    else if (r == CSG_CANON_ROLE_OTHER) slot = -1;
+    else return 0;
+    G->role[p] = (signed char)r;
+    if (slot >= 0) {
+      if (seen[slot]++) return 0;
+      pred_ids[slot] = p;
+    }
+    if (slot != 0 && slot != 1) {
+      G->rank[p] = (unsigned char)G->K;
+      G->nm[G->K++] = (unsigned char)p;
+    }
+  }
+  for (int k = 0; k < 8; ++k)
+    if (!seen[k]) return 0;
+  G->pid_padding = pred_ids[0];
+  G->pid_in_image = pred_ids[1];
+  return 1;
+}
+
+#define GEN_CHECK_COMMON(fn)                                                                                           \
+  CSG_REQUIRE(B > 0 && P > 0, CSG_E_BADSHAPE, fn ": bad shape B=%ld P=%ld", (long)B, (long)P);                         \
+  CSG_REQUIRE(P <= GMAXP, CSG_E_UNSUPPORTED, fn ": at most %d predicates (got %ld)", GMAXP, (long)P);                  \
+  CSG_REQUIRE(roles && workspace, CSG_E_BADSHAPE, fn ": null argument");                                              \
+  CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, 0, nullptr, nullptr), CSG_E_BADSHAPE,                               \
+              fn ": workspace too small (%ld bytes)", (long)workspace_bytes)
 }  // namespace
 
 extern "C" {
@@ -509,6 +893,131 @@ int csg_canon_converse(const int64_t* objs0, const int64_t* n_objs, int64_t B, i
   CSG_LAUNCH(k_canon_converse, dim3((unsigned)B), dim3(256), 0, s, P, objs0, n_objs, workspace, cdf, uniforms, u_off,
              (int)num_preds, conv_counts, counts);
   return check_launch("csg_canon_converse");
+}
+
+int64_t csg_canon_general_workspace(int64_t B, int64_t P, int64_t R) {
+  if (B <= 0 || P <= 0 || P > GMAXP || R < 0) return -1;
+  return gen_layout(B, P, R, nullptr, nullptr);
+}
+
+int csg_canon_general_build(const int64_t* objs0, const float* boxes, const float* centers, const int64_t* n_objs,
+                            int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
+                            const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
+                            int64_t workspace_bytes, int64_t* counts, void* stream) {
+  GEN_CHECK_COMMON("csg_canon_general_build");
+  CSG_REQUIRE(O > 0 && R >= 0 && B * R < (1ll << 31), CSG_E_BADSHAPE, "csg_canon_general_build: bad shape O=%ld R=%ld", (long)O, (long)R);
+  CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "csg_canon_general_build: at most %d objects per sample (got %ld)", MAXN,
+              (long)O);
+  CSG_REQUIRE(objs0 && boxes && centers && n_objs && counts && (R == 0 || rel), CSG_E_BADSHAPE,
+              "csg_canon_general_build: null argument");
+  CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, R, nullptr, nullptr), CSG_E_BADSHAPE,
+              "csg_canon_general_build: workspace too small (%ld bytes, need %ld)", (long)workspace_bytes,
+              (long)gen_layout(B, P, R, nullptr, nullptr));
+  GenParams G;
+  int32_t ids[8];
+  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, O, image_id, include_dummies, 0), CSG_E_BADSHAPE,
+              "csg_canon_general_build: the role table needs one __padding__, one __in_image__ and each location "
+              "relation exactly once");
+  // every input is checked here, before anything is enqueued
+  const int64_t head = gen_align(B * 8) + gen_align((B + 1) * 4);
+  std::vector<char> up((size_t)(head + B * R * 4));
+  int64_t* nob = (int64_t*)up.data();
+  int* rbeg = (int*)(up.data() + gen_align(B * 8));
+  uint32_t* rows = (uint32_t*)(up.data() + head);
+  int nr = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t n = n_objs[b];
+    CSG_REQUIRE(n >= 0 && n <= O, CSG_E_BADSHAPE, "csg_canon_general_build: n_objs[%ld] = %ld outside [0, %ld]", (long)b,
+                (long)n, (long)O);
+    nob[b] = n;
+    rbeg[b] = nr;
+    const int64_t cnt = rel_counts ? rel_counts[b] : R;
+    CSG_REQUIRE(cnt >= 0 && cnt <= R, CSG_E_BADSHAPE, "csg_canon_general_build: rel_counts[%ld] = %ld outside [0, %ld]",
+                (long)b, (long)cnt, (long)R);
+    for (int64_t r = 0; r < cnt; ++r) {
+      const int64_t* t = rel + (b * R + r) * 3;
+      const int64_t s = t[0], p = t[1], o = t[2];
+      if (!rel_counts && p == G.pid_padding) continue;
+      CSG_REQUIRE(p >= 0 && p < P && p != G.pid_padding, CSG_E_BADSHAPE,
+                  "csg_canon_general_build: sample %ld row %ld: predicate %ld outside [0, %ld) or __padding__", (long)b,
+                  (long)r, (long)p, (long)P);
+      CSG_REQUIRE(s >= 0 && s < n && o >= 0 && o < n, CSG_E_BADSHAPE,
+                  "csg_canon_general_build: sample %ld row %ld: object %ld or %ld outside [0, %ld)", (long)b, (long)r,
+                  (long)s, (long)o, (long)n);
+      rows[nr++] = (uint32_t)s | (uint32_t)o << 8 | (uint32_t)p << 16;
+    }
+  }
+  rbeg[B] = nr;
+  GenWs w;
+  gen_layout(B, P, R, workspace, &w);
+  hipStream_t st = (hipStream_t)stream;
+  // nob, rbeg and rows are adjacent in the workspace, as in `up`; a pageable source is copied before the call returns
+  CSG_REQUIRE(hipMemcpyAsync(w.nob, up.data(), (size_t)(head + (int64_t)nr * 4), hipMemcpyHostToDevice, st) == hipSuccess,
+              CSG_E_LAUNCH, "csg_canon_general_build: upload of the annotated rows failed");
+  CanonParams C;
+  fill_params(&C, O, ids, image_id, 0, 0);
+  {
+    ProfScope pr(K_CANON_BUILD, (double)B * O * O, st);
+    CSG_LAUNCH(k_canon_build, dim3((unsigned)B), dim3(256), 0, st, C, objs0, boxes, centers, (const int64_t*)w.nob,
+               workspace, w.geo_counts);
+  }
+  {
+    ProfScope pr(K_CANON_BUILD, (double)B * P * O * W, st);
+    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, objs0, w, workspace);
+    CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, G, w, counts);
+  }
+  return check_launch("csg_canon_general_build");
+}
+
+int csg_canon_general_converse(int64_t B, const int32_t* roles, int64_t P, void* workspace, int64_t workspace_bytes,
+                               const double* cdf, const double* uniforms, const int64_t* u_off, float* conv_counts,
+                               void* stream) {
+  GEN_CHECK_COMMON("csg_canon_general_converse");
+  CSG_REQUIRE(cdf && uniforms && u_off && conv_counts, CSG_E_BADSHAPE, "csg_canon_general_converse: null argument");
+  GenParams G;
+  int32_t ids[8];
+  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, 1, 0, 0, 0) && G.K >= 1, CSG_E_BADSHAPE,
+              "csg_canon_general_converse: bad role table");
+  GenWs w;
+  gen_layout(B, P, 0, workspace, &w);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope pr(K_CANON_BUILD, (double)B * P * MAXN, st);
+  CSG_LAUNCH(k_gen_converse, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, w, cdf, uniforms, u_off, conv_counts);
+  return check_launch("csg_canon_general_converse");
+}
+
+int csg_canon_general_close(int64_t B, const int32_t* roles, int64_t P, int learned_transitivity, void* workspace,
+                            int64_t workspace_bytes, int64_t* counts, void* stream) {
+  GEN_CHECK_COMMON("csg_canon_general_close");
+  CSG_REQUIRE(counts, CSG_E_BADSHAPE, "csg_canon_general_close: null argument");
+  GenParams G;
+  int32_t ids[8];
+  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, 1, 0, 0, learned_transitivity), CSG_E_BADSHAPE,
+              "csg_canon_general_close: bad role table");
+  GenWs w;
+  gen_layout(B, P, 0, workspace, &w);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope pr(K_CANON_BUILD, (double)B * P * MAXN * MAXN, st);
+  CSG_LAUNCH(k_gen_close, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, w);
+  CSG_LAUNCH(k_gen_offsets, dim3((unsigned)B), dim3(256), 0, st, G, w, counts);
+  return check_launch("csg_canon_general_close");
+}
+
+int csg_canon_general_emit(int64_t B, const int32_t* roles, int64_t P, const void* workspace, int64_t workspace_bytes,
+                           const int64_t* counts, int64_t T, int64_t* triplets, int64_t* triplet_type, void* stream) {
+  GEN_CHECK_COMMON("csg_canon_general_emit");
+  CSG_REQUIRE(T >= 0 && counts, CSG_E_BADSHAPE, "csg_canon_general_emit: bad shape T=%ld", (long)T);
+  if (T == 0) return CSG_OK;
+  CSG_REQUIRE(triplets && triplet_type, CSG_E_BADSHAPE, "csg_canon_general_emit: null argument");
+  GenParams G;
+  int32_t ids[8];
+  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, 1, 0, 0, 0), CSG_E_BADSHAPE, "csg_canon_general_emit: bad role table");
+  GenWs w;
+  gen_layout(B, P, 0, (void*)workspace, &w);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope pr(K_CANON_EMIT, (double)B * T * 32, st);
+  CSG_LAUNCH(k_gen_emit, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, w, counts, T, triplets, triplet_type);
+  return check_launch("csg_canon_general_emit");
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@ datasets are out of scope), one process per GPU:
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m canonicalsg2im_amd.scripts.train ...
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as
-the packed data loaders do on the host."""
+the packed data loaders do on the host; `packed_vg` batches carry annotated relationships (synthetic, among the
+vocabulary's non-location predicates) that join the graph as in sg2im/data/packed_vg.py:127-142."""
 import os
 import sys
 import time
@@ -22,9 +23,38 @@ def _vocab_kind(dataset):
     return {"vg": "vg", "packed_vg": "vg", "clevr": "clevr", "packed_clevr": "clevr"}.get(dataset, "coco")
 
 
+def packed_batch(args, trainer, batch, dev):
+    """A synthetic packed batch (CPU tensors from synth.make_batch) on `dev`, with the canonical graph built on the
+    device: the __image__ row appended to every sample, then canonical_triplets in place of the triplets.  packed_vg
+    hands the batch's annotated relationships over, unless --include_relationships 0 (packed_vg.py:128-130)."""
+    from ..sg2im.data import canonical_triplets
+    rel = None
+    if args.dataset == "packed_vg":  # the annotated rows and the object counts are read on the host: hand over CPU tensors
+        rel = batch[3] if args.include_relationships else torch.zeros((batch[3].shape[0], 0, 3), dtype=torch.int64)
+        n = (batch[1][..., 0] != 0).sum(1) + 1              # real objects + the __image__ row appended below
+    batch = [None if x is None else x.to(dev) for x in batch]
+    objs, boxes = batch[1], batch[2]
+    if rel is None:
+        n = (objs[..., 0] != 0).sum(1) + 1
+    O = objs.shape[1] + 1
+    objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
+    boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)
+    centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
+    batch[1], batch[2] = objs, boxes
+    conv_w = None
+    if args.learned_converse:    # the data loader reads the model's converse weights back (scripts/train.py:274-276)
+        from ..sg2im.model import get_conv_converse
+        conv_w = get_conv_converse(trainer.model).detach().cpu().numpy()
+    batch[3], batch[4], batch[5] = canonical_triplets(objs, boxes, centers, n, args.vocab,
+                                                      learned_transitivity=bool(args.learned_transitivity),
+                                                      learned_converse=bool(args.learned_converse),
+                                                      converse_weights=conv_w, triplets=rel)
+    assert batch[3].shape[1] > 0 and objs.shape[1] == O
+    return batch
+
+
 def main(argv=None):
     from .. import dist as csg_dist, train as T
-    from ..sg2im.data import canonical_triplets
     from ..synth import BatchConfig, make_batch, make_vocab
     from .args import build_parser, init_args
     args = build_parser().parse_args(argv)
@@ -50,27 +80,15 @@ def main(argv=None):
     packed = args.dataset.startswith("packed")
     lo = args.min_objects or (16 if packed else 3)
     hi = args.max_objects or (40 if packed else 8)
-    cfg = BatchConfig(per_rank, args.image_size[0], lo, hi, "packed" if packed else "random", mask_size=args.mask_size)
+    graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
+    cfg = BatchConfig(per_rank, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
     tic = time.time()
     for t in range(t0 + 1, args.num_iterations + 1):
-        batch = [None if x is None else x.to(dev) for x in make_batch(args.vocab, cfg, seed=t * max(world, 1) + rank)]
-        if packed:                       # canonical graph from the geometry, on the device
-            objs, boxes = batch[1], batch[2]
-            n = (objs[..., 0] != 0).sum(1) + 1                 # real objects + the __image__ row appended below
-            O = objs.shape[1] + 1
-            objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
-            boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)
-            centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
-            batch[1], batch[2] = objs, boxes
-            conv_w = None
-            if args.learned_converse:    # the data loader reads the model's converse weights back (scripts/train.py:274-276)
-                from ..sg2im.model import get_conv_converse
-                conv_w = get_conv_converse(trainer.model).detach().cpu().numpy()
-            batch[3], batch[4], batch[5] = canonical_triplets(objs, boxes, centers, n, args.vocab,
-                                                              learned_transitivity=bool(args.learned_transitivity),
-                                                              learned_converse=bool(args.learned_converse),
-                                                              converse_weights=conv_w)
-            assert batch[3].shape[1] > 0 and objs.shape[1] == O
+        batch = make_batch(args.vocab, cfg, seed=t * max(world, 1) + rank)
+        if packed:                       # canonical graph from the geometry (and annotations), on the device
+            batch = packed_batch(args, trainer, batch, dev)
+        else:
+            batch = [None if x is None else x.to(dev) for x in batch]
         G, D = trainer.step(batch)
         if rank == 0 and (t % args.print_every == 0 or t == args.num_iterations):
             torch.cuda.synchronize()

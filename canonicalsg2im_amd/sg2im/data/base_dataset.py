@@ -43,8 +43,78 @@ def _choice_cdf(converse_weights, rel, candidates):
     return cdf
 
 
+def _draw_numbers(draws, uniforms):
+    """The uniform numbers of the converse draws: numpy's GLOBAL stream (the reference's np.random.choice), or `uniforms`."""
+    total = int(draws.sum())
+    if uniforms is None:
+        u = np.random.random_sample(total)
+    else:
+        u = np.asarray(uniforms, np.float64).reshape(-1)
+        if u.shape[0] < total:
+            raise ValueError("learned_converse: %d uniform numbers given, %d needed" % (u.shape[0], total))
+    return np.ascontiguousarray(u[:total] if total else np.zeros(1)), torch.cumsum(draws, 0) - draws
+
+
+def _host_int64(t):
+    t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+    return t.detach().to(device="cpu", dtype=torch.int64).contiguous()
+
+
+def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity, include_dummies,
+                       learned_converse, converse_weights, uniforms, triplets):
+    """Annotated rows and any vocabulary (csrc/canon.hip, csg_canon_general_*): packed_vg.py:127-142 + vg_collate_fn."""
+    B, O = objs0.shape
+    dev = objs0.device
+    p2i = vocab["pred_name_to_idx"]
+    P = len(p2i)
+    roles = [-1] * P                                                       # CSG_CANON_ROLE_OTHER
+    roles[p2i["__padding__"]] = -2
+    roles[p2i["__in_image__"]] = -3
+    for slot, name in enumerate(augmented_relations):
+        roles[p2i[name]] = slot
+    roles_c = (ctypes.c_int32 * P)(*roles)
+    n_host = _host_int64(n_objs)
+    rel = _host_int64(triplets) if triplets is not None else torch.zeros((B, 0, 3), dtype=torch.int64)
+    if rel.dim() != 3 or rel.shape[0] != B or rel.shape[2] != 3:
+        raise ValueError("triplets must be (B, R, 3); got %s" % (tuple(rel.shape),))
+    R = rel.shape[1]
+    nbytes = lib.csg_canon_general_workspace(B, P, R)
+    if nbytes < 0:
+        raise RuntimeError("canonical_triplets: at most 256 predicates (the vocabulary has %d)" % P)
+    ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    counts = torch.empty((B, 2), device=dev, dtype=torch.int64)
+    check(lib.csg_canon_general_build(ptr(objs0), ptr(boxes), ptr(obj_centers), ctypes.c_void_p(n_host.data_ptr()), B, O,
+                                      ctypes.c_void_p(rel.data_ptr()) if R else None, None, R, roles_c, P, image_id,
+                                      1 if include_dummies else 0, ptr(ws), nbytes, ptr(counts), stream()),
+          "canon_general_build")
+    conv_counts = torch.zeros((B, P, P + 1), device=dev, dtype=torch.float32)        # base_dataset.py:93
+    if learned_converse:
+        if converse_weights is None:
+            raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
+        w = converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
+        draws = counts[:, 0].cpu()                                   # read-back: the uniforms are the HOST's random stream
+        u, u_off = _draw_numbers(draws, uniforms)
+        non_meta = [p for p in range(P) if roles[p] not in (-2, -3)]
+        cdf = np.zeros((P, len(non_meta)), np.float64)
+        for rel_id in non_meta:                                       # graphs_utils.py:126-140, candidates ascending
+            cdf[rel_id] = _choice_cdf(w, rel_id, [c for c in non_meta if c != rel_id])
+        cdf_d = torch.from_numpy(cdf).to(dev)
+        u_d = torch.from_numpy(u).to(dev)
+        off_d = u_off.to(dev)
+        check(lib.csg_canon_general_converse(B, roles_c, P, ptr(ws), nbytes, ptr(cdf_d), ptr(u_d), ptr(off_d),
+                                             ptr(conv_counts), stream()), "canon_general_converse")
+    check(lib.csg_canon_general_close(B, roles_c, P, 1 if learned_transitivity else 0, ptr(ws), nbytes, ptr(counts),
+                                      stream()), "canon_general_close")
+    T = int(counts.sum(dim=1).max().item())          # vg_collate_fn pads to the longest sample: one 8-byte read-back
+    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
+    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
+    check(lib.csg_canon_general_emit(B, roles_c, P, ptr(ws), nbytes, ptr(counts), T, ptr(out), ptr(triplet_type),
+                                     stream()), "canon_general_emit")
+    return out, conv_counts, triplet_type
+
+
 def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transitivity=False, include_dummies=True,
-                       learned_converse=False, converse_weights=None, uniforms=None):
+                       learned_converse=False, converse_weights=None, uniforms=None, triplets=None):
     """Batched `add_location_triplets` + `add_dummy_triplets` + `add_learnt_triplets` + collate padding.
 
     objs (B,O) or (B,O,A) int64 (attribute 0 is used, as `objs['shape']` in packed_clevr_dialog.py:207),
@@ -56,7 +126,15 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     (`get_conv_converse(model).detach().cpu().numpy()`, scripts/train.py:276); every original triplet of a location relation
     draws one number from numpy's GLOBAL random stream — the reference's `np.random.choice` — in the reference's order
     (samples one after the other), or from `uniforms` (a float64 sequence) when given.  Costs one more 16-byte-per-sample
-    read-back (the number of draws is known only after the graphs are reduced)."""
+    read-back (the number of draws is known only after the graphs are reduced).
+
+    `triplets` (B,R,3) int64: the samples' annotated relationships in local object indices, rows carrying `__padding__`
+    are padding (sg2im/data/packed_vg.py:127-142: they join the location relations and the dummies before
+    add_learnt_triplets, which then runs over every non-meta predicate).  With them, or with a vocabulary whose non-meta
+    predicates are more than the six location relations (the converse candidates are then all other non-meta predicates,
+    scripts/graphs_utils.py:126-152), the general kernels run (csg_canon_general_*, one (sample, predicate) bit matrix
+    per block).  They read `triplets` and `n_objs` on the host: pass CPU tensors (or arrays) to spare a copy.
+    Otherwise the location-only kernels run, as before."""
     objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
     first = list(vocab["attributes"].keys())[0]
     image_id = vocab["object_name_to_idx"]["__image__"]
@@ -65,9 +143,12 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     B, O = objs0.shape
     p2i = vocab["pred_name_to_idx"]
     names = meta_relations + augmented_relations
-    ids = (ctypes.c_int32 * 8)(*[p2i[n] for n in names])
     boxes = boxes.to(torch.float32).contiguous()
     obj_centers = obj_centers.to(torch.float32).contiguous()
+    if triplets is not None or set(p2i.values()) != {p2i[n] for n in names}:
+        return _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity,
+                                  include_dummies, learned_converse, converse_weights, uniforms, triplets)
+    ids = (ctypes.c_int32 * 8)(*[p2i[n] for n in names])
     n_objs = n_objs.to(device=objs0.device, dtype=torch.int64).contiguous()
     dev = objs0.device
     nbytes = lib.csg_canon_workspace(B)

@@ -70,7 +70,7 @@ class BatchConfig:
     image_size: int = 64
     min_objects: int = 3
     max_objects: int = 8
-    graph: str = "random"          # random | packed | closure
+    graph: str = "random"          # random | packed | closure | annotated
     pad_objects_to: int = 0        # 0 = pad to the batch max
     pad_triplets_to: int = 0
     extra: dict = field(default_factory=dict)
@@ -100,6 +100,33 @@ def _relation(bs, bo, name_to_idx):
     if abs(dx) >= abs(dy):
         return name_to_idx["__left of__"] if dx < 0 else name_to_idx["__right of__"]
     return name_to_idx["__above__"] if dy < 0 else name_to_idx["__below__"]
+
+
+def annotated_relations(rng, n, vocab):
+    """Annotated relationships of one sample, as a Visual Genome image carries them (sg2im/data/packed_vg.py:127-138):
+    random (s, p, o) rows among ~3/4 of the n objects (the others have none), predicates drawn from the vocabulary's
+    predicates that are neither meta nor location relations, plus a duplicate row, a self-relation, a 2-cycle and (n >= 3)
+    a 3-cycle."""
+    names = set(PACKED_PREDICATES)
+    preds = sorted(i for name, i in vocab["pred_name_to_idx"].items() if name not in names)
+    if not preds:
+        raise ValueError("annotated graphs need predicates beyond the packed ones (e.g. make_vocab('vg'))")
+    if n < 2:
+        return []
+    active = [int(i) for i in rng.permutation(n)[:max(2, (3 * n) // 4)]]
+    pick = lambda: int(preds[int(rng.integers(0, len(preds)))])                      # noqa: E731
+    rows = []
+    for _ in range(int(rng.integers(len(active) // 2, len(active) + 1))):
+        s, o = rng.choice(len(active), size=2, replace=False)
+        rows.append([active[int(s)], pick(), active[int(o)]])
+    rows.append(list(rows[0]))                                                        # duplicate
+    rows.append([active[0], pick(), active[0]])                                       # self-relation
+    p = pick()
+    rows += [[active[0], p, active[1]], [active[1], p, active[0]]]                    # 2-cycle
+    if len(active) >= 3:
+        p = pick()
+        rows += [[active[0], p, active[1]], [active[1], p, active[2]], [active[2], p, active[0]]]   # 3-cycle
+    return rows
 
 
 def _sample_graph(rng, boxes, n, mode, vocab):
@@ -132,6 +159,9 @@ def _sample_graph(rng, boxes, n, mode, vocab):
                     continue
                 trip.append([s, _relation(boxes[s], boxes[o], p2i), o])
                 ttype.append(0 if (s + o) % 4 == 0 else 1)
+    elif mode == "annotated":
+        trip = annotated_relations(rng, n, vocab)
+        ttype = [0] * len(trip)
     else:
         raise ValueError("unknown graph mode %r" % mode)
     return trip, ttype

@@ -42,7 +42,8 @@ extern "C" {
 #define CSG_MAX_TAPS 16
 
 /* 100 + the number of additive revisions of this header: entry points are only ever added, never changed or removed
- * (108: csg_wino4_conv_spade, csg_wino4_conv_spade_supported, csg_avgpool3s2_bwd_add, csg_hinge_mean_fwd / _bwd) */
+ * (108: csg_wino4_conv_spade, csg_wino4_conv_spade_supported, csg_avgpool3s2_bwd_add, csg_hinge_mean_fwd / _bwd;
+ * 109: csg_canon_general_workspace, csg_canon_general_build / _converse / _close / _emit) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -550,6 +551,53 @@ int csg_canon_converse(const int64_t* objs0, const int64_t* n_objs, int64_t B, i
                        int64_t image_id, int include_dummies, int learned_transitivity, void* workspace,
                        const double* cdf, const double* uniforms, const int64_t* u_off, int64_t num_preds,
                        float* conv_counts, int64_t* counts, void* stream);
+
+/* ---- canonical graphs with annotated relationships, any vocabulary -------------------------------------------------
+ * The same pipeline for a sample's annotated (s, p, o) rows and every predicate of the vocabulary, in the order
+ * sg2im/data/packed_vg.py:127-142 runs it (replacing, per batch, that loop and the triplet padding of vg_collate_fn,
+ * packed_vg.py:207-212): the annotated rows (duplicates, self-relations and cycles allowed; never reduced), the location
+ * relations of the geometry reduced per relation as csg_canon_build does (base_dataset.py:35-87), the __in_image__
+ * dummies (:141-151), np.unique, then add_learnt_triplets (:89-139) over EVERY non-meta predicate by ascending id:
+ * converse draws among all other non-meta predicates and "none" (scripts/graphs_utils.py:126-152), transitive extras of
+ * each predicate's rows including the converse edges drawn into it (graphs_utils.py:15-27,96-100; cycles give (i, p, i)).
+ * Output as csg_canon_emit: originals by (s, p, o), then the extras by (p, s, o), rows past a sample's count
+ * [0, __padding__, 0] with type 0.
+ *
+ * roles (host, P int32): per predicate id, CSG_CANON_ROLE_PADDING, CSG_CANON_ROLE_IN_IMAGE, the location slot 0..5
+ * (__below__ __above__ __left of__ __right of__ __inside__ __surrounding__) or CSG_CANON_ROLE_OTHER; each of the first
+ * eight exactly once.  Ids may come in any order.
+ * Call order: _build, [_converse], _close, then _emit with T = max_b(counts[b][0] + counts[b][1]).
+ *   csg_canon_general_build: objs0 / boxes / centers as for csg_canon_build (device); n_objs (host, B) objects per sample
+ *     incl. __image__; rel (host, (B,R,3) int64) the annotated rows in local object indices, a sample's first
+ *     rel_counts[b] rows (host, B), or with rel_counts NULL every row whose predicate is not __padding__.  Everything is
+ *     checked before anything is enqueued; the rows are copied into the workspace on `stream`.  counts[b] = {number of
+ *     draws of sample b (its original rows of non-meta predicates), 0}.
+ *   csg_canon_general_converse (learned_converse = 1): cdf (P, K) float64, K = the number of non-meta predicates: row rel
+ *     = the cumulative distribution numpy.random.choice searches for relation rel (candidates = the other non-meta
+ *     predicates by ascending id, then "none"; rows of meta predicates unused); uniforms / u_off as for
+ *     csg_canon_converse; conv_counts (B, P, P + 1) float32, zero-initialised by the caller, column P = "none".
+ *   csg_canon_general_close: closure and counts[b] = {original triplets, transitive triplets}.
+ *   csg_canon_general_emit: triplets (B,T,3) int64 and triplet_type (B,T) int64.
+ * LIMITS: at most 256 objects per sample (O <= 256, CSG_E_UNSUPPORTED) and at most 256 predicates (P <= 256,
+ * CSG_E_UNSUPPORTED); B * R < 2^31; an annotated object index outside [0, n_objs[b]), a predicate id outside [0, P), a
+ * __padding__ row among a sample's counted rows, n_objs[b] outside [0, O] or a bad role table is CSG_E_BADSHAPE.
+ * Workspace: csg_canon_general_workspace(B, P, R) bytes (about B * (P * 18 KB + 103 KB) + B * R * 4); the later
+ * entries take the same workspace and size.                                                                                       */
+#define CSG_CANON_ROLE_OTHER (-1)
+#define CSG_CANON_ROLE_PADDING (-2)
+#define CSG_CANON_ROLE_IN_IMAGE (-3)
+int64_t csg_canon_general_workspace(int64_t B, int64_t P, int64_t R);
+int csg_canon_general_build(const int64_t* objs0, const float* boxes, const float* centers, const int64_t* n_objs,
+                            int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
+                            const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
+                            int64_t workspace_bytes, int64_t* counts, void* stream);
+int csg_canon_general_converse(int64_t B, const int32_t* roles, int64_t P, void* workspace, int64_t workspace_bytes,
+                               const double* cdf, const double* uniforms, const int64_t* u_off, float* conv_counts,
+                               void* stream);
+int csg_canon_general_close(int64_t B, const int32_t* roles, int64_t P, int learned_transitivity, void* workspace,
+                            int64_t workspace_bytes, int64_t* counts, void* stream);
+int csg_canon_general_emit(int64_t B, const int32_t* roles, int64_t P, const void* workspace, int64_t workspace_bytes,
+                           const int64_t* counts, int64_t T, int64_t* triplets, int64_t* triplet_type, void* stream);
 
 /* ---- spectral normalisation of a conv weight (a13) ----------------------------------------------
  * torch.nn.utils.spectral_norm's forward pre-hook (reference call sites architecture.py:35-39,
