@@ -1029,6 +1029,16 @@ def _multi(world, syncs):
     return bool(syncs) and (world > 1 or csg_dist.active())
 
 
+def _drop_clamped_invstd_term(dsums, invstd, eps, C):
+    """N-replica form only: inv_std = max(var, eps)^-1/2 does not depend on the statistics where var < eps (the clamp of
+    reference batchnorm.py:145 is flat there), so the sum(dn xhat) half of the backward reductions — the inv_std term of
+    dx — is dropped for those channels; a channel clamps exactly when its inv_std is eps^-1/2.  Linear per channel and the
+    same on every rank, so it may be applied before the all-reduce."""
+    live = invstd < (float(eps) ** -0.5) * (1.0 - 1e-6)
+    dsums.view(-1, 2 * C)[:, C:].mul_(live.to(dsums.dtype))
+    return dsums
+
+
 class _NormAct(torch.autograd.Function):
     """BatchNorm (G=1) or InstanceNorm (G=B) statistics + optional SPADE modulation + LeakyReLU.
 
@@ -1073,13 +1083,13 @@ class _NormAct(torch.autograd.Function):
                                      stream()),
               "norm_apply_fwd")
         ctx.save_for_backward(x, gbn, mean, invstd)
-        ctx.cfg = (G, P, C, slope, use_batch_stats, multi, count)
+        ctx.cfg = (G, P, C, slope, use_batch_stats, multi, count, eps)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gb, mean, invstd = ctx.saved_tensors
-        G, P, C, slope, use_batch_stats, multi, count = ctx.cfg
+        G, P, C, slope, use_batch_stats, multi, count, eps = ctx.cfg
         dy = nhwc(dy)
         dev = dy.device
         dgb = torch.empty_like(gb) if gb is not None else None
@@ -1093,7 +1103,7 @@ class _NormAct(torch.autograd.Function):
             if not use_batch_stats:
                 dsums.zero_()                       # eval mode: statistics are constants
             elif multi:
-                csg_dist.all_reduce_stats(dsums)
+                csg_dist.all_reduce_stats(_drop_clamped_invstd_term(dsums, invstd, eps, C))
             dx = torch.empty_like(x)
             check(lib.csg_norm_apply_bwd_dx(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), slope, ptr(dsums), count,
                                             G, P, C, ptr(dx), None, None, 1.0, ptr(dgb), None, 2 * C, stream()), "norm_bwd_dx")
@@ -1135,13 +1145,13 @@ class _NormActPair(torch.autograd.Function):
         check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb0), slope0, 1, P, C, ptr(y0), ptr(gb1), slope1,
                                      ptr(y1), stream()), "norm_apply_fwd")
         ctx.save_for_backward(x, gb0, gb1, mean, invstd)
-        ctx.cfg = (P, C, slope0, slope1, multi, count)
+        ctx.cfg = (P, C, slope0, slope1, multi, count, eps)
         return y0, y1
 
     @staticmethod
     def backward(ctx, dy0, dy1):
         x, gb0, gb1, mean, invstd = ctx.saved_tensors
-        P, C, slope0, slope1, multi, count = ctx.cfg
+        P, C, slope0, slope1, multi, count, eps = ctx.cfg
         dy0, dy1 = nhwc(dy0), nhwc(dy1)
         dev = x.device
         nch = _chunks(P, 1)
@@ -1156,7 +1166,7 @@ class _NormActPair(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             both = dsums[0] + dsums[1]                    # the reductions are linear in dn: 4C doubles
             if multi:
-                csg_dist.all_reduce_stats(both)
+                csg_dist.all_reduce_stats(_drop_clamped_invstd_term(both, invstd, eps, C))
             dx = torch.empty_like(x)
             check(lib.csg_norm_apply_bwd_dx(ptr(dy0), ptr(x), ptr(mean), ptr(invstd), ptr(gb0), slope0, ptr(both), count,
                                             1, P, C, ptr(dx), ptr(dy1), ptr(gb1), slope1, ptr(dgb0), ptr(dgb1), 2 * C, stream()),
@@ -1197,6 +1207,14 @@ class _SpadeFused(torch.autograd.Function):
         K = len(mods) // _SpadeFused.NARG
         x = nhwc(_f32(x))
         B, C, H, W = x.shape
+        # refused before the first launch: the statistics pass below already updates the running buffers
+        if C % 32 != 0:
+            raise RuntimeError("spade_fused: C = %d must be a multiple of 32 (the modulation rides on 32-channel tiles)" % C)
+        for k in range(K):
+            actv, w = mods[k * 7], mods[k * 7 + 1]
+            if actv.dim() != 4 or tuple(w.shape) != (2 * C, actv.shape[1], 3, 3) or tuple(actv.shape) != (B, actv.shape[1], H, W):
+                raise RuntimeError("spade_fused: weight %s / actv %s do not fit x %s" % (tuple(w.shape), tuple(actv.shape),
+                                                                                         tuple(x.shape)))
         P = B * H * W
         dev = x.device
         world = _sync_world() if sync else 1
@@ -1229,9 +1247,6 @@ class _SpadeFused(torch.autograd.Function):
             actv, w, b, rm, rv, slope, in_slope = mods[k * 7:(k + 1) * 7]
             actv = nhwc(_f32(actv))
             nh = actv.shape[1]
-            if tuple(w.shape) != (2 * C, nh, 3, 3) or tuple(actv.shape) != (B, nh, H, W):
-                raise RuntimeError("spade_fused: weight %s / actv %s do not fit x %s" % (tuple(w.shape), tuple(actv.shape),
-                                                                                         tuple(x.shape)))
             up = wino_pack(w, False, None, 4)
             # the joined gamma || beta convolution's backward passes (_conv_bwd on d(gamma || beta))
             plans.append(plan_conv(B, H, W, nh, 2 * C, 3, 3, 1, 1, has_bias=True,
@@ -1268,13 +1283,13 @@ class _SpadeFused(torch.autograd.Function):
                                           ptr(mean), ptr(invstd), slope, ptr(y), stream()), "wino4_conv_part(beta)")
             outs[k], groups[k] = y, [actv, w, gbuf, y]
         ctx.save_for_backward(x, mean, invstd, *[t for g in groups for t in g])
-        ctx.cfg = (K, P, C, B, H, W, multi, count, tuple(mods[k * 7 + 5] for k in range(K)))
+        ctx.cfg = (K, P, C, B, H, W, multi, count, eps, tuple(mods[k * 7 + 5] for k in range(K)))
         ctx.plans, ctx.ut_pres = plans, pres
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dys):
-        K, P, C, B, H, W, multi, count, slopes = ctx.cfg
+        K, P, C, B, H, W, multi, count, eps, slopes = ctx.cfg
         sv = ctx.saved_tensors
         x, mean, invstd = sv[0], sv[1], sv[2]
         dev = x.device
@@ -1293,7 +1308,7 @@ class _SpadeFused(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             both = dsums[0] + dsums[1] if K == 2 else dsums[0]
             # N > 1: the reductions travel while the convolution's backward passes (which need only d(gamma || beta)) run
-            pending = csg_dist.all_reduce_stats_async(both) if multi else None
+            pending = csg_dist.all_reduce_stats_async(_drop_clamped_invstd_term(both, invstd, eps, C)) if multi else None
         grads = [None, None, None, None]
         for k in range(K):
             actv, w, gbuf, y = sv[3 + 4 * k:7 + 4 * k]
@@ -1358,13 +1373,13 @@ class _SpadeJoined(torch.autograd.Function):
         check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb), slope, 1, P, C, ptr(y), None, 1.0, None, stream()),
               "norm_apply_fwd")
         ctx.save_for_backward(x, gb, mean, invstd, actv, w)
-        ctx.cfg = (P, C, slope, multi, count)
+        ctx.cfg = (P, C, slope, multi, count, eps)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gb, mean, invstd, cx, cw = ctx.saved_tensors
-        P, C, slope, multi, count = ctx.cfg
+        P, C, slope, multi, count, eps = ctx.cfg
         dy = nhwc(dy)
         dev = x.device
         nch = _chunks(P, 1)
@@ -1373,7 +1388,8 @@ class _SpadeJoined(torch.autograd.Function):
         dgb = torch.empty_like(gb)
         check(lib.csg_norm_apply_bwd_reduce(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), None, slope, 1, P, C, ptr(dgb),
                                             ptr(dsums), ptr(part), nch, 2 * C, stream()), "norm_bwd_reduce")
-        pending = csg_dist.all_reduce_stats_async(dsums) if (multi and ctx.needs_input_grad[0]) else None
+        pending = (csg_dist.all_reduce_stats_async(_drop_clamped_invstd_term(dsums, invstd, eps, C))
+                   if (multi and ctx.needs_input_grad[0]) else None)
         r = _conv_bwd(ctx.plan, dgb, cx, cw, None, ctx.needs_input_grad[1:4], None, ctx.ut_pre)
         dx = None
         if ctx.needs_input_grad[0]:
