@@ -5,7 +5,7 @@ The reference's only parallel strategy is `nn.DataParallel`: p
 re-broadcast every forward and gradients reduce-added onto GPU 0.  Here replicas hold identical
 parameters and exchange only (1) gradients — bucketed all-reduce, averaged, which equals the
 reference because its per-replica losses are means over equal shards averaged with `.mean()`
-(scripts/train.py:363,391) — and (2) SyncBN statistics (ops._NormAct)."""
+(scripts/train.py:363,391) — and (2) SyncBN statistics (ops._Norm.stats; the backward's reductions: ops._Norm.backward)."""
 import os
 
 import torch

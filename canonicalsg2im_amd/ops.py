@@ -1039,6 +1039,105 @@ def _drop_clamped_invstd_term(dsums, invstd, eps, C):
     return dsums
 
 
+def _nothing():
+    return None
+
+
+class _Norm:
+    """Host-side record of one normalisation's geometry — G groups of P pixels by C channels, `count` pixels per statistic
+    over all ranks, and whether the N-replica SyncBN form runs (`syncs`: see _multi) — and the ONE implementation of each
+    stage the four Functions below share.  What sits between the stages is theirs: one or two modulations, a materialised
+    gamma || beta map or a convolution, work that hides a SyncBN message.  Python scalars only: it is kept on `ctx`."""
+
+    __slots__ = ("G", "P", "C", "count", "eps", "multi", "nch")
+
+    def __init__(self, x, G, eps, syncs):
+        B, C, H, W = x.shape
+        world = _sync_world() if syncs else 1
+        self.G, self.P, self.C, self.eps = G, (B * H * W) // G, C, eps
+        self.multi = _multi(world, syncs)
+        self.count = float(self.P * world)
+        self.nch = _chunks(self.P, G)
+
+    @staticmethod
+    def _exchange(sums, overlap):
+        """The SyncBN message of the N-replica form: blocking (None), or the handle to wait() on before `sums` is read."""
+        if overlap:
+            return csg_dist.all_reduce_stats_async(sums)
+        csg_dist.all_reduce_stats(sums)
+        return None
+
+    def stats(self, x, momentum, running, overlap=False):
+        """Batch statistics of x: (mean, invstd, finish).  `running`: one or two (running_mean, running_var) pairs, each
+        updated from the same statistics (a running_var only together with its running_mean).  mean and invstd hold the
+        statistics once finish() has been called.  `overlap`: the SyncBN message of the N-replica form travels
+        asynchronously until finish() — the caller enqueues work that does not need the statistics in between."""
+        G, P, C, dev = self.G, self.P, self.C, x.device
+        mean = torch.empty(G * C, device=dev, dtype=torch.float32)
+        invstd = torch.empty(G * C, device=dev, dtype=torch.float32)
+        part = torch.empty(G * self.nch * 2 * C, device=dev, dtype=torch.float64)
+        running = [(rm, rv if rm is not None else None) for rm, rv in running]
+        if not self.multi:                           # one rank: second reduction stage and finalisation in one launch, the
+            # same batch statistics into each module's own running buffers
+            (rm0, rv0), (rm1, rv1) = (running + [(None, None)])[:2]
+            check(lib.csg_norm_stats_finalize(ptr(x), G, P, C, ptr(part), self.nch, self.count, self.eps, ptr(mean), ptr(invstd),
+                                              ptr(rm0), ptr(rv0), ptr(rm1), ptr(rv1), momentum, stream()), "norm_stats_finalize")
+            return mean, invstd, _nothing
+        sums = torch.empty(G * 2 * C, device=dev, dtype=torch.float64)
+        check(lib.csg_norm_stats(ptr(x), G, P, C, ptr(sums), ptr(part), self.nch, stream()), "norm_stats")
+        work = self._exchange(sums, overlap)
+
+        def finish():
+            if work is not None:
+                work.wait()
+            for rm, rv in running:                   # the same statistics, each module's own running buffers
+                check(lib.csg_norm_finalize(ptr(sums), G, C, self.count, self.eps, 1, ptr(mean), ptr(invstd), ptr(rm), ptr(rv),
+                                            momentum, stream()), "norm_finalize")
+        return mean, invstd, finish
+
+    def apply(self, x, mean, invstd, mods):
+        """[leaky(xhat (1 + gamma) + beta, slope) for each of the one or two (gb, slope) in `mods`]; gb None: leaky(xhat)."""
+        ys = [torch.empty_like(x) for _ in mods]
+        (gb0, slope0), (gb1, slope1) = (list(mods) + [(None, 1.0)])[:2]
+        check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb0), slope0, self.G, self.P, self.C, ptr(ys[0]),
+                                     ptr(gb1), slope1, ptr(ys[1]) if len(mods) == 2 else None, stream()), "norm_apply_fwd")
+        return ys
+
+    def backward(self, x, mean, invstd, mods, want_dx, gamma_only=False, batch_stats=True, overlap=False):
+        """Pass 1 of the backward for the one or two modulations `mods`, each (dy, gb, yact, slope, dgb): dgb is written and
+        the two reductions sum(dn), sum(dn xhat) are formed.  `yact`: the saved output whose sign is the LeakyReLU gate
+        where gb holds gamma alone (`gamma_only`), else None.  Returns finish(), which runs pass 2 and returns dx — None,
+        with no exchange and no launch, unless `want_dx`.  `batch_stats` False: the statistics were constants (eval mode).
+        `overlap`: the N-replica form's message travels asynchronously until finish()."""
+        G, P, C, dev = self.G, self.P, self.C, x.device
+        gb_cs = C if gamma_only else 2 * C
+        part = torch.empty(G * self.nch * 2 * C, device=dev, dtype=torch.float64)
+        dsums = torch.empty(len(mods), G * 2 * C, device=dev, dtype=torch.float64)
+        for k, (dy, gb, yact, slope, dgb) in enumerate(mods):
+            check(lib.csg_norm_apply_bwd_reduce(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), ptr(yact), slope, G, P, C,
+                                                ptr(dgb), ptr(dsums[k]), ptr(part), self.nch, gb_cs, stream()), "norm_bwd_reduce")
+        if not want_dx:
+            return _nothing
+        total = dsums[0] + dsums[1] if len(mods) == 2 else dsums[0]       # the reductions are linear in dn: 4C doubles
+        work = None
+        if not batch_stats:
+            total.zero_()
+        elif self.multi:
+            _drop_clamped_invstd_term(total, invstd, self.eps, C)
+            work = self._exchange(total, overlap)
+
+        def finish():
+            if work is not None:
+                work.wait()
+            (dy0, gb0, _, slope0, dgb0), (dy1, gb1, _, slope1, dgb1) = (list(mods) + [(None, None, None, 1.0, None)])[:2]
+            dx = torch.empty_like(x)
+            check(lib.csg_norm_apply_bwd_dx(ptr(dy0), ptr(x), ptr(mean), ptr(invstd), ptr(gb0), slope0, ptr(total), self.count,
+                                            G, P, C, ptr(dx), ptr(dy1), ptr(gb1), slope1, ptr(dgb0), ptr(dgb1), gb_cs, stream()),
+                  "norm_bwd_dx")
+            return dx
+        return finish
+
+
 class _NormAct(torch.autograd.Function):
     """BatchNorm (G=1) or InstanceNorm (G=B) statistics + optional SPADE modulation + LeakyReLU.
 
@@ -1049,65 +1148,29 @@ class _NormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gb, running_mean, running_var, instance, training, slope, eps, momentum, sync):
         x = nhwc(_f32(x))
-        B, C, H, W = x.shape
-        G = B if instance else 1
-        P = (B * H * W) // G
-        dev = x.device
-        syncs = bool(sync and not instance and training)
-        world = _sync_world() if syncs else 1
-        multi = _multi(world, syncs)
-        use_batch_stats = training or instance
-        mean = torch.empty(G * C, device=dev, dtype=torch.float32)
-        invstd = torch.empty(G * C, device=dev, dtype=torch.float32)
-        count = float(P * world)
-        if use_batch_stats:
-            nch = _chunks(P, G)
-            part = torch.empty(G * nch * 2 * C, device=dev, dtype=torch.float64)
-            rm = running_mean if (training and not instance and running_mean is not None) else None
-            rv = running_var if rm is not None else None
-            if not multi:                            # one rank: second reduction stage and finalisation in one launch
-                check(lib.csg_norm_stats_finalize(ptr(x), G, P, C, ptr(part), nch, count, eps, ptr(mean), ptr(invstd), ptr(rm),
-                                                  ptr(rv), None, None, momentum, stream()), "norm_stats_finalize")
-            else:
-                sums = torch.empty(G * 2 * C, device=dev, dtype=torch.float64)
-                check(lib.csg_norm_stats(ptr(x), G, P, C, ptr(sums), ptr(part), nch, stream()), "norm_stats")
-                csg_dist.all_reduce_stats(sums)
-                check(lib.csg_norm_finalize(ptr(sums), G, C, count, eps, 1, ptr(mean), ptr(invstd), ptr(rm), ptr(rv), momentum,
-                                            stream()), "norm_finalize")
+        norm = _Norm(x, x.shape[0] if instance else 1, eps, bool(sync and not instance and training))
+        batch_stats = training or instance
+        if batch_stats:
+            mean, invstd, finish = norm.stats(x, momentum, [(running_mean if (training and not instance) else None, running_var)])
+            finish()
         else:
+            mean = torch.empty(norm.C, device=x.device, dtype=torch.float32)
+            invstd = torch.empty(norm.C, device=x.device, dtype=torch.float32)
             mean.copy_(running_mean)
             invstd.copy_(torch.rsqrt(running_var + eps))
         gbn = nhwc(gb) if gb is not None else None
-        y = torch.empty_like(x)
-        check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gbn), slope, G, P, C, ptr(y), None, 1.0, None,
-                                     stream()),
-              "norm_apply_fwd")
+        y, = norm.apply(x, mean, invstd, [(gbn, slope)])
         ctx.save_for_backward(x, gbn, mean, invstd)
-        ctx.cfg = (G, P, C, slope, use_batch_stats, multi, count, eps)
+        ctx.norm, ctx.slope, ctx.batch_stats = norm, slope, batch_stats
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gb, mean, invstd = ctx.saved_tensors
-        G, P, C, slope, use_batch_stats, multi, count, eps = ctx.cfg
-        dy = nhwc(dy)
-        dev = dy.device
         dgb = torch.empty_like(gb) if gb is not None else None
-        nch = _chunks(P, G)
-        part = torch.empty(G * nch * 2 * C, device=dev, dtype=torch.float64)
-        dsums = torch.empty(G * 2 * C, device=dev, dtype=torch.float64)
-        check(lib.csg_norm_apply_bwd_reduce(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), None, slope, G, P, C, ptr(dgb),
-                                            ptr(dsums), ptr(part), nch, 2 * C, stream()), "norm_bwd_reduce")
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if not use_batch_stats:
-                dsums.zero_()                       # eval mode: statistics are constants
-            elif multi:
-                csg_dist.all_reduce_stats(_drop_clamped_invstd_term(dsums, invstd, eps, C))
-            dx = torch.empty_like(x)
-            check(lib.csg_norm_apply_bwd_dx(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), slope, ptr(dsums), count,
-                                            G, P, C, ptr(dx), None, None, 1.0, ptr(dgb), None, 2 * C, stream()), "norm_bwd_dx")
-        return dx, dgb, None, None, None, None, None, None, None, None
+        finish = ctx.norm.backward(x, mean, invstd, [(nhwc(dy), gb, None, ctx.slope, dgb)], ctx.needs_input_grad[0],
+                                   batch_stats=ctx.batch_stats)
+        return finish(), dgb, None, None, None, None, None, None, None, None
 
 
 class _NormActPair(torch.autograd.Function):
@@ -1119,59 +1182,22 @@ class _NormActPair(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gb0, gb1, rm0, rv0, rm1, rv1, slope0, slope1, eps, momentum, sync):
         x = nhwc(_f32(x))
-        B, C, H, W = x.shape
-        P = B * H * W
-        dev = x.device
-        world = _sync_world() if sync else 1
-        multi = _multi(world, sync)
-        count = float(P * world)
-        mean = torch.empty(C, device=dev, dtype=torch.float32)
-        invstd = torch.empty(C, device=dev, dtype=torch.float32)
-        nch = _chunks(P, 1)
-        part = torch.empty(nch * 2 * C, device=dev, dtype=torch.float64)
-        if not multi:                                # same batch statistics, each module's own running buffers: one launch
-            check(lib.csg_norm_stats_finalize(ptr(x), 1, P, C, ptr(part), nch, count, eps, ptr(mean), ptr(invstd), ptr(rm0),
-                                              ptr(rv0 if rm0 is not None else None), ptr(rm1),
-                                              ptr(rv1 if rm1 is not None else None), momentum, stream()), "norm_stats_finalize")
-        else:
-            sums = torch.empty(2 * C, device=dev, dtype=torch.float64)
-            check(lib.csg_norm_stats(ptr(x), 1, P, C, ptr(sums), ptr(part), nch, stream()), "norm_stats")
-            csg_dist.all_reduce_stats(sums)
-            for rm, rv in ((rm0, rv0), (rm1, rv1)):
-                check(lib.csg_norm_finalize(ptr(sums), 1, C, count, eps, 1, ptr(mean), ptr(invstd), ptr(rm),
-                                            ptr(rv if rm is not None else None), momentum, stream()), "norm_finalize")
+        norm = _Norm(x, 1, eps, sync)
+        mean, invstd, finish = norm.stats(x, momentum, [(rm0, rv0), (rm1, rv1)])
+        finish()
         gb0, gb1 = nhwc(gb0), nhwc(gb1)
-        y0, y1 = torch.empty_like(x), torch.empty_like(x)
-        check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb0), slope0, 1, P, C, ptr(y0), ptr(gb1), slope1,
-                                     ptr(y1), stream()), "norm_apply_fwd")
+        y0, y1 = norm.apply(x, mean, invstd, [(gb0, slope0), (gb1, slope1)])
         ctx.save_for_backward(x, gb0, gb1, mean, invstd)
-        ctx.cfg = (P, C, slope0, slope1, multi, count, eps)
+        ctx.norm, ctx.slopes = norm, (slope0, slope1)
         return y0, y1
 
     @staticmethod
     def backward(ctx, dy0, dy1):
         x, gb0, gb1, mean, invstd = ctx.saved_tensors
-        P, C, slope0, slope1, multi, count, eps = ctx.cfg
-        dy0, dy1 = nhwc(dy0), nhwc(dy1)
-        dev = x.device
-        nch = _chunks(P, 1)
-        part = torch.empty(nch * 2 * C, device=dev, dtype=torch.float64)
-        dsums = torch.empty(2, 2 * C, device=dev, dtype=torch.float64)
         dgb0, dgb1 = torch.empty_like(gb0), torch.empty_like(gb1)
-        check(lib.csg_norm_apply_bwd_reduce(ptr(dy0), ptr(x), ptr(mean), ptr(invstd), ptr(gb0), None, slope0, 1, P, C, ptr(dgb0),
-                                            ptr(dsums[0]), ptr(part), nch, 2 * C, stream()), "norm_bwd_reduce")
-        check(lib.csg_norm_apply_bwd_reduce(ptr(dy1), ptr(x), ptr(mean), ptr(invstd), ptr(gb1), None, slope1, 1, P, C, ptr(dgb1),
-                                            ptr(dsums[1]), ptr(part), nch, 2 * C, stream()), "norm_bwd_reduce")
-        dx = None
-        if ctx.needs_input_grad[0]:
-            both = dsums[0] + dsums[1]                    # the reductions are linear in dn: 4C doubles
-            if multi:
-                csg_dist.all_reduce_stats(_drop_clamped_invstd_term(both, invstd, eps, C))
-            dx = torch.empty_like(x)
-            check(lib.csg_norm_apply_bwd_dx(ptr(dy0), ptr(x), ptr(mean), ptr(invstd), ptr(gb0), slope0, ptr(both), count,
-                                            1, P, C, ptr(dx), ptr(dy1), ptr(gb1), slope1, ptr(dgb0), ptr(dgb1), 2 * C, stream()),
-                  "norm_bwd_dx")
-        return dx, dgb0, dgb1, None, None, None, None, None, None, None, None, None
+        finish = ctx.norm.backward(x, mean, invstd, [(nhwc(dy0), gb0, None, ctx.slopes[0], dgb0),
+                                                     (nhwc(dy1), gb1, None, ctx.slopes[1], dgb1)], ctx.needs_input_grad[0])
+        return finish(), dgb0, dgb1, None, None, None, None, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------ SPADE with the modulation in the
@@ -1180,16 +1206,27 @@ SPADE_FUSED = os.environ.get("CSG_SPADE_FUSED", "1") != "0"
 SPADE_JOINED = os.environ.get("CSG_SPADE_JOINED", "1") != "0"     # _SpadeJoined for the maps the fused epilogue does not serve
 
 
-def spade_fused_eligible(x, nhidden, C, ks, training):
-    """Training-mode SPADE layers whose gamma || beta convolution runs Winograd F(4x4,3x3) (maps >= 32 wide): the beta half
-    of the convolution writes leaky(xhat (1 + gamma) + beta) itself (csg_wino4_conv_part)."""
-    if not (SPADE_FUSED and WINO_ENABLED and training and ks == 3 and x.dim() == 4 and C % 32 == 0):
+def spade_fused_eligible(x, nhidden, C, ks):
+    """SPADE layers whose gamma || beta convolution runs Winograd F(4x4,3x3) (maps >= 32 wide): the beta half of the
+    convolution writes leaky(xhat (1 + gamma) + beta) itself (csg_wino4_conv_part).  Training mode is the caller's to test
+    (SPADE.fusable): the Function takes batch statistics."""
+    if not (SPADE_FUSED and WINO_ENABLED and ks == 3 and x.dim() == 4 and C % 32 == 0):
         return False
     B, _, H, W = x.shape
     return lib.csg_wino4_supported(_wino_desc(B, H, W, nhidden, C)) == 1
 
 
 SPADE_JOINT = os.environ.get("CSG_SPADE_JOINT", "1") != "0"      # 0: the gamma / beta launch pair also on one rank (A/B)
+
+# _SpadeFused: what spade_fused passes per modulation, and what the forward saves per modulation for the backward
+_SpadeMod = collections.namedtuple("_SpadeMod", "actv w b rm rv slope in_slope")
+_SpadeSaved = collections.namedtuple("_SpadeSaved", "actv w gamma y")
+
+
+def _groups(flat, kind):
+    """A flat argument list as consecutive `kind` records."""
+    n = len(kind._fields)
+    return [kind(*flat[i:i + n]) for i in range(0, len(flat), n)]
 
 
 class _SpadeFused(torch.autograd.Function):
@@ -1200,60 +1237,51 @@ class _SpadeFused(torch.autograd.Function):
     _NormAct / _NormActPair (the LeakyReLU gate read off y's sign), then the joined convolution's backward-data and
     weight-gradient passes on d(gamma || beta)."""
 
-    NARG = 7          # per modulation: actv, w, b, running_mean, running_var, slope, in_slope
+    HEAD = 4                                # forward's x, eps, momentum, sync in front of the flat _SpadeMod records
+    NARG = len(_SpadeMod._fields)
 
     @staticmethod
-    def forward(ctx, x, eps, momentum, sync, *mods):
-        K = len(mods) // _SpadeFused.NARG
+    def _conv_needs(ctx, k):
+        """needs_input_grad of modulation k's convolution operands (actv, w, b): the first three of its record."""
+        at = _SpadeFused.HEAD + k * _SpadeFused.NARG
+        return ctx.needs_input_grad[at:at + 3]
+
+    @staticmethod
+    def forward(ctx, x, eps, momentum, sync, *flat):
+        mods = _groups(flat, _SpadeMod)
+        K = len(mods)
         x = nhwc(_f32(x))
         B, C, H, W = x.shape
         # refused before the first launch: the statistics pass below already updates the running buffers
         if C % 32 != 0:
             raise RuntimeError("spade_fused: C = %d must be a multiple of 32 (the modulation rides on 32-channel tiles)" % C)
-        for k in range(K):
-            actv, w = mods[k * 7], mods[k * 7 + 1]
-            if actv.dim() != 4 or tuple(w.shape) != (2 * C, actv.shape[1], 3, 3) or tuple(actv.shape) != (B, actv.shape[1], H, W):
-                raise RuntimeError("spade_fused: weight %s / actv %s do not fit x %s" % (tuple(w.shape), tuple(actv.shape),
+        for m in mods:
+            if (m.actv.dim() != 4 or tuple(m.w.shape) != (2 * C, m.actv.shape[1], 3, 3)
+                    or tuple(m.actv.shape) != (B, m.actv.shape[1], H, W)):
+                raise RuntimeError("spade_fused: weight %s / actv %s do not fit x %s" % (tuple(m.w.shape), tuple(m.actv.shape),
                                                                                          tuple(x.shape)))
-        P = B * H * W
         dev = x.device
-        world = _sync_world() if sync else 1
-        multi = _multi(world, sync)
-        count = float(P * world)
-        mean = torch.empty(C, device=dev, dtype=torch.float32)
-        invstd = torch.empty(C, device=dev, dtype=torch.float32)
-        nch = _chunks(P, 1)
-        part = torch.empty(nch * 2 * C, device=dev, dtype=torch.float64)
-        pending = sums = None
-        if not multi:                                # one rank: statistics finalised right away (two launches in all)
-            r0, r1 = (mods[3], mods[4]), ((mods[10], mods[11]) if K == 2 else (None, None))
-            check(lib.csg_norm_stats_finalize(ptr(x), 1, P, C, ptr(part), nch, count, eps, ptr(mean), ptr(invstd), ptr(r0[0]),
-                                              ptr(r0[1] if r0[0] is not None else None), ptr(r1[0]),
-                                              ptr(r1[1] if r1[0] is not None else None), momentum, stream()),
-                  "norm_stats_finalize")
-        else:
-            sums = torch.empty(2 * C, device=dev, dtype=torch.float64)
-            check(lib.csg_norm_stats(ptr(x), 1, P, C, ptr(sums), ptr(part), nch, stream()), "norm_stats")
-            # N > 1: the statistics travel while the gamma halves (which do not need them) are computed
-            pending = csg_dist.all_reduce_stats_async(sums)
+        norm = _Norm(x, 1, eps, sync)
+        # one rank: statistics finalised right away (two launches in all).  N > 1: the statistics travel while the gamma
+        # halves (which do not need them) are computed
+        mean, invstd, finish_stats = norm.stats(x, momentum, [(m.rm, m.rv) for m in mods], overlap=True)
         # per modulation, by index k: its output and saved (actv, w, gamma, y) — the joint launches finish inside the loop,
         # the launch pairs after it
         outs, groups, launches, plans, pres = [None] * K, [None] * K, [], [], []
         # One rank, C a multiple of 32: ONE launch per modulation (csg_wino4_conv_spade: blocks own a gamma tile and its beta
         # tile; gamma is written for the backward but never read back, the 128-channel input is staged once).  N > 1 ranks keep
         # the launch pair: the gamma halves, which need no statistics, run while the SyncBN message travels.
-        joint = SPADE_JOINT and not multi and C % 32 == 0
-        for k in range(K):
-            actv, w, b, rm, rv, slope, in_slope = mods[k * 7:(k + 1) * 7]
-            actv = nhwc(_f32(actv))
+        joint = SPADE_JOINT and not norm.multi
+        for k, m in enumerate(mods):
+            actv = nhwc(_f32(m.actv))
             nh = actv.shape[1]
-            up = wino_pack(w, False, None, 4)
+            up = wino_pack(m.w, False, None, 4)
             # the joined gamma || beta convolution's backward passes (_conv_bwd on d(gamma || beta))
             plans.append(plan_conv(B, H, W, nh, 2 * C, 3, 3, 1, 1, has_bias=True,
-                                   in_act=(ACT_LEAKY, in_slope) if in_slope is not None else None,
-                                   need=ctx.needs_input_grad[4 + 7 * k:7 + 7 * k]))
-            pres.append(_take_dx_operand(plans[k], w))
-            bd = b.detach().contiguous()
+                                   in_act=(ACT_LEAKY, m.in_slope) if m.in_slope is not None else None,
+                                   need=_SpadeFused._conv_needs(ctx, k)))
+            pres.append(_take_dx_operand(plans[k], m.w))
+            bd = m.b.detach().contiguous()
             gbuf = empty_nhwc(B, C, H, W, dev)                # gamma only: beta is consumed in the epilogue that forms it
             d = _wino_desc(B, H, W, nh, C)
             d.y_cs = C
@@ -1261,69 +1289,44 @@ class _SpadeFused(torch.autograd.Function):
                 y = torch.empty_like(x)
                 _wino4_audit("spade_joint", B * H * W, nh + 3 * C, up)          # actv, x read; gamma, y written
                 check(lib.csg_wino4_conv_spade(d, ptr(actv), ptr(up), ptr(bd), ptr(x), ptr(gbuf), C, ptr(mean), ptr(invstd),
-                                               slope, ptr(y), stream()), "wino4_conv_spade")
-                outs[k], groups[k] = y, [actv, w, gbuf, y]
+                                               m.slope, ptr(y), stream()), "wino4_conv_spade")
+                outs[k], groups[k] = y, _SpadeSaved(actv, m.w, gbuf, y)
                 continue
             _wino4_audit("spade_gamma", B * H * W, nh + C, up)
             _wino4_audit("spade_beta", B * H * W, nh + 3 * C, up)
             check(lib.csg_wino4_conv_part(d, ptr(actv), ptr(up), 0, 2 * C // 32, ptr(bd), None, None, 0, None, None, 1.0,
                                           ptr(gbuf), stream()), "wino4_conv_part(gamma)")
-            launches.append((k, actv, w, up, bd, gbuf, nh, slope))
-        if pending is not None:
-            pending.wait()
-        for k in range(K if multi else 0):
-            rm, rv = mods[k * 7 + 3], mods[k * 7 + 4]
-            check(lib.csg_norm_finalize(ptr(sums), 1, C, count, eps, 1, ptr(mean), ptr(invstd), ptr(rm),
-                                        ptr(rv if rm is not None else None), momentum, stream()), "norm_finalize")
-        for (k, actv, w, up, bd, gbuf, nh, slope) in launches:
+            launches.append((k, actv, up, bd, gbuf, nh))
+        finish_stats()
+        for (k, actv, up, bd, gbuf, nh) in launches:
             y = torch.empty_like(x)
             d = _wino_desc(B, H, W, nh, C)
             d.y_cs = C
             check(lib.csg_wino4_conv_part(d, ptr(actv), ptr(up), C // 32, 2 * C // 32, ptr(bd[C:]), ptr(x), ptr(gbuf), C,
-                                          ptr(mean), ptr(invstd), slope, ptr(y), stream()), "wino4_conv_part(beta)")
-            outs[k], groups[k] = y, [actv, w, gbuf, y]
+                                          ptr(mean), ptr(invstd), mods[k].slope, ptr(y), stream()), "wino4_conv_part(beta)")
+            outs[k], groups[k] = y, _SpadeSaved(actv, mods[k].w, gbuf, y)
         ctx.save_for_backward(x, mean, invstd, *[t for g in groups for t in g])
-        ctx.cfg = (K, P, C, B, H, W, multi, count, eps, tuple(mods[k * 7 + 5] for k in range(K)))
+        ctx.norm, ctx.slopes = norm, tuple(m.slope for m in mods)
         ctx.plans, ctx.ut_pres = plans, pres
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dys):
-        K, P, C, B, H, W, multi, count, eps, slopes = ctx.cfg
-        sv = ctx.saved_tensors
-        x, mean, invstd = sv[0], sv[1], sv[2]
-        dev = x.device
-        nch = _chunks(P, 1)
-        part = torch.empty(nch * 2 * C, device=dev, dtype=torch.float64)
-        dsums = torch.empty(K, 2 * C, device=dev, dtype=torch.float64)
-        dys = [nhwc(dy) for dy in dys]
-        dgbs = []
-        for k in range(K):
-            actv, w, gbuf, y = sv[3 + 4 * k:7 + 4 * k]
-            dgb = empty_nhwc(B, 2 * C, H, W, dev)             # d(gamma || beta): the joined convolution's incoming gradient
-            check(lib.csg_norm_apply_bwd_reduce(ptr(dys[k]), ptr(x), ptr(mean), ptr(invstd), ptr(gbuf), ptr(y), slopes[k], 1, P,
-                                                C, ptr(dgb), ptr(dsums[k]), ptr(part), nch, C, stream()), "norm_bwd_reduce")
-            dgbs.append(dgb)
-        dx, both, pending = None, None, None
-        if ctx.needs_input_grad[0]:
-            both = dsums[0] + dsums[1] if K == 2 else dsums[0]
-            # N > 1: the reductions travel while the convolution's backward passes (which need only d(gamma || beta)) run
-            pending = csg_dist.all_reduce_stats_async(_drop_clamped_invstd_term(both, invstd, eps, C)) if multi else None
-        grads = [None, None, None, None]
-        for k in range(K):
-            actv, w, gbuf, y = sv[3 + 4 * k:7 + 4 * k]
-            need = ctx.needs_input_grad[4 + 7 * k:7 + 7 * k]
-            grads += list(_conv_bwd(ctx.plans[k], dgbs[k], actv, w, None, need, None, ctx.ut_pres[k])) + [None] * 4
-        if ctx.needs_input_grad[0]:
-            if pending is not None:
-                pending.wait()
-            dx = torch.empty_like(x)
-            two = K == 2
-            check(lib.csg_norm_apply_bwd_dx(ptr(dys[0]), ptr(x), ptr(mean), ptr(invstd), ptr(sv[5]), slopes[0], ptr(both), count,
-                                            1, P, C, ptr(dx), ptr(dys[1]) if two else None, ptr(sv[9]) if two else None,
-                                            slopes[1] if two else 1.0, ptr(dgbs[0]), ptr(dgbs[1]) if two else None, C, stream()),
-                  "norm_bwd_dx")
-            grads[0] = dx
+        x, mean, invstd, *rest = ctx.saved_tensors
+        saved = _groups(rest, _SpadeSaved)
+        B, C, H, W = x.shape
+        want_dx, *_ = ctx.needs_input_grad
+        # d(gamma || beta) per modulation: the joined convolution's incoming gradient
+        dgbs = [empty_nhwc(B, 2 * C, H, W, x.device) for _ in saved]
+        # N > 1: the reductions travel while the convolution's backward passes (which need only d(gamma || beta)) run
+        finish_dx = ctx.norm.backward(x, mean, invstd, [(nhwc(dy), s.gamma, s.y, slope, dgb)
+                                                        for dy, s, slope, dgb in zip(dys, saved, ctx.slopes, dgbs)],
+                                      want_dx, gamma_only=True, overlap=True)
+        grads = [None] * _SpadeFused.HEAD
+        for k, s in enumerate(saved):
+            r = _conv_bwd(ctx.plans[k], dgbs[k], s.actv, s.w, None, _SpadeFused._conv_needs(ctx, k), None, ctx.ut_pres[k])
+            grads += list(r) + [None] * (_SpadeFused.NARG - len(r))
+        grads[0] = finish_dx()
         return tuple(grads)
 
 
@@ -1339,66 +1342,28 @@ class _SpadeJoined(torch.autograd.Function):
     def forward(ctx, x, actv, w, b, running_mean, running_var, pad, slope, in_slope, eps, momentum, sync):
         x = nhwc(_f32(x))
         B, C, H, W = x.shape
-        P = B * H * W
-        dev = x.device
-        world = _sync_world() if sync else 1
-        multi = _multi(world, sync)
-        count = float(P * world)
-        mean = torch.empty(C, device=dev, dtype=torch.float32)
-        invstd = torch.empty(C, device=dev, dtype=torch.float32)
-        nch = _chunks(P, 1)
-        part = torch.empty(nch * 2 * C, device=dev, dtype=torch.float64)
-        pending = sums = None
-        if not multi:
-            check(lib.csg_norm_stats_finalize(ptr(x), 1, P, C, ptr(part), nch, count, eps, ptr(mean), ptr(invstd),
-                                              ptr(running_mean), ptr(running_var if running_mean is not None else None), None,
-                                              None, momentum, stream()), "norm_stats_finalize")
-        else:
-            sums = torch.empty(2 * C, device=dev, dtype=torch.float64)
-            check(lib.csg_norm_stats(ptr(x), 1, P, C, ptr(sums), ptr(part), nch, stream()), "norm_stats")
-            pending = csg_dist.all_reduce_stats_async(sums)
+        norm = _Norm(x, 1, eps, sync)
+        mean, invstd, finish_stats = norm.stats(x, momentum, [(running_mean, running_var)], overlap=True)
         # the joined convolution, planned for all three gradients whatever this call needs (the backward-data operand is
         # taken now, as for any convolution whose input needs a gradient)
         actv = nhwc(_f32(actv))
         ctx.plan = plan_conv(B, H, W, actv.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, int(pad), has_bias=b is not None,
                              in_act=(ACT_LEAKY, float(in_slope)) if in_slope is not None else None, need=(True, True, True))
         gb, ctx.ut_pre = _conv_fwd(ctx.plan, actv, w, b, None, None)
-        if pending is not None:
-            pending.wait()
-        if multi:
-            check(lib.csg_norm_finalize(ptr(sums), 1, C, count, eps, 1, ptr(mean), ptr(invstd),
-                                        ptr(running_mean), ptr(running_var if running_mean is not None else None), momentum,
-                                        stream()), "norm_finalize")
-        y = torch.empty_like(x)
-        check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb), slope, 1, P, C, ptr(y), None, 1.0, None, stream()),
-              "norm_apply_fwd")
+        finish_stats()
+        y, = norm.apply(x, mean, invstd, [(gb, slope)])
         ctx.save_for_backward(x, gb, mean, invstd, actv, w)
-        ctx.cfg = (P, C, slope, multi, count, eps)
+        ctx.norm, ctx.slope = norm, slope
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gb, mean, invstd, cx, cw = ctx.saved_tensors
-        P, C, slope, multi, count, eps = ctx.cfg
-        dy = nhwc(dy)
-        dev = x.device
-        nch = _chunks(P, 1)
-        part = torch.empty(nch * 2 * C, device=dev, dtype=torch.float64)
-        dsums = torch.empty(2 * C, device=dev, dtype=torch.float64)
         dgb = torch.empty_like(gb)
-        check(lib.csg_norm_apply_bwd_reduce(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), None, slope, 1, P, C, ptr(dgb),
-                                            ptr(dsums), ptr(part), nch, 2 * C, stream()), "norm_bwd_reduce")
-        pending = (csg_dist.all_reduce_stats_async(_drop_clamped_invstd_term(dsums, invstd, eps, C))
-                   if (multi and ctx.needs_input_grad[0]) else None)
+        finish_dx = ctx.norm.backward(x, mean, invstd, [(nhwc(dy), gb, None, ctx.slope, dgb)], ctx.needs_input_grad[0],
+                                      overlap=True)
         r = _conv_bwd(ctx.plan, dgb, cx, cw, None, ctx.needs_input_grad[1:4], None, ctx.ut_pre)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if pending is not None:
-                pending.wait()
-            dx = torch.empty_like(x)
-            check(lib.csg_norm_apply_bwd_dx(ptr(dy), ptr(x), ptr(mean), ptr(invstd), ptr(gb), slope, ptr(dsums), count,
-                                            1, P, C, ptr(dx), None, None, 1.0, ptr(dgb), None, 2 * C, stream()), "norm_bwd_dx")
-        return dx, r[0], r[1], r[2], None, None, None, None, None, None, None, None
+        return finish_dx(), r[0], r[1], r[2], None, None, None, None, None, None, None, None
 
 
 def spade_joined(x, actv, w, b, running_mean, running_var, pad, slope, in_slope, eps=1e-5, momentum=0.1, sync=True):

@@ -119,6 +119,12 @@ def _joined(mod, name, pa, pb):
     return _JoinedPair.apply(pa, pb, j)
 
 
+def _training_batchnorm(pn):
+    """A param-free (Synchronized|Local)BatchNorm2d in training mode: batch statistics and nothing else, what
+    ops._SpadeFused, ops._SpadeJoined and ops._NormActPair serve."""
+    return isinstance(pn, (SynchronizedBatchNorm2d, LocalBatchNorm2d)) and not pn.affine and pn.training
+
+
 class SPADE(nn.Module):
     def __init__(self, config_text, norm_nc, label_nc):
         super().__init__()
@@ -155,17 +161,15 @@ class SPADE(nn.Module):
         """Training-mode param-free BatchNorm on a map the fused epilogue does not serve (8 x 8, 16 x 16): statistics,
         convolution and modulation ordered inside one Function (ops._SpadeJoined) so that the SyncBN messages of N > 1 ranks
         travel under the gamma || beta convolution; the kernels are those of the plain path."""
-        pn = self.param_free_norm
-        return (ops.SPADE_JOINED and isinstance(pn, (SynchronizedBatchNorm2d, LocalBatchNorm2d)) and not pn.affine
-                and pn.training and x.dim() == 4 and x.is_cuda and self.mlp_gamma.weight.shape[0] % 4 == 0)
+        return (ops.SPADE_JOINED and _training_batchnorm(self.param_free_norm) and x.dim() == 4 and x.is_cuda
+                and self.mlp_gamma.weight.shape[0] % 4 == 0)
 
     def fusable(self, x):
         """The modulation can ride in the epilogue of the gamma || beta convolution (ops._SpadeFused): a param-free
         BatchNorm in training mode, 3x3 convolutions on a map F(4x4,3x3) serves."""
-        pn = self.param_free_norm
-        return (isinstance(pn, (SynchronizedBatchNorm2d, LocalBatchNorm2d)) and not pn.affine and pn.training
+        return (_training_batchnorm(self.param_free_norm)
                 and ops.spade_fused_eligible(x, self.mlp_gamma.weight.shape[1], self.mlp_gamma.weight.shape[0],
-                                             self.mlp_gamma.weight.shape[2], pn.training))
+                                             self.mlp_gamma.weight.shape[2]))
 
     def joined_weight(self):
         """The gamma || beta weight as ONE (2C, nhidden, ks, ks) tensor (the two parameters' own memory), joined now if it
@@ -173,20 +177,8 @@ class SPADE(nn.Module):
         _joined(self, "_joined_w", self.mlp_gamma.weight, self.mlp_beta.weight)
         return self.__dict__.get("_joined_w")
 
-    def fused_operands(self, x, segmap, slope):
-        if isinstance(segmap, SegPyramid):
-            seg = segmap.at(x.size(2))
-        else:
-            seg = segmap if segmap.shape[2:] == x.shape[2:] else ops.nearest_resize(segmap, x.shape[2:])
-        sh = self.mlp_shared[0]
-        actv = ops.conv2d(seg, sh.weight, sh.bias, 1, sh.padding[0], sh.act, sh.slope, grad_is_pre=True)
-        w = _joined(self, "_joined_w", self.mlp_gamma.weight, self.mlp_beta.weight)
-        b = _joined(self, "_joined_b", self.mlp_gamma.bias, self.mlp_beta.bias)
-        pn = self.param_free_norm
-        return (actv, w, b, pn.running_mean, pn.running_var, slope, sh.slope)
-
-    def modulation(self, x, segmap):
-        """gamma || beta (B, 2C, h, w) of this SPADE for a feature map shaped like x."""
+    def _conv_operands(self, x, segmap):
+        """(actv, w, b) of the gamma || beta convolution for a feature map shaped like x."""
         if isinstance(segmap, SegPyramid):
             seg = segmap.at(x.size(2))
         else:
@@ -200,7 +192,18 @@ class SPADE(nn.Module):
         # parameters laid out back to back in one allocation (no torch.cat per call)
         w = _joined(self, "_joined_w", self.mlp_gamma.weight, self.mlp_beta.weight)
         b = _joined(self, "_joined_b", self.mlp_gamma.bias, self.mlp_beta.bias)
-        return ops.conv2d(actv, w, b, 1, self.pw, in_act=(sh.act, sh.slope))    # (B, 2C, h, w): gamma || beta
+        return actv, w, b
+
+    def fused_operands(self, x, segmap, slope):
+        """One modulation of ops.spade_fused (the operands of ops.spade_joined): the convolution runs inside the Function."""
+        pn = self.param_free_norm
+        return self._conv_operands(x, segmap) + (pn.running_mean, pn.running_var, slope, self.mlp_shared[0].slope)
+
+    def modulation(self, x, segmap):
+        """gamma || beta (B, 2C, h, w) of this SPADE for a feature map shaped like x."""
+        actv, w, b = self._conv_operands(x, segmap)
+        sh = self.mlp_shared[0]
+        return ops.conv2d(actv, w, b, 1, self.pw, in_act=(sh.act, sh.slope))
 
 
 def spade_pair(norm_a, norm_b, x, segmap, slope_a, slope_b):
@@ -209,9 +212,8 @@ def spade_pair(norm_a, norm_b, x, segmap, slope_a, slope_b):
     pass over x (ops.norm_act_pair).  Anything else (eval mode: each module has its own running statistics; instance
     norm; affine norms) takes the two ordinary calls."""
     pa, pb = norm_a.param_free_norm, norm_b.param_free_norm
-    same = (type(pa) is type(pb) and isinstance(pa, (SynchronizedBatchNorm2d, LocalBatchNorm2d)) and not pa.affine
-            and not pb.affine and pa.training and pb.training and pa.eps == pb.eps and pa.momentum == pb.momentum
-            and getattr(pa, "sync", True) == getattr(pb, "sync", True) and x.dim() == 4)
+    same = (type(pa) is type(pb) and _training_batchnorm(pa) and _training_batchnorm(pb) and pa.eps == pb.eps
+            and pa.momentum == pb.momentum and getattr(pa, "sync", True) == getattr(pb, "sync", True) and x.dim() == 4)
     if not same:
         return norm_a(x, segmap, fused_slope=slope_a), norm_b(x, segmap, fused_slope=slope_b)
     if norm_a.fusable(x) and norm_b.fusable(x):
