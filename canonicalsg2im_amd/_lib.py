@@ -67,6 +67,11 @@ class SnBwdItem(ctypes.Structure):
                 ("workspace", c_p), ("workspace_bytes", c_i64)]
 
 
+class NormEvalItem(ctypes.Structure):
+    """Mirror of `csg_norm_eval_item` (include/csg_hip.h)."""
+    _fields_ = [("running_mean", c_p), ("running_var", c_p), ("C", c_i64), ("offset", c_i64)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/csg_hip.h
 class GemmDesc(ctypes.Structure):
     """csg_gemm_desc (include/csg_hip.h)."""
@@ -154,6 +159,10 @@ SIGNATURES = {
     "csg_norm_stats_finalize": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_f64, c_f32, c_p, c_p, c_p, c_p, c_p, c_p, c_f32,
                                         c_p]),
     "csg_norm_apply_fwd": (c_i32, [c_p, c_p, c_p, c_p, c_f32, c_i64, c_i64, c_i64, c_p, c_p, c_f32, c_p, c_p]),
+    "csg_norm_eval_stats_multi": (c_i32, [ctypes.POINTER(NormEvalItem), c_i32, c_f32, c_p, c_p]),
+    "csg_deprocess_u8_workspace": (c_i64, [c_i64]),
+    "csg_deprocess_u8": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_i32, c_p, c_p,
+                                 c_i64, c_p]),
     "csg_norm_apply_bwd_reduce": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64,
                                           c_i64, c_p]),
     "csg_norm_apply_bwd_dx": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_f64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_f32,

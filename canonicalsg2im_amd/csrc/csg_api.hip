@@ -125,13 +125,14 @@ static const char* kNames[K_COUNT] = {
     "wino_conv",      "wino_pack",      "wino_wgrad",
     "few_fwd",        "few_bwd_data",   "few_bwd_weight",
     "wino4_conv",     "wino4_wgrad",
-    "gemm_nt",        "gemm_tn"};
+    "gemm_nt",        "gemm_tn",
+    "norm_eval_stats", "deprocess_u8"};
 
 }  // namespace csg
 
 extern "C" {
 
-int csg_version(void) { return 109; }
+int csg_version(void) { return 110; }
 const char* csg_last_error(void) { return csg::g_err; }
 
 int csg_prof_enable(int on) {

@@ -61,6 +61,8 @@ enum KernelId {
   K_WINO4_WGRAD,
   K_GEMM_NT,
   K_GEMM_TN,
+  K_NORM_EVAL_STATS,
+  K_DEPROCESS,
   K_COUNT
 };
 

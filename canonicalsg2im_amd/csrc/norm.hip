@@ -198,6 +198,26 @@ __global__ void k_norm_finalize(const double* __restrict__ sums, int G, int C, d
   }
 }
 
+// eval-mode statistics of many BatchNorms in one launch: item i's (running_mean, running_var) -> out[offset .. offset + C) = mean,
+// out[offset + C .. offset + 2C) = 1 / sqrt(var + eps) — the one-device F.batch_norm formula, correctly rounded sqrt and division
+constexpr int kEvalStatsMax = 32;   // items per launch (the table travels in the kernel arguments: capturable)
+struct EvalStatsTable {
+  const float* mean[kEvalStatsMax];
+  const float* var[kEvalStatsMax];
+  int C[kEvalStatsMax];
+  int64_t off[kEvalStatsMax];
+};
+
+__global__ __launch_bounds__(256) void k_norm_eval_stats(EvalStatsTable t, float eps, float* __restrict__ out) {
+  const int i = blockIdx.y;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int C = t.C[i];
+  if (c >= C) return;
+  float* o = out + t.off[i];
+  o[c] = t.mean[i][c];
+  o[C + c] = 1.0f / sqrtf(t.var[i][c] + eps);
+}
+
 // --------------------------------------------------------------------------------- apply fwd
 // (gb2, slope2, y2), nullable: a second modulation of the same normalised x, written in the same pass (x read once)
 __global__ __launch_bounds__(256) void k_norm_apply_fwd(const float* __restrict__ x, const float* __restrict__ mean,
@@ -577,6 +597,35 @@ int csg_norm_finalize(const double* sums, int64_t G, int64_t C, double count, fl
   CSG_LAUNCH(k_norm_finalize, dim3((unsigned)cdiv(G * C, 256)), dim3(256), 0, s, sums, (int)G, (int)C, count,
                      eps, mode, mean, invstd, running_mean, running_var, momentum);
   return check_launch("csg_norm_finalize");
+}
+
+int csg_norm_eval_stats_multi(const csg_norm_eval_item* items, int32_t n, float eps, float* out, void* stream) {
+  CSG_REQUIRE(items != nullptr && n > 0 && out != nullptr, CSG_E_BADSHAPE, "csg_norm_eval_stats_multi: no items");
+  int64_t end = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const csg_norm_eval_item& it = items[i];
+    CSG_REQUIRE(it.running_mean != nullptr && it.running_var != nullptr && it.C > 0 && it.C <= (1 << 24), CSG_E_BADSHAPE,
+                "csg_norm_eval_stats_multi: item %d: null statistics or bad C = %ld", (int)i, (long)it.C);
+    // the caller packs the items back to back, in order: no item writes into another's slot
+    CSG_REQUIRE(it.offset >= end, CSG_E_BADSHAPE, "csg_norm_eval_stats_multi: item %d overlaps its predecessor", (int)i);
+    end = it.offset + 2 * it.C;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope p(K_NORM_EVAL_STATS, (double)end * 8, s);
+  for (int32_t i0 = 0; i0 < n; i0 += kEvalStatsMax) {
+    EvalStatsTable t = {};
+    const int m = n - i0 < kEvalStatsMax ? n - i0 : kEvalStatsMax;
+    int64_t maxC = 0;
+    for (int i = 0; i < m; ++i) {
+      t.mean[i] = items[i0 + i].running_mean;
+      t.var[i] = items[i0 + i].running_var;
+      t.C[i] = (int)items[i0 + i].C;
+      t.off[i] = items[i0 + i].offset;
+      if (items[i0 + i].C > maxC) maxC = items[i0 + i].C;
+    }
+    CSG_LAUNCH(k_norm_eval_stats, dim3((unsigned)cdiv(maxC, 256), (unsigned)m), dim3(256), 0, s, t, eps, out);
+  }
+  return check_launch("csg_norm_eval_stats_multi");
 }
 
 int csg_norm_apply_fwd(const float* x, const float* mean, const float* invstd, const float* gb, float slope,

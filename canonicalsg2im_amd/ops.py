@@ -21,7 +21,7 @@ from ._lib import ACT_LEAKY, ACT_NONE, ACT_TANH, ConvDesc, FewDesc, GemmDesc, Hi
 __all__ = [
     "nhwc", "empty_nhwc", "conv2d", "linear", "norm_act", "upsample2x", "nearest_resize", "avgpool3s2", "embed", "real_object_mask",
     "norm_act_pair", "graph_csr", "gather_concat", "segment_avg", "layout_pyramid", "layout_paint", "disc_input", "crop_objects", "maxpool2", "avgpool2", "l1_mean",
-    "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
+    "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
 ]
 
 
@@ -1391,6 +1391,126 @@ def norm_act(x, gb=None, running_mean=None, running_var=None, instance=False, tr
              momentum=0.1, sync=True):
     return _NormAct.apply(x, gb, running_mean, running_var, bool(instance), bool(training), float(slope), float(eps),
                           float(momentum), bool(sync))
+
+
+# ------------------------------------------------------------------------------------ inference forms (sample.py)
+# Plain functions, no autograd: frozen weights, running statistics.  Nothing above calls them — SPADE.forward and spade_pair
+# serve eval mode exactly as before; the sampler's generator walk is the one caller.
+def pack_frozen_forward(weight):
+    """pack_conv_weight for a weight that only ever runs FORWARD: [Cout][KH][KW][Cin] (input channels zero-padded to a
+    multiple of 4; a view of a channels-last weight) and, for 3x3 weights, the F(2x2,3x3) operand; the F(4x4,3x3) one joins
+    on first use (_frozen_pack).  No backward-data layouts."""
+    pc = (-weight.shape[1]) % 4
+    w = F.pad(weight.detach(), (0, 0, 0, 0, 0, pc)) if pc else weight.detach()
+    fwd = w.permute(0, 2, 3, 1).contiguous()
+    if WINO_ENABLED and w.shape[2] == 3 and w.shape[3] == 3 and w.shape[0] % 4 == 0:
+        return FrozenPacks(fwd, None, wino_pack(w, False), None, {"w": w})
+    return FrozenPacks(fwd, None)
+
+
+def norm_eval_stats(pairs, eps=1e-5):
+    """[(running_mean, running_var), ...] -> [(mean, invstd), ...] with invstd = 1 / sqrt(running_var + eps): F.batch_norm's
+    eval formula for every pair in ONE launch (csg_norm_eval_stats_multi), views of one flat buffer.  A sampler calls this
+    once per loaded checkpoint."""
+    if not pairs:
+        return []
+    items = (_lib.NormEvalItem * len(pairs))()
+    off, offs = 0, []
+    for i, (rm, rv) in enumerate(pairs):
+        rm, rv = _f32(rm), _f32(rv)
+        C = rm.numel()
+        if rv.numel() != C or not rm.is_contiguous() or not rv.is_contiguous():
+            raise RuntimeError("norm_eval_stats: running mean and variance must be dense vectors of one length")
+        items[i].running_mean, items[i].running_var = ptr(rm).value, ptr(rv).value
+        items[i].C, items[i].offset = C, off
+        offs.append((off, C))
+        off += 2 * ((C + 3) // 4 * 4)                 # every vector starts on a 16-byte boundary
+    flat = torch.empty(off, device=pairs[0][0].device, dtype=torch.float32)
+    check(lib.csg_norm_eval_stats_multi(items, len(pairs), float(eps), ptr(flat), stream()), "norm_eval_stats_multi")
+    return [(flat[o:o + C], flat[o + C:o + 2 * C]) for o, C in offs]
+
+
+# what spade_infer takes per modulation: spade_fused's record with the frozen layouts of `w` (pack_frozen_forward, or None:
+# packed per call) in place of the slope of the producing ReLU, which only a backward needs
+_SpadeInferMod = collections.namedtuple("_SpadeInferMod", "actv w b rm rv slope packs")
+
+
+def spade_infer(x, mods, eps=1e-5, stats=None, scratch=None, outs=None):
+    """Eval-mode SPADE modulations of x (reference normalization.py:96-110 with F.batch_norm(training=False)): for each of
+    the one or two records (actv, w, b, running_mean, running_var, slope, packs) in `mods`,
+    leaky(((x - mean) * invstd) * (1 + gamma) + beta, slope) with gamma || beta = conv3x3(actv, w) + b, mean the running
+    mean and invstd = 1 / sqrt(running_var + eps).  Two modulations (norm_s and norm_0 of a block) have their own running
+    statistics in eval mode: they are independent.  `stats`: [(mean, invstd)] as norm_eval_stats made them (None: made
+    here).  `scratch`: a float buffer of at least x.numel() entries for the launch pair's gamma map (None: allocated).
+    `outs`: the maps to write, shaped and laid out like x (None: allocated).
+    Maps the F(4x4,3x3) kernel serves (wino_variant, i.e. CSG_WINO4_MIN_ITEMS applies): ONE csg_wino4_conv_spade launch
+    that writes neither gamma nor beta, or the csg_wino4_conv_part pair where that launch does not exist.  Other maps (8 x 8,
+    16 x 16, small batches): the plain convolution, then csg_norm_apply_fwd.  Returns the list of modulated maps."""
+    mods = [_SpadeInferMod(*m) for m in mods]
+    x = nhwc(_f32(x))
+    B, C, H, W = x.shape
+    if stats is None:
+        stats = norm_eval_stats([(m.rm, m.rv) for m in mods], eps)
+    done = []
+    for m, (mean, invstd) in zip(mods, stats):
+        actv = nhwc(_f32(m.actv))
+        nh = actv.shape[1]
+        if tuple(m.w.shape) != (2 * C, nh, 3, 3) or tuple(actv.shape) != (B, nh, H, W) or mean.numel() != C:
+            raise RuntimeError("spade_infer: weight %s / actv %s / statistics %d do not fit x %s" % (
+                tuple(m.w.shape), tuple(actv.shape), mean.numel(), tuple(x.shape)))
+        y = torch.empty_like(x) if outs is None else outs[len(done)]
+        if y.shape != x.shape or y.stride() != x.stride() or y.dtype != x.dtype:
+            raise RuntimeError("spade_infer: an output must be shaped and laid out like x")
+        if spade_fused_eligible(x, nh, C, 3) and wino_variant(B, H, W, nh, 2 * C) == 4:
+            up = _frozen_pack(m.packs, False, 4) if m.packs is not None else wino_pack(m.w, False, None, 4)
+            bd = m.b.detach().contiguous()
+            d = _wino_desc(B, H, W, nh, C)
+            d.y_cs = C
+            if SPADE_JOINT and lib.csg_wino4_conv_spade_supported(d):
+                _wino4_audit("spade_infer", B * H * W, nh + 2 * C, up)             # actv, x read; y written
+                check(lib.csg_wino4_conv_spade(d, ptr(actv), ptr(up), ptr(bd), ptr(x), None, C, ptr(mean), ptr(invstd),
+                                               float(m.slope), ptr(y), stream()), "wino4_conv_spade(infer)")
+            else:
+                gbuf = scratch if (scratch is not None and scratch.numel() >= x.numel()) else \
+                    torch.empty(x.numel(), device=x.device, dtype=torch.float32)
+                check(lib.csg_wino4_conv_part(d, ptr(actv), ptr(up), 0, 2 * C // 32, ptr(bd), None, None, 0, None, None, 1.0,
+                                              ptr(gbuf), stream()), "wino4_conv_part(gamma)")
+                check(lib.csg_wino4_conv_part(d, ptr(actv), ptr(up), C // 32, 2 * C // 32, ptr(bd[C:]), ptr(x), ptr(gbuf), C,
+                                              ptr(mean), ptr(invstd), float(m.slope), ptr(y), stream()), "wino4_conv_part(beta)")
+        else:
+            with torch.no_grad():
+                gb = nhwc(conv2d(actv, m.w, m.b, 1, 1, packs=m.packs))
+            check(lib.csg_norm_apply_fwd(ptr(x), ptr(mean), ptr(invstd), ptr(gb), float(m.slope), 1, B * H * W, C, ptr(y),
+                                         None, 1.0, None, stream()), "norm_apply_fwd")
+        done.append(y)
+    return done
+
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)                 # sg2im/data/utils.py:6-10
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def deprocess_u8(img, rescale=True):
+    """deprocess_batch(img, rescale, imagenet_deprocess) (sg2im/data/utils.py:36-65) on the device: a logical (B,3|4,H,W)
+    fp32 image with NHWC memory (a channels-last image, or conv_img's 4-padded output: a 3-channel slice of it is taken
+    with its padding) -> uint8 (B,3,H,W), byte for byte what the fp32 host code gives (csg_deprocess_u8)."""
+    img = _f32(img)
+    if img.dim() != 4 or img.stride(1) != 1 or img.shape[1] not in (3, 4):
+        raise RuntimeError("deprocess_u8: a (B,3,H,W) image with NHWC memory is needed, got %s strides %s" % (
+            tuple(img.shape), tuple(img.stride())))
+    B, _, H, W = img.shape
+    cs = img.stride(3)
+    if cs not in (3, 4) or img.stride(2) != W * cs or img.stride(0) != H * W * cs:
+        raise RuntimeError("deprocess_u8: pixels must be dense rows of 3 or 4 floats, got strides %s" % (tuple(img.stride()),))
+    out = torch.empty((B, 3, H, W), device=img.device, dtype=torch.uint8)
+    nws = lib.csg_deprocess_u8_workspace(B) if rescale else 0
+    ws = torch.empty(nws // 4, device=img.device, dtype=torch.float32) if nws else None
+    # the fp32 values torch.as_tensor(INV_IMAGENET_STD / INV_IMAGENET_MEAN, dtype=float32) holds (T.Normalize, utils.py:38-39)
+    div = (_lib.c_f32 * 3)(*[1.0 / s for s in IMAGENET_STD])
+    sub = (_lib.c_f32 * 3)(*[-m for m in IMAGENET_MEAN])
+    check(lib.csg_deprocess_u8(ptr(img), B, H, W, cs, div, sub, 1 if rescale else 0, ptr(out), ptr(ws), nws, stream()),
+          "deprocess_u8")
+    return out
 
 
 # ------------------------------------------------------------------------------------ resampling

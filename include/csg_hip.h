@@ -43,7 +43,8 @@ extern "C" {
 
 /* 100 + the number of additive revisions of this header: entry points are only ever added, never changed or removed
  * (108: csg_wino4_conv_spade, csg_wino4_conv_spade_supported, csg_avgpool3s2_bwd_add, csg_hinge_mean_fwd / _bwd;
- * 109: csg_canon_general_workspace, csg_canon_general_build / _converse / _close / _emit) */
+ * 109: csg_canon_general_workspace, csg_canon_general_build / _converse / _close / _emit;
+ * 110: csg_norm_eval_stats_multi, csg_deprocess_u8_workspace, csg_deprocess_u8) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -430,6 +431,20 @@ int csg_norm_stats_finalize(const float* x, int64_t G, int64_t P, int64_t C, dou
 int csg_norm_apply_fwd(const float* x, const float* mean, const float* invstd, const float* gb, float slope,
                        int64_t G, int64_t P, int64_t C, float* y, const float* gb2, float slope2, float* y2,
                        void* stream);
+/* Eval-mode statistics of MANY BatchNorms in one launch (F.batch_norm(training=False), sync_batchnorm/batchnorm.py:65-68, for
+ * every param-free norm of the generator's SPADE layers, normalization.py:100): item i turns its (running_mean, running_var)
+ * into out[offset, offset + C) = mean and out[offset + C, offset + 2C) = invstd = 1 / sqrt(var + eps) — fp32, correctly rounded
+ * square root and division (the one-device formula, not the N-replica clamp).  What csg_norm_apply_fwd, csg_wino4_conv_part and
+ * csg_wino4_conv_spade take as (mean, invstd) at inference: computed once per loaded checkpoint, not per call.  `items` is
+ * host memory read during the call (the table travels in the kernel arguments, 32 items per launch); the slots must not
+ * overlap and come in ascending order; offsets that are multiples of 4 keep the vectors 16-byte aligned.              */
+typedef struct csg_norm_eval_item {
+  const float* running_mean;
+  const float* running_var;
+  int64_t C;
+  int64_t offset;            /* in floats, into `out` */
+} csg_norm_eval_item;
+int csg_norm_eval_stats_multi(const csg_norm_eval_item* items, int32_t n, float eps, float* out, void* stream);
 /* pass 1: dgb (if gb; always (G*P, 2C) = [d gamma | d beta]) and dsums (G,2C) double = [sum dn | sum dn*xhat].  `yact`
  * (nullable, with gb): the activated output y of the forward — the LeakyReLU gate is then read off y's sign and beta is
  * never read; gb may then be a gamma-only map.  `gb_cs`: floats per pixel of gb — 2C ([gamma | beta]) or, with yact, C
@@ -447,6 +462,25 @@ int csg_norm_apply_bwd_dx(const float* dy, const float* x, const float* mean, co
                           float slope, const double* dsums, double count, int64_t G, int64_t P, int64_t C, float* dx,
                           const float* dy2, const float* gb2, float slope2, const float* dgb, const float* dgb2,
                           int64_t gb_cs, void* stream);
+
+/* ---- generated image -> uint8 picture (csrc/deprocess.hip) ------------------------------------------
+ * deprocess_batch(imgs, rescale, imagenet_deprocess) (sg2im/data/utils.py:36-65) on the device, with the reference's order of
+ * fp32 operations per element (T.Normalize is sub_(mean).div_(std)):
+ *   t = x / div3[c]  (:38, INV_IMAGENET_STD);  t = t - sub3[c]  (:39, INV_IMAGENET_MEAN);
+ *   rescale: t = (t - lo_b) / (hi_b - lo_b) with lo_b, hi_b = min, max over the whole image b after the two steps (:31-33);
+ *   out = byte(clamp(t * 255, 0, 255))  (:62, truncation).
+ * No multiply-add is contracted and the divisions are correctly rounded: the bytes EQUAL those of the fp32 host code.
+ * img (B,H,W,img_cs) NHWC fp32, img_cs 3 or 4 (channels-last 3-channel image, or conv_img's 4-padded output), W a multiple
+ * of 4; out (B,3,H,W) uint8 planar; div3 / sub3: three floats each, HOST memory, read during the call.  Two launches with
+ * rescale (per-image min / max partials in `workspace`, csg_deprocess_u8_workspace(B) bytes — ordered trees, no atomics,
+ * NaN propagates as in torch.min / max), one without (workspace may be NULL).
+ * An image with hi_b == lo_b (constant, or one holding a NaN) makes every element NaN in the reference's arithmetic, and
+ * byte() of a NaN is undefined in C++; this entry point writes 0, what torch's x86 host kernels produce
+ * (tests/test_gpu_sample.py pins that against torch on the host).  The case cannot be refused with an error code without
+ * a device synchronisation, which the capturable-launch convention above rules out.                              */
+int64_t csg_deprocess_u8_workspace(int64_t B);
+int csg_deprocess_u8(const float* img, int64_t B, int64_t H, int64_t W, int64_t img_cs, const float* div3, const float* sub3,
+                     int32_t rescale, uint8_t* out, float* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- K7 / pooling ------------------------------------------------------------------------------
  * nearest 2x upsample (generator.py:48,102-121) and its adjoint */
