@@ -63,6 +63,7 @@ enum KernelId {
   K_GEMM_TN,
   K_NORM_EVAL_STATS,
   K_DEPROCESS,
+  K_BOX_IOU,
   K_COUNT
 };
 

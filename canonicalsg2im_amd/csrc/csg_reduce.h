@@ -79,4 +79,30 @@ static inline void launch_slab_reduce(const float* ws_w, int64_t n_w, float* out
     CSG_LAUNCH(k_slab_reduce<0>, dim3(grid), dim3(256), 0, s, a, b, nsplit);
 }
 
+// Ordered fp64 sum over a block of NW waves of N accumulators per thread (metrics.hip): a shuffle tree inside each wave,
+// then the waves in wave order through `part` — one fixed association, so the same bits on every run; no atomics.  Every
+// thread of the block must call it; the sums are valid in thread 0 only.
+template <int N, int NW>
+__device__ __forceinline__ void block_sum_f64(double (&v)[N], double (*part)[N]) {
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off, 64);
+  }
+  if (NW > 1) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < N; ++q) part[w][q] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int k = 1; k < NW; ++k) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) v[q] += part[k][q];
+      }
+    }
+  }
+}
+
 }  // namespace csg

@@ -1827,6 +1827,30 @@ def real_object_mask(objs, image_id):
     return m
 
 
+def box_iou(boxes_pred, boxes_gt, objs, image_id, totals):
+    """The reference's validation metric for a padded batch (csg_box_iou): jaccard (sg2im/metrics.py:18-36) of
+    clamp(boxes_pred, 0, 1) (scripts/train.py:196) against boxes_gt over the objects remove_dummies_and_padding keeps
+    (sg2im/utils.py:66-71: any ground-truth value != -1, and objs[...,0] != __image__).  boxes (B,O,4) fp32 xywh, objs
+    (B,O,A) int64, `totals` a float64 vector of 4 on the device that the call ADDS to in place.
+    Returns (iou (B,O) fp32 — the reference's bits, 0 where not counted; counted (B,O) uint8; per_sample (B,4) float64 =
+    sum iou, #(iou > 0.5), #(iou > 0.3), #counted).  Nothing is read back and nothing synchronises."""
+    if objs.dtype != torch.int64 or objs.dim() != 3:
+        raise RuntimeError("box_iou: objs must be (B,O,A) int64 (collate contract)")
+    B, O, A = objs.shape
+    if tuple(boxes_pred.shape) != (B, O, 4) or tuple(boxes_gt.shape) != (B, O, 4):
+        raise RuntimeError("box_iou: boxes must be (B,O,4) like objs %s, got %s and %s" % (
+            tuple(objs.shape), tuple(boxes_pred.shape), tuple(boxes_gt.shape)))
+    if totals.dtype != torch.float64 or totals.numel() != 4 or not totals.is_contiguous() or totals.device != objs.device:
+        raise RuntimeError("box_iou: totals must be a dense float64 vector of 4 on the batch's device")
+    p, g, o = _f32(boxes_pred.detach()).contiguous(), _f32(boxes_gt).contiguous(), objs.contiguous()
+    iou = torch.empty((B, O), device=o.device, dtype=torch.float32)
+    counted = torch.empty((B, O), device=o.device, dtype=torch.uint8)
+    per_sample = torch.empty((B, 4), device=o.device, dtype=torch.float64)
+    check(lib.csg_box_iou(ptr(p), ptr(g), ptr(o), B, O, A, int(image_id), ptr(iou), ptr(counted), ptr(per_sample), ptr(totals),
+                          stream()), "box_iou")
+    return iou, counted, per_sample
+
+
 def graph_csr(triplets, O):
     """(row_ptr (B,O+1) int32, col (B,2T) int32) — incident triplets per object, reference order."""
     B, T, _ = triplets.shape

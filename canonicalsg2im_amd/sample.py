@@ -2,7 +2,7 @@
 scripts/generation_attspade.py and the samples of check_model: `model(objs, triplets, triplet_type, test_mode=True)`
 followed by `deprocess_batch`, sg2im/data/utils.py:46-65).
 
-`Sampler` owns a `MetaGeneratorModel` in eval mode and nothing else (no discriminators, no optimisers).  The scene-graph
+`Sampler` owns a `MetaGeneratorModel` in eval mode (or adopts one: `model=`, evaluate.py) and nothing else (no discriminators, no optimisers).  The scene-graph
 encoder runs as the module does; the generator is WALKED here on the inference forms of the kernels instead of through
 `SPADEGenerator.forward` (whose eval-mode behaviour is untouched):
 
@@ -61,10 +61,16 @@ class _Replay:
 
 
 class Sampler:
-    def __init__(self, opt, device, checkpoint=None):
+    def __init__(self, opt, device, checkpoint=None, model=None):
+        """`model`: a MetaGeneratorModel to ADOPT instead of constructing one (the evaluator walks the trainer's own module:
+        one copy of the weights).  Its mode is left alone here; `generate` puts it in eval mode and leaves it there.  Whoever
+        trains an adopted model calls `invalidate()` before the next walk: a fused optimiser step and a replayed training
+        step write parameters and running statistics without touching the `_version` counters `_signature` reads."""
         self.opt, self.device = opt, torch.device(device)
-        self.model = MetaGeneratorModel(opt, self.device)
-        self.model.eval()
+        if model is None:
+            model = MetaGeneratorModel(opt, self.device)
+            model.eval()
+        self.model = model
         self._prep = None                # everything derived from the frozen weights (see _prepare)
         self._replays, self._seen = {}, {}
         self.replays = self.eager_calls = 0

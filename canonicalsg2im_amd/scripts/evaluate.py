@@ -1,0 +1,122 @@
+"""Command-line validation: a checkpoint and seeded SYNTHETIC validation batches in, the reference's `GT VAL` / `VAL` lines
+(scripts/train.py:410-424, :446-449) out.
+
+The reference validates on its datasets' validation split; real datasets are out of scope here (as in scripts/train.py of
+this package), so the validation set is seeded synthetic batches of the chosen dataset's shape.  The reference's flags
+describe the model; on top of them:
+
+    --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (required)
+    --output_dir DIR         where <pass>_<key>_%03d.png, metrics.json and table.json go (default: nothing is written)
+    --num_val_samples N      images to validate (default 1024, the reference's), in batches of --batch_size
+
+    python -m canonicalsg2im_amd.scripts.evaluate --dataset packed_coco --image_size 256,256 --batch_size 16 \\
+        --checkpoint_name out/itr_100000.pt --output_dir val --num_val_samples 1024
+
+Seeds.  scripts.train draws batch t of rank r from seed t * world + r, t >= 1: a positive integer below
+num_iterations * world + world, which `validation_batches` requires to stay below VAL_SEED_BASE = 2**40.  Validation batch i
+is drawn from seed VAL_SEED_BASE + i: the two sets of seeds are disjoint, and the validation set does not depend on how
+long or on how many ranks the model was trained.
+
+Two passes, as the reference runs them at every checkpoint: ground-truth boxes and masks into the generator (`GT VAL`), then
+the predicted ones (`VAL`; with --skip_graph_model 1 there is no prediction and the second pass uses the ground truth too,
+:419).  The samples written are those of the second pass (:424).
+"""
+import json
+import os
+import sys
+
+import torch
+
+VAL_SEED_BASE = 2 ** 40
+_NO_CHECKPOINT = "checkpoint"           # the reference's default of --checkpoint_name: no file was named
+
+
+def build_parser():
+    from .args import build_parser as train_parser
+    return train_parser()
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.checkpoint_name == _NO_CHECKPOINT:
+        raise SystemExit("--checkpoint_name PATH is required: there is nothing to validate without trained weights")
+    if not os.path.isfile(args.checkpoint_name):
+        raise SystemExit("--checkpoint_name %s: no such file" % args.checkpoint_name)
+    if args.num_val_samples is None or args.num_val_samples < 1 or args.batch_size < 1:
+        raise SystemExit("--num_val_samples and --batch_size must be positive")
+    return args
+
+
+def validation_batches(args, trainer, dev, world=1):
+    """Generator of the seeded validation batches on `dev` (see Seeds above): ceil(num_val_samples / batch_size) of them."""
+    from ..synth import BatchConfig, make_batch
+    from .train import packed_batch
+    if (args.num_iterations + 1) * max(world, 1) >= VAL_SEED_BASE:
+        raise SystemExit("--num_iterations * ranks must stay below 2**40: the seeds above are the validation set's")
+    packed = args.dataset.startswith("packed")
+    lo = args.min_objects or (16 if packed else 3)
+    hi = args.max_objects or (40 if packed else 8)
+    graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
+    cfg = BatchConfig(args.batch_size, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
+    for i in range(-(-args.num_val_samples // args.batch_size)):
+        batch = make_batch(args.vocab, cfg, seed=VAL_SEED_BASE + i)
+        yield packed_batch(args, trainer, batch, dev) if packed else [None if x is None else x.to(dev) for x in batch]
+
+
+def log_results(losses, t, prefix):
+    """The reference's log_results (:446-449) and its G [name] lines, on one line per pass."""
+    head = "Iter: %s, %s avg_iou: %.4f total_iou_03: %.4f total_iou_05: %.4f" % (
+        t, prefix, float(losses.get("avg_iou", 0.0)), float(losses.get("total_iou_03", 0.0)), float(losses.get("total_iou_05", 0.0)))
+    rest = " ".join("%s %.4f" % (k, float(v)) for k, v in losses.items() if k not in ("avg_iou", "total_iou_03", "total_iou_05"))
+    print(head + ("  " + rest if rest else ""), flush=True)
+
+
+def validate(args, evaluator, dev, t, world=1):
+    """The two passes of scripts/train.py:410-424 -> (gt_val_losses, val_losses, val_samples, val_table)."""
+    tr = evaluator.trainer
+    gt_losses, _, _ = evaluator.check_model(validation_batches(args, tr, dev, world), use_gt=True)
+    log_results(gt_losses, t, "GT VAL")
+    use_gt = bool(args.skip_graph_model)                                          # :419
+    losses, samples, table = evaluator.check_model(validation_batches(args, tr, dev, world), use_gt=use_gt)
+    log_results(losses, t, "VAL")
+    return gt_losses, losses, samples, table
+
+
+def write_outputs(out_dir, gt_losses, losses, samples, table, tag="val"):
+    from PIL import Image                      # only here: importing the package never needs PIL
+    os.makedirs(out_dir, exist_ok=True)
+    for key, imgs in samples.items():
+        host = imgs.numpy()
+        for i in range(host.shape[0]):
+            Image.fromarray(host[i]).save(os.path.join(out_dir, "%s_%s_%03d.png" % (tag, key, i)))
+    num = lambda d: {k: float(v) for k, v in d.items()}
+    with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+        json.dump({"GT VAL": num(gt_losses), "VAL": num(losses)}, f, indent=1)
+    with open(os.path.join(out_dir, "table.json"), "w") as f:
+        json.dump({k: v.tolist() for k, v in table.items()}, f)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
+    from .. import train as T
+    from ..evaluate import Evaluator
+    from ..synth import make_vocab
+    from .args import init_args
+    from .train import _vocab_kind
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    args.vocab = make_vocab(_vocab_kind(args.dataset))
+    init_args(args)
+    torch.manual_seed(0)
+    trainer = T.Trainer(args, dev)
+    t, _ = trainer.load_checkpoint(args.checkpoint_name)
+    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t)
+    if args.output_dir:
+        write_outputs(args.output_dir, gt_losses, losses, samples, table)
+    torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -11,7 +11,13 @@ datasets are out of scope), one process per GPU:
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as
 the packed data loaders do on the host; `packed_vg` batches carry annotated relationships (synthetic, among the
-vocabulary's non-location predicates) that join the graph as in sg2im/data/packed_vg.py:127-142."""
+vocabulary's non-location predicates) that join the graph as in sg2im/data/packed_vg.py:127-142.
+
+`--val_every N` (default 0: off) runs the reference's two validation passes (scripts/train.py:410-424, `GT VAL` and `VAL`)
+every N iterations on the seeded synthetic validation set of scripts/evaluate.py (`--num_val_samples` images, seeds disjoint
+from the training seeds).  With N > 1 ranks every rank validates the SAME batches and rank 0 prints: the passes advance the
+discriminators' spectral-norm vectors and BatchNorm statistics (evaluate.py), which must stay identical across ranks, and
+no collective is issued."""
 import os
 import sys
 import time
@@ -53,11 +59,29 @@ def packed_batch(args, trainer, batch, dev):
     return batch
 
 
+def build_parser():
+    from .args import build_parser as base_parser
+    p = base_parser()
+    p.add_argument('--val_every', default=0, type=int)
+    return p
+
+
+def argparse_copy(args, **changes):
+    """A shallow copy of the namespace with some entries replaced."""
+    import argparse
+    out = argparse.Namespace(**vars(args))
+    for k, v in changes.items():
+        setattr(out, k, v)
+    return out
+
+
 def main(argv=None):
     from .. import dist as csg_dist, train as T
     from ..synth import BatchConfig, make_batch, make_vocab
-    from .args import build_parser, init_args
+    from .args import init_args
     args = build_parser().parse_args(argv)
+    if args.val_every < 0:
+        raise SystemExit("--val_every must be >= 0 (0: no validation)")
     rank, world, local = csg_dist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
@@ -82,6 +106,11 @@ def main(argv=None):
     hi = args.max_objects or (40 if packed else 8)
     graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
     cfg = BatchConfig(per_rank, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
+    evaluator = None
+    if args.val_every > 0:
+        from ..evaluate import Evaluator
+        from . import evaluate as val_cli
+        evaluator = Evaluator(trainer)
     tic = time.time()
     for t in range(t0 + 1, args.num_iterations + 1):
         batch = make_batch(args.vocab, cfg, seed=t * max(world, 1) + rank)
@@ -96,6 +125,12 @@ def main(argv=None):
             tic = time.time()
             terms = " ".join("%s %.4f" % (k, float(v.detach())) for k, v in list(G.items()) + list(D.items()) if v.numel() == 1)
             print("t = %d / %d  [%.1f img/s]  %s" % (t, args.num_iterations, rate, terms), flush=True)
+        if evaluator is not None and t % args.val_every == 0:
+            import contextlib
+            vargs = argparse_copy(args, batch_size=per_rank)
+            with (contextlib.nullcontext() if rank == 0 else contextlib.redirect_stdout(open(os.devnull, "w"))):
+                val_cli.validate(vargs, evaluator, dev, t, world)
+            tic = time.time()
         if args.output_dir and t % args.checkpoint_every == 0:
             os.makedirs(args.output_dir, exist_ok=True)
             trainer.save_checkpoint(os.path.join(args.output_dir, "itr_%s.pt" % t), t, epoch)      # scripts/train.py:427

@@ -44,7 +44,8 @@ extern "C" {
 /* 100 + the number of additive revisions of this header: entry points are only ever added, never changed or removed
  * (108: csg_wino4_conv_spade, csg_wino4_conv_spade_supported, csg_avgpool3s2_bwd_add, csg_hinge_mean_fwd / _bwd;
  * 109: csg_canon_general_workspace, csg_canon_general_build / _converse / _close / _emit;
- * 110: csg_norm_eval_stats_multi, csg_deprocess_u8_workspace, csg_deprocess_u8) */
+ * 110: csg_norm_eval_stats_multi, csg_deprocess_u8_workspace, csg_deprocess_u8;
+ * 111: csg_box_iou) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -481,6 +482,23 @@ int csg_norm_apply_bwd_dx(const float* dy, const float* x, const float* mean, co
 int64_t csg_deprocess_u8_workspace(int64_t B);
 int csg_deprocess_u8(const float* img, int64_t B, int64_t H, int64_t W, int64_t img_cs, const float* div3, const float* sub3,
                      int32_t rescale, uint8_t* out, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- validation metric: box IoU of a padded batch (csrc/metrics.hip) ---------------------------------
+ * The reference's jaccard (sg2im/metrics.py:4-36) behind remove_dummies_and_padding (sg2im/utils.py:66-71), with the clamp
+ * of scripts/train.py:196 and the sums check_model keeps (:211-217).
+ * boxes_pred, boxes_gt (B,O,4) fp32 xywh, 16-byte aligned; objs (B,O,A) int64.  An object is COUNTED when any of its four
+ * ground-truth values differs from -1 and objs[b,o,0] != image_id (not remove_dummy_objects: that mask tests != 0).
+ * boxes_pred is clamped to [0,1] as xywh, then both boxes become corner points; inter, the two areas,
+ * union = (area_pred + area_gt) - inter and iou = inter / union are single correctly rounded fp32 operations in the
+ * reference's order (no contraction): iou EQUALS the reference's bits.  0 / 0 (both boxes of zero area) is NaN; it fails
+ * both comparisons and makes the sums NaN, as in the reference.
+ * iou (B,O) fp32, 0 where not counted; counted (B,O) uint8; per_sample (B,4) fp64 = {sum iou, #(iou > 0.5), #(iou > 0.3),
+ * #counted}; totals[4] fp64 += the same four over the batch (a running buffer the caller zeroes once).  The sums are
+ * ordered (fixed trees, no atomics): bit-reproducible.  Two launches (one block per sample; a one-wave fold), stream
+ * ordered and capturable; nothing is read back.
+ * LIMITS: 1 <= B <= 65535, 1 <= O <= 2^20, 1 <= A <= 64 (CSG_E_BADSHAPE otherwise, before the first launch).          */
+int csg_box_iou(const float* boxes_pred, const float* boxes_gt, const int64_t* objs, int64_t B, int64_t O, int64_t A,
+                int64_t image_id, float* iou, uint8_t* counted, double* per_sample, double* totals, void* stream);
 
 /* ---- K7 / pooling ------------------------------------------------------------------------------
  * nearest 2x upsample (generator.py:48,102-121) and its adjoint */
