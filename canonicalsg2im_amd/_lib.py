@@ -93,6 +93,7 @@ SIGNATURES = {
     "csg_embed_bwd": (c_i32, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p]),
     "csg_real_object_mask": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     "csg_graph_csr_build": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
+    "csg_graph_csr_lds": (c_i64, [c_i64, c_i64]),
     "csg_gather_concat_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
     "csg_gather_concat_bwd_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "csg_gather_concat_bwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),

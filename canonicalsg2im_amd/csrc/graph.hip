@@ -644,6 +644,13 @@ int csg_real_object_mask(const int64_t* objs, int64_t B, int64_t O, int64_t A, i
   return check_launch("csg_real_object_mask");
 }
 
+// which builder serves (T, O): the counting sort's dynamic LDS in bytes, 0 = the plain builder, -1 = refused
+int64_t csg_graph_csr_lds(int64_t T, int64_t O) {
+  if (T < 0 || O <= 0 || O > 256 * CSR_MAXJ || T >= (1 << 29)) return -1;
+  const size_t shm = csr_sorted_lds(T, O);
+  return (O <= 254 && T >= 512 && T <= 65535 && shm <= 150 * 1024) ? (int64_t)shm : 0;   // dense graphs: counting sort
+}
+
 int csg_graph_csr_build(const int64_t* triplets, int64_t B, int64_t T, int64_t O, int32_t* row_ptr, int32_t* col,
                         void* stream) {
   CSG_REQUIRE(B > 0 && T >= 0 && O > 0, CSG_E_BADSHAPE, "csg_graph_csr_build: bad shape B=%ld T=%ld O=%ld", (long)B,
@@ -653,8 +660,8 @@ int csg_graph_csr_build(const int64_t* triplets, int64_t B, int64_t T, int64_t O
   CSG_REQUIRE(T < (1 << 29), CSG_E_UNSUPPORTED, "csg_graph_csr_build: T too large");
   hipStream_t s = (hipStream_t)stream;
   ProfScope p(K_CSR_BUILD, (double)B * T * (24 + 8), s);
-  const size_t shm = csr_sorted_lds(T, O);
-  if (O <= 254 && T >= 512 && T <= 65535 && shm <= 150 * 1024) {      // dense graphs: counting sort
+  const size_t shm = (size_t)csg_graph_csr_lds(T, O);
+  if (shm > 0) {
     static size_t attr = 0;
     if (shm > attr) {
       (void)hipFuncSetAttribute((const void*)k_csr_build_sorted, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);

@@ -93,6 +93,10 @@ int csg_real_object_mask(const int64_t* objs, int64_t B, int64_t O, int64_t A, i
  * which the reference's two scatter_add calls accumulate (sg2im/graph.py:98-99).               */
 int csg_graph_csr_build(const int64_t* triplets, int64_t B, int64_t T, int64_t O, int32_t* row_ptr, int32_t* col,
                         void* stream);
+/* The builder csg_graph_csr_build launches for (T, O): > 0 = the counting sort (O <= 254, 512 <= T <= 65535) and its
+ * dynamic LDS in bytes (at most 150 KB), 0 = the plain builder, -1 = refused.  LIMITS: O <= 1024 objects per image and
+ * T < 2^29 (CSG_E_UNSUPPORTED otherwise, before any launch).  Ids outside [0, O) get no entry from either builder. */
+int64_t csg_graph_csr_lds(int64_t T, int64_t O);
 
 /* K2: cur_t = cat(obj[s], pred, obj[o])   (sg2im/graph.py:63-66) */
 int csg_gather_concat_fwd(const float* obj, const float* pred, const int64_t* triplets, int64_t B, int64_t O,
