@@ -164,6 +164,9 @@ SIGNATURES = {
     "csg_deprocess_u8_workspace": (c_i64, [c_i64]),
     "csg_deprocess_u8": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_i32, c_p, c_p,
                                  c_i64, c_p]),
+    "csg_preprocess_workspace": (c_i64, [c_p, c_i64, c_i64]),
+    "csg_preprocess": (c_i32, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_p, c_p,
+                               c_p, c_i64, c_p]),
     "csg_box_iou": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "csg_norm_apply_bwd_reduce": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64,
                                           c_i64, c_p]),

@@ -64,6 +64,7 @@ enum KernelId {
   K_NORM_EVAL_STATS,
   K_DEPROCESS,
   K_BOX_IOU,
+  K_PREPROCESS,
   K_COUNT
 };
 

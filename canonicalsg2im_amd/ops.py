@@ -21,7 +21,7 @@ from ._lib import ACT_LEAKY, ACT_NONE, ACT_TANH, ConvDesc, FewDesc, GemmDesc, Hi
 __all__ = [
     "nhwc", "empty_nhwc", "conv2d", "linear", "norm_act", "upsample2x", "nearest_resize", "avgpool3s2", "embed", "real_object_mask",
     "norm_act_pair", "graph_csr", "gather_concat", "segment_avg", "layout_pyramid", "layout_paint", "disc_input", "crop_objects", "maxpool2", "avgpool2", "l1_mean",
-    "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
+    "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "preprocess_images", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
 ]
 
 
@@ -1511,6 +1511,59 @@ def deprocess_u8(img, rescale=True):
     check(lib.csg_deprocess_u8(ptr(img), B, H, W, cs, div, sub, 1 if rescale else 0, ptr(out), ptr(ws), nws, stream()),
           "deprocess_u8")
     return out
+
+
+def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_host=None, out=None, out_u8=None,
+                      workspace=None):
+    """The loader's per-sample transform (sg2im/data/packed_coco.py:269-272: T.Resize, T.ToTensor, T.Normalize) for a batch
+    of differently sized decoded pictures, on the device (csg_preprocess): Pillow's 8-bit bilinear resize byte for byte,
+    then torch's three fp32 operations bit for bit.
+
+    src_u8: uint8 device tensor, B interleaved RGB pictures back to back (dense rows, any alignment); desc: int64 (B,3)
+    rows (byte offset, h, w).  The sizes are needed on the host (refusals, launch geometry, workspace): pass `desc` as a
+    CPU tensor (it is uploaded here), or as a device tensor together with its CPU copy `desc_host`; a device `desc` alone
+    is read back, which synchronises.  normalize=False gives ToTensor alone (byte / 255).
+    Returns fp32 (B,3,H,W) contiguous NCHW — what Trainer.step takes without a copy — and with want_u8 also the resized
+    uint8 (B,H,W,3).  `out`, `out_u8`, `workspace` (uint8, csg_preprocess_workspace bytes): caller-owned buffers, for a
+    captured graph; `out` must start on a 16-byte boundary, `out_u8` and `workspace` on a 4-byte one (a view into a larger
+    buffer may not: refused).  No autograd."""
+    if not src_u8.is_cuda:
+        raise RuntimeError("preprocess_images: the packed pictures must be a HIP (cuda) tensor; got a %s tensor — there is "
+                           "no CPU path" % src_u8.device)
+    if src_u8.dtype != torch.uint8 or not src_u8.is_contiguous():
+        raise RuntimeError("preprocess_images: src_u8 must be a contiguous uint8 tensor, got %s" % src_u8.dtype)
+    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 3:
+        raise RuntimeError("preprocess_images: desc must be int64 (B,3) rows of (byte offset, h, w); got %s %s" % (
+            desc.dtype, tuple(desc.shape)))
+    dev = src_u8.device
+    if not desc.is_cuda:
+        desc_host, desc = desc.contiguous(), desc.to(dev, non_blocking=True)
+    elif desc_host is None:
+        desc_host = desc.cpu()
+    desc, desc_host = desc.contiguous(), desc_host.to(torch.int64).contiguous()
+    if desc_host.is_cuda or tuple(desc_host.shape) != tuple(desc.shape):
+        raise RuntimeError("preprocess_images: desc_host must be the CPU copy of desc")
+    B, H, W = desc.shape[0], int(H), int(W)
+    host = ctypes.c_void_p(desc_host.data_ptr())
+    nws = lib.csg_preprocess_workspace(host, B, W)
+    if workspace is None:
+        workspace = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+    if want_u8 and out_u8 is None:
+        out_u8 = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)
+    if tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise RuntimeError("preprocess_images: out must be contiguous fp32 (B,3,H,W)")
+    if want_u8 and (tuple(out_u8.shape) != (B, H, W, 3) or out_u8.dtype != torch.uint8 or not out_u8.is_contiguous()):
+        raise RuntimeError("preprocess_images: out_u8 must be contiguous uint8 (B,H,W,3)")
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("preprocess_images: workspace must be a contiguous uint8 tensor")
+    # the fp32 values torch.as_tensor(IMAGENET_MEAN / IMAGENET_STD, dtype=float32) holds (T.Normalize, utils.py:13-14)
+    sub = (_lib.c_f32 * 3)(*(IMAGENET_MEAN if normalize else (0.0, 0.0, 0.0)))
+    div = (_lib.c_f32 * 3)(*(IMAGENET_STD if normalize else (1.0, 1.0, 1.0)))
+    check(lib.csg_preprocess(ptr(src_u8), src_u8.numel(), ptr(desc), host, B, H, W, sub, div, ptr(out),
+                             ptr(out_u8) if want_u8 else None, ptr(workspace), workspace.numel(), stream()), "preprocess")
+    return (out, out_u8) if want_u8 else out
 
 
 # ------------------------------------------------------------------------------------ resampling

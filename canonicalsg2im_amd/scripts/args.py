@@ -22,6 +22,11 @@ _OFF_PATH_FLAGS = {
     'shuffle_val': (True, 'bool'), 'loader_num_workers': (1, 'int'), 'include_relationships': (True, 'bool'),
     'vg_image_dir': ('datasets/vg/images', 'str'), 'train_h5': ('datasets/vg/train.h5', 'str'),
     'val_h5': ('datasets/vg/val.h5', 'str'), 'vocab_json': ('datasets/vg/vocab.json', 'str'),
+    # COCO from a folder (sg2im/data/packed_coco.py of this package): unset, the paths follow the reference's layout under
+    # --dataroot (<dataroot>/MSCoco/images/<split>2017, .../annotations/{instances,stuff}_<split>2017.json)
+    'coco_train_image_dir': (None, 'str'), 'coco_val_image_dir': (None, 'str'),
+    'coco_train_instances_json': (None, 'str'), 'coco_train_stuff_json': (None, 'str'),
+    'coco_val_instances_json': (None, 'str'), 'coco_val_stuff_json': (None, 'str'),
     'max_objects_per_image': (10, 'int'), 'vg_use_orphaned_objects': (True, 'bool'), 'dataroot': ('./datasets', 'str'),
     'preprocess_mode': ('scale_width_and_crop', 'str'), 'no_flip': (False, 'flag'), 'nThreads': (0, 'int'),
     'cache_filelist_write': (False, 'flag'), 'cache_filelist_read': (False, 'flag'), 'dense_scenes': (0, 'int'),

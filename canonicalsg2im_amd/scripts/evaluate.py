@@ -1,9 +1,11 @@
-"""Command-line validation: a checkpoint and seeded SYNTHETIC validation batches in, the reference's `GT VAL` / `VAL` lines
+"""Command-line validation: a checkpoint and a validation set in, the reference's `GT VAL` / `VAL` lines
 (scripts/train.py:410-424, :446-449) out.
 
-The reference validates on its datasets' validation split; real datasets are out of scope here (as in scripts/train.py of
-this package), so the validation set is seeded synthetic batches of the chosen dataset's shape.  The reference's flags
-describe the model; on top of them:
+The reference validates on its datasets' validation split.  With `--dataset packed_coco` and an existing val image directory
+(`--coco_val_image_dir`, by default <dataroot>/MSCoco/images/val2017) so does this: the first `--num_val_samples` pictures in
+file order, not shuffled, through the same device input stage as scripts/train.py of this package.  Otherwise the
+validation set is seeded synthetic batches of the chosen dataset's shape.  The reference's flags describe the model; on top
+of them:
 
     --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (required)
     --output_dir DIR         where <pass>_<key>_%03d.png, metrics.json and table.json go (default: nothing is written)
@@ -47,10 +49,23 @@ def parse_args(argv=None):
     return args
 
 
-def validation_batches(args, trainer, dev, world=1):
-    """Generator of the seeded validation batches on `dev` (see Seeds above): ceil(num_val_samples / batch_size) of them."""
+def validation_batches(args, trainer, dev, world=1, val_set=None):
+    """Generator of the validation batches on `dev`, ceil(num_val_samples / batch_size) of them: the first pictures of
+    `val_set` (a folder dataset, `coco_val_set`) in file order, or the seeded synthetic batches (see Seeds above)."""
     from ..synth import BatchConfig, make_batch
     from .train import packed_batch
+    if val_set is not None:              # the first num_val_samples pictures in file order; every rank sees the same batches
+        from ..sg2im.data.packed_coco import CocoBatchBuilder, epoch_batches
+        builder = CocoBatchBuilder(val_set, args, trainer, dev, num_workers=args.loader_num_workers)
+        n = len(val_set)
+        lists = epoch_batches(n, args.batch_size, shuffle=False)
+        if n % args.batch_size:
+            lists.append(list(range(n - n % args.batch_size, n)))
+        try:
+            yield from builder.batches(lists)
+        finally:
+            builder.close()
+        return
     if (args.num_iterations + 1) * max(world, 1) >= VAL_SEED_BASE:
         raise SystemExit("--num_iterations * ranks must stay below 2**40: the seeds above are the validation set's")
     packed = args.dataset.startswith("packed")
@@ -63,6 +78,22 @@ def validation_batches(args, trainer, dev, world=1):
         yield packed_batch(args, trainer, batch, dev) if packed else [None if x is None else x.to(dev) for x in batch]
 
 
+def coco_val_set(args, vocab=None):
+    """The val split's folder dataset, or None (synthetic validation batches).  `vocab`: the vocabulary the model was built
+    with; a val split whose categories differ from it is refused here, on the host — its category ids would index the
+    model's embedding tables."""
+    if args.dataset != "packed_coco":
+        return None
+    from ..sg2im.data.packed_coco import build_coco_dataset
+    val_set = build_coco_dataset(args, "val")
+    if val_set is not None and vocab is not None and val_set.vocab["object_name_to_idx"] != vocab["object_name_to_idx"]:
+        raise SystemExit("the val split's categories (%d names, largest id %d) are not the model's (%d names, largest id %d): "
+                         "train and validate on annotation files of one category set" % (
+                             len(val_set.vocab["object_name_to_idx"]), max(val_set.vocab["object_name_to_idx"].values()),
+                             len(vocab["object_name_to_idx"]), max(vocab["object_name_to_idx"].values())))
+    return val_set
+
+
 def log_results(losses, t, prefix):
     """The reference's log_results (:446-449) and its G [name] lines, on one line per pass."""
     head = "Iter: %s, %s avg_iou: %.4f total_iou_03: %.4f total_iou_05: %.4f" % (
@@ -71,13 +102,13 @@ def log_results(losses, t, prefix):
     print(head + ("  " + rest if rest else ""), flush=True)
 
 
-def validate(args, evaluator, dev, t, world=1):
+def validate(args, evaluator, dev, t, world=1, val_set=None):
     """The two passes of scripts/train.py:410-424 -> (gt_val_losses, val_losses, val_samples, val_table)."""
     tr = evaluator.trainer
-    gt_losses, _, _ = evaluator.check_model(validation_batches(args, tr, dev, world), use_gt=True)
+    gt_losses, _, _ = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=True)
     log_results(gt_losses, t, "GT VAL")
     use_gt = bool(args.skip_graph_model)                                          # :419
-    losses, samples, table = evaluator.check_model(validation_batches(args, tr, dev, world), use_gt=use_gt)
+    losses, samples, table = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=use_gt)
     log_results(losses, t, "VAL")
     return gt_losses, losses, samples, table
 
@@ -107,12 +138,15 @@ def main(argv=None):
     from .train import _vocab_kind
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    args.vocab = make_vocab(_vocab_kind(args.dataset))
+    val_set = coco_val_set(args)
+    args.vocab = val_set.vocab if val_set is not None else make_vocab(_vocab_kind(args.dataset))
+    print("data: %s" % ("%d pictures of %s" % (len(val_set), val_set.image_dir) if val_set is not None
+                        else "seeded synthetic batches (%s shapes)" % args.dataset), flush=True)
     init_args(args)
     torch.manual_seed(0)
     trainer = T.Trainer(args, dev)
     t, _ = trainer.load_checkpoint(args.checkpoint_name)
-    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t)
+    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t, val_set=val_set)
     if args.output_dir:
         write_outputs(args.output_dir, gt_losses, losses, samples, table)
     torch.cuda.synchronize()

@@ -1,8 +1,10 @@
 """Command-line sampler: a checkpoint and seeded SYNTHETIC scene graphs in, PNG files out.
 
-The reference's scripts/run_model.py and scripts/generation_attspade.py read scene graphs from its datasets; real datasets
-are out of scope here (as in scripts/train.py of this package), so the graphs are the seeded synthetic batches of the chosen
-dataset's shape.  The reference's flags describe the model; on top of them:
+The reference's scripts/run_model.py and scripts/generation_attspade.py read scene graphs from its datasets.  This command
+does not yet: scripts/train.py and scripts/evaluate.py of this package read a COCO folder (sg2im/data/packed_coco.py), the
+sampler's graphs are still the seeded synthetic batches of the chosen dataset's shape — with a checkpoint trained on the
+folder, whose vocabulary the checkpoint carries, pass graphs to `Sampler.generate` directly.  The reference's flags describe
+the model; on top of them:
 
     --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (default: none — the freshly
                              initialised weights, which is only good for timing)

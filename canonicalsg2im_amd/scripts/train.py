@@ -1,23 +1,29 @@
-"""Command-line trainer for the HIP hot path on SYNTHETIC batches.
+"""Command-line trainer for the HIP hot path, on a COCO folder or on SYNTHETIC batches.
 
 The reference's scripts/train.py owns data loading, logging, evaluation and checkpoint policy; of it only the
 iteration (:353-393, :468-485) is on the hot path and lives in `canonicalsg2im_amd.train.Trainer`.  This entry point
-drives that iteration with the reference's flags on seeded synthetic batches of the chosen dataset's shape (real
-datasets are out of scope), one process per GPU:
+drives that iteration with the reference's flags, one process per GPU:
 
     python -m canonicalsg2im_amd.scripts.train --dataset packed_clevr --image_size 256,256 --batch_size 48 \\
         --num_iterations 100 --no_vgg_loss --learned_transitivity 1
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m canonicalsg2im_amd.scripts.train ...
+
+Data.  `--dataset packed_coco` trains on real pictures when the train image directory exists (`--coco_train_image_dir`, by
+default <dataroot>/MSCoco/images/train2017 with the annotation files beside it, the reference's layout): the pictures are
+decoded on the host in `--loader_num_workers` threads and resized, converted and normalised on the device, one batch ahead of
+the step (sg2im/data/packed_coco.py of this package; `--mask_size` must be 0 there).  Every epoch is a permutation seeded by
+the epoch number; with N ranks each takes every N-th sample of a global batch.  Without that directory, and for every other
+dataset, the batches are seeded synthetic ones of the chosen dataset's shape.  One line says which of the two it is.
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as
 the packed data loaders do on the host; `packed_vg` batches carry annotated relationships (synthetic, among the
 vocabulary's non-location predicates) that join the graph as in sg2im/data/packed_vg.py:127-142.
 
 `--val_every N` (default 0: off) runs the reference's two validation passes (scripts/train.py:410-424, `GT VAL` and `VAL`)
-every N iterations on the seeded synthetic validation set of scripts/evaluate.py (`--num_val_samples` images, seeds disjoint
-from the training seeds).  With N > 1 ranks every rank validates the SAME batches and rank 0 prints: the passes advance the
-discriminators' spectral-norm vectors and BatchNorm statistics (evaluate.py), which must stay identical across ranks, and
-no collective is issued."""
+every N iterations on the validation set of scripts/evaluate.py: the first `--num_val_samples` pictures of the val split
+when its directory exists, seeded synthetic batches (seeds disjoint from the training seeds) otherwise.  With N > 1 ranks
+every rank validates the SAME batches and rank 0 prints: the passes advance the discriminators' spectral-norm vectors and
+BatchNorm statistics (evaluate.py), which must stay identical across ranks, and no collective is issued."""
 import os
 import sys
 import time
@@ -30,33 +36,10 @@ def _vocab_kind(dataset):
 
 
 def packed_batch(args, trainer, batch, dev):
-    """A synthetic packed batch (CPU tensors from synth.make_batch) on `dev`, with the canonical graph built on the
-    device: the __image__ row appended to every sample, then canonical_triplets in place of the triplets.  packed_vg
-    hands the batch's annotated relationships over, unless --include_relationships 0 (packed_vg.py:128-130)."""
-    from ..sg2im.data import canonical_triplets
-    rel = None
-    if args.dataset == "packed_vg":  # the annotated rows and the object counts are read on the host: hand over CPU tensors
-        rel = batch[3] if args.include_relationships else torch.zeros((batch[3].shape[0], 0, 3), dtype=torch.int64)
-        n = (batch[1][..., 0] != 0).sum(1) + 1              # real objects + the __image__ row appended below
-    batch = [None if x is None else x.to(dev) for x in batch]
-    objs, boxes = batch[1], batch[2]
-    if rel is None:
-        n = (objs[..., 0] != 0).sum(1) + 1
-    O = objs.shape[1] + 1
-    objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
-    boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)
-    centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
-    batch[1], batch[2] = objs, boxes
-    conv_w = None
-    if args.learned_converse:    # the data loader reads the model's converse weights back (scripts/train.py:274-276)
-        from ..sg2im.model import get_conv_converse
-        conv_w = get_conv_converse(trainer.model).detach().cpu().numpy()
-    batch[3], batch[4], batch[5] = canonical_triplets(objs, boxes, centers, n, args.vocab,
-                                                      learned_transitivity=bool(args.learned_transitivity),
-                                                      learned_converse=bool(args.learned_converse),
-                                                      converse_weights=conv_w, triplets=rel)
-    assert batch[3].shape[1] > 0 and objs.shape[1] == O
-    return batch
+    """sg2im.data.collate.packed_batch, its home since the folder dataset shares it (imported there on first use: this
+    module parses command lines without the library)."""
+    from ..sg2im.data.collate import packed_batch as impl
+    return impl(args, trainer, batch, dev)
 
 
 def build_parser():
@@ -87,7 +70,11 @@ def main(argv=None):
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    args.vocab = make_vocab(_vocab_kind(args.dataset))
+    train_set = None
+    if args.dataset == "packed_coco":
+        from ..sg2im.data.packed_coco import CocoBatchBuilder, build_coco_dataset, epoch_batches
+        train_set = build_coco_dataset(args, "train")
+    args.vocab = train_set.vocab if train_set is not None else make_vocab(_vocab_kind(args.dataset))
     if world > 1:
         args.gpu_ids = ",".join(str(i) for i in range(world))
     init_args(args)
@@ -111,13 +98,37 @@ def main(argv=None):
         from ..evaluate import Evaluator
         from . import evaluate as val_cli
         evaluator = Evaluator(trainer)
+        val_set = val_cli.coco_val_set(args, args.vocab)     # read once; refused if its categories are not the model's
+    builder = real = None
+    if train_set is not None:
+        steps_per_epoch = len(train_set) // (per_rank * max(world, 1))
+        if steps_per_epoch < 1:
+            raise SystemExit("the training set has %d images after filtering: fewer than one batch of %d" % (
+                len(train_set), per_rank * max(world, 1)))
+        builder = CocoBatchBuilder(train_set, args, trainer, dev, num_workers=args.loader_num_workers)
+
+        def index_lists():               # iteration t is step (t - 1) % steps_per_epoch of epoch (t - 1) // steps_per_epoch
+            for t in range(t0 + 1, args.num_iterations + 1):
+                e, s = divmod(t - 1, steps_per_epoch)
+                if s == 0 or t == t0 + 1:
+                    lists = epoch_batches(len(train_set), per_rank, rank, max(world, 1), seed=0, epoch=e)
+                yield lists[s]
+
+        real = builder.batches(index_lists())
+    if rank == 0:
+        print("data: %s" % ("%d pictures of %s, %d loader threads" % (len(train_set), train_set.image_dir, builder.num_workers)
+                            if train_set is not None else "seeded synthetic batches (%s shapes)" % args.dataset), flush=True)
     tic = time.time()
     for t in range(t0 + 1, args.num_iterations + 1):
-        batch = make_batch(args.vocab, cfg, seed=t * max(world, 1) + rank)
-        if packed:                       # canonical graph from the geometry (and annotations), on the device
-            batch = packed_batch(args, trainer, batch, dev)
+        if real is not None:
+            batch = next(real)
+            epoch = (t - 1) // steps_per_epoch
         else:
-            batch = [None if x is None else x.to(dev) for x in batch]
+            batch = make_batch(args.vocab, cfg, seed=t * max(world, 1) + rank)
+            if packed:                   # canonical graph from the geometry (and annotations), on the device
+                batch = packed_batch(args, trainer, batch, dev)
+            else:
+                batch = [None if x is None else x.to(dev) for x in batch]
         G, D = trainer.step(batch)
         if rank == 0 and (t % args.print_every == 0 or t == args.num_iterations):
             torch.cuda.synchronize()
@@ -129,11 +140,15 @@ def main(argv=None):
             import contextlib
             vargs = argparse_copy(args, batch_size=per_rank)
             with (contextlib.nullcontext() if rank == 0 else contextlib.redirect_stdout(open(os.devnull, "w"))):
-                val_cli.validate(vargs, evaluator, dev, t, world)
+                val_cli.validate(vargs, evaluator, dev, t, world, val_set)
             tic = time.time()
         if args.output_dir and t % args.checkpoint_every == 0:
             os.makedirs(args.output_dir, exist_ok=True)
             trainer.save_checkpoint(os.path.join(args.output_dir, "itr_%s.pt" % t), t, epoch)      # scripts/train.py:427
+    if builder is not None:
+        if rank == 0:
+            print("loader: %d of %d steps waited for their batch" % (builder.waited, builder.steps), flush=True)
+        builder.close()
     if world > 1:
         torch.distributed.destroy_process_group()
 

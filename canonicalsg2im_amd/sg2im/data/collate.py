@@ -1,0 +1,33 @@
+"""The device half of the packed datasets' collate: objects and boxes in, the trainer's batch with its canonical graph out."""
+import torch
+
+
+def packed_batch(args, trainer, batch, dev):
+    """A packed batch (the tensors of synth.make_batch or of a dataset's batch builder, on the host or on `dev`) on `dev`,
+    with the canonical graph built on the device: the __image__ row appended to every sample, then canonical_triplets in
+    place of the triplets.  packed_vg hands the batch's annotated relationships over, unless --include_relationships 0
+    (packed_vg.py:128-130)."""
+    from . import canonical_triplets
+    rel = None
+    if args.dataset == "packed_vg":  # the annotated rows and the object counts are read on the host: hand over CPU tensors
+        rel = batch[3] if args.include_relationships else torch.zeros((batch[3].shape[0], 0, 3), dtype=torch.int64)
+        n = (batch[1][..., 0] != 0).sum(1) + 1              # real objects + the __image__ row appended below
+    batch = [None if x is None else x.to(dev) for x in batch]
+    objs, boxes = batch[1], batch[2]
+    if rel is None:
+        n = (objs[..., 0] != 0).sum(1) + 1
+    O = objs.shape[1] + 1
+    objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
+    boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)
+    centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
+    batch[1], batch[2] = objs, boxes
+    conv_w = None
+    if args.learned_converse:    # the data loader reads the model's converse weights back (scripts/train.py:274-276)
+        from ..model import get_conv_converse
+        conv_w = get_conv_converse(trainer.model).detach().cpu().numpy()
+    batch[3], batch[4], batch[5] = canonical_triplets(objs, boxes, centers, n, args.vocab,
+                                                      learned_transitivity=bool(args.learned_transitivity),
+                                                      learned_converse=bool(args.learned_converse),
+                                                      converse_weights=conv_w, triplets=rel)
+    assert batch[3].shape[1] > 0 and objs.shape[1] == O
+    return batch

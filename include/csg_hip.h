@@ -45,7 +45,8 @@ extern "C" {
  * (108: csg_wino4_conv_spade, csg_wino4_conv_spade_supported, csg_avgpool3s2_bwd_add, csg_hinge_mean_fwd / _bwd;
  * 109: csg_canon_general_workspace, csg_canon_general_build / _converse / _close / _emit;
  * 110: csg_norm_eval_stats_multi, csg_deprocess_u8_workspace, csg_deprocess_u8;
- * 111: csg_box_iou) */
+ * 111: csg_box_iou;
+ * 112: csg_preprocess_workspace, csg_preprocess) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -486,6 +487,40 @@ int csg_norm_apply_bwd_dx(const float* dy, const float* x, const float* mean, co
 int64_t csg_deprocess_u8_workspace(int64_t B);
 int csg_deprocess_u8(const float* img, int64_t B, int64_t H, int64_t W, int64_t img_cs, const float* div3, const float* sub3,
                      int32_t rescale, uint8_t* out, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- decoded pictures -> the trainer's image tensor (csrc/preprocess.hip) ------------------------------
+ * The per-sample transform of the reference's loader (sg2im/data/packed_coco.py:269-272: T.Resize(image_size), T.ToTensor(),
+ * T.Normalize(mean, std)) for a batch of DIFFERENTLY SIZED 8-bit RGB pictures, the exact inverse direction of
+ * csg_deprocess_u8.
+ *   src        uint8, device: B interleaved RGB pictures back to back, dense rows of 3 * w_i bytes at ANY byte alignment;
+ *   desc       int64 (B,3), device: (byte offset in src, h_i, w_i) per picture;  desc_host: the same rows in HOST memory,
+ *              read during the call — every refusal below is decided from it, before the first launch, without a
+ *              device synchronisation.  A device row that disagrees with what was validated (a stale buffer under a
+ *              replayed graph) is re-checked on the device and that picture is skipped rather than read out of bounds;
+ *   out        fp32 (B,3,H,W), contiguous NCHW, 16-byte aligned;
+ *   out_u8     nullable: the resized picture, uint8 (B,H,W,3), 4-byte aligned;
+ *   sub3, div3 three floats each, HOST memory: mean and std of T.Normalize as fp32 (0 / 1: ToTensor alone).
+ * Resize is Pillow's 8-bit bilinear `resize((W, H))` restated exactly: per axis fp64 coefficients (scale = in / out,
+ * support = max(scale, 1), triangle weights normalised by their in-order sum, rounded to 22-bit fixed point), integer
+ * accumulation, the horizontal pass first into a uint8 intermediate (`workspace`), then the vertical pass; a pass whose size
+ * does not change is skipped.  The coefficients are computed on the device, in fp64, by the block that uses them.  Then
+ * float(byte) / 255, - sub3[c], / div3[c]: three correctly rounded fp32 operations, no contraction.  out_u8 EQUALS Pillow's
+ * bytes and out EQUALS torch's bits on the host (tests/test_gpu_preprocess.py).
+ * Two launches, always (the horizontal one's blocks return at once for a picture with w_i == W), stream ordered and
+ * capturable; no atomics, nothing read back.  A captured pair serves any later batch of the same B in the same buffers
+ * whose heights do not exceed the captured maximum and whose workspace need does not exceed the captured size.
+ * ALIGNMENT: out 16 bytes, out_u8 and workspace 4 bytes (CSG_E_BADSHAPE otherwise); src any.
+ * LIMITS: 1 <= B <= CSG_PREPROCESS_MAX_BATCH; every side (h_i, w_i, H, W) in 1 .. CSG_PREPROCESS_MAX_SIDE (CSG_E_BADSHAPE);
+ * h_i <= CSG_PREPROCESS_MAX_SCALE * H and w_i <= CSG_PREPROCESS_MAX_SCALE * W, i.e. a table of 2 * 64 + 1 = 129 taps per output (Pillow's width; at most 128 are ever used)
+ * (CSG_E_UNSUPPORTED); offset_i >= 0 and offset_i + 3 h_i w_i <= src_bytes (CSG_E_BADSHAPE).
+ * csg_preprocess_workspace = sum_i 3 * h_i * W bytes.                                                                     */
+#define CSG_PREPROCESS_MAX_SCALE 64
+#define CSG_PREPROCESS_MAX_SIDE 8192
+#define CSG_PREPROCESS_MAX_BATCH 1024
+int64_t csg_preprocess_workspace(const int64_t* desc_host, int64_t B, int64_t W);
+int csg_preprocess(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, int64_t H,
+                   int64_t W, const float* sub3, const float* div3, float* out, uint8_t* out_u8, uint8_t* workspace,
+                   int64_t workspace_bytes, void* stream);
 
 /* ---- validation metric: box IoU of a padded batch (csrc/metrics.hip) ---------------------------------
  * The reference's jaccard (sg2im/metrics.py:4-36) behind remove_dummies_and_padding (sg2im/utils.py:66-71), with the clamp
