@@ -65,6 +65,7 @@ enum KernelId {
   K_DEPROCESS,
   K_BOX_IOU,
   K_PREPROCESS,
+  K_CLEVR_BOXES,
   K_COUNT
 };
 

@@ -1514,7 +1514,7 @@ def deprocess_u8(img, rescale=True):
 
 
 def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_host=None, out=None, out_u8=None,
-                      workspace=None):
+                      workspace=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """The loader's per-sample transform (sg2im/data/packed_coco.py:269-272: T.Resize, T.ToTensor, T.Normalize) for a batch
     of differently sized decoded pictures, on the device (csg_preprocess): Pillow's 8-bit bilinear resize byte for byte,
     then torch's three fp32 operations bit for bit.
@@ -1522,7 +1522,11 @@ def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_ho
     src_u8: uint8 device tensor, B interleaved RGB pictures back to back (dense rows, any alignment); desc: int64 (B,3)
     rows (byte offset, h, w).  The sizes are needed on the host (refusals, launch geometry, workspace): pass `desc` as a
     CPU tensor (it is uploaded here), or as a device tensor together with its CPU copy `desc_host`; a device `desc` alone
-    is read back, which synchronises.  normalize=False gives ToTensor alone (byte / 255).
+    is read back, which synchronises.  normalize=False gives ToTensor alone (byte / 255); `mean` / `std` (a number or three)
+    are T.Normalize's, by default ImageNet's — CLEVR's encode_image() is Normalize(0.5, 0.5) (sg2im/data/utils.py:13-14).
+    A desc of FOUR columns (byte offset, h, w, bytes per pixel) goes to csg_preprocess_px: a picture with 4 bytes per pixel
+    is R, G, B and an ignored byte (a decoded RGBA picture as it is), one with 3 is as above; src_u8 must then start on a
+    4-byte boundary.
     Returns fp32 (B,3,H,W) contiguous NCHW — what Trainer.step takes without a copy — and with want_u8 also the resized
     uint8 (B,H,W,3).  `out`, `out_u8`, `workspace` (uint8, csg_preprocess_workspace bytes): caller-owned buffers, for a
     captured graph; `out` must start on a 16-byte boundary, `out_u8` and `workspace` on a 4-byte one (a view into a larger
@@ -1532,9 +1536,9 @@ def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_ho
                            "no CPU path" % src_u8.device)
     if src_u8.dtype != torch.uint8 or not src_u8.is_contiguous():
         raise RuntimeError("preprocess_images: src_u8 must be a contiguous uint8 tensor, got %s" % src_u8.dtype)
-    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 3:
-        raise RuntimeError("preprocess_images: desc must be int64 (B,3) rows of (byte offset, h, w); got %s %s" % (
-            desc.dtype, tuple(desc.shape)))
+    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] not in (3, 4):
+        raise RuntimeError("preprocess_images: desc must be int64 (B,3) rows of (byte offset, h, w) or (B,4) rows of (byte "
+                           "offset, h, w, bytes per pixel); got %s %s" % (desc.dtype, tuple(desc.shape)))
     dev = src_u8.device
     if not desc.is_cuda:
         desc_host, desc = desc.contiguous(), desc.to(dev, non_blocking=True)
@@ -1545,7 +1549,8 @@ def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_ho
         raise RuntimeError("preprocess_images: desc_host must be the CPU copy of desc")
     B, H, W = desc.shape[0], int(H), int(W)
     host = ctypes.c_void_p(desc_host.data_ptr())
-    nws = lib.csg_preprocess_workspace(host, B, W)
+    px = desc.shape[1] == 4
+    nws = (lib.csg_preprocess_px_workspace if px else lib.csg_preprocess_workspace)(host, B, W)
     if workspace is None:
         workspace = torch.empty(max(nws, 1), device=dev, dtype=torch.uint8)
     if out is None:
@@ -1559,11 +1564,55 @@ def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_ho
     if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
         raise RuntimeError("preprocess_images: workspace must be a contiguous uint8 tensor")
     # the fp32 values torch.as_tensor(IMAGENET_MEAN / IMAGENET_STD, dtype=float32) holds (T.Normalize, utils.py:13-14)
-    sub = (_lib.c_f32 * 3)(*(IMAGENET_MEAN if normalize else (0.0, 0.0, 0.0)))
-    div = (_lib.c_f32 * 3)(*(IMAGENET_STD if normalize else (1.0, 1.0, 1.0)))
-    check(lib.csg_preprocess(ptr(src_u8), src_u8.numel(), ptr(desc), host, B, H, W, sub, div, ptr(out),
-                             ptr(out_u8) if want_u8 else None, ptr(workspace), workspace.numel(), stream()), "preprocess")
+    sub = (_lib.c_f32 * 3)(*(_three("mean", mean) if normalize else (0.0, 0.0, 0.0)))
+    div = (_lib.c_f32 * 3)(*(_three("std", std) if normalize else (1.0, 1.0, 1.0)))
+    check((lib.csg_preprocess_px if px else lib.csg_preprocess)(
+        ptr(src_u8), src_u8.numel(), ptr(desc), host, B, H, W, sub, div, ptr(out), ptr(out_u8) if want_u8 else None,
+        ptr(workspace), workspace.numel(), stream()), "preprocess_px" if px else "preprocess")
     return (out, out_u8) if want_u8 else out
+
+
+def _three(name, v):
+    """T.Normalize's `mean` / `std`: one number for all channels, or one per channel."""
+    v = tuple(float(x) for x in v) if isinstance(v, (tuple, list)) else (float(v),) * 3
+    if len(v) != 3:
+        raise RuntimeError("preprocess_images: %s must be a number or three, got %d" % (name, len(v)))
+    return v
+
+
+def clevr_boxes(geom, objs, rot, counts, objs_host=None, counts_host=None, out=None):
+    """The reference's extract_bounding_boxes (sg2im/data/packed_clevr_dialog.py:21-77) for a padded batch, on the device
+    (csg_clevr_boxes): fp64 in the reference's operation order, rounded once to fp32 — the reference's bits.
+
+    geom: fp64 (B,O,5) = pixel x, pixel y, 3d x, y, z per object; objs: int64 (B,O,A) whose attribute 0 is the shape id
+    (1 cube, 2 sphere, 3 cylinder); rot: fp64 (B,2) = (cos, sin) of directions['right']; counts: int64 (B,) objects per
+    scene.  All on the device; the counts and shape ids are needed on the host too (refusals): pass their CPU copies
+    `objs_host` / `counts_host`, or they are read back, which synchronises.  Returns fp32 (B,O,4) rows (x_min, y_min, w, h),
+    -1 in the rows at or beyond a scene's count.  `out`: a caller-owned buffer, for a captured graph.  No autograd."""
+    for name, t, dt, shape in (("geom", geom, torch.float64, (None, None, 5)), ("objs", objs, torch.int64, (None, None, None)),
+                               ("rot", rot, torch.float64, (None, 2)), ("counts", counts, torch.int64, (None,))):
+        if not t.is_cuda:
+            raise RuntimeError("clevr_boxes: %s must be a HIP (cuda) tensor; got a %s tensor — there is no CPU path" % (
+                name, t.device))
+        if t.dtype != dt or t.dim() != len(shape) or not t.is_contiguous() or any(
+                w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise RuntimeError("clevr_boxes: %s must be contiguous %s of %d dimensions %s; got %s %s" % (
+                name, dt, len(shape), shape, t.dtype, tuple(t.shape)))
+    B, O, A = objs.shape
+    if tuple(geom.shape[:2]) != (B, O) or rot.shape[0] != B or counts.shape[0] != B:
+        raise RuntimeError("clevr_boxes: geom %s, rot %s and counts %s do not fit objs %s" % (
+            tuple(geom.shape), tuple(rot.shape), tuple(counts.shape), tuple(objs.shape)))
+    objs_host = (objs.cpu() if objs_host is None else objs_host).to(torch.int64).contiguous()
+    counts_host = (counts.cpu() if counts_host is None else counts_host).to(torch.int64).contiguous()
+    if objs_host.is_cuda or counts_host.is_cuda or objs_host.shape != objs.shape or counts_host.shape != counts.shape:
+        raise RuntimeError("clevr_boxes: objs_host / counts_host must be the CPU copies of objs / counts")
+    if out is None:
+        out = torch.empty((B, O, 4), device=geom.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, O, 4) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError("clevr_boxes: out must be contiguous fp32 (B,O,4) on the device")
+    check(lib.csg_clevr_boxes(ptr(geom), ptr(objs), A, ptr(rot), ptr(counts), ctypes.c_void_p(objs_host.data_ptr()),
+                              ctypes.c_void_p(counts_host.data_ptr()), B, O, ptr(out), stream()), "clevr_boxes")
+    return out
 
 
 # ------------------------------------------------------------------------------------ resampling

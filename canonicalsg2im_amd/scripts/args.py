@@ -27,6 +27,11 @@ _OFF_PATH_FLAGS = {
     'coco_train_image_dir': (None, 'str'), 'coco_val_image_dir': (None, 'str'),
     'coco_train_instances_json': (None, 'str'), 'coco_train_stuff_json': (None, 'str'),
     'coco_val_instances_json': (None, 'str'), 'coco_val_stuff_json': (None, 'str'),
+    # CLEVR from a folder (sg2im/data/packed_clevr.py of this package): unset, the reference's layout under --dataroot
+    # (<dataroot>/CLEVR/CLEVR_Dialog/scenes/CLEVR_<split>_scenes.json, .../images/<split>/); an image dir given here holds the
+    # split's pictures themselves
+    'clevr_train_scenes_json': (None, 'str'), 'clevr_val_scenes_json': (None, 'str'),
+    'clevr_train_image_dir': (None, 'str'), 'clevr_val_image_dir': (None, 'str'),
     'max_objects_per_image': (10, 'int'), 'vg_use_orphaned_objects': (True, 'bool'), 'dataroot': ('./datasets', 'str'),
     'preprocess_mode': ('scale_width_and_crop', 'str'), 'no_flip': (False, 'flag'), 'nThreads': (0, 'int'),
     'cache_filelist_write': (False, 'flag'), 'cache_filelist_read': (False, 'flag'), 'dense_scenes': (0, 'int'),

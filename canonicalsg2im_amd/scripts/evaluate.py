@@ -2,7 +2,8 @@
 (scripts/train.py:410-424, :446-449) out.
 
 The reference validates on its datasets' validation split.  With `--dataset packed_coco` and an existing val image directory
-(`--coco_val_image_dir`, by default <dataroot>/MSCoco/images/val2017) so does this: the first `--num_val_samples` pictures in
+(`--coco_val_image_dir`, by default <dataroot>/MSCoco/images/val2017), or `--dataset packed_clevr` and an existing
+`--clevr_val_image_dir` (by default <dataroot>/CLEVR/CLEVR_Dialog/images/val), so does this: the first `--num_val_samples` pictures in
 file order, not shuffled, through the same device input stage as scripts/train.py of this package.  Otherwise the
 validation set is seeded synthetic batches of the chosen dataset's shape.  The reference's flags describe the model; on top
 of them:
@@ -51,12 +52,13 @@ def parse_args(argv=None):
 
 def validation_batches(args, trainer, dev, world=1, val_set=None):
     """Generator of the validation batches on `dev`, ceil(num_val_samples / batch_size) of them: the first pictures of
-    `val_set` (a folder dataset, `coco_val_set`) in file order, or the seeded synthetic batches (see Seeds above)."""
+    `val_set` (a folder dataset, `folder_val_set`) in file order, or the seeded synthetic batches (see Seeds above)."""
     from ..synth import BatchConfig, make_batch
     from .train import packed_batch
     if val_set is not None:              # the first num_val_samples pictures in file order; every rank sees the same batches
-        from ..sg2im.data.packed_coco import CocoBatchBuilder, epoch_batches
-        builder = CocoBatchBuilder(val_set, args, trainer, dev, num_workers=args.loader_num_workers)
+        from ..sg2im.data.loader import epoch_batches
+        from .train import folder_builder
+        builder = folder_builder(val_set, args, trainer, dev)
         n = len(val_set)
         lists = epoch_batches(n, args.batch_size, shuffle=False)
         if n % args.batch_size:
@@ -78,14 +80,17 @@ def validation_batches(args, trainer, dev, world=1, val_set=None):
         yield packed_batch(args, trainer, batch, dev) if packed else [None if x is None else x.to(dev) for x in batch]
 
 
-def coco_val_set(args, vocab=None):
+def folder_val_set(args, vocab=None):
     """The val split's folder dataset, or None (synthetic validation batches).  `vocab`: the vocabulary the model was built
-    with; a val split whose categories differ from it is refused here, on the host — its category ids would index the
-    model's embedding tables."""
-    if args.dataset != "packed_coco":
-        return None
-    from ..sg2im.data.packed_coco import build_coco_dataset
-    val_set = build_coco_dataset(args, "val")
+    with; a val split whose categories or attribute tables differ from it is refused here, on the host — its ids would
+    index the model's embedding tables."""
+    from .train import folder_dataset
+    val_set = folder_dataset(args, "val")
+    if val_set is not None and vocab is not None and val_set.vocab["attributes"] != vocab["attributes"] and \
+            val_set.vocab["object_name_to_idx"] == vocab["object_name_to_idx"]:
+        raise SystemExit("the val split's attribute tables (%s rows) are not the model's (%s rows): train and validate on one "
+                         "vocabulary" % ([len(t) for t in val_set.vocab["attributes"].values()],
+                                         [len(t) for t in vocab["attributes"].values()]))
     if val_set is not None and vocab is not None and val_set.vocab["object_name_to_idx"] != vocab["object_name_to_idx"]:
         raise SystemExit("the val split's categories (%d names, largest id %d) are not the model's (%d names, largest id %d): "
                          "train and validate on annotation files of one category set" % (
@@ -138,7 +143,7 @@ def main(argv=None):
     from .train import _vocab_kind
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    val_set = coco_val_set(args)
+    val_set = folder_val_set(args)
     args.vocab = val_set.vocab if val_set is not None else make_vocab(_vocab_kind(args.dataset))
     print("data: %s" % ("%d pictures of %s" % (len(val_set), val_set.image_dir) if val_set is not None
                         else "seeded synthetic batches (%s shapes)" % args.dataset), flush=True)

@@ -1,4 +1,4 @@
-"""Command-line trainer for the HIP hot path, on a COCO folder or on SYNTHETIC batches.
+"""Command-line trainer for the HIP hot path, on a COCO or CLEVR folder or on SYNTHETIC batches.
 
 The reference's scripts/train.py owns data loading, logging, evaluation and checkpoint policy; of it only the
 iteration (:353-393, :468-485) is on the hot path and lives in `canonicalsg2im_amd.train.Trainer`.  This entry point
@@ -12,8 +12,12 @@ Data.  `--dataset packed_coco` trains on real pictures when the train image dire
 default <dataroot>/MSCoco/images/train2017 with the annotation files beside it, the reference's layout): the pictures are
 decoded on the host in `--loader_num_workers` threads and resized, converted and normalised on the device, one batch ahead of
 the step (sg2im/data/packed_coco.py of this package; `--mask_size` must be 0 there).  Every epoch is a permutation seeded by
-the epoch number; with N ranks each takes every N-th sample of a global batch.  Without that directory, and for every other
-dataset, the batches are seeded synthetic ones of the chosen dataset's shape.  One line says which of the two it is.
+the epoch number; with N ranks each takes every N-th sample of a global batch.  `--dataset packed_clevr` does the same when
+its train image directory exists (`--clevr_train_image_dir`, by default <dataroot>/CLEVR/CLEVR_Dialog/images/train with
+scenes/CLEVR_train_scenes.json beside `images`): the renders go up as decoded, RGBA included, and the boxes are computed on
+the device from the scene geometry (sg2im/data/packed_clevr.py of this package; `--mask_size` must be 0 there too).  Without
+that directory, and for every other dataset, the batches are seeded synthetic ones of the chosen dataset's shape.  One line
+says which of the two it is.
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as
 the packed data loaders do on the host; `packed_vg` batches carry annotated relationships (synthetic, among the
@@ -40,6 +44,26 @@ def packed_batch(args, trainer, batch, dev):
     module parses command lines without the library)."""
     from ..sg2im.data.collate import packed_batch as impl
     return impl(args, trainer, batch, dev)
+
+
+def folder_dataset(args, split):
+    """The dataset of `split` when --dataset names a folder dataset whose image directory exists, None otherwise: the batches
+    are then synthetic."""
+    if args.dataset == "packed_coco":
+        from ..sg2im.data.packed_coco import build_coco_dataset
+        return build_coco_dataset(args, split)
+    if args.dataset == "packed_clevr":
+        from ..sg2im.data.packed_clevr import build_clevr_dataset
+        return build_clevr_dataset(args, split)
+    return None
+
+
+def folder_builder(dataset, args, trainer, dev):
+    """The batch builder of a folder dataset, with --loader_num_workers threads."""
+    from ..sg2im.data.packed_clevr import ClevrBatchBuilder, PackedClevrDataset
+    from ..sg2im.data.packed_coco import CocoBatchBuilder
+    cls = ClevrBatchBuilder if isinstance(dataset, PackedClevrDataset) else CocoBatchBuilder
+    return cls(dataset, args, trainer, dev, num_workers=args.loader_num_workers)
 
 
 def build_parser():
@@ -70,10 +94,8 @@ def main(argv=None):
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    train_set = None
-    if args.dataset == "packed_coco":
-        from ..sg2im.data.packed_coco import CocoBatchBuilder, build_coco_dataset, epoch_batches
-        train_set = build_coco_dataset(args, "train")
+    from ..sg2im.data.loader import epoch_batches
+    train_set = folder_dataset(args, "train")
     args.vocab = train_set.vocab if train_set is not None else make_vocab(_vocab_kind(args.dataset))
     if world > 1:
         args.gpu_ids = ",".join(str(i) for i in range(world))
@@ -98,14 +120,14 @@ def main(argv=None):
         from ..evaluate import Evaluator
         from . import evaluate as val_cli
         evaluator = Evaluator(trainer)
-        val_set = val_cli.coco_val_set(args, args.vocab)     # read once; refused if its categories are not the model's
+        val_set = val_cli.folder_val_set(args, args.vocab)   # read once; refused if its vocabulary is not the model's
     builder = real = None
     if train_set is not None:
         steps_per_epoch = len(train_set) // (per_rank * max(world, 1))
         if steps_per_epoch < 1:
             raise SystemExit("the training set has %d images after filtering: fewer than one batch of %d" % (
                 len(train_set), per_rank * max(world, 1)))
-        builder = CocoBatchBuilder(train_set, args, trainer, dev, num_workers=args.loader_num_workers)
+        builder = folder_builder(train_set, args, trainer, dev)
 
         def index_lists():               # iteration t is step (t - 1) % steps_per_epoch of epoch (t - 1) // steps_per_epoch
             for t in range(t0 + 1, args.num_iterations + 1):

@@ -17,15 +17,13 @@ centre fall on different sides of another object's the graphs can differ from th
 import json
 import os
 from collections import defaultdict
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import register_augmented_relations
 from .collate import packed_batch
-
-MAX_LOADER_THREADS = 16
+from .loader import MAX_LOADER_THREADS, BatchBuilder, _Pending, _Staging, epoch_batches  # noqa: F401  (their first home)
 
 _NO_MASKS = ("PackedCocoSceneGraphDataset: mask_size must be 0 (got %d): segmentation masks need pycocotools, which is not "
              "a dependency; object centres are box centres, not mask centroids as in the reference")
@@ -119,66 +117,13 @@ class PackedCocoSceneGraphDataset:
         return pixels, torch.from_numpy(objs), torch.from_numpy(boxes), self.image_ids[index]
 
 
-def epoch_batches(n, per_rank, rank=0, world=1, seed=0, epoch=0, shuffle=True):
-    """The sample indices of one rank's batches in one epoch over n samples: a permutation seeded by (seed, epoch), cut into
-    global batches of per_rank * world samples of which rank r takes every world-th, starting at r.  Ranks are disjoint and
-    take the same number of steps; the ragged tail (fewer samples than a global batch) is dropped."""
-    order = np.random.default_rng([seed, epoch]).permutation(n) if shuffle else np.arange(n)
-    step = per_rank * world
-    return [[int(i) for i in order[s * step:(s + 1) * step][rank::world]] for s in range(n // step)]
+class CocoBatchBuilder(BatchBuilder):
+    """Batches of a PackedCocoSceneGraphDataset as the 8-tuple Trainer.step takes (loader.BatchBuilder has the staging, the
+    look-ahead and the rule that the workers make no HIP call).
 
-
-class _Staging:
-    """A pinned byte buffer that grows, and the event after which the device has read it."""
-
-    def __init__(self):
-        self.buf, self.read = None, None
-
-    def take(self, nbytes):
-        if self.read is not None:
-            self.read.synchronize()
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.empty(int(nbytes * 1.25) + 64, dtype=torch.uint8, pin_memory=True)
-        return self.buf
-
-
-class _Pending:
-    """A batch whose host half is under way: the decode futures and what the device half needs."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-    def done(self):
-        return all(f.done() for f in self.futures)
-
-
-class CocoBatchBuilder:
-    """Batches of a PackedCocoSceneGraphDataset as the 8-tuple Trainer.step takes.
-
-    A batch has a host half and a device half.  start(indices): `num_workers` threads open the files and decode them into a
-    pinned buffer; descriptor, image ids, objects and boxes are laid out in a second one.  finish(pending), on the current
-    stream: ONE copy of the packed bytes and ONE of the second buffer to the device, ops.preprocess_images,
-    collate.packed_batch.  build(indices) is the two in a row.
-
-    batches(lists) runs the HOST half one batch ahead: the decode of batch k + 1 — the host-bound part of the loader — runs
-    in the worker threads while step k is enqueued and executed, and the device half of a batch is issued at hand-over, by
-    the consumer's thread on the consumer's stream.  The workers make no HIP call at all.  That is deliberate: Trainer.step
-    captures HIP graphs (graphs.py, capture mode "global"), and a HIP call another thread makes while a capture is open —
-    an allocation, an event or stream synchronisation, the read-back of canonical_triplets — fails or invalidates the
-    capture; the hand-over lies between two steps, where no capture is open.  `waited` counts the batches whose decode was
-    not finished at hand-over, `steps` all of them."""
-
-    def __init__(self, dataset, args, trainer, device, num_workers=1):
-        self.ds, self.args, self.trainer, self.dev = dataset, args, trainer, device
-        self.num_workers = max(1, min(int(num_workers), MAX_LOADER_THREADS))       # never sized from the machine's CPUs
-        self.pool = ThreadPoolExecutor(max_workers=self.num_workers)
-        self.pixels = [_Staging(), _Staging()]
-        self.meta = [_Staging(), _Staging()]
-        self.turn = 0
-        self.steps = self.waited = 0
-
-    def close(self):
-        self.pool.shutdown(wait=True)
+    start(indices): `num_workers` threads open the files and decode them into a pinned buffer; descriptor, image ids,
+    objects and boxes are laid out in a second one.  finish(pending), on the current stream: ONE copy of the packed bytes
+    and ONE of the second buffer to the device, ops.preprocess_images, collate.packed_batch."""
 
     @staticmethod
     def _decode(im, dst):
@@ -191,8 +136,7 @@ class CocoBatchBuilder:
         """The host half.  Called by the consumer's thread between two steps: the one HIP call it can make, the pinned
         allocation when a staging buffer has to grow, is made here and not by a worker."""
         B = len(indices)
-        slot = self.turn
-        self.turn ^= 1
+        slot = self._take_slot()
         opened = list(self.pool.map(self.ds.open, indices))              # headers: the sizes
         sizes = [(im.size[1], im.size[0]) for im in opened]              # (h, w)
         ann = [self.ds.annotations(i, w, h) for i, (h, w) in zip(indices, sizes)]
@@ -221,14 +165,8 @@ class CocoBatchBuilder:
     def finish(self, p):
         """The device half, enqueued on the current stream."""
         from ... import ops
-        for f in p.futures:
-            f.result()                                                    # a worker's exception is raised here
         B, O, n64 = p.B, p.O, p.n64
-        src = p.stage.to(self.dev, non_blocking=True)
-        meta_dev = p.meta.to(self.dev, non_blocking=True)
-        read = torch.cuda.Event()
-        read.record()
-        self.pixels[p.slot].read = self.meta[p.slot].read = read          # the slot is taken again two batches on
+        src, meta_dev = self._upload(p)
         i64_dev = meta_dev[:8 * n64].view(torch.int64)
         H, W = self.ds.image_size
         imgs = ops.preprocess_images(src, i64_dev[:3 * B].view(B, 3), H, W, normalize=self.ds.normalize_images,
@@ -236,25 +174,6 @@ class CocoBatchBuilder:
         raw = [imgs, i64_dev[4 * B:].view(B, O, 1), meta_dev[8 * n64:].view(torch.float32).view(B, O, 4), None, None, None,
                None, i64_dev[3 * B:4 * B]]
         return packed_batch(self.args, self.trainer, raw, self.dev)
-
-    def build(self, indices):
-        """One batch, enqueued on the current stream."""
-        return self.finish(self.start(indices))
-
-    def batches(self, index_lists):
-        """Generator over build(indices) for every list, with the host half of the next batch started before a batch is
-        handed over."""
-        index_lists = iter(index_lists)
-        nxt = next(index_lists, None)
-        pending = self.start(nxt) if nxt is not None else None
-        while pending is not None:
-            self.steps += 1
-            if not pending.done():
-                self.waited += 1
-            batch = self.finish(pending)
-            nxt = next(index_lists, None)
-            pending = self.start(nxt) if nxt is not None else None        # decoded while the consumer runs its step
-            yield batch
 
 
 def build_coco_dataset(args, split):

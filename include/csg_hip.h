@@ -46,7 +46,8 @@ extern "C" {
  * 109: csg_canon_general_workspace, csg_canon_general_build / _converse / _close / _emit;
  * 110: csg_norm_eval_stats_multi, csg_deprocess_u8_workspace, csg_deprocess_u8;
  * 111: csg_box_iou;
- * 112: csg_preprocess_workspace, csg_preprocess) */
+ * 112: csg_preprocess_workspace, csg_preprocess;
+ * 113: csg_preprocess_px_workspace, csg_preprocess_px, csg_clevr_boxes) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -521,6 +522,42 @@ int64_t csg_preprocess_workspace(const int64_t* desc_host, int64_t B, int64_t W)
 int csg_preprocess(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, int64_t H,
                    int64_t W, const float* sub3, const float* div3, float* out, uint8_t* out_u8, uint8_t* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* The same transform for pictures of 3 OR 4 bytes per pixel, chosen per picture: desc and desc_host are int64 (B,4) rows
+ * (byte offset in src, h_i, w_i, bytes per pixel).  With 4, rows are 4 * w_i bytes and a pixel is R, G, B and a fourth byte
+ * that is ignored: what Pillow's RGBA -> RGB conversion drops, so a decoded RGBA picture (CLEVR's renders) needs no pass on
+ * the host.  The pass that reads the picture itself (the horizontal one, or the vertical one when w_i == W) loads such a
+ * pixel as one dword when offset_i is a multiple of 4, byte by byte otherwise.  Output, workspace layout (the horizontal
+ * result is 3 bytes per pixel), launches, ranges, alignment and the device's re-check of its row are those of csg_preprocess,
+ * with 3 h_i w_i replaced by (bytes per pixel) h_i w_i; in addition src must be 4-byte aligned and a bytes-per-pixel entry
+ * other than 3 or 4 is CSG_E_BADSHAPE.  The kernels are the two instantiations of one template: a batch of 3-byte
+ * pictures gives the bits csg_preprocess gives (tests/test_gpu_clevr.py).                                              */
+int64_t csg_preprocess_px_workspace(const int64_t* desc_host, int64_t B, int64_t W);
+int csg_preprocess_px(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, int64_t H,
+                      int64_t W, const float* sub3, const float* div3, float* out, uint8_t* out_u8, uint8_t* workspace,
+                      int64_t workspace_bytes, void* stream);
+
+/* ---- CLEVR scene geometry -> object boxes (csrc/clevr.hip) ---------------------------------------------
+ * The reference's extract_bounding_boxes (sg2im/data/packed_clevr_dialog.py:21-77) for a padded batch, one lane per object.
+ *   geom    fp64 (B,O,5), device: pixel_coords[0], pixel_coords[1], 3d_coords[0..2] of every object;
+ *   objs    int64 (B,O,A), device: attribute 0 is the shape id, 1 cube, 2 sphere, 3 cylinder (:121);
+ *   rot     fp64 (B,2), device: directions['right'][0..1] = (cos, sin) of the scene;
+ *   counts  int64 (B,), device: objects of the scene; rows at or beyond it are padding;
+ *   objs_host, counts_host: the same two in HOST memory, read during the call — the refusals are decided from them,
+ *           before the launch, without a device synchronisation; a device row that disagrees (a stale buffer under a replayed
+ *           graph) is written as a padding row;
+ *   boxes   fp32 (B,O,4), 16-byte aligned: (x_min, y_min, x_max - x_min, y_max - y_min), -1 in padding rows.
+ * The reference computes in Python floats and rounds once, when the lists become a FloatTensor; so does this: fp64 in the
+ * reference's association order (the second rotation line reads the x1 the first has overwritten; 6.9 * z1 * (15 - y1) /
+ * 2.0 left to right; (1.3 * 10) / (10 + y1); the cylinder's upper height first, the lower one derived from it; the
+ * divisors 320 and 480 whatever the picture's size), no contraction, one rounding to fp32: boxes EQUAL the reference's bits
+ * (tests/golden/clevr_boxes.npz).  One launch, stream ordered and capturable; nothing is read back.
+ * LIMITS: 1 <= B <= CSG_CLEVR_MAX_BATCH, 1 <= O <= CSG_CLEVR_MAX_OBJECTS, 1 <= A <= 64, 0 <= counts <= O, every shape id
+ * below its scene's count in 1 .. 3 (CSG_E_BADSHAPE otherwise); geom, rot, objs, counts 8-byte aligned.                   */
+#define CSG_CLEVR_MAX_BATCH 65535
+#define CSG_CLEVR_MAX_OBJECTS 1024
+int csg_clevr_boxes(const double* geom, const int64_t* objs, int64_t A, const double* rot, const int64_t* counts,
+                    const int64_t* objs_host, const int64_t* counts_host, int64_t B, int64_t O, float* boxes, void* stream);
 
 /* ---- validation metric: box IoU of a padded batch (csrc/metrics.hip) ---------------------------------
  * The reference's jaccard (sg2im/metrics.py:4-36) behind remove_dummies_and_padding (sg2im/utils.py:66-71), with the clamp
