@@ -66,6 +66,7 @@ enum KernelId {
   K_BOX_IOU,
   K_PREPROCESS,
   K_CLEVR_BOXES,
+  K_VG_ROWS,
   K_COUNT
 };
 

@@ -1615,6 +1615,54 @@ def clevr_boxes(geom, objs, rot, counts, objs_host=None, counts_host=None, out=N
     return out
 
 
+def vg_rows(rows, sizes, counts, num_object_names, rows_host=None, sizes_host=None, counts_host=None, out_objs=None,
+            out_boxes=None):
+    """The per-object loop of the reference's Visual Genome __getitem__ (sg2im/data/packed_vg.py:110-125) and the padding of
+    its collate for a padded batch, on the device (csg_vg_rows): objs = name, box = (x / WW, y / HH, w / WW, h / HH) as
+    fp64 quotients rounded once to fp32 — the reference's bits.
+
+    rows: int32 (B,O,5) = name id, x, y, w, h (pixels) per chosen object; sizes: int64 (B,2) = (HH, WW) of the decoded
+    pictures; counts: int64 (B,) objects per sample.  All on the device; they are needed on the host too (refusals): pass
+    their CPU copies `rows_host` / `sizes_host` / `counts_host`, or they are read back, which synchronises.
+    `num_object_names`: len(vocab['object_idx_to_name']); a name id is 1 .. that minus 1 (0 is __image__).
+    Returns (objs int64 (B,O,1), boxes fp32 (B,O,4)): what collate.packed_batch takes; 0 and -1 in the rows at or beyond a
+    sample's count.  `out_objs` (int64 (B,O) or (B,O,1)), `out_boxes`: caller-owned buffers, for a captured graph.
+    No autograd."""
+    for name, t, dt, shape in (("rows", rows, torch.int32, (None, None, 5)), ("sizes", sizes, torch.int64, (None, 2)),
+                               ("counts", counts, torch.int64, (None,))):
+        if not t.is_cuda:
+            raise RuntimeError("vg_rows: %s must be a HIP (cuda) tensor; got a %s tensor — there is no CPU path" % (
+                name, t.device))
+        if t.dtype != dt or t.dim() != len(shape) or not t.is_contiguous() or any(
+                w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise RuntimeError("vg_rows: %s must be contiguous %s of %d dimensions %s; got %s %s" % (
+                name, dt, len(shape), shape, t.dtype, tuple(t.shape)))
+    B, O = rows.shape[:2]
+    if sizes.shape[0] != B or counts.shape[0] != B:
+        raise RuntimeError("vg_rows: sizes %s and counts %s do not fit rows %s" % (
+            tuple(sizes.shape), tuple(counts.shape), tuple(rows.shape)))
+    rows_host = (rows.cpu() if rows_host is None else rows_host).to(torch.int32).contiguous()
+    sizes_host = (sizes.cpu() if sizes_host is None else sizes_host).to(torch.int64).contiguous()
+    counts_host = (counts.cpu() if counts_host is None else counts_host).to(torch.int64).contiguous()
+    if rows_host.is_cuda or sizes_host.is_cuda or counts_host.is_cuda or rows_host.shape != rows.shape or \
+            sizes_host.shape != sizes.shape or counts_host.shape != counts.shape:
+        raise RuntimeError("vg_rows: rows_host / sizes_host / counts_host must be the CPU copies of rows / sizes / counts")
+    if out_objs is None:
+        out_objs = torch.empty((B, O, 1), device=rows.device, dtype=torch.int64)
+    if out_boxes is None:
+        out_boxes = torch.empty((B, O, 4), device=rows.device, dtype=torch.float32)
+    if tuple(out_objs.shape) not in ((B, O), (B, O, 1)) or out_objs.dtype != torch.int64 or not out_objs.is_contiguous() or \
+            not out_objs.is_cuda:
+        raise RuntimeError("vg_rows: out_objs must be contiguous int64 (B,O) or (B,O,1) on the device")
+    if tuple(out_boxes.shape) != (B, O, 4) or out_boxes.dtype != torch.float32 or not out_boxes.is_contiguous() or \
+            not out_boxes.is_cuda:
+        raise RuntimeError("vg_rows: out_boxes must be contiguous fp32 (B,O,4) on the device")
+    check(lib.csg_vg_rows(ptr(rows), ptr(sizes), ptr(counts), ctypes.c_void_p(rows_host.data_ptr()),
+                          ctypes.c_void_p(sizes_host.data_ptr()), ctypes.c_void_p(counts_host.data_ptr()),
+                          int(num_object_names), B, O, ptr(out_objs), ptr(out_boxes), stream()), "vg_rows")
+    return out_objs, out_boxes
+
+
 # ------------------------------------------------------------------------------------ resampling
 class _Upsample2x(torch.autograd.Function):
     @staticmethod

@@ -3,7 +3,9 @@
 
 The reference validates on its datasets' validation split.  With `--dataset packed_coco` and an existing val image directory
 (`--coco_val_image_dir`, by default <dataroot>/MSCoco/images/val2017), or `--dataset packed_clevr` and an existing
-`--clevr_val_image_dir` (by default <dataroot>/CLEVR/CLEVR_Dialog/images/val), so does this: the first `--num_val_samples` pictures in
+`--clevr_val_image_dir` (by default <dataroot>/CLEVR/CLEVR_Dialog/images/val), or `--dataset packed_vg` and an existing image
+directory and val split file (`--vg_image_dir`, `--val_h5`, by default <dataroot>/vg/images and val.h5 or val.npz; the objects
+of a sample are drawn from a stream seeded anew for every pass, so every pass sees the same ones), so does this: the first `--num_val_samples` pictures in
 file order, not shuffled, through the same device input stage as scripts/train.py of this package.  Otherwise the
 validation set is seeded synthetic batches of the chosen dataset's shape.  The reference's flags describe the model; on top
 of them:
@@ -57,8 +59,10 @@ def validation_batches(args, trainer, dev, world=1, val_set=None):
     from .train import packed_batch
     if val_set is not None:              # the first num_val_samples pictures in file order; every rank sees the same batches
         from ..sg2im.data.loader import epoch_batches
+        import random
         from .train import folder_builder
-        builder = folder_builder(val_set, args, trainer, dev)
+        # a Visual Genome builder samples objects: a fresh stream per call, so every rank and every call sees the same ones
+        builder = folder_builder(val_set, args, trainer, dev, rng=random.Random(0))
         n = len(val_set)
         lists = epoch_batches(n, args.batch_size, shuffle=False)
         if n % args.batch_size:
@@ -82,8 +86,8 @@ def validation_batches(args, trainer, dev, world=1, val_set=None):
 
 def folder_val_set(args, vocab=None):
     """The val split's folder dataset, or None (synthetic validation batches).  `vocab`: the vocabulary the model was built
-    with; a val split whose categories or attribute tables differ from it is refused here, on the host — its ids would
-    index the model's embedding tables."""
+    with; a val split whose categories, attribute tables or predicates differ from it is refused here, on the host — its
+    ids would index the model's embedding tables."""
     from .train import folder_dataset
     val_set = folder_dataset(args, "val")
     if val_set is not None and vocab is not None and val_set.vocab["attributes"] != vocab["attributes"] and \
@@ -91,6 +95,10 @@ def folder_val_set(args, vocab=None):
         raise SystemExit("the val split's attribute tables (%s rows) are not the model's (%s rows): train and validate on one "
                          "vocabulary" % ([len(t) for t in val_set.vocab["attributes"].values()],
                                          [len(t) for t in vocab["attributes"].values()]))
+    if val_set is not None and vocab is not None and "pred_idx_to_name" in vocab and \
+            list(val_set.vocab["pred_idx_to_name"]) != list(vocab["pred_idx_to_name"]):
+        raise SystemExit("the val split's predicates (%d names) are not the model's (%d names): train and validate on one "
+                         "vocabulary" % (len(val_set.vocab["pred_idx_to_name"]), len(vocab["pred_idx_to_name"])))
     if val_set is not None and vocab is not None and val_set.vocab["object_name_to_idx"] != vocab["object_name_to_idx"]:
         raise SystemExit("the val split's categories (%d names, largest id %d) are not the model's (%d names, largest id %d): "
                          "train and validate on annotation files of one category set" % (
@@ -144,6 +152,8 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     val_set = folder_val_set(args)
+    if val_set is not None and args.dataset == "packed_vg":        # vocab.json is a file of its own: hold it to the checkpoint's
+        val_set = folder_val_set(args, torch.load(args.checkpoint_name, map_location="cpu").get("vocab"))
     args.vocab = val_set.vocab if val_set is not None else make_vocab(_vocab_kind(args.dataset))
     print("data: %s" % ("%d pictures of %s" % (len(val_set), val_set.image_dir) if val_set is not None
                         else "seeded synthetic batches (%s shapes)" % args.dataset), flush=True)

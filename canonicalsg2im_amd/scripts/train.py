@@ -1,4 +1,4 @@
-"""Command-line trainer for the HIP hot path, on a COCO or CLEVR folder or on SYNTHETIC batches.
+"""Command-line trainer for the HIP hot path, on a COCO, CLEVR or Visual Genome folder or on SYNTHETIC batches.
 
 The reference's scripts/train.py owns data loading, logging, evaluation and checkpoint policy; of it only the
 iteration (:353-393, :468-485) is on the hot path and lives in `canonicalsg2im_amd.train.Trainer`.  This entry point
@@ -15,13 +15,17 @@ the step (sg2im/data/packed_coco.py of this package; `--mask_size` must be 0 the
 the epoch number; with N ranks each takes every N-th sample of a global batch.  `--dataset packed_clevr` does the same when
 its train image directory exists (`--clevr_train_image_dir`, by default <dataroot>/CLEVR/CLEVR_Dialog/images/train with
 scenes/CLEVR_train_scenes.json beside `images`): the renders go up as decoded, RGBA included, and the boxes are computed on
-the device from the scene geometry (sg2im/data/packed_clevr.py of this package; `--mask_size` must be 0 there too).  Without
-that directory, and for every other dataset, the batches are seeded synthetic ones of the chosen dataset's shape.  One line
-says which of the two it is.
+the device from the scene geometry (sg2im/data/packed_clevr.py of this package; `--mask_size` must be 0 there too).
+`--dataset packed_vg` does the same when its image directory and its split file exist (`--vg_image_dir`, `--train_h5`,
+`--vocab_json` where they exist, else <dataroot>/vg/{images, train.h5 or train.npz, vocab.json}): the objects of a sample are
+chosen on the host as the reference chooses them, their pixel boxes are divided by the decoded picture's size on the device,
+and the annotated relationships join the canonical graph (sg2im/data/packed_vg.py of this package; `--mask_size` must be 0;
+a .h5 split needs h5py, a .npz split does not: tools/vg_h5_to_npz.py).  Without the directory, and for every other dataset,
+the batches are seeded synthetic ones of the chosen dataset's shape.  One line says which of the two it is.
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as
-the packed data loaders do on the host; `packed_vg` batches carry annotated relationships (synthetic, among the
-vocabulary's non-location predicates) that join the graph as in sg2im/data/packed_vg.py:127-142.
+the packed data loaders do on the host; `packed_vg` batches carry annotated relationships (the split file's, or synthetic
+ones among the vocabulary's non-location predicates) that join the graph as in sg2im/data/packed_vg.py:127-142.
 
 `--val_every N` (default 0: off) runs the reference's two validation passes (scripts/train.py:410-424, `GT VAL` and `VAL`)
 every N iterations on the validation set of scripts/evaluate.py: the first `--num_val_samples` pictures of the val split
@@ -55,13 +59,20 @@ def folder_dataset(args, split):
     if args.dataset == "packed_clevr":
         from ..sg2im.data.packed_clevr import build_clevr_dataset
         return build_clevr_dataset(args, split)
+    if args.dataset == "packed_vg":
+        from ..sg2im.data.packed_vg import build_vg_dataset
+        return build_vg_dataset(args, split)
     return None
 
 
-def folder_builder(dataset, args, trainer, dev):
-    """The batch builder of a folder dataset, with --loader_num_workers threads."""
+def folder_builder(dataset, args, trainer, dev, rng=None):
+    """The batch builder of a folder dataset, with --loader_num_workers threads.  `rng`: where a Visual Genome builder draws
+    its object sampling (by default its own random.Random, seeded from the rank); the other datasets draw nothing."""
     from ..sg2im.data.packed_clevr import ClevrBatchBuilder, PackedClevrDataset
     from ..sg2im.data.packed_coco import CocoBatchBuilder
+    from ..sg2im.data.packed_vg import PackedVGDataset, VGBatchBuilder
+    if isinstance(dataset, PackedVGDataset):
+        return VGBatchBuilder(dataset, args, trainer, dev, num_workers=args.loader_num_workers, rng=rng)
     cls = ClevrBatchBuilder if isinstance(dataset, PackedClevrDataset) else CocoBatchBuilder
     return cls(dataset, args, trainer, dev, num_workers=args.loader_num_workers)
 

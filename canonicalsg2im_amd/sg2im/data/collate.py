@@ -2,20 +2,23 @@
 import torch
 
 
-def packed_batch(args, trainer, batch, dev):
+def packed_batch(args, trainer, batch, dev, counts=None):
     """A packed batch (the tensors of synth.make_batch or of a dataset's batch builder, on the host or on `dev`) on `dev`,
     with the canonical graph built on the device: the __image__ row appended to every sample, then canonical_triplets in
     place of the triplets.  packed_vg hands the batch's annotated relationships over, unless --include_relationships 0
-    (packed_vg.py:128-130)."""
+    (packed_vg.py:128-130).  `counts`: the real objects per sample as a HOST int64 tensor, from a builder that knows them
+    (its objects live on the device: deriving the counts from them would be a read-back per batch); by default they are
+    derived from the objects, as before."""
     from . import canonical_triplets
     rel = None
     if args.dataset == "packed_vg":  # the annotated rows and the object counts are read on the host: hand over CPU tensors
         rel = batch[3] if args.include_relationships else torch.zeros((batch[3].shape[0], 0, 3), dtype=torch.int64)
-        n = (batch[1][..., 0] != 0).sum(1) + 1              # real objects + the __image__ row appended below
+        n = (batch[1][..., 0] != 0).sum(1) if counts is None else counts
+        n = n + 1                                           # real objects + the __image__ row appended below
     batch = [None if x is None else x.to(dev) for x in batch]
     objs, boxes = batch[1], batch[2]
     if rel is None:
-        n = (objs[..., 0] != 0).sum(1) + 1
+        n = ((objs[..., 0] != 0).sum(1) if counts is None else counts.to(dev)) + 1
     O = objs.shape[1] + 1
     objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
     boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)

@@ -47,7 +47,8 @@ extern "C" {
  * 110: csg_norm_eval_stats_multi, csg_deprocess_u8_workspace, csg_deprocess_u8;
  * 111: csg_box_iou;
  * 112: csg_preprocess_workspace, csg_preprocess;
- * 113: csg_preprocess_px_workspace, csg_preprocess_px, csg_clevr_boxes) */
+ * 113: csg_preprocess_px_workspace, csg_preprocess_px, csg_clevr_boxes;
+ * 114: csg_vg_rows) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -558,6 +559,32 @@ int csg_preprocess_px(const uint8_t* src, int64_t src_bytes, const int64_t* desc
 #define CSG_CLEVR_MAX_OBJECTS 1024
 int csg_clevr_boxes(const double* geom, const int64_t* objs, int64_t A, const double* rot, const int64_t* counts,
                     const int64_t* objs_host, const int64_t* counts_host, int64_t B, int64_t O, float* boxes, void* stream);
+
+/* ---- Visual Genome object rows -> object ids and boxes (csrc/vg.hip) ------------------------------------
+ * The per-object loop of the reference's __getitem__ (sg2im/data/packed_vg.py:110-125) and the padding of vg_collate_fn
+ * (:186-205) for a padded batch, one lane per (sample, object) row.
+ *   rows    int32 (B,O,5), device: name id, x, y, w, h of every chosen object, the box in pixels as the split file has it;
+ *   sizes   int64 (B,2), device: (HH, WW) of the DECODED picture of the sample (:81);
+ *   counts  int64 (B,), device: chosen objects of the sample; rows at or beyond it are padding;
+ *   rows_host, sizes_host, counts_host: the same three in HOST memory, read during the call — the refusals are decided from
+ *           them, before the launch, without a device synchronisation; a device row that disagrees (a stale buffer under a
+ *           replayed graph: a name out of range, a size below 1) is written as a padding row;
+ *   objs    int64 (B,O): the name id, 0 in padding rows (the collate's zeros, :193-196);
+ *   boxes   fp32 (B,O,4), 16-byte aligned, one 16-byte store per row:
+ *               ((float)((double)x / WW), (float)((double)y / HH), (float)((double)w / WW), (float)((double)h / HH)),
+ *           -1 in padding rows (:203-205).
+ * The reference divides Python floats, `float(x) / WW`, and rounds once when the list becomes a FloatTensor (:118-120); so
+ * does this: boxes EQUAL the reference's bits (tests/golden/vg_samples.npz).  Nothing clips a box to the picture: the
+ * reference does not.  The __image__ row is not written here (collate.packed_batch appends it).  One launch, stream
+ * ordered and capturable; nothing is read back.
+ * LIMITS: 1 <= B <= CSG_VG_MAX_BATCH; 1 <= O <= CSG_VG_MAX_OBJECTS (csg_canon_general_* takes 256 rows with __image__);
+ * 0 <= counts <= O; HH, WW >= 1; every name id below its sample's count in 1 .. num_object_names - 1 (0 is __image__)
+ * (CSG_E_BADSHAPE otherwise); sizes, counts, objs 8-byte aligned, rows 4-byte aligned.                                */
+#define CSG_VG_MAX_BATCH 1024
+#define CSG_VG_MAX_OBJECTS 255
+int csg_vg_rows(const int32_t* rows, const int64_t* sizes, const int64_t* counts, const int32_t* rows_host,
+                const int64_t* sizes_host, const int64_t* counts_host, int64_t num_object_names, int64_t B, int64_t O,
+                int64_t* objs, float* boxes, void* stream);
 
 /* ---- validation metric: box IoU of a padded batch (csrc/metrics.hip) ---------------------------------
  * The reference's jaccard (sg2im/metrics.py:4-36) behind remove_dummies_and_padding (sg2im/utils.py:66-71), with the clamp
