@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void k_gen_scatter(GenParams P, const int64_t*
   }
   __syncthreads();
   if (tid < n) {
-    if (role >= 0) {                                                  // base_dataset.py:83-87
+    if (role >= 0 && geo != nullptr) {                                // base_dataset.py:83-87; no geometry: authored rows alone
       const uint64_t* Rg = ws_R(geo, b) + ((int64_t)role * MAXN + tid) * W;
       for (int k = 0; k < nw; ++k) adj[tid][k] = Rg[k];
     }
@@ -908,8 +908,9 @@ int csg_canon_general_build(const int64_t* objs0, const float* boxes, const floa
   CSG_REQUIRE(O > 0 && R >= 0 && B * R < (1ll << 31), CSG_E_BADSHAPE, "csg_canon_general_build: bad shape O=%ld R=%ld", (long)O, (long)R);
   CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "csg_canon_general_build: at most %d objects per sample (got %ld)", MAXN,
               (long)O);
-  CSG_REQUIRE(objs0 && boxes && centers && n_objs && counts && (R == 0 || rel), CSG_E_BADSHAPE,
+  CSG_REQUIRE(objs0 && n_objs && counts && (R == 0 || rel) && (boxes != nullptr) == (centers != nullptr), CSG_E_BADSHAPE,
               "csg_canon_general_build: null argument");
+  const bool geometry = boxes != nullptr;      // boxes = centers = NULL: the location relations are the given rows alone
   CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, R, nullptr, nullptr), CSG_E_BADSHAPE,
               "csg_canon_general_build: workspace too small (%ld bytes, need %ld)", (long)workspace_bytes,
               (long)gen_layout(B, P, R, nullptr, nullptr));
@@ -956,14 +957,15 @@ int csg_canon_general_build(const int64_t* objs0, const float* boxes, const floa
               CSG_E_LAUNCH, "csg_canon_general_build: upload of the annotated rows failed");
   CanonParams C;
   fill_params(&C, O, ids, image_id, 0, 0);
-  {
+  if (geometry) {
     ProfScope pr(K_CANON_BUILD, (double)B * O * O, st);
     CSG_LAUNCH(k_canon_build, dim3((unsigned)B), dim3(256), 0, st, C, objs0, boxes, centers, (const int64_t*)w.nob,
                workspace, w.geo_counts);
   }
   {
     ProfScope pr(K_CANON_BUILD, (double)B * P * O * W, st);
-    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, objs0, w, workspace);
+    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, objs0, w,
+               geometry ? workspace : (void*)nullptr);
     CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, G, w, counts);
   }
   return check_launch("csg_canon_general_build");

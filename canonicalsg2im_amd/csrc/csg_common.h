@@ -67,6 +67,7 @@ enum KernelId {
   K_PREPROCESS,
   K_CLEVR_BOXES,
   K_VG_ROWS,
+  K_DRAW_BOXES,
   K_COUNT
 };
 

@@ -1513,6 +1513,29 @@ def deprocess_u8(img, rescale=True):
     return out
 
 
+def draw_boxes_u8(img, boxes, objs, image_id, palette, thickness=2):
+    """Box outlines on a uint8 picture (csg_draw_boxes_u8; the pixel rule is DESIGN 4.10b and include/csg_hip.h): img uint8
+    (B,3,H,W) as `Sampler.generate` returns it, boxes fp32 (B,O,4) xywh, objs int64 (B,O,A), palette uint8 (P,3) RGB on the
+    device.  Rows carrying `image_id`, padded rows (all -1), rows with a NaN and rows without area are not drawn; a pixel
+    on several outlines takes palette[o % P] of the highest row o.  Returns a new uint8 (B,3,H,W); img is not written.
+    One launch, nothing read back.  No autograd."""
+    for name, t, dt in (("img", img, torch.uint8), ("objs", objs, torch.int64), ("palette", palette, torch.uint8)):
+        if t.dtype != dt:
+            raise RuntimeError("draw_boxes_u8: %s must be %s, got %s" % (name, dt, t.dtype))
+    boxes = _f32(boxes)
+    if img.dim() != 4 or img.shape[1] != 3 or boxes.dim() != 3 or boxes.shape[2] != 4 or objs.dim() != 3 \
+            or tuple(objs.shape[:2]) != tuple(boxes.shape[:2]) or boxes.shape[0] != img.shape[0] \
+            or palette.dim() != 2 or palette.shape[1] != 3:
+        raise RuntimeError("draw_boxes_u8: img (B,3,H,W), boxes (B,O,4), objs (B,O,A), palette (P,3); got %s %s %s %s" % (
+            tuple(img.shape), tuple(boxes.shape), tuple(objs.shape), tuple(palette.shape)))
+    img, boxes, objs, palette = img.contiguous(), boxes.contiguous(), objs.contiguous(), palette.contiguous()
+    B, _, H, W = img.shape
+    out = torch.empty_like(img)
+    check(lib.csg_draw_boxes_u8(ptr(img), ptr(boxes), ptr(objs), B, objs.shape[1], objs.shape[2], H, W, int(image_id),
+                                ptr(palette), palette.shape[0], int(thickness), ptr(out), stream()), "draw_boxes_u8")
+    return out
+
+
 def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_host=None, out=None, out_u8=None,
                       workspace=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """The loader's per-sample transform (sg2im/data/packed_coco.py:269-272: T.Resize, T.ToTensor, T.Normalize) for a batch

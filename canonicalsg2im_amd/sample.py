@@ -13,6 +13,9 @@ encoder runs as the module does; the generator is WALKED here on the inference f
   * the picture leaves the device as uint8 (`ops.deprocess_u8`), bit-identical to the host's deprocess_batch;
   * the walk — layout pyramid through conv_img and the deprocess — is captured per (batch, padded objects, size, attributes,
     masks) key the second time the key is seen and replayed (`CSG_GRAPHS=0`: always eager); one stream, no branches.
+
+`Sampler.generate_from_graphs` takes scene graphs a person wrote (authored.py: the reference's scripts/run_model.py form,
+or a flat one) instead of a dataset's batch, and can draw the predicted boxes on the pictures (`ops.draw_boxes_u8`).
 """
 import torch
 
@@ -249,3 +252,36 @@ class Sampler:
             img, u8 = self._generator(objs, boxes.float().contiguous(), None if masks is None else masks.float().contiguous(),
                                       uint8, rescale)
         return (u8 if uint8 else img), boxes_pred, masks_pred
+
+    def generate_from_graphs(self, graphs, overlay=False, thickness=2, palette=None):
+        """Authored scene graphs (authored.py: a list of graphs or the path of a JSON file) -> (images uint8 (B,3,H,W),
+        boxes_pred (B,O,4), overlays uint8 (B,3,H,W) or None).  The graphs are encoded and checked on the host, uploaded
+        once, and made canonical without boxes (`canonical_triplets(boxes=None)`: the authored rows are the location
+        relations; converse and transitive edges and triplet_type as the model's learned_converse / learned_transitivity
+        settings make them in training, converse draws from numpy's global stream as the data loader's).  The pictures come
+        from `generate` on the predicted boxes, under its replay keys.  `overlay`: the pictures with the outlines of the
+        predicted boxes, `thickness` pixels wide, row o in palette[o % P] — `palette` a sequence of RGB
+        triples, by default authored.DEFAULT_PALETTE."""
+        from . import authored
+        from .sg2im.data import canonical_triplets
+        if self.device.type != "cuda":
+            raise RuntimeError(NO_CPU)
+        vocab = self.opt.vocab
+        objs, rows, counts = authored.encode_graphs(authored.load_graphs(graphs, vocab), vocab)
+        conv_w = None
+        if getattr(self.opt, "learned_converse", False):
+            from .sg2im.model import get_conv_converse
+            conv_w = get_conv_converse(self.model).detach().cpu().numpy()
+        objs = objs.to(self.device)
+        triplets, _, triplet_type = canonical_triplets(
+            objs, None, None, counts, vocab, learned_transitivity=bool(getattr(self.opt, "learned_transitivity", False)),
+            include_dummies=False, learned_converse=conv_w is not None, converse_weights=conv_w, triplets=rows)
+        imgs, boxes_pred, _ = self.generate(objs, triplets, triplet_type)
+        overlays = None
+        if overlay:
+            if imgs is None or boxes_pred is None:
+                raise RuntimeError("generate_from_graphs(overlay=True) needs a model that predicts boxes and pictures")
+            pal = torch.tensor(authored.DEFAULT_PALETTE if palette is None else palette, dtype=torch.uint8).reshape(-1, 3)
+            overlays = ops.draw_boxes_u8(imgs, boxes_pred.detach().float(), objs, vocab["object_name_to_idx"]["__image__"],
+                                         pal.to(self.device), thickness)
+        return imgs, boxes_pred, overlays

@@ -134,7 +134,11 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     predicates are more than the six location relations (the converse candidates are then all other non-meta predicates,
     scripts/graphs_utils.py:126-152), the general kernels run (csg_canon_general_*, one (sample, predicate) bit matrix
     per block).  They read `triplets` and `n_objs` on the host: pass CPU tensors (or arrays) to spare a copy.
-    Otherwise the location-only kernels run, as before."""
+    Otherwise the location-only kernels run, as before.
+
+    `boxes=None` (and `obj_centers=None`), with `triplets`: a graph without geometry (canonicalsg2im_amd/authored.py).  No
+    location relation is derived; the given rows — which may carry location predicates and `__in_image__` — are the
+    graph, and converse draws, transitive extras, order and padding are formed from them exactly as above."""
     objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
     first = list(vocab["attributes"].keys())[0]
     image_id = vocab["object_name_to_idx"]["__image__"]
@@ -143,8 +147,11 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     B, O = objs0.shape
     p2i = vocab["pred_name_to_idx"]
     names = meta_relations + augmented_relations
-    boxes = boxes.to(torch.float32).contiguous()
-    obj_centers = obj_centers.to(torch.float32).contiguous()
+    if (boxes is None) != (obj_centers is None) or (boxes is None and triplets is None):
+        raise ValueError("canonical_triplets: boxes=None needs obj_centers=None and the graph's rows in `triplets`")
+    if boxes is not None:
+        boxes = boxes.to(torch.float32).contiguous()
+        obj_centers = obj_centers.to(torch.float32).contiguous()
     if triplets is not None or set(p2i.values()) != {p2i[n] for n in names}:
         return _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity,
                                   include_dummies, learned_converse, converse_weights, uniforms, triplets)

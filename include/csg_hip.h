@@ -48,7 +48,8 @@ extern "C" {
  * 111: csg_box_iou;
  * 112: csg_preprocess_workspace, csg_preprocess;
  * 113: csg_preprocess_px_workspace, csg_preprocess_px, csg_clevr_boxes;
- * 114: csg_vg_rows) */
+ * 114: csg_vg_rows;
+ * 115: csg_draw_boxes_u8; csg_canon_general_build takes boxes = centers = NULL) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -490,6 +491,25 @@ int64_t csg_deprocess_u8_workspace(int64_t B);
 int csg_deprocess_u8(const float* img, int64_t B, int64_t H, int64_t W, int64_t img_cs, const float* div3, const float* sub3,
                      int32_t rescale, uint8_t* out, float* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- box outlines on a uint8 picture (csrc/overlay.hip) -------------------------------------------------
+ * The layout picture of scripts/run_model.py (the generated image with the predicted boxes on it, sg2im/vis.py:128-146)
+ * without text labels.  img (B,3,H,W) uint8 planar as csg_deprocess_u8 writes it, W a multiple of 4; boxes (B,O,4) fp32
+ * xywh; objs (B,O,A) int64 (attribute 0 is read); palette (P,3) uint8 RGB; out (B,3,H,W) uint8, another buffer than img,
+ * which is only read.  All device memory.
+ * Row o of sample b is skipped when objs[b,o,0] == image_id, when all four box values are -1, when one of them is NaN, or
+ * when w <= 0 or h <= 0.  For the others, in fp32 and in this order (no multiply-add is contracted):
+ *   x0 = clamp(x, 0, 1), x1 = clamp(x + w, 0, 1), likewise y  (the clamp of a NaN sum, -inf + inf, is 0);
+ *   px0 = min(W - 1, (int)(x0 * W)), px1 = max(px0, min(W - 1, (int)(x1 * W) - 1)), likewise y with H.
+ * A pixel is on row o's outline when it lies in [px0, px1] x [py0, py1] and its distance to the nearest side of that
+ * rectangle is < thickness (>= 1).  A pixel on no outline keeps its byte; one on several takes palette[o % P] of the
+ * HIGHEST such o.  One launch, capturable, nothing is read back; each lane decides its own pixels, so the bytes are the
+ * same on every run.
+ * LIMITS: 1 <= B <= 65535; O <= 256 and P <= 256 (CSG_E_UNSUPPORTED beyond); H * W < 2^31; img and out on a 4-byte
+ * boundary, boxes on a 16-byte one.                                                                                */
+int csg_draw_boxes_u8(const uint8_t* img, const float* boxes, const int64_t* objs, int64_t B, int64_t O, int64_t A, int64_t H,
+                      int64_t W, int64_t image_id, const uint8_t* palette, int64_t P, int32_t thickness, uint8_t* out,
+                      void* stream);
+
 /* ---- decoded pictures -> the trainer's image tensor (csrc/preprocess.hip) ------------------------------
  * The per-sample transform of the reference's loader (sg2im/data/packed_coco.py:269-272: T.Resize(image_size), T.ToTensor(),
  * T.Normalize(mean, std)) for a batch of DIFFERENTLY SIZED 8-bit RGB pictures, the exact inverse direction of
@@ -722,7 +742,8 @@ int csg_canon_converse(const int64_t* objs0, const int64_t* n_objs, int64_t B, i
  * (__below__ __above__ __left of__ __right of__ __inside__ __surrounding__) or CSG_CANON_ROLE_OTHER; each of the first
  * eight exactly once.  Ids may come in any order.
  * Call order: _build, [_converse], _close, then _emit with T = max_b(counts[b][0] + counts[b][1]).
- *   csg_canon_general_build: objs0 / boxes / centers as for csg_canon_build (device); n_objs (host, B) objects per sample
+ *   csg_canon_general_build: objs0 / boxes / centers as for csg_canon_build (device), or boxes = centers = NULL: no
+ *     geometry, the location relations are the given rows alone (authored graphs); n_objs (host, B) objects per sample
  *     incl. __image__; rel (host, (B,R,3) int64) the annotated rows in local object indices, a sample's first
  *     rel_counts[b] rows (host, B), or with rel_counts NULL every row whose predicate is not __padding__.  Everything is
  *     checked before anything is enqueued; the rows are copied into the workspace on `stream`.  counts[b] = {number of
