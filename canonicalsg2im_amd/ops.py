@@ -1603,6 +1603,29 @@ def _three(name, v):
     return v
 
 
+def _device_operands(fn, operands):
+    """Refuse an operand (name, tensor, dtype, shape with None for a free dimension) of `fn` that is not on the device, or
+    not contiguous of that dtype, rank and fixed dimensions."""
+    for name, t, dt, shape in operands:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s must be a HIP (cuda) tensor; got a %s tensor — there is no CPU path" % (
+                fn, name, t.device))
+        if t.dtype != dt or t.dim() != len(shape) or not t.is_contiguous() or any(
+                w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise RuntimeError("%s: %s must be contiguous %s of %d dimensions %s; got %s %s" % (
+                fn, name, dt, len(shape), shape, t.dtype, tuple(t.shape)))
+
+
+def _host_copies(fn, operands):
+    """For every (name, device tensor, its CPU copy or None) the copy as a contiguous CPU tensor of the device tensor's
+    dtype, read back (which synchronises) where none is given; a copy of another shape or on the device is refused."""
+    copies = [(t.cpu() if host is None else host).to(t.dtype).contiguous() for _, t, host in operands]
+    if any(host.is_cuda or host.shape != t.shape for (_, t, _), host in zip(operands, copies)):
+        raise RuntimeError("%s: %s must be the CPU copies of %s" % (
+            fn, " / ".join(name + "_host" for name, _, _ in operands), " / ".join(name for name, _, _ in operands)))
+    return copies
+
+
 def clevr_boxes(geom, objs, rot, counts, objs_host=None, counts_host=None, out=None):
     """The reference's extract_bounding_boxes (sg2im/data/packed_clevr_dialog.py:21-77) for a padded batch, on the device
     (csg_clevr_boxes): fp64 in the reference's operation order, rounded once to fp32 — the reference's bits.
@@ -1612,23 +1635,13 @@ def clevr_boxes(geom, objs, rot, counts, objs_host=None, counts_host=None, out=N
     scene.  All on the device; the counts and shape ids are needed on the host too (refusals): pass their CPU copies
     `objs_host` / `counts_host`, or they are read back, which synchronises.  Returns fp32 (B,O,4) rows (x_min, y_min, w, h),
     -1 in the rows at or beyond a scene's count.  `out`: a caller-owned buffer, for a captured graph.  No autograd."""
-    for name, t, dt, shape in (("geom", geom, torch.float64, (None, None, 5)), ("objs", objs, torch.int64, (None, None, None)),
-                               ("rot", rot, torch.float64, (None, 2)), ("counts", counts, torch.int64, (None,))):
-        if not t.is_cuda:
-            raise RuntimeError("clevr_boxes: %s must be a HIP (cuda) tensor; got a %s tensor — there is no CPU path" % (
-                name, t.device))
-        if t.dtype != dt or t.dim() != len(shape) or not t.is_contiguous() or any(
-                w is not None and w != g for w, g in zip(shape, t.shape)):
-            raise RuntimeError("clevr_boxes: %s must be contiguous %s of %d dimensions %s; got %s %s" % (
-                name, dt, len(shape), shape, t.dtype, tuple(t.shape)))
+    _device_operands("clevr_boxes", (("geom", geom, torch.float64, (None, None, 5)), ("objs", objs, torch.int64, (None,) * 3),
+                                     ("rot", rot, torch.float64, (None, 2)), ("counts", counts, torch.int64, (None,))))
     B, O, A = objs.shape
     if tuple(geom.shape[:2]) != (B, O) or rot.shape[0] != B or counts.shape[0] != B:
         raise RuntimeError("clevr_boxes: geom %s, rot %s and counts %s do not fit objs %s" % (
             tuple(geom.shape), tuple(rot.shape), tuple(counts.shape), tuple(objs.shape)))
-    objs_host = (objs.cpu() if objs_host is None else objs_host).to(torch.int64).contiguous()
-    counts_host = (counts.cpu() if counts_host is None else counts_host).to(torch.int64).contiguous()
-    if objs_host.is_cuda or counts_host.is_cuda or objs_host.shape != objs.shape or counts_host.shape != counts.shape:
-        raise RuntimeError("clevr_boxes: objs_host / counts_host must be the CPU copies of objs / counts")
+    objs_host, counts_host = _host_copies("clevr_boxes", (("objs", objs, objs_host), ("counts", counts, counts_host)))
     if out is None:
         out = torch.empty((B, O, 4), device=geom.device, dtype=torch.float32)
     if tuple(out.shape) != (B, O, 4) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
@@ -1651,25 +1664,14 @@ def vg_rows(rows, sizes, counts, num_object_names, rows_host=None, sizes_host=No
     Returns (objs int64 (B,O,1), boxes fp32 (B,O,4)): what collate.packed_batch takes; 0 and -1 in the rows at or beyond a
     sample's count.  `out_objs` (int64 (B,O) or (B,O,1)), `out_boxes`: caller-owned buffers, for a captured graph.
     No autograd."""
-    for name, t, dt, shape in (("rows", rows, torch.int32, (None, None, 5)), ("sizes", sizes, torch.int64, (None, 2)),
-                               ("counts", counts, torch.int64, (None,))):
-        if not t.is_cuda:
-            raise RuntimeError("vg_rows: %s must be a HIP (cuda) tensor; got a %s tensor — there is no CPU path" % (
-                name, t.device))
-        if t.dtype != dt or t.dim() != len(shape) or not t.is_contiguous() or any(
-                w is not None and w != g for w, g in zip(shape, t.shape)):
-            raise RuntimeError("vg_rows: %s must be contiguous %s of %d dimensions %s; got %s %s" % (
-                name, dt, len(shape), shape, t.dtype, tuple(t.shape)))
+    _device_operands("vg_rows", (("rows", rows, torch.int32, (None, None, 5)), ("sizes", sizes, torch.int64, (None, 2)),
+                                 ("counts", counts, torch.int64, (None,))))
     B, O = rows.shape[:2]
     if sizes.shape[0] != B or counts.shape[0] != B:
         raise RuntimeError("vg_rows: sizes %s and counts %s do not fit rows %s" % (
             tuple(sizes.shape), tuple(counts.shape), tuple(rows.shape)))
-    rows_host = (rows.cpu() if rows_host is None else rows_host).to(torch.int32).contiguous()
-    sizes_host = (sizes.cpu() if sizes_host is None else sizes_host).to(torch.int64).contiguous()
-    counts_host = (counts.cpu() if counts_host is None else counts_host).to(torch.int64).contiguous()
-    if rows_host.is_cuda or sizes_host.is_cuda or counts_host.is_cuda or rows_host.shape != rows.shape or \
-            sizes_host.shape != sizes.shape or counts_host.shape != counts.shape:
-        raise RuntimeError("vg_rows: rows_host / sizes_host / counts_host must be the CPU copies of rows / sizes / counts")
+    rows_host, sizes_host, counts_host = _host_copies("vg_rows", (("rows", rows, rows_host), ("sizes", sizes, sizes_host),
+                                                                  ("counts", counts, counts_host)))
     if out_objs is None:
         out_objs = torch.empty((B, O, 1), device=rows.device, dtype=torch.int64)
     if out_boxes is None:

@@ -55,8 +55,8 @@ def parse_args(argv=None):
 def validation_batches(args, trainer, dev, world=1, val_set=None):
     """Generator of the validation batches on `dev`, ceil(num_val_samples / batch_size) of them: the first pictures of
     `val_set` (a folder dataset, `folder_val_set`) in file order, or the seeded synthetic batches (see Seeds above)."""
-    from ..synth import BatchConfig, make_batch
-    from .train import packed_batch
+    from ..synth import make_batch
+    from .train import packed_batch, synth_config
     if val_set is not None:              # the first num_val_samples pictures in file order; every rank sees the same batches
         from ..sg2im.data.loader import epoch_batches
         import random
@@ -75,10 +75,7 @@ def validation_batches(args, trainer, dev, world=1, val_set=None):
     if (args.num_iterations + 1) * max(world, 1) >= VAL_SEED_BASE:
         raise SystemExit("--num_iterations * ranks must stay below 2**40: the seeds above are the validation set's")
     packed = args.dataset.startswith("packed")
-    lo = args.min_objects or (16 if packed else 3)
-    hi = args.max_objects or (40 if packed else 8)
-    graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
-    cfg = BatchConfig(args.batch_size, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
+    cfg = synth_config(args, args.batch_size)
     for i in range(-(-args.num_val_samples // args.batch_size)):
         batch = make_batch(args.vocab, cfg, seed=VAL_SEED_BASE + i)
         yield packed_batch(args, trainer, batch, dev) if packed else [None if x is None else x.to(dev) for x in batch]

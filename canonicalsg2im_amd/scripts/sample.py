@@ -99,9 +99,9 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
     from ..sample import Sampler
-    from ..synth import BatchConfig, make_batch, make_vocab
+    from ..synth import make_batch, make_vocab
     from .args import init_args
-    from .train import _vocab_kind, packed_batch
+    from .train import _vocab_kind, packed_batch, synth_config
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if args.scene_graphs is not None:
@@ -111,10 +111,7 @@ def main(argv=None):
     torch.manual_seed(0)
     sampler = Sampler(args, dev, None if args.checkpoint_name == _NO_CHECKPOINT else args.checkpoint_name)
     packed = args.dataset.startswith("packed")
-    lo = args.min_objects or (16 if packed else 3)
-    hi = args.max_objects or (40 if packed else 8)
-    graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
-    cfg = BatchConfig(args.batch_size, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
+    cfg = synth_config(args, args.batch_size)
     Image = None
     if args.output_dir:
         from PIL import Image                      # only here: importing the package never needs PIL

@@ -53,28 +53,25 @@ def packed_batch(args, trainer, batch, dev):
 def folder_dataset(args, split):
     """The dataset of `split` when --dataset names a folder dataset whose image directory exists, None otherwise: the batches
     are then synthetic."""
-    if args.dataset == "packed_coco":
-        from ..sg2im.data.packed_coco import build_coco_dataset
-        return build_coco_dataset(args, split)
-    if args.dataset == "packed_clevr":
-        from ..sg2im.data.packed_clevr import build_clevr_dataset
-        return build_clevr_dataset(args, split)
-    if args.dataset == "packed_vg":
-        from ..sg2im.data.packed_vg import build_vg_dataset
-        return build_vg_dataset(args, split)
-    return None
+    from ..sg2im.data import build_folder_dataset
+    return build_folder_dataset(args, split)
 
 
 def folder_builder(dataset, args, trainer, dev, rng=None):
     """The batch builder of a folder dataset, with --loader_num_workers threads.  `rng`: where a Visual Genome builder draws
     its object sampling (by default its own random.Random, seeded from the rank); the other datasets draw nothing."""
-    from ..sg2im.data.packed_clevr import ClevrBatchBuilder, PackedClevrDataset
-    from ..sg2im.data.packed_coco import CocoBatchBuilder
-    from ..sg2im.data.packed_vg import PackedVGDataset, VGBatchBuilder
-    if isinstance(dataset, PackedVGDataset):
-        return VGBatchBuilder(dataset, args, trainer, dev, num_workers=args.loader_num_workers, rng=rng)
-    cls = ClevrBatchBuilder if isinstance(dataset, PackedClevrDataset) else CocoBatchBuilder
-    return cls(dataset, args, trainer, dev, num_workers=args.loader_num_workers)
+    cls = dataset.builder_class
+    return cls(dataset, args, trainer, dev, num_workers=args.loader_num_workers, **({"rng": rng} if cls.takes_rng else {}))
+
+
+def synth_config(args, batch_size):
+    """The synth.BatchConfig of the seeded synthetic batches of --dataset's shape."""
+    from ..synth import BatchConfig
+    packed = args.dataset.startswith("packed")
+    lo = args.min_objects or (16 if packed else 3)
+    hi = args.max_objects or (40 if packed else 8)
+    graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
+    return BatchConfig(batch_size, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
 
 
 def build_parser():
@@ -95,7 +92,7 @@ def argparse_copy(args, **changes):
 
 def main(argv=None):
     from .. import dist as csg_dist, train as T
-    from ..synth import BatchConfig, make_batch, make_vocab
+    from ..synth import make_batch, make_vocab
     from .args import init_args
     args = build_parser().parse_args(argv)
     if args.val_every < 0:
@@ -122,10 +119,7 @@ def main(argv=None):
                                       "of a checkpoint, e.g. <output_dir>/itr_<t>.pt)" % args.checkpoint_name)
         t0, epoch = trainer.load_checkpoint(args.checkpoint_name)
     packed = args.dataset.startswith("packed")
-    lo = args.min_objects or (16 if packed else 3)
-    hi = args.max_objects or (40 if packed else 8)
-    graph = ("annotated" if args.dataset == "packed_vg" else "packed") if packed else "random"
-    cfg = BatchConfig(per_rank, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
+    cfg = synth_config(args, per_rank)
     evaluator = None
     if args.val_every > 0:
         from ..evaluate import Evaluator

@@ -24,8 +24,7 @@ import numpy as np
 import torch
 
 from . import register_augmented_relations
-from .collate import packed_batch
-from .loader import BatchBuilder, _Pending
+from .loader import BatchBuilder
 
 CLEVR_MEAN = CLEVR_STD = 0.5                               # encode_image(), sg2im/data/utils.py:13-14
 ATTRIBUTES = {                                             # packed_clevr_dialog.py:121-125, in this order
@@ -113,79 +112,33 @@ class PackedClevrDataset:
 
 
 class ClevrBatchBuilder(BatchBuilder):
-    """Batches of a PackedClevrDataset as the 8-tuple Trainer.step takes (loader.BatchBuilder has the staging, the
-    look-ahead and the rule that the workers make no HIP call).
+    """Batches of a PackedClevrDataset (loader.BatchBuilder has the two halves of a batch): RGBA renders go up as 4-byte
+    pixels; the fields of its own are the object counts, the attribute rows (int64) and the scene numbers (fp64: geometry,
+    rotation), from which ops.clevr_boxes makes the boxes; Normalize(0.5, 0.5)."""
 
-    start(indices): the worker threads decode into a pinned buffer — a picture whose decoded mode is RGBA as 4-byte pixels,
-    one whose mode is RGB as 3-byte pixels, any other mode converted to RGB on the host first; every picture starts on a
-    4-byte boundary, so the device reads 4-byte pixels as dwords.  The descriptor, the image ids, the object counts, the
-    attribute rows (int64) and the scene numbers (fp64: geometry, rotation) are laid out in a second one.  finish(pending):
-    ONE copy of each, ops.clevr_boxes, ops.preprocess_images with Normalize(0.5, 0.5), collate.packed_batch."""
+    keep_rgba = True
+    mean, std = CLEVR_MEAN, CLEVR_STD
 
-    @staticmethod
-    def _decode(im, dst, mode):
-        try:
-            dst[:] = np.asarray(im if im.mode == mode else im.convert(mode)).reshape(-1)
-        finally:
-            im.close()
-
-    def start(self, indices):
-        """The host half.  Called by the consumer's thread between two steps: the one HIP call it can make, the pinned
-        allocation when a staging buffer has to grow, is made here and not by a worker."""
-        B = len(indices)
-        slot = self._take_slot()
-        opened = list(self.pool.map(self.ds.open, indices))              # headers: sizes and modes
-        modes = ["RGBA" if im.mode == "RGBA" else "RGB" for im in opened]
-        desc = np.zeros((B, 4), np.int64)
-        end = 0
-        for b, (im, mode) in enumerate(zip(opened, modes)):
-            desc[b] = (-(-end // 4) * 4, im.size[1], im.size[0], len(mode))
-            end = int(desc[b, 0] + desc[b, 1] * desc[b, 2] * desc[b, 3])
+    def rows(self, indices, sizes, drawn):
         ann = [self.ds.annotations(i) for i in indices]
         O = max(a[0].shape[0] for a in ann)
         if O < 1:
             raise ValueError("a batch of scenes without objects")
-        stage = self.pixels[slot].take(end)[:end]
-        host = stage.numpy()                                              # the workers write through numpy: no torch call
-        futures = [self.pool.submit(self._decode, im, host[desc[b, 0]:desc[b, 0] + desc[b, 1] * desc[b, 2] * desc[b, 3]], mode)
-                   for b, (im, mode) in enumerate(zip(opened, modes))]
-        # descriptor | image ids | counts | attribute rows (int64), then geometry | rotation (fp64): one buffer, one copy
-        n64 = 4 * B + B + B + 4 * B * O
-        nf64 = 5 * B * O + 2 * B
-        meta = self.meta[slot].take(8 * (n64 + nf64))[:8 * (n64 + nf64)]
-        i64 = meta[:8 * n64].view(torch.int64)
-        f64 = meta[8 * n64:].view(torch.float64)
-        i64[:4 * B] = torch.from_numpy(desc.reshape(-1))
-        i64[4 * B:5 * B] = torch.as_tensor([self.ds.image_ids[i] for i in indices], dtype=torch.int64)
-        counts_host = i64[5 * B:6 * B]
-        objs_host = i64[6 * B:].view(B, O, 4)
-        geom_host = f64[:5 * B * O].view(B, O, 5)
-        rot_host = f64[5 * B * O:].view(B, 2)
-        objs_host.zero_()
-        geom_host.zero_()
-        for b, (o, g, r) in enumerate(ann):
-            counts_host[b] = o.shape[0]
-            objs_host[b, :o.shape[0]] = torch.from_numpy(o)
-            geom_host[b, :g.shape[0]] = torch.from_numpy(g)
-            rot_host[b] = torch.from_numpy(r)
-        return _Pending(futures=futures, slot=slot, stage=stage, meta=meta, desc=torch.from_numpy(desc),
-                        objs=objs_host.clone(), counts=counts_host.clone(), B=B, O=O, n64=n64)
+        objs = np.zeros((len(ann), O, 4), np.int64)
+        geom = np.zeros((len(ann), O, 5), np.float64)
+        for b, (o, g, _) in enumerate(ann):
+            objs[b, :o.shape[0]] = o
+            geom[b, :g.shape[0]] = g
+        return {"counts": np.asarray([a[0].shape[0] for a in ann], np.int64), "objs": objs, "geom": geom,
+                "rot": np.stack([a[2] for a in ann])}, {}
 
-    def finish(self, p):
-        """The device half, enqueued on the current stream."""
+    def assemble(self, dev, p):
         from ... import ops
-        B, O, n64 = p.B, p.O, p.n64
-        src, meta_dev = self._upload(p)
-        i64_dev = meta_dev[:8 * n64].view(torch.int64)
-        f64_dev = meta_dev[8 * n64:].view(torch.float64)
-        objs = i64_dev[6 * B:].view(B, O, 4)
-        boxes = ops.clevr_boxes(f64_dev[:5 * B * O].view(B, O, 5), objs, f64_dev[5 * B * O:].view(B, 2), i64_dev[5 * B:6 * B],
-                                objs_host=p.objs, counts_host=p.counts)
-        H, W = self.ds.image_size
-        imgs = ops.preprocess_images(src, i64_dev[:4 * B].view(B, 4), H, W, normalize=self.ds.normalize_images,
-                                     desc_host=p.desc, mean=CLEVR_MEAN, std=CLEVR_STD)
-        raw = [imgs, objs, boxes, None, None, None, None, i64_dev[4 * B:5 * B]]
-        return packed_batch(self.args, self.trainer, raw, self.dev)
+        boxes = ops.clevr_boxes(dev["geom"], dev["objs"], dev["rot"], dev["counts"], objs_host=p.objs, counts_host=p.counts)
+        return dev["objs"], boxes, None, None
+
+
+PackedClevrDataset.builder_class = ClevrBatchBuilder
 
 
 def build_clevr_dataset(args, split):

@@ -22,8 +22,7 @@ import numpy as np
 import torch
 
 from . import register_augmented_relations
-from .collate import packed_batch
-from .loader import MAX_LOADER_THREADS, BatchBuilder, _Pending, _Staging, epoch_batches  # noqa: F401  (their first home)
+from .loader import BatchBuilder
 
 _NO_MASKS = ("PackedCocoSceneGraphDataset: mask_size must be 0 (got %d): segmentation masks need pycocotools, which is not "
              "a dependency; object centres are box centres, not mask centroids as in the reference")
@@ -118,62 +117,24 @@ class PackedCocoSceneGraphDataset:
 
 
 class CocoBatchBuilder(BatchBuilder):
-    """Batches of a PackedCocoSceneGraphDataset as the 8-tuple Trainer.step takes (loader.BatchBuilder has the staging, the
-    look-ahead and the rule that the workers make no HIP call).
+    """Batches of a PackedCocoSceneGraphDataset (loader.BatchBuilder has the two halves of a batch): every picture goes up as
+    RGB; the fields of its own are the category ids and the boxes over the decoded sizes, and no kernel of its own runs."""
 
-    start(indices): `num_workers` threads open the files and decode them into a pinned buffer; descriptor, image ids,
-    objects and boxes are laid out in a second one.  finish(pending), on the current stream: ONE copy of the packed bytes
-    and ONE of the second buffer to the device, ops.preprocess_images, collate.packed_batch."""
-
-    @staticmethod
-    def _decode(im, dst):
-        try:
-            dst[:] = np.asarray(im.convert("RGB")).reshape(-1)
-        finally:
-            im.close()
-
-    def start(self, indices):
-        """The host half.  Called by the consumer's thread between two steps: the one HIP call it can make, the pinned
-        allocation when a staging buffer has to grow, is made here and not by a worker."""
-        B = len(indices)
-        slot = self._take_slot()
-        opened = list(self.pool.map(self.ds.open, indices))              # headers: the sizes
-        sizes = [(im.size[1], im.size[0]) for im in opened]              # (h, w)
-        ann = [self.ds.annotations(i, w, h) for i, (h, w) in zip(indices, sizes)]
+    def rows(self, indices, sizes, drawn):
+        ann = [self.ds.annotations(i, w, h) for i, (h, w) in zip(indices, sizes.tolist())]
         O = max(a[0].shape[0] for a in ann)
-        offsets = np.concatenate([[0], np.cumsum([3 * h * w for h, w in sizes])]).astype(np.int64)
-        stage = self.pixels[slot].take(int(offsets[-1]))[:int(offsets[-1])]
-        host = stage.numpy()                                              # the workers write through numpy: no torch call
-        futures = [self.pool.submit(self._decode, im, host[offsets[i]:offsets[i + 1]]) for i, im in enumerate(opened)]
-        # descriptor | image ids | objects (int64), then boxes (fp32): one buffer, one copy
-        n64 = 3 * B + B + B * O
-        meta = self.meta[slot].take(8 * n64 + 16 * B * O)[:8 * n64 + 16 * B * O]
-        i64 = meta[:8 * n64].view(torch.int64)
-        f32 = meta[8 * n64:].view(torch.float32).view(B, O, 4)
-        desc_host = i64[:3 * B].view(B, 3)
-        desc_host[:, 0] = torch.from_numpy(offsets[:-1])
-        desc_host[:, 1:] = torch.as_tensor(sizes, dtype=torch.int64)
-        i64[3 * B:4 * B] = torch.as_tensor([self.ds.image_ids[i] for i in indices], dtype=torch.int64)
-        objs_host = i64[4 * B:].view(B, O)
-        objs_host.zero_()
-        f32.fill_(-1.0)
+        objs = np.zeros((len(ann), O, 1), np.int64)
+        boxes = np.full((len(ann), O, 4), -1.0, np.float32)
         for b, (o, bx) in enumerate(ann):
-            objs_host[b, :o.shape[0]] = torch.from_numpy(o)
-            f32[b, :bx.shape[0]] = torch.from_numpy(bx)
-        return _Pending(futures=futures, slot=slot, stage=stage, meta=meta, desc=desc_host.clone(), B=B, O=O, n64=n64)
+            objs[b, :o.shape[0], 0] = o
+            boxes[b, :bx.shape[0]] = bx
+        return {"objs": objs, "boxes": boxes}, {}
 
-    def finish(self, p):
-        """The device half, enqueued on the current stream."""
-        from ... import ops
-        B, O, n64 = p.B, p.O, p.n64
-        src, meta_dev = self._upload(p)
-        i64_dev = meta_dev[:8 * n64].view(torch.int64)
-        H, W = self.ds.image_size
-        imgs = ops.preprocess_images(src, i64_dev[:3 * B].view(B, 3), H, W, normalize=self.ds.normalize_images,
-                                     desc_host=p.desc)
-        raw = [imgs, i64_dev[4 * B:].view(B, O, 1), meta_dev[8 * n64:].view(torch.float32).view(B, O, 4), None, None, None,
-               None, i64_dev[3 * B:4 * B]]
-        return packed_batch(self.args, self.trainer, raw, self.dev)
+    def assemble(self, dev, p):
+        return dev["objs"], dev["boxes"], None, None
+
+
+PackedCocoSceneGraphDataset.builder_class = CocoBatchBuilder
 
 
 def build_coco_dataset(args, split):

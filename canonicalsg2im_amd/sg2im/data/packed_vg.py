@@ -33,8 +33,7 @@ import numpy as np
 import torch
 
 from . import register_augmented_relations
-from .collate import packed_batch
-from .loader import BatchBuilder, _Pending
+from .loader import BatchBuilder
 
 VG_MEAN = VG_STD = 0.5                                     # encode_image(), sg2im/data/utils.py:13-14
 VG_MAX_OBJECTS, VG_MIN_OBJECTS = 100, 16                   # sg2im/data/dataset_params.py:42-44
@@ -166,19 +165,19 @@ class PackedVGDataset:
 
 
 class VGBatchBuilder(BatchBuilder):
-    """Batches of a PackedVGDataset as the 8-tuple Trainer.step takes (loader.BatchBuilder has the staging, the look-ahead
-    and the rule that the workers make no HIP call).
-
-    start(indices), on the consumer's thread: `select` for every sample in batch order (the order decides what the random
-    stream gives whom, so the workers do not do it); the pictures are opened for sizes and modes and decoded by the worker
-    threads into a pinned buffer — RGB as 3-byte pixels, RGBA as 4-byte pixels, any other mode (L, CMYK, P: Visual Genome
-    has some of each) converted to RGB on the host first; every picture starts on a 4-byte boundary.  The descriptor, the
-    image ids, the counts, the decoded sizes (HH, WW) (int64) and the gathered rows (B,O,5) int32 = name, x, y, w, h (-1 in
-    padding rows) are laid out in a second one.  finish(pending): ONE copy of each, ops.vg_rows, ops.preprocess_images with
-    Normalize(0.5, 0.5), collate.packed_batch with the annotated rows and the counts as host tensors.
+    """Batches of a PackedVGDataset (loader.BatchBuilder has the two halves of a batch): RGBA pictures go up as 4-byte pixels,
+    any mode but RGB and RGBA (L, CMYK, P: Visual Genome has some of each) is converted to RGB on the host first.  Before
+    anything else start() calls `select` for every sample in batch order on the consumer's thread (the order decides what
+    the random stream gives whom, so the workers do not do it).  The fields of its own are the counts, the decoded sizes
+    (HH, WW) (int64) and the gathered rows (B,O,5) int32 = name, x, y, w, h (-1 in padding rows), from which ops.vg_rows
+    makes objects and boxes; the annotated rows and the counts reach collate.packed_batch as host tensors;
+    Normalize(0.5, 0.5).
 
     `rng`: where `select` draws; by default a random.Random of the builder's own, seeded from (0, rank).  A resumed run
     starts it afresh: its epoch order is the interrupted run's, its object sampling is not."""
+
+    keep_rgba = takes_rng = True
+    mean, std = VG_MEAN, VG_STD
 
     def __init__(self, dataset, args, trainer, device, num_workers=1, rng=None):
         super().__init__(dataset, args, trainer, device, num_workers=num_workers)
@@ -187,74 +186,34 @@ class VGBatchBuilder(BatchBuilder):
             rng = random.Random((0 << 32) | dist.rank())
         self.rng = rng
 
-    @staticmethod
-    def _decode(im, dst, mode):
-        try:
-            dst[:] = np.asarray(im if im.mode == mode else im.convert(mode)).reshape(-1)
-        finally:
-            im.close()
-
-    def start(self, indices):
-        """The host half.  Called by the consumer's thread between two steps: the one HIP call it can make, the pinned
-        allocation when a staging buffer has to grow, is made here and not by a worker."""
-        B = len(indices)
-        ds = self.ds
-        picked = [ds.select(i, self.rng) for i in indices]                 # in batch order: the stream's order
-        O = max(len(chosen) for chosen, _ in picked)
-        if O < 1:
+    def draw(self, indices):
+        picked = [self.ds.select(i, self.rng) for i in indices]            # in batch order: the stream's order
+        if max(len(chosen) for chosen, _ in picked) < 1:
             raise ValueError("a batch of samples without objects")
-        R = max(len(rel) for _, rel in picked)
-        slot = self._take_slot()
-        opened = list(self.pool.map(ds.open, indices))                     # headers: sizes and modes
-        modes = ["RGBA" if im.mode == "RGBA" else "RGB" for im in opened]
-        desc = np.zeros((B, 4), np.int64)
-        end = 0
-        for b, (im, mode) in enumerate(zip(opened, modes)):
-            desc[b] = (-(-end // 4) * 4, im.size[1], im.size[0], len(mode))
-            end = int(desc[b, 0] + desc[b, 1] * desc[b, 2] * desc[b, 3])
-        stage = self.pixels[slot].take(end)[:end]
-        host = stage.numpy()                                               # the workers write through numpy: no torch call
-        futures = [self.pool.submit(self._decode, im, host[desc[b, 0]:desc[b, 0] + desc[b, 1] * desc[b, 2] * desc[b, 3]], mode)
-                   for b, (im, mode) in enumerate(zip(opened, modes))]
-        # descriptor | image ids | counts | sizes (int64), then the rows (int32): one buffer, one copy
-        n64 = 4 * B + B + B + 2 * B
-        nbytes = 8 * n64 + 4 * 5 * B * O
-        meta = self.meta[slot].take(nbytes)[:nbytes]
-        i64 = meta[:8 * n64].view(torch.int64)
-        rows_host = meta[8 * n64:].view(torch.int32).view(B, O, 5)
-        i64[:4 * B] = torch.from_numpy(desc.reshape(-1))
-        i64[4 * B:5 * B] = torch.as_tensor([ds.image_ids[i] for i in indices], dtype=torch.int64)
-        counts_host = i64[5 * B:6 * B]
-        sizes_host = i64[6 * B:8 * B].view(B, 2)
-        sizes_host.copy_(torch.from_numpy(desc[:, 1:3]))                   # (HH, WW) of the decoded pictures
-        rows_np = np.full((B, O, 5), -1, np.int32)
+        return picked
+
+    def rows(self, indices, sizes, picked):
+        ds = self.ds
+        B, O, R = len(picked), max(len(chosen) for chosen, _ in picked), max(len(rel) for _, rel in picked)
+        rows = np.full((B, O, 5), -1, np.int32)
         rel = torch.zeros((B, R, 3), dtype=torch.int64)
         rel[:, :, 1] = ds.vocab["pred_name_to_idx"]["__padding__"]
-        for b, (i, (chosen, rows)) in enumerate(zip(indices, picked)):
-            n = len(chosen)
-            counts_host[b] = n
-            rows_np[b, :n, 0] = ds.data["object_names"][i, chosen]
-            rows_np[b, :n, 1:] = ds.data["object_boxes"][i, chosen]
-            if rows:
-                rel[b, :len(rows)] = torch.as_tensor(rows, dtype=torch.int64)
-        rows_host.copy_(torch.from_numpy(rows_np))
-        return _Pending(futures=futures, slot=slot, stage=stage, meta=meta, desc=torch.from_numpy(desc), rows=rows_host.clone(),
-                        sizes=sizes_host.clone(), counts=counts_host.clone(), rel=rel, B=B, O=O, n64=n64)
+        for b, (i, (chosen, annotated)) in enumerate(zip(indices, picked)):
+            rows[b, :len(chosen), 0] = ds.data["object_names"][i, chosen]
+            rows[b, :len(chosen), 1:] = ds.data["object_boxes"][i, chosen]
+            if annotated:
+                rel[b, :len(annotated)] = torch.as_tensor(annotated, dtype=torch.int64)
+        return {"counts": np.asarray([len(chosen) for chosen, _ in picked], np.int64), "sizes": sizes, "rows": rows}, \
+            {"rel": rel}
 
-    def finish(self, p):
-        """The device half, enqueued on the current stream."""
+    def assemble(self, dev, p):
         from ... import ops
-        B, O, n64 = p.B, p.O, p.n64
-        src, meta_dev = self._upload(p)
-        i64_dev = meta_dev[:8 * n64].view(torch.int64)
-        rows_dev = meta_dev[8 * n64:].view(torch.int32).view(B, O, 5)
-        objs, boxes = ops.vg_rows(rows_dev, i64_dev[6 * B:8 * B].view(B, 2), i64_dev[5 * B:6 * B], self.ds.num_objects,
-                                  rows_host=p.rows, sizes_host=p.sizes, counts_host=p.counts)
-        H, W = self.ds.image_size
-        imgs = ops.preprocess_images(src, i64_dev[:4 * B].view(B, 4), H, W, normalize=self.ds.normalize_images,
-                                     desc_host=p.desc, mean=VG_MEAN, std=VG_STD)
-        raw = [imgs, objs, boxes, p.rel, None, None, None, i64_dev[4 * B:5 * B]]
-        return packed_batch(self.args, self.trainer, raw, self.dev, counts=p.counts)
+        objs, boxes = ops.vg_rows(dev["rows"], dev["sizes"], dev["counts"], self.ds.num_objects, rows_host=p.rows,
+                                  sizes_host=p.sizes, counts_host=p.counts)
+        return objs, boxes, p.rel, p.counts
+
+
+PackedVGDataset.builder_class = VGBatchBuilder
 
 
 def build_vg_dataset(args, split):

@@ -320,6 +320,9 @@ def test_dataset_on_a_tiny_folder(cuda, tmp_path):
     t2, c2, tt2 = canonical_triplets(bobjs, bboxes, centers, torch.as_tensor(counts + 1).to(cuda), v)
     assert torch.equal(triplets, t2) and torch.equal(conv_counts, c2) and torch.equal(ttype, tt2)
     assert triplets.shape[1] > O                           # the __in_image__ rows and location relations
+    again = builder.build(order)                           # start + finish is build, tensor for tensor
+    torch.cuda.synchronize()
+    assert len(again) == len(batch) and all((a is None and b is None) or torch.equal(a, b) for a, b in zip(again, batch))
     # ---- five steps through the look-ahead iterator: graphs are captured and replayed while the workers decode
     assert trainer.graphs is not None and trainer.graphs.captures == 0
     for step, got in enumerate(builder.batches([order, order[::-1], order, order[::-1], order])):

@@ -302,7 +302,11 @@ def test_dataset_on_a_tiny_folder(cuda, tmp_path):
     trainer = T.Trainer(opt, cuda)
     builder = CocoBatchBuilder(ds, opt, trainer, cuda, num_workers=2)
     order = [3, 0, 2, 1]
-    batch = builder.build(order)
+    pending = builder.start(order)
+    assert pending.desc.shape == (4, 3)                   # the three-column entry, every picture as RGB, back to back
+    assert pending.desc.tolist() == [[sum(3 * h * w for h, w in (pixels[ds.image_ids[j]].shape[:2] for j in order[:b]))] +
+                                     list(pixels[ds.image_ids[i]].shape[:2]) for b, i in enumerate(order)]
+    batch = builder.finish(pending)
     torch.cuda.synchronize()
     imgs, bobjs, bboxes, triplets, conv_counts, ttype, masks, ids = batch
     assert masks is None and ids.tolist() == [105, 101, 103, 102]
@@ -345,7 +349,7 @@ def test_dataset_on_a_tiny_folder(cuda, tmp_path):
 
 
 def test_epoch_order_is_seeded_and_ranks_take_disjoint_slices():
-    from canonicalsg2im_amd.sg2im.data.packed_coco import epoch_batches
+    from canonicalsg2im_amd.sg2im.data.loader import epoch_batches
     n, per_rank, world = 37, 3, 2
     a = [epoch_batches(n, per_rank, r, world, seed=5, epoch=2) for r in range(world)]
     b = [epoch_batches(n, per_rank, r, world, seed=5, epoch=2) for r in range(world)]
