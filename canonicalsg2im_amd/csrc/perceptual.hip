@@ -184,7 +184,7 @@ struct HingeItems {
 __device__ __forceinline__ float hinge_term(float x, int kind) {
   if (kind == 0) return x;
   const float m = kind == 1 ? x - 1.0f : -x - 1.0f;
-  return m < 0.f ? m : 0.f;
+  return (m < 0.f || m != m) ? m : 0.f;      // a NaN prediction gives a NaN loss, as torch.min(x - 1, 0) does
 }
 __global__ __launch_bounds__(1024) void k_hinge_mean(HingeItems it, int kind, float* __restrict__ out) {
   __shared__ double red[1024];

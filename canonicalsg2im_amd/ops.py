@@ -904,6 +904,8 @@ class _SpectralWeight(torch.autograd.Function):
         K = w.numel() // Cout
         Cin, KH, KW = (w.shape[1], w.shape[2], w.shape[3]) if w.dim() == 4 else (K, 1, 1)
         dweff = _f32(dweff)
+        if dweff.dim() != 4:                            # (a 2-D gradient may arrive transposed: the kernel reads it row-major)
+            dweff = dweff.contiguous()
         st = dweff.stride() if dweff.dim() == 4 else (K, 1, 1, 1)
         if not _rows_dense(st, (Cin, KH, KW), K):       # e.g. a slice of a channel-padded gradient
             dweff = dweff.contiguous()
@@ -953,6 +955,7 @@ class _SpectralWeightMulti(torch.autograd.Function):
             keep.append(wsb)
         check(lib.csg_spectral_norm_fwd_multi(items, n, 1 if iterate else 0, eps, stream()), "spectral_norm_fwd_multi")
         ctx.n = n
+        ctx.set_materialize_grads(False)          # an output left out of the backward arrives as None, not as zeros to push through
         ctx.save_for_backward(*ws, *smalls)
         return tuple(outs)
 
@@ -972,6 +975,8 @@ class _SpectralWeightMulti(torch.autograd.Function):
             K = w.numel() // Cout
             Cin, KH, KW = (w.shape[1], w.shape[2], w.shape[3]) if w.dim() == 4 else (K, 1, 1)
             dweff = _f32(dweffs[i])
+            if dweff.dim() != 4:
+                dweff = dweff.contiguous()
             st = dweff.stride() if dweff.dim() == 4 else (K, 1, 1, 1)
             if not _rows_dense(st, (Cin, KH, KW), K):
                 dweff = dweff.contiguous()
