@@ -215,6 +215,10 @@ SIGNATURES = {
     "csg_canon_general_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "csg_canon_general_build": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, ctypes.POINTER(c_i32), c_i64,
                                         c_i64, c_i32, c_p, c_i64, c_p, c_p]),
+    "csg_canon_general_build_dev": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, ctypes.POINTER(c_i32), c_i64,
+                                            c_i64, c_i32, c_p, c_i64, c_p, c_p]),
+    "csg_pair_relations": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, ctypes.POINTER(c_i32), c_i32, c_p,
+                                   c_p]),
     "csg_canon_general_converse": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "csg_canon_general_close": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_i32, c_p, c_i64, c_p, c_p]),
     "csg_canon_general_emit": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),

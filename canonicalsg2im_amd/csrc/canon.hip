@@ -15,6 +15,12 @@
 // Integer/bit work end to end: results are bit-identical to the reference's.  Emission order is
 // the one np.unique(axis=0) produces — (s, p, o) lexicographic — followed by the transitive extras
 // in (ascending predicate id, s, o) order.
+//
+// Further down: the same pipeline per (sample, predicate) for annotated rows and any vocabulary (csg_canon_general_*), and
+// for the unpacked COCO dataset's sampled pairs (sg2im/data/coco.py:365-428) k_pair_relations, which gives each drawn pair
+// its predicate, and k_gen_pack, which takes such device rows into that pipeline (csg_canon_general_build_dev).
+// This file is NOT compiled with -ffp-contract=off; k_pair_relations, the one kernel here that adds to a product, turns
+// contraction off for itself.
 #include "csg_common.h"
 
 #include <vector>
@@ -486,6 +492,7 @@ struct GenWs {
   int* flag;                     // [B][P] converse edges were drawn into the predicate
   int* doff;                     // [B][P] first draw of the predicate's rows within the sample
   int64_t* geo_counts;           // [B][2] k_canon_build's counts (unused)
+  int* bad;                      // [B] a row given on the device was dropped (csg_canon_general_build_dev); else 0
   int64_t* nob;                  // [B] objects per sample
   int* rbeg;                     // [B + 1] first annotated row of a sample
   uint32_t* rows;                // annotated rows: s | o << 8 | p << 16
@@ -516,6 +523,8 @@ inline int64_t gen_layout(int64_t B, int64_t P, int64_t R, void* base, GenWs* w)
   at += gen_align(B * P * 4);
   if (w) w->geo_counts = (int64_t*)(b + at);
   at += gen_align(B * 2 * 8);
+  if (w) w->bad = (int*)(b + at);
+  at += gen_align(B * 4);
   if (w) w->nob = (int64_t*)(b + at);
   at += gen_align(B * 8);
   if (w) w->rbeg = (int*)(b + at);
@@ -599,7 +608,7 @@ __global__ __launch_bounds__(256) void k_gen_draws(GenParams P, GenWs w, int64_t
   const int ex = block_exscan(c, scan, &total);
   if (tid < P.P) w.doff[(int64_t)b * P.P + tid] = ex;
   if (tid == 0) {
-    counts[b * 2 + 0] = total;
+    counts[b * 2 + 0] = w.bad[b] ? -1 - (int64_t)total : total;      // negative: a device row was refused
     counts[b * 2 + 1] = 0;
   }
 }
@@ -747,7 +756,7 @@ __global__ __launch_bounds__(256) void k_gen_offsets(GenParams P, GenWs w, int64
     run += t;
   }
   if (tid == 0) {
-    counts[b * 2 + 0] = n_orig;
+    counts[b * 2 + 0] = w.bad[b] ? -1 - (int64_t)n_orig : n_orig;    // negative: a device row was refused
     counts[b * 2 + 1] = run - n_orig;
   }
 }
@@ -790,6 +799,92 @@ __global__ __launch_bounds__(256) void k_gen_emit(GenParams P, GenWs w, const in
   const int64_t used = counts[b * 2 + 0] + counts[b * 2 + 1];
   for (int64_t t = used + (int64_t)p * 256 + tid; t < T; t += (int64_t)P.P * 256)    // vg_collate_fn: packed_vg.py:207-212
     put(trip, tt, t, 0, P.pid_padding, 0, 0);
+}
+
+// ---- pack: annotated rows that are already on the device -> the workspace's 4-byte form (csg_canon_general_build_dev).
+// One thread per (sample, row); rbeg came from the host's counts.  The host cannot check these rows, so nothing is indexed
+// with one: a row outside [0, n_b) x [0, P), or carrying __padding__, is stored as a predicate no block owns (0xFFFF) and
+// marks its sample in `bad`; k_gen_draws / k_gen_offsets then report a negative count.  Every thread that stores to bad[b]
+// stores the same 1.
+constexpr uint32_t kDroppedRow = 0xFFFF0000u;
+
+__global__ __launch_bounds__(256) void k_gen_pack(GenParams P, GenWs w, const int64_t* __restrict__ rel, int R) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)P.B * R) return;
+  const int b = (int)(i / R), r = (int)(i - (int64_t)b * R);
+  const int r0 = w.rbeg[b];
+  if (r >= w.rbeg[b + 1] - r0) return;
+  const int n = gen_n(w, P, b);
+  const int64_t s = rel[i * 3 + 0], p = rel[i * 3 + 1], o = rel[i * 3 + 2];
+  const bool ok = s >= 0 && s < n && o >= 0 && o < n && p >= 0 && p < P.P && p != P.pid_padding;
+  w.rows[r0 + r] = ok ? ((uint32_t)s | (uint32_t)o << 8 | (uint32_t)p << 16) : kDroppedRow;
+  if (!ok) w.bad[b] = 1;
+}
+
+// ---- sampled pairs (reference sg2im/data/coco.py:372-421): one predicate per (sample, object) from the pair the host drew.
+// One thread per (sample, object) row `cur`: (s, o) = (cur, other), or (other, cur) when flipped; surrounding / inside by the
+// reference's strict comparisons of x0, y0 and of x0 + w / 2, y0 + h / 2 (the box CENTRE: what the reference compares),
+// otherwise the quadrant of atan2(dy, dx) of d = centers[s] - centers[o].  The reference takes math.atan2 in double of the
+// fp32 differences and compares with multiples of pi / 4; the sector is decided here by exact comparisons of |dx|, |dy| and
+// the signs instead, which agree with those four inequalities for every fp32 pair, ties and signed zeros included
+// (tests/test_pair_cases.py): a device atan2 one ulp from glibc's would flip a predicate on a tie.
+// fp32 in the reference's order, no contraction.  A row at or beyond counts[b], or whose `other` is not another counted
+// row of its sample (the host refused that from its copies; a stale device buffer can still disagree), is the collate's
+// padding [0, __padding__, 0]: nothing is indexed with it.
+struct PairIds {
+  int padding, below, above, left, right, inside, surrounding;
+};
+
+__global__ __launch_bounds__(256) void k_pair_relations(const float4* __restrict__ boxes, const float2* __restrict__ centers,
+                                                        const int64_t* __restrict__ counts, const int32_t* __restrict__ other,
+                                                        const uint8_t* __restrict__ flip, PairIds id, int use_converse, int B,
+                                                        int O, int64_t* __restrict__ rows) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * O) return;
+  const int b = i / O, cur = i - b * O;
+  int64_t n = counts[b];
+  n = n > O ? O : n;
+  const int oth = other[i];
+  int64_t rs = 0, rp = id.padding, ro = 0;
+  if (cur < n && oth >= 0 && oth < n && oth != cur) {
+    int s = cur, o = oth;
+    if (flip[i]) {
+      s = oth;
+      o = cur;
+    }
+    const float4 sb = boxes[(int64_t)b * O + s], ob = boxes[(int64_t)b * O + o];
+    const float2 cs = centers[(int64_t)b * O + s], co = centers[(int64_t)b * O + o];
+    const float sx0 = sb.x, sy0 = sb.y, sx1 = sb.x + sb.z / 2.0f, sy1 = sb.y + sb.w / 2.0f;
+    const float ox0 = ob.x, oy0 = ob.y, ox1 = ob.x + ob.z / 2.0f, oy1 = ob.y + ob.w / 2.0f;
+    const float dx = cs.x - co.x, dy = cs.y - co.y;
+    const float ax = fabsf(dx), ay = fabsf(dy);
+    const bool neg = signbit(dx);
+    int p;
+    bool swap = false;
+    if (sx0 < ox0 && sx1 > ox1 && sy0 < oy0 && sy1 > oy1) {
+      p = id.surrounding;
+    } else if (sx0 > ox0 && sx1 < ox1 && sy0 > oy0 && sy1 < oy1) {
+      p = use_converse ? id.surrounding : id.inside;
+      swap = use_converse;
+    } else if (neg && ay <= ax) {
+      p = id.left;
+    } else if (!neg && (ay < ax || (ay == ax && dy <= 0.0f))) {
+      p = use_converse ? id.left : id.right;
+      swap = use_converse;
+    } else if (dy < 0.0f) {
+      p = id.above;
+    } else {
+      p = use_converse ? id.above : id.below;
+      swap = use_converse;
+    }
+    rs = swap ? o : s;
+    rp = p;
+    ro = swap ? s : o;
+  }
+  rows[(int64_t)i * 3 + 0] = rs;
+  rows[(int64_t)i * 3 + 1] = rp;
+  rows[(int64_t)i * 3 + 2] = ro;
 }
 
 // roles -> GenParams and the eight ids of k_canon_build; 0 if the table is not a vocabulary's
@@ -920,10 +1015,10 @@ int csg_canon_general_build(const int64_t* objs0, const float* boxes, const floa
               "csg_canon_general_build: the role table needs one __padding__, one __in_image__ and each location "
               "relation exactly once");
   // every input is checked here, before anything is enqueued
-  const int64_t head = gen_align(B * 8) + gen_align((B + 1) * 4);
-  std::vector<char> up((size_t)(head + B * R * 4));
-  int64_t* nob = (int64_t*)up.data();
-  int* rbeg = (int*)(up.data() + gen_align(B * 8));
+  const int64_t head = gen_align(B * 4) + gen_align(B * 8) + gen_align((B + 1) * 4);
+  std::vector<char> up((size_t)(head + B * R * 4));          // zeros: `bad` stays 0, every row was checked here
+  int64_t* nob = (int64_t*)(up.data() + gen_align(B * 4));
+  int* rbeg = (int*)(up.data() + gen_align(B * 4) + gen_align(B * 8));
   uint32_t* rows = (uint32_t*)(up.data() + head);
   int nr = 0;
   for (int64_t b = 0; b < B; ++b) {
@@ -952,8 +1047,8 @@ int csg_canon_general_build(const int64_t* objs0, const float* boxes, const floa
   GenWs w;
   gen_layout(B, P, R, workspace, &w);
   hipStream_t st = (hipStream_t)stream;
-  // nob, rbeg and rows are adjacent in the workspace, as in `up`; a pageable source is copied before the call returns
-  CSG_REQUIRE(hipMemcpyAsync(w.nob, up.data(), (size_t)(head + (int64_t)nr * 4), hipMemcpyHostToDevice, st) == hipSuccess,
+  // bad, nob, rbeg and rows are adjacent in the workspace, as in `up`; a pageable source is copied before the call returns
+  CSG_REQUIRE(hipMemcpyAsync(w.bad, up.data(), (size_t)(head + (int64_t)nr * 4), hipMemcpyHostToDevice, st) == hipSuccess,
               CSG_E_LAUNCH, "csg_canon_general_build: upload of the annotated rows failed");
   CanonParams C;
   fill_params(&C, O, ids, image_id, 0, 0);
@@ -1020,6 +1115,105 @@ int csg_canon_general_emit(int64_t B, const int32_t* roles, int64_t P, const voi
   ProfScope pr(K_CANON_EMIT, (double)B * T * 32, st);
   CSG_LAUNCH(k_gen_emit, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, w, counts, T, triplets, triplet_type);
   return check_launch("csg_canon_general_emit");
+}
+
+int csg_canon_general_build_dev(const int64_t* objs0, const float* boxes, const float* centers, const int64_t* n_objs,
+                                int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
+                                const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
+                                int64_t workspace_bytes, int64_t* counts, void* stream) {
+  GEN_CHECK_COMMON("csg_canon_general_build_dev");
+  CSG_REQUIRE(O > 0 && R >= 0 && B * R < (1ll << 31), CSG_E_BADSHAPE, "csg_canon_general_build_dev: bad shape O=%ld R=%ld",
+              (long)O, (long)R);
+  CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "csg_canon_general_build_dev: at most %d objects per sample (got %ld)", MAXN,
+              (long)O);
+  CSG_REQUIRE(objs0 && n_objs && counts && rel_counts && (R == 0 || rel), CSG_E_BADSHAPE,
+              "csg_canon_general_build_dev: null argument");
+  CSG_REQUIRE(boxes == nullptr && centers == nullptr, CSG_E_UNSUPPORTED,
+              "csg_canon_general_build_dev: boxes and centers must be NULL (the given rows are the whole graph)");
+  CSG_REQUIRE(((uintptr_t)rel & 7) == 0, CSG_E_BADSHAPE, "csg_canon_general_build_dev: rel must be 8-byte aligned");
+  CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, R, nullptr, nullptr), CSG_E_BADSHAPE,
+              "csg_canon_general_build_dev: workspace too small (%ld bytes, need %ld)", (long)workspace_bytes,
+              (long)gen_layout(B, P, R, nullptr, nullptr));
+  GenParams G;
+  int32_t ids[8];
+  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, O, image_id, include_dummies, 0), CSG_E_BADSHAPE,
+              "csg_canon_general_build_dev: the role table needs one __padding__, one __in_image__ and each location "
+              "relation exactly once");
+  // what the host has is checked here, before anything is enqueued; the rows themselves by k_gen_pack
+  const int64_t head = gen_align(B * 4) + gen_align(B * 8) + gen_align((B + 1) * 4);
+  std::vector<char> up((size_t)head);                         // zeros: `bad` starts at 0
+  int64_t* nob = (int64_t*)(up.data() + gen_align(B * 4));
+  int* rbeg = (int*)(up.data() + gen_align(B * 4) + gen_align(B * 8));
+  int nr = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t n = n_objs[b];
+    CSG_REQUIRE(n >= 0 && n <= O, CSG_E_BADSHAPE, "csg_canon_general_build_dev: n_objs[%ld] = %ld outside [0, %ld]", (long)b,
+                (long)n, (long)O);
+    const int64_t cnt = rel_counts[b];
+    CSG_REQUIRE(cnt >= 0 && cnt <= R, CSG_E_BADSHAPE, "csg_canon_general_build_dev: rel_counts[%ld] = %ld outside [0, %ld]",
+                (long)b, (long)cnt, (long)R);
+    nob[b] = n;
+    rbeg[b] = nr;
+    nr += (int)cnt;
+  }
+  rbeg[B] = nr;
+  GenWs w;
+  gen_layout(B, P, R, workspace, &w);
+  hipStream_t st = (hipStream_t)stream;
+  CSG_REQUIRE(hipMemcpyAsync(w.bad, up.data(), (size_t)head, hipMemcpyHostToDevice, st) == hipSuccess, CSG_E_LAUNCH,
+              "csg_canon_general_build_dev: upload of the row offsets failed");
+  {
+    ProfScope pr(K_CANON_BUILD, (double)B * P * O * W, st);
+    if (nr > 0) CSG_LAUNCH(k_gen_pack, dim3((unsigned)cdiv(B * R, 256)), dim3(256), 0, st, G, w, rel, (int)R);
+    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, objs0, w, (void*)nullptr);
+    CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, G, w, counts);
+  }
+  return check_launch("csg_canon_general_build_dev");
+}
+
+int csg_pair_relations(const float* boxes, const float* centers, const int64_t* counts, const int32_t* other,
+                       const uint8_t* flip, const int64_t* counts_host, const int32_t* other_host, const uint8_t* flip_host,
+                       int64_t B, int64_t O, const int32_t* pred_ids, int use_converse, int64_t* rows, void* stream) {
+  CSG_REQUIRE(B >= 1 && O >= 1 && B * O < (1ll << 31), CSG_E_BADSHAPE, "csg_pair_relations: bad shape B=%ld O=%ld", (long)B,
+              (long)O);
+  CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "csg_pair_relations: at most %d objects per sample (got %ld)", MAXN, (long)O);
+  CSG_REQUIRE(boxes && centers && counts && other && flip && counts_host && other_host && flip_host && pred_ids && rows,
+              CSG_E_BADSHAPE, "csg_pair_relations: null operand");
+  CSG_REQUIRE(((uintptr_t)boxes & 15) == 0 && (((uintptr_t)centers | (uintptr_t)counts | (uintptr_t)rows) & 7) == 0 &&
+                  ((uintptr_t)other & 3) == 0,
+              CSG_E_BADSHAPE,
+              "csg_pair_relations: boxes must be 16-byte aligned, centers, counts and rows 8-byte aligned, other 4-byte aligned");
+  for (int a = 0; a < 8; ++a) {
+    CSG_REQUIRE(pred_ids[a] >= 0, CSG_E_BADSHAPE, "csg_pair_relations: predicate id %d is negative", (int)pred_ids[a]);
+    for (int c = a + 1; c < 8; ++c)
+      CSG_REQUIRE(pred_ids[a] != pred_ids[c], CSG_E_BADSHAPE, "csg_pair_relations: the eight predicate ids must be distinct");
+  }
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t n = counts_host[b];
+    CSG_REQUIRE(n >= 0 && n <= O, CSG_E_BADSHAPE, "csg_pair_relations: sample %ld has %ld rows, 0 .. O = %ld", (long)b, (long)n,
+                (long)O);
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t j = other_host[b * O + i];
+      CSG_REQUIRE(j >= 0 && j < n && j != i, CSG_E_BADSHAPE,
+                  "csg_pair_relations: sample %ld row %ld: other = %ld, another row of [0, %ld)", (long)b, (long)i, (long)j,
+                  (long)n);
+      CSG_REQUIRE(flip_host[b * O + i] <= 1, CSG_E_BADSHAPE, "csg_pair_relations: sample %ld row %ld: flip = %d, 0 or 1",
+                  (long)b, (long)i, (int)flip_host[b * O + i]);
+    }
+  }
+  PairIds id;        // pred_ids: __padding__ __in_image__ __below__ __above__ __left of__ __right of__ __inside__ __surrounding__
+  id.padding = pred_ids[0];
+  id.below = pred_ids[2];
+  id.above = pred_ids[3];
+  id.left = pred_ids[4];
+  id.right = pred_ids[5];
+  id.inside = pred_ids[6];
+  id.surrounding = pred_ids[7];
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope p(K_CANON_BUILD, (double)B * O, s);
+  CSG_LAUNCH(k_pair_relations, dim3((unsigned)cdiv(B * O, 256)), dim3(256), 0, s, (const float4*)boxes, (const float2*)centers,
+             counts, other, flip, id, use_converse ? 1 : 0, (int)B, (int)O, rows);
+  return check_launch("csg_pair_relations");
 }
 
 }  // extern "C"

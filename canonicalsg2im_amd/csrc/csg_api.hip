@@ -132,7 +132,7 @@ static const char* kNames[K_COUNT] = {
 
 extern "C" {
 
-int csg_version(void) { return 115; }
+int csg_version(void) { return 116; }
 const char* csg_last_error(void) { return csg::g_err; }
 
 int csg_prof_enable(int on) {

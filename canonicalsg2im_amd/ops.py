@@ -1693,6 +1693,46 @@ def vg_rows(rows, sizes, counts, num_object_names, rows_host=None, sizes_host=No
     return out_objs, out_boxes
 
 
+PAIR_PREDICATES = ("__padding__", "__in_image__", "__below__", "__above__", "__left of__", "__right of__", "__inside__",
+                   "__surrounding__")
+
+
+def pair_relations(boxes, centers, counts, other, flip, vocab, use_converse=False, other_host=None, flip_host=None,
+                   counts_host=None, out=None):
+    """The sampled-pair loop of the reference's COCO __getitem__ (sg2im/data/coco.py:381-421) for a padded batch, on the
+    device (csg_pair_relations): every object `cur` of a sample drew one other object and a coin on the host; the pair
+    (cur, other), or (other, cur) where flip is set, gets __surrounding__ / __inside__ from the boxes or the quadrant of
+    the centre difference — the reference's predicate, ties of atan2 included; `use_converse` as coco.py:404-421.
+
+    boxes: fp32 (B,O,4) xywh; centers: fp32 (B,O,2); counts: int64 (B,) rows per sample (its objects, or 0 for a sample
+    that draws nothing); other: int32 (B,O), -1 in padding rows; flip: uint8 (B,O).  All on the device; counts, other and
+    flip are needed on the host too (refusals): pass their CPU copies `counts_host` / `other_host` / `flip_host`, or they
+    are read back, which synchronises.  `vocab`: its pred_name_to_idx gives the eight ids.
+    Returns int64 (B,O,3) rows (s, p, o), [0, __padding__, 0] in the rows at or beyond a sample's count: what
+    canonical_triplets takes as the rows of `pairs`.  `out`: a caller-owned buffer, for a captured graph.  No autograd."""
+    _device_operands("pair_relations", (("boxes", boxes, torch.float32, (None, None, 4)),
+                                        ("centers", centers, torch.float32, (None, None, 2)),
+                                        ("counts", counts, torch.int64, (None,)), ("other", other, torch.int32, (None, None)),
+                                        ("flip", flip, torch.uint8, (None, None))))
+    B, O = boxes.shape[:2]
+    if tuple(centers.shape[:2]) != (B, O) or counts.shape[0] != B or tuple(other.shape) != (B, O) or \
+            tuple(flip.shape) != (B, O):
+        raise RuntimeError("pair_relations: centers %s, counts %s, other %s and flip %s do not fit boxes %s" % (
+            tuple(centers.shape), tuple(counts.shape), tuple(other.shape), tuple(flip.shape), tuple(boxes.shape)))
+    counts_host, other_host, flip_host = _host_copies("pair_relations", (
+        ("counts", counts, counts_host), ("other", other, other_host), ("flip", flip, flip_host)))
+    if out is None:
+        out = torch.empty((B, O, 3), device=boxes.device, dtype=torch.int64)
+    if tuple(out.shape) != (B, O, 3) or out.dtype != torch.int64 or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError("pair_relations: out must be contiguous int64 (B,O,3) on the device")
+    ids = (ctypes.c_int32 * 8)(*[vocab["pred_name_to_idx"][n] for n in PAIR_PREDICATES])
+    check(lib.csg_pair_relations(ptr(boxes), ptr(centers), ptr(counts), ptr(other), ptr(flip),
+                                 ctypes.c_void_p(counts_host.data_ptr()), ctypes.c_void_p(other_host.data_ptr()),
+                                 ctypes.c_void_p(flip_host.data_ptr()), B, O, ids, 1 if use_converse else 0, ptr(out),
+                                 stream()), "pair_relations")
+    return out
+
+
 # ------------------------------------------------------------------------------------ resampling
 class _Upsample2x(torch.autograd.Function):
     @staticmethod

@@ -27,6 +27,8 @@ _OFF_PATH_FLAGS = {
     'coco_train_image_dir': (None, 'str'), 'coco_val_image_dir': (None, 'str'),
     'coco_train_instances_json': (None, 'str'), 'coco_train_stuff_json': (None, 'str'),
     'coco_val_instances_json': (None, 'str'), 'coco_val_stuff_json': (None, 'str'),
+    # --dataset coco (sg2im/data/coco.py of this package): a JSON list of image ids; the val split keeps the images on it
+    'coco_val_ids': (None, 'str'),
     # CLEVR from a folder (sg2im/data/packed_clevr.py of this package): unset, the reference's layout under --dataroot
     # (<dataroot>/CLEVR/CLEVR_Dialog/scenes/CLEVR_<split>_scenes.json, .../images/<split>/); an image dir given here holds the
     # split's pictures themselves

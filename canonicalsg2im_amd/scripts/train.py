@@ -20,7 +20,10 @@ the device from the scene geometry (sg2im/data/packed_clevr.py of this package; 
 `--vocab_json` where they exist, else <dataroot>/vg/{images, train.h5 or train.npz, vocab.json}): the objects of a sample are
 chosen on the host as the reference chooses them, their pixel boxes are divided by the decoded picture's size on the device,
 and the annotated relationships join the canonical graph (sg2im/data/packed_vg.py of this package; `--mask_size` must be 0;
-a .h5 split needs h5py, a .npz split does not: tools/vg_h5_to_npz.py).  Without the directory, and for every other dataset,
+a .h5 split needs h5py, a .npz split does not: tools/vg_h5_to_npz.py).  `--dataset coco`, the default, reads the COCO folder
+of `packed_coco` with the original sg2im graph: 3 to 8 objects, every object draws one partner on the host and the pair's
+predicate and the graph are made on the device (sg2im/data/coco.py of this package; `--mask_size` must be 0; `--coco_val_ids`
+names the val split's image ids).  Without the directory, and for every other dataset,
 the batches are seeded synthetic ones of the chosen dataset's shape.  One line says which of the two it is.
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as

@@ -60,9 +60,22 @@ def _host_int64(t):
     return t.detach().to(device="cpu", dtype=torch.int64).contiguous()
 
 
+_BAD_DEVICE_ROW = ("canonical_triplets: sample %d has a sampled row whose objects lie outside [0, n_objs) or whose predicate "
+                   "lies outside the vocabulary or is __padding__; the row was dropped on the device and no graph was written")
+
+
+def _refuse_dropped_rows(first):
+    """Raise when csg_canon_general_build_dev marked a sample: `first` is the host copy of counts[:, 0]."""
+    bad = (first < 0).nonzero()
+    if bad.numel():
+        raise RuntimeError(_BAD_DEVICE_ROW % int(bad[0, 0]))
+
+
 def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity, include_dummies,
-                       learned_converse, converse_weights, uniforms, triplets):
-    """Annotated rows and any vocabulary (csrc/canon.hip, csg_canon_general_*): packed_vg.py:127-142 + vg_collate_fn."""
+                       learned_converse, converse_weights, uniforms, triplets, rel_dev=None, rel_counts=None):
+    """Annotated rows and any vocabulary (csrc/canon.hip, csg_canon_general_*): packed_vg.py:127-142 + vg_collate_fn.
+    `rel_dev` (B,R,3) int64 on the device with `rel_counts` (B,) on the host, in place of `triplets`: rows that never were
+    on the host (the sampled pairs), through csg_canon_general_build_dev."""
     B, O = objs0.shape
     dev = objs0.device
     p2i = vocab["pred_name_to_idx"]
@@ -74,7 +87,10 @@ def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learn
         roles[p2i[name]] = slot
     roles_c = (ctypes.c_int32 * P)(*roles)
     n_host = _host_int64(n_objs)
-    rel = _host_int64(triplets) if triplets is not None else torch.zeros((B, 0, 3), dtype=torch.int64)
+    if rel_dev is not None:
+        rel = rel_dev
+    else:
+        rel = _host_int64(triplets) if triplets is not None else torch.zeros((B, 0, 3), dtype=torch.int64)
     if rel.dim() != 3 or rel.shape[0] != B or rel.shape[2] != 3:
         raise ValueError("triplets must be (B, R, 3); got %s" % (tuple(rel.shape),))
     R = rel.shape[1]
@@ -83,16 +99,24 @@ def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learn
         raise RuntimeError("canonical_triplets: at most 256 predicates (the vocabulary has %d)" % P)
     ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
     counts = torch.empty((B, 2), device=dev, dtype=torch.int64)
-    check(lib.csg_canon_general_build(ptr(objs0), ptr(boxes), ptr(obj_centers), ctypes.c_void_p(n_host.data_ptr()), B, O,
-                                      ctypes.c_void_p(rel.data_ptr()) if R else None, None, R, roles_c, P, image_id,
-                                      1 if include_dummies else 0, ptr(ws), nbytes, ptr(counts), stream()),
-          "canon_general_build")
+    if rel_dev is not None:
+        rel_counts = _host_int64(rel_counts)
+        check(lib.csg_canon_general_build_dev(ptr(objs0), None, None, ctypes.c_void_p(n_host.data_ptr()), B, O,
+                                              ptr(rel) if R else None, ctypes.c_void_p(rel_counts.data_ptr()), R, roles_c,
+                                              P, image_id, 1 if include_dummies else 0, ptr(ws), nbytes, ptr(counts),
+                                              stream()), "canon_general_build_dev")
+    else:
+        check(lib.csg_canon_general_build(ptr(objs0), ptr(boxes), ptr(obj_centers), ctypes.c_void_p(n_host.data_ptr()), B, O,
+                                          ctypes.c_void_p(rel.data_ptr()) if R else None, None, R, roles_c, P, image_id,
+                                          1 if include_dummies else 0, ptr(ws), nbytes, ptr(counts), stream()),
+              "canon_general_build")
     conv_counts = torch.zeros((B, P, P + 1), device=dev, dtype=torch.float32)        # base_dataset.py:93
     if learned_converse:
         if converse_weights is None:
             raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
         w = converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
         draws = counts[:, 0].cpu()                                   # read-back: the uniforms are the HOST's random stream
+        _refuse_dropped_rows(draws)
         u, u_off = _draw_numbers(draws, uniforms)
         non_meta = [p for p in range(P) if roles[p] not in (-2, -3)]
         cdf = np.zeros((P, len(non_meta)), np.float64)
@@ -105,7 +129,12 @@ def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learn
                                              ptr(conv_counts), stream()), "canon_general_converse")
     check(lib.csg_canon_general_close(B, roles_c, P, 1 if learned_transitivity else 0, ptr(ws), nbytes, ptr(counts),
                                       stream()), "canon_general_close")
-    T = int(counts.sum(dim=1).max().item())          # vg_collate_fn pads to the longest sample: one 8-byte read-back
+    if rel_dev is not None:                          # the same single read-back, of every count: a negative one is a refusal
+        counts_host = counts.cpu()
+        _refuse_dropped_rows(counts_host[:, 0])
+        T = int(counts_host.sum(dim=1).max())
+    else:
+        T = int(counts.sum(dim=1).max().item())      # vg_collate_fn pads to the longest sample: one 8-byte read-back
     out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
     triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
     check(lib.csg_canon_general_emit(B, roles_c, P, ptr(ws), nbytes, ptr(counts), T, ptr(out), ptr(triplet_type),
@@ -114,7 +143,8 @@ def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learn
 
 
 def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transitivity=False, include_dummies=True,
-                       learned_converse=False, converse_weights=None, uniforms=None, triplets=None):
+                       learned_converse=False, converse_weights=None, uniforms=None, triplets=None, pairs=None,
+                       use_converse=False, pairs_host=None):
     """Batched `add_location_triplets` + `add_dummy_triplets` + `add_learnt_triplets` + collate padding.
 
     objs (B,O) or (B,O,A) int64 (attribute 0 is used, as `objs['shape']` in packed_clevr_dialog.py:207),
@@ -138,7 +168,15 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
 
     `boxes=None` (and `obj_centers=None`), with `triplets`: a graph without geometry (canonicalsg2im_amd/authored.py).  No
     location relation is derived; the given rows — which may carry location predicates and `__in_image__` — are the
-    graph, and converse draws, transitive extras, order and padding are formed from them exactly as above."""
+    graph, and converse draws, transitive extras, order and padding are formed from them exactly as above.
+
+    `pairs` = (other int32 (B,O), flip uint8 (B,O)), with `boxes` and `obj_centers`: the sampled-pair graph of the unpacked
+    COCO dataset (sg2im/data/coco.py:365-428).  Row i of a sample names the ONE other object it drew (-1: the row draws
+    nothing: padding, the `__image__` row, a sample with fewer than two objects) and whether the pair is flipped.  No
+    all-pairs location relation is derived: ops.pair_relations gives every pair its predicate (`use_converse` as
+    coco.py:404-421), the rows stay on the device (csg_canon_general_build_dev) and dummies, converse draws, transitive
+    extras, order and padding follow as above.  The tensors may be on the host or the device; the host needs them
+    (refusals): `pairs_host` = their CPU copies spares the read-back of device tensors."""
     objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
     first = list(vocab["attributes"].keys())[0]
     image_id = vocab["object_name_to_idx"]["__image__"]
@@ -152,6 +190,24 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     if boxes is not None:
         boxes = boxes.to(torch.float32).contiguous()
         obj_centers = obj_centers.to(torch.float32).contiguous()
+    if pairs is not None:
+        if boxes is None or triplets is not None:
+            raise ValueError("canonical_triplets: pairs needs boxes and obj_centers, and no `triplets`")
+        from ... import ops
+        host = pairs if pairs_host is None else pairs_host
+        other_h = torch.as_tensor(host[0]).detach().to(device="cpu", dtype=torch.int32).contiguous()
+        flip_h = torch.as_tensor(host[1]).detach().to(device="cpu", dtype=torch.uint8).contiguous()
+        if tuple(other_h.shape) != (B, O) or tuple(flip_h.shape) != (B, O):
+            raise ValueError("canonical_triplets: pairs must be two (B, O) = %s tensors; got %s and %s" % (
+                (B, O), tuple(other_h.shape), tuple(flip_h.shape)))
+        other_d = torch.as_tensor(pairs[0]).to(device=objs0.device, dtype=torch.int32).contiguous()
+        flip_d = torch.as_tensor(pairs[1]).to(device=objs0.device, dtype=torch.uint8).contiguous()
+        rows_h = (other_h >= 0).sum(1)                  # a -1 among a sample's leading rows is refused by the entry
+        rows_d = (other_d >= 0).sum(1)
+        rel = ops.pair_relations(boxes, obj_centers, rows_d, other_d, flip_d, vocab, use_converse=use_converse,
+                                 other_host=other_h, flip_host=flip_h, counts_host=rows_h)
+        return _canonical_general(objs0, None, None, n_objs, vocab, image_id, learned_transitivity, include_dummies,
+                                  learned_converse, converse_weights, uniforms, None, rel_dev=rel, rel_counts=rows_h)
     if triplets is not None or set(p2i.values()) != {p2i[n] for n in names}:
         return _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity,
                                   include_dummies, learned_converse, converse_weights, uniforms, triplets)

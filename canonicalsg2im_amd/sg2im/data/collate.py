@@ -8,22 +8,40 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     place of the triplets.  packed_vg hands the batch's annotated relationships over, unless --include_relationships 0
     (packed_vg.py:128-130).  `counts`: the real objects per sample as a HOST int64 tensor, from a builder that knows them
     (its objects live on the device: deriving the counts from them would be a read-back per batch); by default they are
-    derived from the objects, as before."""
+    derived from the objects, as before.  The unpacked coco dataset hands over, in the triplet slot, the pairs its builder
+    drew: (other, flip) on the device and their host copies (None with --include_relationships 0: the dummies alone,
+    sg2im/data/coco.py:374-375); its graph is the sampled rows, not the all-pairs relations of the geometry."""
     from . import canonical_triplets
-    rel = None
+    rel = pairs = None
+    if args.dataset == "coco":
+        if counts is None:
+            raise ValueError("packed_batch: a coco batch comes from CocoPairsBatchBuilder, with the objects per sample")
+        batch = list(batch)
+        pairs, batch[3] = batch[3], None
+        n = counts + 1
+        if pairs is None:
+            rel = torch.zeros((counts.shape[0], 0, 3), dtype=torch.int64)
     if args.dataset == "packed_vg":  # the annotated rows and the object counts are read on the host: hand over CPU tensors
         rel = batch[3] if args.include_relationships else torch.zeros((batch[3].shape[0], 0, 3), dtype=torch.int64)
         n = (batch[1][..., 0] != 0).sum(1) if counts is None else counts
         n = n + 1                                           # real objects + the __image__ row appended below
     batch = [None if x is None else x.to(dev) for x in batch]
     objs, boxes = batch[1], batch[2]
-    if rel is None:
+    if rel is None and pairs is None:
         n = ((objs[..., 0] != 0).sum(1) if counts is None else counts.to(dev)) + 1
     O = objs.shape[1] + 1
     objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
     boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)
     centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
     batch[1], batch[2] = objs, boxes
+    extra = {"triplets": rel}
+    if args.dataset == "coco":
+        if pairs is None:                                  # no geometry: the (empty) rows are the whole graph
+            boxes = centers = None
+        else:                                              # the __image__ row draws nothing
+            extra = {"pairs": tuple(torch.nn.functional.pad(t.to(dev), (0, 1), value=v) for t, v in zip(pairs[:2], (-1, 0))),
+                     "pairs_host": tuple(torch.nn.functional.pad(t, (0, 1), value=v) for t, v in zip(pairs[2:], (-1, 0))),
+                     "use_converse": bool(args.use_converse)}
     conv_w = None
     if args.learned_converse:    # the data loader reads the model's converse weights back (scripts/train.py:274-276)
         from ..model import get_conv_converse
@@ -31,6 +49,6 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     batch[3], batch[4], batch[5] = canonical_triplets(objs, boxes, centers, n, args.vocab,
                                                       learned_transitivity=bool(args.learned_transitivity),
                                                       learned_converse=bool(args.learned_converse),
-                                                      converse_weights=conv_w, triplets=rel)
+                                                      converse_weights=conv_w, **extra)
     assert batch[3].shape[1] > 0 and objs.shape[1] == O
     return batch

@@ -49,7 +49,8 @@ extern "C" {
  * 112: csg_preprocess_workspace, csg_preprocess;
  * 113: csg_preprocess_px_workspace, csg_preprocess_px, csg_clevr_boxes;
  * 114: csg_vg_rows;
- * 115: csg_draw_boxes_u8; csg_canon_general_build takes boxes = centers = NULL) */
+ * 115: csg_draw_boxes_u8; csg_canon_general_build takes boxes = centers = NULL;
+ * 116: csg_pair_relations, csg_canon_general_build_dev) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -774,6 +775,43 @@ int csg_canon_general_close(int64_t B, const int32_t* roles, int64_t P, int lear
                             int64_t workspace_bytes, int64_t* counts, void* stream);
 int csg_canon_general_emit(int64_t B, const int32_t* roles, int64_t P, const void* workspace, int64_t workspace_bytes,
                            const int64_t* counts, int64_t T, int64_t* triplets, int64_t* triplet_type, void* stream);
+
+/* csg_canon_general_build for annotated rows that are already ON THE DEVICE (the sampled pairs of csg_pair_relations).
+ * Arguments as csg_canon_general_build, except: rel is a DEVICE pointer ((B,R,3) int64, 8-byte aligned); rel_counts (host, B)
+ * is required: a sample's first rel_counts[b] rows are its rows and give the row offsets; boxes = centers = NULL
+ * (CSG_E_UNSUPPORTED otherwise): the given rows are the whole graph, no location relation is derived.  The shapes, the
+ * role table, n_objs and rel_counts are checked before anything is enqueued, with the messages of csg_canon_general_build
+ * under this entry's name.  The rows cannot be: the kernel that packs them indexes nothing with a row whose object lies
+ * outside [0, n_objs[b]), whose predicate lies outside [0, P) or is __padding__; it drops the row, and counts[b][0] of
+ * that sample is then NEGATIVE (-1 - the count) after this entry and after csg_canon_general_close.  The caller reads
+ * counts back for T anyway: on a negative one it must not call csg_canon_general_emit.  Then _converse / _close / _emit as
+ * above, with the same workspace (csg_canon_general_workspace(B, P, R)). */
+int csg_canon_general_build_dev(const int64_t* objs0, const float* boxes, const float* centers, const int64_t* n_objs,
+                                int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
+                                const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
+                                int64_t workspace_bytes, int64_t* counts, void* stream);
+
+/* ---- sampled-pair relations of the unpacked COCO dataset (reference sg2im/data/coco.py:372-421) ---------------------
+ * Every object `cur` of a sample drew ONE other object and a coin on the host; this gives the pair's predicate, one thread
+ * per (sample, object).  (s, o) = (cur, other[cur]), or (other[cur], cur) where flip[cur] != 0.  In fp32, in the reference's
+ * order and without contraction: sx1 = sx0 + sw / 2 (the box centre: what the reference compares), likewise sy1, ox1, oy1;
+ * __surrounding__ if sx0 < ox0 && sx1 > ox1 && sy0 < oy0 && sy1 > oy1, else __inside__ with every comparison reversed
+ * (strict), else the quadrant of atan2(dy, dx), d = centers[s] - centers[o], decided WITHOUT atan2 by exact comparisons
+ * that equal the reference's four double-precision inequalities for every fp32 pair: with ax = |dx|, ay = |dy|,
+ * neg = signbit(dx): __left of__ if neg && ay <= ax; __right of__ if !neg && (ay < ax || (ay == ax && dy <= 0));
+ * otherwise __above__ if dy < 0, else __below__.  use_converse != 0 (coco.py:404-421): __inside__ becomes __surrounding__,
+ * __right of__ becomes __left of__ and __below__ becomes __above__, each with s and o swapped.
+ * boxes (B,O,4) fp32 xywh, centers (B,O,2) fp32, counts (B,) int64 = rows per sample, other (B,O) int32, flip (B,O) uint8:
+ * device; counts_host / other_host / flip_host: their host copies.  pred_ids (host, 8 int32): __padding__ __in_image__
+ * __below__ __above__ __left of__ __right of__ __inside__ __surrounding__.  rows (B,O,3) int64 (device) receives (s, p, o);
+ * a row at or beyond counts[b] is [0, __padding__, 0] — and so is one whose DEVICE `other` is not another counted row of
+ * its sample (nothing is indexed with it).
+ * Checked on the host before the launch (CSG_E_BADSHAPE): 0 <= counts_host[b] <= O; for every counted row
+ * other_host[b][i] in [0, counts_host[b]) and != i, flip_host[b][i] in {0, 1}; distinct non-negative ids; alignment (boxes
+ * 16, centers / counts / rows 8, other 4 bytes).  O <= 256 (CSG_E_UNSUPPORTED), as csg_canon_general_build requires. */
+int csg_pair_relations(const float* boxes, const float* centers, const int64_t* counts, const int32_t* other,
+                       const uint8_t* flip, const int64_t* counts_host, const int32_t* other_host, const uint8_t* flip_host,
+                       int64_t B, int64_t O, const int32_t* pred_ids, int use_converse, int64_t* rows, void* stream);
 
 /* ---- spectral normalisation of a conv weight (a13) ----------------------------------------------
  * torch.nn.utils.spectral_norm's forward pre-hook (reference call sites architecture.py:35-39,

@@ -1,0 +1,86 @@
+"""The DEVICE half of a folder dataset's batch, timed with events: what BatchBuilder.finish enqueues and waits for.
+
+    python tools/batch_device_half.py --dataset coco|packed_coco [--package-root DIR] [--batch 16] [--size 256]
+                                      [--objects 8] [--batches 60] [--warmup 10] [--learned_transitivity 0|1]
+
+A batch's host half (PIL decode into pinned memory, the draws, the second staging buffer) is started and WAITED FOR first;
+then two events bracket finish(): the two uploads, the dataset's kernels, ops.preprocess_images, the `__image__` row and the
+canonical graph with its one read-back of the triplet counts.  So the figure is device time plus the host time between the
+launches of one batch, per batch; the median and the spread over `--batches` batches after `--warmup` are printed as one
+JSON line.  The pictures are tools/input_stage_speed.py's 480 x 640 JPEGs with `--objects` boxes each, generated into a
+temporary folder that is removed at exit.
+
+`--package-root DIR` imports canonicalsg2im_amd from another checkout (built there), so that two commits are timed by one
+tool: run them alternately, in fresh processes.  It uses nothing a checkout before the `coco` dataset lacks, for
+`--dataset packed_coco`."""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+from input_stage_speed import make_folder  # noqa: E402  (inserts this checkout's root into sys.path)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dataset", choices=["coco", "packed_coco"], default="coco")
+    ap.add_argument("--package-root")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--objects", type=int, default=8)
+    ap.add_argument("--batches", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--learned_transitivity", type=int, default=0)
+    a = ap.parse_args()
+    if a.package_root:
+        sys.path.insert(0, os.path.abspath(a.package_root))
+    import torch
+    assert torch.cuda.is_available(), "a measurement needs the GPU"
+    from canonicalsg2im_amd import train as T
+    from canonicalsg2im_amd.scripts.train import build_parser, folder_builder, folder_dataset
+    dev = torch.device("cuda:0")
+    tmp = tempfile.mkdtemp(prefix="device_half_")
+    try:
+        make_folder(tmp, 2 * a.batch, objects=a.objects)
+        flags = ["--dataset", a.dataset, "--image_size", "%d,%d" % (a.size, a.size), "--batch_size", str(a.batch),
+                 "--coco_train_image_dir", os.path.join(tmp, "images"), "--coco_train_instances_json",
+                 os.path.join(tmp, "instances.json"), "--coco_train_stuff_json", os.path.join(tmp, "stuff.json"),
+                 "--min_objects", "1", "--max_objects", str(a.objects), "--loader_num_workers", str(a.workers),
+                 "--learned_transitivity", str(a.learned_transitivity)]
+        ds = folder_dataset(build_parser().parse_args(flags), "train")
+        assert ds is not None and len(ds) == 2 * a.batch, "the generated folder was not read whole"
+        opt = T.make_opt(ds.vocab, flags + ["--no_vgg_loss"])
+        builder = folder_builder(ds, opt, None, dev)
+        lists = [list(range(a.batch)), list(range(a.batch, 2 * a.batch))]
+        ms, shape = [], None
+        for k in range(a.warmup + a.batches):
+            pending = builder.start(lists[k % 2])
+            for f in pending.futures:
+                f.result()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            batch = builder.finish(pending)
+            e1.record()
+            e1.synchronize()
+            if k >= a.warmup:
+                ms.append(e0.elapsed_time(e1))
+            shape = [list(batch[0].shape), list(batch[1].shape), list(batch[3].shape)]
+        builder.close()
+        ms.sort()
+        print(json.dumps({"dataset": a.dataset, "package": a.package_root or ".",
+                          "batches": len(ms), "imgs_objs_triplets": shape, "learned_transitivity": a.learned_transitivity,
+                          "median_ms": round(statistics.median(ms), 4), "p10_ms": round(ms[len(ms) // 10], 4),
+                          "p90_ms": round(ms[len(ms) * 9 // 10], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
