@@ -87,6 +87,55 @@ def _reduced(rows, pid):
     return [[s, pid, o] for s in range(n) for o in range(n) if m[s][o]]
 
 
+def object_ids(objects, vocab, bad):
+    """Authored objects — names (vocabularies with one attribute) or {attribute: name} dictionaries — -> their id rows
+    [n][A], in the vocabulary's attribute order and without an `__image__` row.  `bad(what)` makes the exception of an
+    unknown or missing name: the caller says which graph or row it was."""
+    attrs = vocab["attributes"]
+    names = list(attrs.keys())
+    rows = []
+    for i, obj in enumerate(objects):
+        if isinstance(obj, str):
+            if len(names) != 1:
+                raise bad("object %d is the name %r, but the vocabulary has the attributes %s" % (i, obj, names))
+            obj = {names[0]: obj}
+        if not isinstance(obj, dict):
+            raise bad("object %d: %r is neither a name nor a dictionary of attributes" % (i, obj))
+        row = []
+        for a in names:
+            if a not in obj:
+                raise bad("object %d lacks the attribute %r" % (i, a))
+            v = obj[a]
+            if not isinstance(v, str) or v not in attrs[a] or v == "__image__":
+                raise bad("object %d: unknown %s %r" % (i, a, v))
+            row.append(attrs[a][v])
+        rows.append(row)
+    return rows
+
+
+def object_names(rows, vocab):
+    """The other direction of `object_ids`: id rows [n][A] -> the objects as a person writes them, a list of names for a
+    vocabulary with one attribute and a list of {attribute: name} otherwise.  An id no name maps to raises ValueError; of
+    several names with one id the first in the table's order is taken."""
+    attrs = vocab["attributes"]
+    names = list(attrs.keys())
+    back = {}
+    for a in names:
+        back[a] = {}
+        for name, idx in attrs[a].items():
+            back[a].setdefault(int(idx), name)
+    out = []
+    for i, row in enumerate(rows):
+        if len(row) != len(names):
+            raise ValueError("object %d has %d ids, the vocabulary has the attributes %s" % (i, len(row), names))
+        for a, idx in zip(names, row):
+            if int(idx) not in back[a]:
+                raise ValueError("object %d: no %s has the id %d" % (i, a, int(idx)))
+        named = {a: back[a][int(idx)] for a, idx in zip(names, row)}
+        out.append(named[names[0]] if len(names) == 1 else named)
+    return out
+
+
 def _encode_one(g, graph, vocab):
     """-> (object rows [n + 1][A], triplets [[s, p, o], ...]) of graph number g."""
     if not isinstance(graph, dict) or "objects" not in graph or "relationships" not in graph:
@@ -98,23 +147,7 @@ def _encode_one(g, graph, vocab):
     names = list(attrs.keys())
     n = len(objects)
     flat = not isinstance(rels, dict)
-    rows = []
-    for i, obj in enumerate(objects):
-        if isinstance(obj, str):
-            if len(names) != 1:
-                raise _bad(g, "object %d is the name %r, but the vocabulary has the attributes %s" % (i, obj, names))
-            obj = {names[0]: obj}
-        if not isinstance(obj, dict):
-            raise _bad(g, "object %d: %r is neither a name nor a dictionary of attributes" % (i, obj))
-        row = []
-        for a in names:
-            if a not in obj:
-                raise _bad(g, "object %d lacks the attribute %r" % (i, a))
-            v = obj[a]
-            if not isinstance(v, str) or v not in attrs[a] or v == "__image__":
-                raise _bad(g, "object %d: unknown %s %r" % (i, a, v))
-            row.append(attrs[a][v])
-        rows.append(row)
+    rows = object_ids(objects, vocab, lambda what: _bad(g, what))
     rows.append([attrs[a]["__image__"] for a in names])
     triplets = []
     if flat:

@@ -1495,10 +1495,23 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)                 # sg2im/data/utils.py:6-10
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
-def deprocess_u8(img, rescale=True):
-    """deprocess_batch(img, rescale, imagenet_deprocess) (sg2im/data/utils.py:36-65) on the device: a logical (B,3|4,H,W)
+DEPROCESS = {              # name -> (div3, sub3) of csg_deprocess_u8: x / div - sub per channel
+    # the fp32 values torch.as_tensor(INV_IMAGENET_STD / INV_IMAGENET_MEAN, dtype=float32) holds (T.Normalize, utils.py:38-39)
+    "imagenet": (tuple(1.0 / s for s in IMAGENET_STD), tuple(-m for m in IMAGENET_MEAN)),
+    # decode_img (utils.py:17-24): x.sub_(0).div_(2) then .sub_(-0.5).div_(1.0); x - 0 and t / 1.0 change no bit
+    "decode_img": ((2.0, 2.0, 2.0), (-0.5, -0.5, -0.5)),
+}
+
+
+def deprocess_u8(img, rescale=True, deprocess="imagenet"):
+    """deprocess_batch(img, rescale, <deprocess>) (sg2im/data/utils.py:36-65) on the device: a logical (B,3|4,H,W)
     fp32 image with NHWC memory (a channels-last image, or conv_img's 4-padded output: a 3-channel slice of it is taken
-    with its padding) -> uint8 (B,3,H,W), byte for byte what the fp32 host code gives (csg_deprocess_u8)."""
+    with its padding) -> uint8 (B,3,H,W), byte for byte what the fp32 host code gives (csg_deprocess_u8).  `deprocess`:
+    "imagenet" (imagenet_deprocess, the inverse of the COCO folders' normalisation) or "decode_img" (the inverse of
+    Normalize(0.5, 0.5): CLEVR and Visual Genome, and the reference's default of --img_deprocess)."""
+    if deprocess not in DEPROCESS:
+        raise ValueError("deprocess_u8: deprocess must be one of %s, got %r" % (
+            " or ".join(repr(k) for k in DEPROCESS), deprocess))
     img = _f32(img)
     if img.dim() != 4 or img.stride(1) != 1 or img.shape[1] not in (3, 4):
         raise RuntimeError("deprocess_u8: a (B,3,H,W) image with NHWC memory is needed, got %s strides %s" % (
@@ -1510,9 +1523,9 @@ def deprocess_u8(img, rescale=True):
     out = torch.empty((B, 3, H, W), device=img.device, dtype=torch.uint8)
     nws = lib.csg_deprocess_u8_workspace(B) if rescale else 0
     ws = torch.empty(nws // 4, device=img.device, dtype=torch.float32) if nws else None
-    # the fp32 values torch.as_tensor(INV_IMAGENET_STD / INV_IMAGENET_MEAN, dtype=float32) holds (T.Normalize, utils.py:38-39)
-    div = (_lib.c_f32 * 3)(*[1.0 / s for s in IMAGENET_STD])
-    sub = (_lib.c_f32 * 3)(*[-m for m in IMAGENET_MEAN])
+    div3, sub3 = DEPROCESS[deprocess]
+    div = (_lib.c_f32 * 3)(*div3)
+    sub = (_lib.c_f32 * 3)(*sub3)
     check(lib.csg_deprocess_u8(ptr(img), B, H, W, cs, div, sub, 1 if rescale else 0, ptr(out), ptr(ws), nws, stream()),
           "deprocess_u8")
     return out

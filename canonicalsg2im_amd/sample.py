@@ -181,7 +181,7 @@ class Sampler:
         h, = self._spade(dx, seg, (blk.norm_1, 0.2))
         return self._conv(blk.conv_1, h, residual=x_s)
 
-    def _walk(self, objs, boxes, masks, uint8, rescale):
+    def _walk(self, objs, boxes, masks, uint8, rescale, deprocess="imagenet"):
         """SPADEGenerator.forward(test_mode=True) (generator.py:79-127): layout pyramid -> fc -> blocks -> conv_img [-> uint8]."""
         gen = self.model.layout_to_image_model.module
         if gen.sw != gen.sh:
@@ -203,26 +203,28 @@ class Sampler:
             x = self._block(getattr(gen, name), x, seg)
         ci = gen.conv_img
         img = ops.conv2d(x, ci.weight, ci.bias, 1, ci.padding[0], ci.act, ci.slope, pre_slope=2e-1)
-        return img, (ops.deprocess_u8(img, rescale) if uint8 else None)
+        return img, (ops.deprocess_u8(img, rescale, deprocess) if uint8 else None)
 
-    def _generator(self, objs, boxes, masks, uint8, rescale):
+    def _generator(self, objs, boxes, masks, uint8, rescale, deprocess="imagenet"):
         B, O, A = objs.shape
         M = 0 if masks is None else int(masks.shape[-1])
-        key = (B, csg_graphs._pad_objects(O), int(self.opt.image_size[0]), A, M, bool(uint8), bool(rescale))
+        # the deprocess function's constants are baked into a captured walk: its name is part of the key
+        key = (B, csg_graphs._pad_objects(O), int(self.opt.image_size[0]), A, M, bool(uint8), bool(rescale),
+               str(deprocess) if uint8 else None)
         rp = self._replays.get(key)
         if rp is None:
             n = self._seen.get(key, 0)
             self._seen[key] = n + 1
             if not csg_graphs.ENABLED or n < csg_graphs.CAPTURE_AFTER or len(self._replays) >= csg_graphs.MAX_SETS:
                 self.eager_calls += 1
-                return self._walk(objs, boxes, masks, uint8, rescale)
+                return self._walk(objs, boxes, masks, uint8, rescale, deprocess)
             rp = self._replays[key] = _Replay(B, key[1], A, M, objs.device, objs.dtype)
         rp.load(objs, boxes, masks)
         if rp.graph is None:
             g = torch.cuda.CUDAGraph()
             csg_graphs._quiesce_before_capture()
             with csg_graphs._Capture(g):
-                rp.img, rp.u8 = self._walk(rp.objs, rp.boxes, rp.masks, uint8, rescale)
+                rp.img, rp.u8 = self._walk(rp.objs, rp.boxes, rp.masks, uint8, rescale, deprocess)
             rp.graph = g
         rp.graph.replay()
         self.replays += 1
@@ -230,19 +232,27 @@ class Sampler:
         return rp.img.clone(), (None if rp.u8 is None else rp.u8.clone())
 
     # ------------------------------------------------------------------ public
-    def generate(self, objs, triplets, triplet_type, boxes_gt=None, masks_gt=None, uint8=True, rescale=True):
+    def generate(self, objs, triplets, triplet_type, boxes_gt=None, masks_gt=None, uint8=True, rescale=True,
+                 deprocess="imagenet"):
         """(images, boxes_pred, masks_pred) of MetaGeneratorModel.forward(..., test_mode=True) (reference
         sg2im/meta_models.py:25-51): ground-truth boxes / masks win over the predictions where given; with masks the layout
-        is painter's compositing.  images: uint8 (B,3,H,W) = deprocess_batch(imgs, rescale, imagenet_deprocess), or with
-        uint8=False the fp32 (B,3,H,W) image in channels-last memory."""
+        is painter's compositing.  images: uint8 (B,3,H,W) = deprocess_batch(imgs, rescale, <deprocess>) with `deprocess`
+        "imagenet" or "decode_img" (ops.deprocess_u8), or with uint8=False the fp32 (B,3,H,W) image in channels-last memory.
+        triplets=None with boxes_gt: the picture of that layout from the generator alone; the scene-graph encoder is not run
+        and boxes_pred / masks_pred are None."""
         if self.device.type != "cuda" or not objs.is_cuda:
             raise RuntimeError(NO_CPU)
+        if deprocess not in ops.DEPROCESS:
+            raise ValueError("generate: deprocess must be one of %s, got %r" % (
+                " or ".join(repr(k) for k in ops.DEPROCESS), deprocess))
         model = self.model
         with torch.no_grad():
             if model.training:
                 model.eval()
             boxes_pred = masks_pred = None
-            if model.has_graph:
+            if triplets is None and boxes_gt is None:
+                raise ValueError("generate: without triplets there is no graph to predict a layout from: pass boxes_gt")
+            if model.has_graph and triplets is not None:      # a layout alone (split.generate_layouts): no encoder pass
                 boxes_pred, masks_pred = model.sg_to_layout(objs, triplets, triplet_type, boxes_gt)[1:]
             if not model.has_image:
                 return None, boxes_pred, masks_pred
@@ -250,7 +260,7 @@ class Sampler:
             boxes = boxes_gt if boxes_gt is not None else boxes_pred
             masks = masks_gt if masks_gt is not None else masks_pred
             img, u8 = self._generator(objs, boxes.float().contiguous(), None if masks is None else masks.float().contiguous(),
-                                      uint8, rescale)
+                                      uint8, rescale, deprocess)
         return (u8 if uint8 else img), boxes_pred, masks_pred
 
     def generate_from_graphs(self, graphs, overlay=False, thickness=2, palette=None):

@@ -58,17 +58,13 @@ def validation_batches(args, trainer, dev, world=1, val_set=None):
     from ..synth import make_batch
     from .train import packed_batch, synth_config
     if val_set is not None:              # the first num_val_samples pictures in file order; every rank sees the same batches
-        from ..sg2im.data.loader import epoch_batches
+        from ..sg2im.data.loader import file_order_batches
         import random
         from .train import folder_builder
         # a Visual Genome builder samples objects: a fresh stream per call, so every rank and every call sees the same ones
         builder = folder_builder(val_set, args, trainer, dev, rng=random.Random(0))
-        n = len(val_set)
-        lists = epoch_batches(n, args.batch_size, shuffle=False)
-        if n % args.batch_size:
-            lists.append(list(range(n - n % args.batch_size, n)))
         try:
-            yield from builder.batches(lists)
+            yield from builder.batches(file_order_batches(len(val_set), args.batch_size))
         finally:
             builder.close()
         return
@@ -85,23 +81,8 @@ def folder_val_set(args, vocab=None):
     """The val split's folder dataset, or None (synthetic validation batches).  `vocab`: the vocabulary the model was built
     with; a val split whose categories, attribute tables or predicates differ from it is refused here, on the host — its
     ids would index the model's embedding tables."""
-    from .train import folder_dataset
-    val_set = folder_dataset(args, "val")
-    if val_set is not None and vocab is not None and val_set.vocab["attributes"] != vocab["attributes"] and \
-            val_set.vocab["object_name_to_idx"] == vocab["object_name_to_idx"]:
-        raise SystemExit("the val split's attribute tables (%s rows) are not the model's (%s rows): train and validate on one "
-                         "vocabulary" % ([len(t) for t in val_set.vocab["attributes"].values()],
-                                         [len(t) for t in vocab["attributes"].values()]))
-    if val_set is not None and vocab is not None and "pred_idx_to_name" in vocab and \
-            list(val_set.vocab["pred_idx_to_name"]) != list(vocab["pred_idx_to_name"]):
-        raise SystemExit("the val split's predicates (%d names) are not the model's (%d names): train and validate on one "
-                         "vocabulary" % (len(val_set.vocab["pred_idx_to_name"]), len(vocab["pred_idx_to_name"])))
-    if val_set is not None and vocab is not None and val_set.vocab["object_name_to_idx"] != vocab["object_name_to_idx"]:
-        raise SystemExit("the val split's categories (%d names, largest id %d) are not the model's (%d names, largest id %d): "
-                         "train and validate on annotation files of one category set" % (
-                             len(val_set.vocab["object_name_to_idx"]), max(val_set.vocab["object_name_to_idx"].values()),
-                             len(vocab["object_name_to_idx"]), max(vocab["object_name_to_idx"].values())))
-    return val_set
+    from .train import folder_dataset, hold_to_vocab
+    return hold_to_vocab(folder_dataset(args, "val"), vocab, "val")
 
 
 def log_results(losses, t, prefix):

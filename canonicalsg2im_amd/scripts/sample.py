@@ -1,9 +1,12 @@
 """Command-line sampler: a checkpoint and scene graphs in, PNG files out.
 
 With --scene_graphs FILE.json the graphs are the ones a person wrote (canonicalsg2im_amd/authored.py: the form of the
-reference's scripts/run_model.py, or a flat one), as that script draws them.  Without it they are seeded SYNTHETIC batches
-of the chosen dataset's shape (the reference's scripts/generation_attspade.py reads its datasets; for a dataset folder,
-pass a batch builder's batch to `Sampler.generate` directly).  The reference's flags describe the model; on top of them:
+reference's scripts/run_model.py, or a flat one), as that script draws them.  With --split train|val they are the graphs of
+a dataset folder, and every image id gets its real, ground-truth-layout and predicted-layout picture (the reference's
+scripts/generation_attspade.py; canonicalsg2im_amd/split.py).  With --layouts FILE.json they are rows of object classes and
+boxes, drawn by the generator alone (its scripts/generation_dataframe.py).  Without any of the three they are seeded
+SYNTHETIC batches of the chosen dataset's shape.  The three flags exclude each other.  The reference's flags describe the
+model; on top of them:
 
     --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (default: none — the freshly
                              initialised weights, which is only good for timing)
@@ -14,9 +17,29 @@ pass a batch builder's batch to `Sampler.generate` directly).  The reference's f
                              --draw_boxes 1 (the default) img_%06d_layout.png — the picture with the outlines of the
                              predicted boxes, no text labels — and graphs.json, the encoded triplets with their
                              predicates' names (in place of the reference's GraphViz picture)
+    --split train|val        the split's folder (the paths of scripts/train.py; --num_train_samples / --num_val_samples cap
+                             it, --coco_val_ids narrows coco's val) in file order, batches of --batch_size decoded in
+                             --loader_num_workers threads.  Needs --checkpoint_name; the folder's vocabulary is held to the
+                             checkpoint's.  A missing folder ends the run: there is no synthetic stand-in.  Writes
+                             <output_dir>/gt/, generation/gt_box_gt_mask/, generation/pred_box_pred_mask/ (not with
+                             --skip_graph_model 1), with --draw_boxes 1 layout/gt/ and layout/pred/ — <image id>.<ext> in
+                             each — and layouts.json: the IoU figures and per image the counted objects' names, boxes,
+                             predicted boxes and IoU.  The pictures go through --img_deprocess (decode_img, the default and
+                             the inverse of CLEVR's and Visual Genome's normalisation, or imagenet, the COCO folders')
+    --max_pictures N         with --split: stop after N images (0, the default: the whole split)
+    --image_format png|jpg   with --split / --layouts: png (default, lossless) or jpg (Pillow, quality 95)
+    --num_writers N          with --split / --layouts: threads that encode the files, 1 .. 16 (default 8)
+    --layouts FILE           a layouts.json (its `images` rows, or a bare list of rows); needs --checkpoint_name and
+                             --output_dir; the vocabulary is the checkpoint's.  Writes
+                             generation/<which>_box_<which>_mask/<image id>.<ext>; the scene-graph encoder is not run
+    --layout_boxes pred|gt   with --layouts: which boxes of the rows to draw (default pred)
+
+The two modes without --split / --layouts deprocess with imagenet_deprocess whatever --img_deprocess says.
 
     python -m canonicalsg2im_amd.scripts.sample --dataset packed_coco --image_size 256,256 --batch_size 16 \\
         --checkpoint_name out/itr_100000.pt --output_dir samples --num_samples 64
+    python -m canonicalsg2im_amd.scripts.sample --dataset packed_clevr --image_size 256,256 --batch_size 16 \\
+        --checkpoint_name out/itr_100000.pt --output_dir val_pictures --split val --loader_num_workers 16
 """
 import os
 import sys
@@ -33,6 +56,12 @@ def build_parser():
     p.add_argument('--num_samples', default=16, type=int)
     p.add_argument('--scene_graphs', default=None, type=str)
     p.add_argument('--draw_boxes', default=1, type=int)
+    p.add_argument('--split', default=None, choices=["train", "val"])
+    p.add_argument('--max_pictures', default=0, type=int)
+    p.add_argument('--image_format', default="png", choices=["png", "jpg"])
+    p.add_argument('--num_writers', default=8, type=int)
+    p.add_argument('--layouts', default=None, type=str)
+    p.add_argument('--layout_boxes', default="pred", choices=["pred", "gt"])
     return p
 
 
@@ -44,7 +73,104 @@ def parse_args(argv=None):
         raise SystemExit("--checkpoint_name %s: no such file" % args.checkpoint_name)
     if args.scene_graphs is not None and not os.path.isfile(args.scene_graphs):
         raise SystemExit("--scene_graphs %s: no such file" % args.scene_graphs)
+    given = [flag for flag, v in (("--split", args.split), ("--layouts", args.layouts), ("--scene_graphs", args.scene_graphs))
+             if v is not None]
+    if len(given) > 1:
+        raise SystemExit("%s exclude each other: a run draws a dataset split, a file of layouts or authored graphs" % (
+            " and ".join(given)))
+    if args.split is not None or args.layouts is not None:
+        flag = given[0]
+        if args.checkpoint_name == _NO_CHECKPOINT:
+            raise SystemExit("%s needs --checkpoint_name: %s" % (flag, "the pictures of untrained weights are of no use to a metric"
+                                                                 if args.split else "the rows are read with the checkpoint's vocabulary"))
+        if args.img_deprocess not in ("decode_img", "imagenet"):
+            raise SystemExit("--img_deprocess %s: %s draws through decode_img or imagenet" % (args.img_deprocess, flag))
+        if args.max_pictures < 0 or not 1 <= args.num_writers <= 16:
+            raise SystemExit("--max_pictures must be >= 0 and --num_writers within 1 .. 16")
+    if args.layouts is not None:
+        if not os.path.isfile(args.layouts):
+            raise SystemExit("--layouts %s: no such file" % args.layouts)
+        if not args.output_dir:
+            raise SystemExit("--layouts needs --output_dir: the pictures are its whole result")
     return args
+
+
+def _rate_line(done, tic, sampler):
+    print("%d images in %.2f s  [%.1f img/s]  (%d replayed, %d eager calls)" % (
+        done, time.time() - tic, done / max(time.time() - tic, 1e-9), sampler.replays, sampler.eager_calls), flush=True)
+
+
+def split_dataset(args):
+    """--split: the folder dataset, or the end of the run — host only, before any device call."""
+    from ..sg2im.data import looked_for
+    from .train import folder_dataset
+    dataset = folder_dataset(args, args.split)
+    if dataset is None:
+        raise SystemExit("--split %s: no dataset folder at %s (--dataset %s); there is no synthetic stand-in for a split" % (
+            args.split, looked_for(args, args.split), args.dataset))
+    return dataset
+
+
+def sample_split(args, dev, dataset):
+    """--split: every picture of the folder through `split.generate_split`."""
+    import random
+
+    from ..sample import Sampler
+    from ..sg2im.data.loader import file_order_batches
+    from ..split import generate_split
+    from .args import init_args
+    from .evaluate import log_results
+    from .train import folder_builder, hold_to_vocab
+    ckpt = torch.load(args.checkpoint_name, map_location="cpu")
+    hold_to_vocab(dataset, ckpt.get("vocab") if isinstance(ckpt, dict) else None, args.split)
+    args.vocab = dataset.vocab
+    init_args(args)
+    print("data: %d pictures of %s" % (len(dataset), dataset.image_dir), flush=True)
+    torch.manual_seed(0)
+    sampler = Sampler(args, dev, ckpt)
+    # a Visual Genome builder samples objects: a stream seeded anew, so every run sees the same ones (scripts/evaluate.py)
+    builder = folder_builder(dataset, args, sampler, dev, rng=random.Random(0))
+    tic = time.time()
+    try:
+        metrics, rows = generate_split(
+            sampler, builder.batches(file_order_batches(len(dataset), args.batch_size)), args.output_dir,
+            deprocess=args.img_deprocess, draw_boxes=bool(args.draw_boxes), image_format=args.image_format,
+            num_writers=args.num_writers, max_pictures=args.max_pictures, split=args.split)
+    finally:
+        builder.close()
+    torch.cuda.synchronize()
+    if metrics:
+        log_results(metrics, ckpt.get("counters", {}).get("t", 0), "SPLIT %s" % args.split)
+    _rate_line(len(rows), tic, sampler)
+
+
+def sample_layouts(args, dev):
+    """--layouts: the rows of a layouts.json through `split.generate_layouts`."""
+    import json
+
+    from ..sample import Sampler
+    from ..split import encode_layouts, generate_layouts
+    from .args import init_args
+    ckpt = torch.load(args.checkpoint_name, map_location="cpu")
+    if not isinstance(ckpt, dict) or not isinstance(ckpt.get("vocab"), dict):
+        raise SystemExit("--checkpoint_name %s carries no vocabulary (no 'vocab' entry): --layouts cannot name its objects"
+                         % args.checkpoint_name)
+    args.vocab = ckpt["vocab"]
+    init_args(args)
+    with open(args.layouts, "r") as f:
+        rows = json.load(f)
+    rows = rows.get("images") if isinstance(rows, dict) else rows
+    try:
+        encode_layouts(rows, args.layout_boxes, args.vocab)
+    except ValueError as e:
+        raise SystemExit("--layouts %s: %s" % (args.layouts, e))
+    torch.manual_seed(0)
+    sampler = Sampler(args, dev, ckpt)
+    tic = time.time()
+    done = generate_layouts(sampler, rows, args.layout_boxes, args.output_dir, deprocess=args.img_deprocess,
+                            batch_size=args.batch_size, image_format=args.image_format, num_writers=args.num_writers)
+    torch.cuda.synchronize()
+    _rate_line(done, tic, sampler)
 
 
 def sample_scene_graphs(args, dev):
@@ -96,6 +222,7 @@ def sample_scene_graphs(args, dev):
 
 def main(argv=None):
     args = parse_args(argv)
+    dataset = split_dataset(args) if args.split is not None else None
     if not torch.cuda.is_available():
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
     from ..sample import Sampler
@@ -106,6 +233,10 @@ def main(argv=None):
     torch.cuda.set_device(dev)
     if args.scene_graphs is not None:
         return sample_scene_graphs(args, dev)
+    if args.split is not None:
+        return sample_split(args, dev, dataset)
+    if args.layouts is not None:
+        return sample_layouts(args, dev)
     args.vocab = make_vocab(_vocab_kind(args.dataset))
     init_args(args)
     torch.manual_seed(0)

@@ -60,6 +60,26 @@ def folder_dataset(args, split):
     return build_folder_dataset(args, split)
 
 
+def hold_to_vocab(ds, vocab, split):
+    """Refuse, on the host, a folder dataset whose categories, attribute tables or predicates differ from `vocab`, the
+    vocabulary the model was built with: its ids would index the model's embedding tables.  -> ds"""
+    if ds is None or vocab is None:
+        return ds
+    if ds.vocab["attributes"] != vocab["attributes"] and ds.vocab["object_name_to_idx"] == vocab["object_name_to_idx"]:
+        raise SystemExit("the %s split's attribute tables (%s rows) are not the model's (%s rows): train and validate on one "
+                         "vocabulary" % (split, [len(t) for t in ds.vocab["attributes"].values()],
+                                         [len(t) for t in vocab["attributes"].values()]))
+    if "pred_idx_to_name" in vocab and list(ds.vocab["pred_idx_to_name"]) != list(vocab["pred_idx_to_name"]):
+        raise SystemExit("the %s split's predicates (%d names) are not the model's (%d names): train and validate on one "
+                         "vocabulary" % (split, len(ds.vocab["pred_idx_to_name"]), len(vocab["pred_idx_to_name"])))
+    if ds.vocab["object_name_to_idx"] != vocab["object_name_to_idx"]:
+        raise SystemExit("the %s split's categories (%d names, largest id %d) are not the model's (%d names, largest id %d): "
+                         "train and validate on annotation files of one category set" % (
+                             split, len(ds.vocab["object_name_to_idx"]), max(ds.vocab["object_name_to_idx"].values()),
+                             len(vocab["object_name_to_idx"]), max(vocab["object_name_to_idx"].values())))
+    return ds
+
+
 def folder_builder(dataset, args, trainer, dev, rng=None):
     """The batch builder of a folder dataset, with --loader_num_workers threads.  `rng`: where a Visual Genome builder draws
     its object sampling (by default its own random.Random, seeded from the rank); the other datasets draw nothing."""

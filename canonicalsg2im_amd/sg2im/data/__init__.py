@@ -20,3 +20,16 @@ def build_folder_dataset(args, split):
     import importlib
     module, build = FOLDER_DATASETS[args.dataset]
     return getattr(importlib.import_module("." + module, __name__), build)(args, split)
+
+
+def looked_for(args, split):
+    """What `build_folder_dataset(args, split)` looks for, for the message of a caller that cannot go on without the folder:
+    the image directory of the split (the dataset module's own `split_image_dir`; Visual Genome also needs its split file)."""
+    if args.dataset not in FOLDER_DATASETS:
+        return "a folder dataset (--dataset %s names none: %s)" % (args.dataset, ", ".join(sorted(FOLDER_DATASETS)))
+    import importlib
+    where = importlib.import_module("." + FOLDER_DATASETS[args.dataset][0], __name__).split_image_dir(args, split)
+    if args.dataset == "packed_vg":
+        import os
+        where = "%s with %s (.h5 or .npz)" % (where, getattr(args, "%s_h5" % split) or os.path.join(args.dataroot, "vg", "%s.h5" % split))
+    return where

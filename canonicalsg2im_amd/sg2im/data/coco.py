@@ -34,7 +34,7 @@ import random
 import numpy as np
 
 from .loader import BatchBuilder
-from .packed_coco import _NO_MASKS, PackedCocoSceneGraphDataset
+from .packed_coco import _NO_MASKS, PackedCocoSceneGraphDataset, split_image_dir
 
 COCO_MIN_OBJECTS, COCO_MAX_OBJECTS = 3, 8                  # sg2im/data/dataset_params.py:132-133
 MAX_OBJECTS_PER_PICTURE = 255                              # csg_canon_general_*: 256 rows with __image__
@@ -134,7 +134,7 @@ def build_coco_pairs_dataset(args, split):
     the reference's layout under --dataroot (sg2im/data/dataset_params.py:142-152).  `val` with --coco_val_ids: the images
     of val2017 whose ids are on that JSON list."""
     root = os.path.join(args.dataroot, "MSCoco")
-    image_dir = getattr(args, "coco_%s_image_dir" % split) or os.path.join(root, "images", "%s2017" % split)
+    image_dir = split_image_dir(args, split)
     if not os.path.isdir(image_dir):
         return None
     if args.mask_size:

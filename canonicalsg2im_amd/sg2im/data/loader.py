@@ -17,6 +17,15 @@ def epoch_batches(n, per_rank, rank=0, world=1, seed=0, epoch=0, shuffle=True):
     return [[int(i) for i in order[s * step:(s + 1) * step][rank::world]] for s in range(n // step)]
 
 
+def file_order_batches(n, batch_size):
+    """The index lists of one pass over n samples in file order, not shuffled: the full batches of `epoch_batches` and then
+    the remainder as a last, shorter one (validation and the split walk: every sample once)."""
+    lists = epoch_batches(n, batch_size, shuffle=False)
+    if n % batch_size:
+        lists.append(list(range(n - n % batch_size, n)))
+    return lists
+
+
 class _Staging:
     """A pinned byte buffer that grows, and the event after which the device has read it."""
 

@@ -141,6 +141,11 @@ class ClevrBatchBuilder(BatchBuilder):
 PackedClevrDataset.builder_class = ClevrBatchBuilder
 
 
+def split_image_dir(args, split):
+    """Where the split's pictures are looked for: --clevr_<split>_image_dir, else the reference's layout under --dataroot."""
+    return getattr(args, "clevr_%s_image_dir" % split) or os.path.join(args.dataroot, "CLEVR", "CLEVR_Dialog", "images", split)
+
+
 def build_clevr_dataset(args, split):
     """The folder dataset of `split` ("train" / "val") named by the command line, or None when its image directory does not
     exist.  Paths: by default the reference's layout under --dataroot (sg2im/data/dataset_params.py:92-109): base =
@@ -149,7 +154,7 @@ def build_clevr_dataset(args, split):
     file; --clevr_<split>_image_dir names the directory that holds the split's pictures themselves."""
     base = os.path.join(args.dataroot, "CLEVR", "CLEVR_Dialog")
     given = getattr(args, "clevr_%s_image_dir" % split)
-    image_dir = given or os.path.join(base, "images", split)
+    image_dir = split_image_dir(args, split)
     if not os.path.isdir(image_dir):
         return None
     if args.mask_size:

@@ -137,12 +137,17 @@ class CocoBatchBuilder(BatchBuilder):
 PackedCocoSceneGraphDataset.builder_class = CocoBatchBuilder
 
 
+def split_image_dir(args, split):
+    """Where the split's pictures are looked for: --coco_<split>_image_dir, else the reference's layout under --dataroot."""
+    return getattr(args, "coco_%s_image_dir" % split) or os.path.join(args.dataroot, "MSCoco", "images", "%s2017" % split)
+
+
 def build_coco_dataset(args, split):
     """The folder dataset of `split` ("train" / "val") named by the command line, or None when its image directory does not
     exist.  Paths: --coco_<split>_image_dir / _instances_json / _stuff_json, by default the reference's layout under
     --dataroot (sg2im/data/dataset_params.py:75-84)."""
     root = os.path.join(args.dataroot, "MSCoco")
-    image_dir = getattr(args, "coco_%s_image_dir" % split) or os.path.join(root, "images", "%s2017" % split)
+    image_dir = split_image_dir(args, split)
     if not os.path.isdir(image_dir):
         return None
     if args.mask_size:

@@ -216,6 +216,11 @@ class VGBatchBuilder(BatchBuilder):
 PackedVGDataset.builder_class = VGBatchBuilder
 
 
+def split_image_dir(args, split):
+    """Where the pictures are looked for: --vg_image_dir when it exists, else <dataroot>/vg/images (every split's)."""
+    return args.vg_image_dir if args.vg_image_dir and os.path.isdir(args.vg_image_dir) else os.path.join(args.dataroot, "vg", "images")
+
+
 def build_vg_dataset(args, split):
     """The folder dataset of `split` ("train" / "val") named by the command line, or None when its image directory or its
     split file is not found.  Each path is the flag's value when that exists (--vg_image_dir, --train_h5 / --val_h5,
@@ -223,7 +228,7 @@ def build_vg_dataset(args, split):
     /train.h5 or /val.h5, /vocab.json; the split file is taken with either extension, .npz or .h5.  max_objects = 100 and
     min_objects = 16 as there, unless --max_objects / --min_objects say otherwise."""
     base = os.path.join(args.dataroot, "vg")
-    image_dir = args.vg_image_dir if args.vg_image_dir and os.path.isdir(args.vg_image_dir) else os.path.join(base, "images")
+    image_dir = split_image_dir(args, split)
     given = getattr(args, "%s_h5" % split)
     found = split_file(given) or split_file(os.path.join(base, "%s.h5" % split))
     if not os.path.isdir(image_dir) or found is None:

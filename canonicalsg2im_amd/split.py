@@ -1,0 +1,423 @@
+"""A dataset split -> pictures: per image id the real picture, the picture generated from the ground-truth layout and the
+one generated from the predicted layout (the reference's scripts/generation_attspade.py, whose folders gt/,
+generation/gt_box_gt_mask/ and generation/pred_box_pred_mask/ are what FID and the Inception score are computed from by
+outside tools), and pictures from a table of layouts alone (its scripts/generation_dataframe.py and layout_to_img.py).
+
+`generate_split(sampler, batches, out_dir, deprocess=...)` walks the trainer's 8-tuples (what `BatchBuilder.batches`
+yields) through calls this package already has, in this order per batch and under `no_grad`:
+
+    generation/gt_box_gt_mask     Sampler.generate(..., boxes_gt=boxes, masks_gt=masks)
+    generation/pred_box_pred_mask Sampler.generate(...)            (not with --skip_graph_model 1); boxes_pred is this call's
+    gt                            ops.deprocess_u8 of the batch's own images: the picture as the model saw it, resized and
+                                  normalised, through the same deprocess (generation_attspade.py:47,71)
+    layout/gt, layout/pred        with draw_boxes: `gt` under the ground-truth boxes, the predicted-layout picture under the
+                                  predicted ones (ops.draw_boxes_u8, palette and thickness of generate_from_graphs); outlines
+                                  never go into gt/ or generation/, which feed the metrics
+    ops.box_iou                   the per-object IoU and the running totals of Evaluator.check_model
+
+Nothing is read back inside the loop.  The uint8 pictures stay planar and leave, with the batch's ids, objects, boxes and
+IoU, in non-blocking copies to one of two pinned host buffers on a side stream (`PictureWriter`); a buffer whose copy has
+completed is handed to a pool of threads that join the planes (PIL.Image.merge) and encode the files (`FileWriter`) while
+the next batch is generated.  The threads make no HIP call (graphs.py captures on the loop's thread).  An error a thread
+meets — or the loop — ends the run: nothing is submitted after it, `close()` joins the threads and raises it.  A file's
+error surfaces one or two batches after the batch it belongs to, since that batch's files are written while the next is
+walked; no batch is walked after it has been seen.
+
+`rows` is one dictionary per image in the order generated — image_id, objects (names, as authored.py reads them),
+gt_boxes, predicted_boxes, iou, over the rows `box_iou` counts — and `layouts.json` holds them.  `generate_layouts` draws
+pictures from such rows with the generator alone: the scene-graph encoder is not run, so a generator-only checkpoint works.
+The rows carry boxes, not masks: a model that predicts masks draws its layouts from the boxes alone there.
+"""
+import json
+import math
+import os
+import queue
+import threading
+
+import torch
+
+from . import authored
+
+MAX_WRITER_THREADS = 16
+FORMATS = {"png": {}, "jpg": {"quality": 95}}
+SETS = ("gt", "generation/gt_box_gt_mask", "generation/pred_box_pred_mask", "layout/gt", "layout/pred")
+_BOX_KEYS = {"pred": "predicted_boxes", "gt": "gt_boxes"}
+
+
+def save_planar(array, path, **options):
+    """uint8 (3,H,W) planes -> an RGB file; the planes are joined here, on the host (PIL.Image.merge)."""
+    from PIL import Image                      # only here: importing the package never needs PIL
+    Image.merge("RGB", [Image.fromarray(p) for p in array]).save(path, **options)
+
+
+class FileWriter:
+    """(array, path) jobs -> files, in `num_threads` threads (1 .. 16, never sized from the machine's CPUs) behind a bounded
+    queue: `submit` blocks while the queue is full.  The first error a job raises is kept: jobs still queued are dropped,
+    `submit` raises it from then on, and `close()` — which joins the threads — raises it.  Host only: no thread makes a
+    device call.  `encode(array, path)` is the job, by default `save_planar` with the format's options."""
+
+    def __init__(self, num_threads=8, image_format="png", queue_size=None, encode=None):
+        if image_format not in FORMATS:
+            raise ValueError("image_format must be one of %s, got %r" % (" or ".join(repr(k) for k in FORMATS), image_format))
+        if int(num_threads) < 1:
+            raise ValueError("num_writers must be at least 1, got %r" % (num_threads,))
+        self.num_threads = min(int(num_threads), MAX_WRITER_THREADS)
+        options = FORMATS[image_format]
+        self.encode = encode if encode is not None else (lambda array, path: save_planar(array, path, **options))
+        self.jobs = queue.Queue(maxsize=int(queue_size) if queue_size else 4 * self.num_threads)
+        self.error = None
+        self._lock = threading.Lock()
+        self._closed = False
+        self.threads = [threading.Thread(target=self._run, name="csg-file-writer-%d" % i, daemon=True)
+                        for i in range(self.num_threads)]
+        for t in self.threads:
+            t.start()
+
+    def _run(self):
+        while True:
+            job = self.jobs.get()
+            try:
+                if job is None:
+                    return
+                if self.error is None:
+                    self.encode(*job)
+            except BaseException as e:                  # kept for the loop's thread, which raises it
+                with self._lock:
+                    if self.error is None:
+                        self.error = e
+            finally:
+                self.jobs.task_done()
+
+    def check(self):
+        if self.error is not None:
+            raise self.error
+
+    def submit(self, array, path, block=True):
+        """Queue one job.  block=False raises queue.Full instead of waiting for room."""
+        if self._closed:
+            raise RuntimeError("FileWriter.submit after close()")
+        self.check()
+        self.jobs.put((array, path), block=block)
+
+    def drain(self):
+        """Wait until every job submitted so far has been written or dropped; raises the kept error."""
+        self.jobs.join()
+        self.check()
+
+    def close(self, reraise=True):
+        """Join the threads (after the jobs queued so far); with `reraise` raise the first error a job met."""
+        if not self._closed:
+            self._closed = True
+            for _ in self.threads:
+                self.jobs.put(None)
+            for t in self.threads:
+                t.join()
+        if reraise:
+            self.check()
+
+
+class _Slot:
+    def __init__(self):
+        self.buf = self.event = self.views = self.refs = self.then = None
+
+
+class PictureWriter:
+    """Device tensors -> the host, beside the next batch.  `put({name: tensor}, then)` enqueues non-blocking copies of the
+    tensors into one of two pinned buffers on a side stream (`streams.beside`), ordered after the work that produced them,
+    and records an event behind them.  The batch put before it is handed over first: its event is waited for and
+    `then({name: numpy view})` runs on the caller's thread — it submits the file jobs, which read the views in place.  A
+    buffer is written again two puts later, after `files.drain()`.  `flush()` hands over what is still in flight."""
+
+    def __init__(self, device, files=None):
+        self.device = torch.device(device)
+        self.files = files
+        self.slots = [_Slot(), _Slot()]
+        self.turn = 0
+        self.inflight = []
+
+    def _hand_over(self):
+        slot = self.inflight.pop(0)
+        slot.event.synchronize()
+        then, views = slot.then, slot.views
+        slot.refs = slot.then = slot.views = None
+        then(views)
+
+    def put(self, tensors, then):
+        from . import streams
+        slot = self.slots[self.turn]
+        self.turn ^= 1
+        if self.files is not None:
+            self.files.drain()                          # the jobs that read this slot's buffer (two puts ago) are done
+        while self.inflight:                            # the previous batch: its jobs encode while this one is copied out
+            self._hand_over()
+        offsets, end = {}, 0
+        tensors = {k: t.contiguous() for k, t in tensors.items()}
+        for k, t in tensors.items():
+            offsets[k] = (end + 15) & ~15
+            end = offsets[k] + t.numel() * t.element_size()
+        if slot.buf is None or slot.buf.numel() < end:
+            slot.buf = torch.empty(int(end * 1.25) + 64, dtype=torch.uint8, pin_memory=True)
+        host = {k: slot.buf[offsets[k]:offsets[k] + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+                for k, t in tensors.items()}
+        with streams.beside("split_copy", self.device):
+            for k, t in tensors.items():
+                if t.numel():
+                    host[k].copy_(t, non_blocking=True)
+            slot.event = torch.cuda.Event()
+            slot.event.record()
+        # the device tensors are held until the hand-over: their blocks cannot be given out again under the copies
+        slot.refs, slot.then, slot.views = tensors, then, {k: v.numpy() for k, v in host.items()}
+        self.inflight.append(slot)
+
+    def flush(self):
+        while self.inflight:
+            self._hand_over()
+        if self.files is not None:
+            self.files.drain()
+
+
+def _finite_box(box):
+    return isinstance(box, (list, tuple)) and len(box) == 4 and all(
+        isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in box)
+
+
+def encode_layouts(rows, which, vocab):
+    """The host checks of `generate_layouts`, before any launch: `rows` (the `images` of a layouts.json) ->
+    [(image_id, object id rows [n][A], boxes [n][4])].  ValueError("layouts row <index>: ... <token>") for an unknown class
+    or attribute name, a row without the chosen boxes, mismatched lengths, a box that is not four finite numbers, a missing
+    or repeated image id."""
+    if which not in _BOX_KEYS:
+        raise ValueError("layouts: which must be 'pred' or 'gt', got %r" % (which,))
+    if not isinstance(rows, list) or len(rows) == 0:
+        raise ValueError("layouts: a non-empty list of rows is needed")
+    key = _BOX_KEYS[which]
+    out, seen = [], set()
+    for index, row in enumerate(rows):
+        bad = lambda what, index=index: ValueError("layouts row %d: %s" % (index, what))
+        if not isinstance(row, dict) or not isinstance(row.get("objects"), list):
+            raise bad("a row is {\"image_id\": ..., \"objects\": [...], %r: [...]}, got %r" % (key, row))
+        image_id = row.get("image_id")
+        if isinstance(image_id, bool) or not isinstance(image_id, (int, str)):
+            raise bad("image_id %r is neither an integer nor a string" % (image_id,))
+        if image_id in seen:
+            raise bad("image_id %r a second time: it would overwrite a file" % (image_id,))
+        seen.add(image_id)
+        ids = authored.object_ids(row["objects"], vocab, bad)
+        boxes = row.get(key)
+        if not isinstance(boxes, list):
+            raise bad("no %r" % key)
+        if len(boxes) != len(ids):
+            raise bad("%d objects but %d %s" % (len(ids), len(boxes), key))
+        for k, box in enumerate(boxes):
+            if not _finite_box(box):
+                raise bad("%s[%d] = %r is not four finite numbers" % (key, k, box))
+        out.append((image_id, ids, [[float(v) for v in box] for box in boxes]))
+    return out
+
+
+def layout_batch(samples, vocab):
+    """[(image_id, id rows, boxes)] -> (objs int64 (B,O,A), boxes fp32 (B,O,4)) on the host as a dataset batch carries them:
+    a sample's real objects, then its `__image__` row with box -1, then rows of 0 with box -1 up to O = the most objects of
+    a sample + 1 (sg2im/data/collate.py)."""
+    names = list(vocab["attributes"].keys())
+    image_row = [vocab["attributes"][a]["__image__"] for a in names]
+    B, O = len(samples), max(len(ids) for _, ids, _ in samples) + 1
+    objs = torch.zeros((B, O, len(names)), dtype=torch.int64)
+    boxes = torch.full((B, O, 4), -1.0, dtype=torch.float32)
+    for b, (_, ids, bx) in enumerate(samples):
+        n = len(ids)
+        if n:
+            objs[b, :n] = torch.tensor(ids, dtype=torch.int64)
+            boxes[b, :n] = torch.tensor(bx, dtype=torch.float64).to(torch.float32)
+        objs[b, n] = torch.tensor(image_row, dtype=torch.int64)
+    return objs, boxes
+
+
+class _Paths:
+    """<out_dir>/<set>/<image_id>.<ext> (the reference's "{}/{}.jpg".format(path, image_ids[i])); a set's directory is
+    made when its first picture is."""
+
+    def __init__(self, out_dir, ext):
+        self.out_dir, self.ext = out_dir, ext
+        self.made = set()
+
+    def of(self, name, image_id):
+        d = os.path.join(self.out_dir, *name.split("/"))
+        if d not in self.made:
+            os.makedirs(d, exist_ok=True)
+            self.made.add(d)
+        return os.path.join(d, "%s.%s" % (image_id, self.ext))
+
+
+class SplitRows:
+    """The host half of the split walk, batch by batch: `take({name: numpy array})` — image_id (B,), objs (B,O,A), boxes
+    (B,O,4), with a graph model boxes_pred, iou and counted, and the uint8 (B,3,H,W) pictures under their SETS names — adds
+    one row per image to `rows` and submits the pictures' files.  An image id seen a second time raises before anything of
+    that sample is written."""
+
+    def __init__(self, vocab, files=None, paths=None):
+        self.vocab, self.files, self.paths = vocab, files, paths
+        self.image_id_obj = vocab["object_name_to_idx"]["__image__"]
+        self.rows, self.seen = [], set()
+
+    def take(self, host):
+        objs, boxes = host["objs"], host["boxes"]
+        counted = host["counted"].astype(bool) if "counted" in host else \
+            (boxes != -1).any(-1) & (objs[..., 0] != self.image_id_obj)        # remove_dummies_and_padding's rule
+        for i, image_id in enumerate(host["image_id"].tolist()):
+            if image_id in self.seen:
+                raise ValueError("image id %r a second time in one run: it would overwrite a file" % (image_id,))
+            self.seen.add(image_id)
+            keep = counted[i]
+            row = {"image_id": image_id, "objects": authored.object_names(objs[i][keep].tolist(), self.vocab),
+                   "gt_boxes": boxes[i][keep].tolist()}
+            if "boxes_pred" in host:
+                row["predicted_boxes"] = host["boxes_pred"][i][keep].tolist()
+                row["iou"] = host["iou"][i][keep].tolist()
+            self.rows.append(row)
+            if self.paths is not None:
+                for name in SETS:
+                    if name in host:
+                        self.files.submit(host[name][i], self.paths.of(name, image_id))
+
+
+def _cut(batch, n):
+    return [x[:n] if torch.is_tensor(x) else (None if x is None else list(x)[:n]) for x in batch]
+
+
+def _open_writers(sampler, out_dir, image_format, num_writers):
+    if image_format not in FORMATS:
+        raise ValueError("image_format must be one of %s, got %r" % (" or ".join(repr(k) for k in FORMATS), image_format))
+    files = FileWriter(num_writers, image_format) if out_dir else None
+    return files, PictureWriter(sampler.device, files), (_Paths(out_dir, image_format) if out_dir else None)
+
+
+def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, draw_boxes=False, thickness=2,
+                   image_format="png", num_writers=8, max_pictures=0, split=None):
+    """Walk `batches` (see the module docstring) -> (metrics, rows).  metrics: avg_iou, total_iou_05, total_iou_03 (the
+    totals / counted boxes, float64, as Evaluator.check_model forms them) and num_boxes; empty for a model without a graph
+    part.  With `out_dir` the pictures and layouts.json are written; without it only metrics and rows are made.
+    `max_pictures`: stop after that many images (a batch may be cut; 0: all).  `split`: the name layouts.json records."""
+    from . import ops
+    from .sample import NO_CPU
+    if sampler.device.type != "cuda":
+        raise RuntimeError(NO_CPU)
+    if deprocess not in ops.DEPROCESS:
+        raise ValueError("generate_split: deprocess must be one of %s, got %r" % (
+            " or ".join(repr(k) for k in ops.DEPROCESS), deprocess))
+    model, vocab, dev = sampler.model, sampler.opt.vocab, sampler.device
+    image_id_obj = vocab["object_name_to_idx"]["__image__"]
+    files, pictures, paths = _open_writers(sampler, out_dir, image_format, num_writers)
+    totals = torch.zeros(4, device=dev, dtype=torch.float64)
+    palette = torch.tensor(authored.DEFAULT_PALETTE, dtype=torch.uint8).reshape(-1, 3).to(dev) if draw_boxes else None
+    taker = SplitRows(vocab, files, paths)
+    rows, done = taker.rows, 0
+    raising = True
+    try:
+        with torch.no_grad():
+            for batch in batches:
+                if files is not None:
+                    files.check()
+                if max_pictures and done + int(batch[1].shape[0]) > max_pictures:
+                    batch = _cut(batch, max_pictures - done)
+                imgs, objs, boxes, triplets, _, triplet_type, masks, image_ids = batch
+                if not objs.is_cuda:
+                    raise RuntimeError(NO_CPU)
+                out = {}
+                u8 = sampler.generate(objs, triplets, triplet_type, boxes_gt=boxes, masks_gt=masks, rescale=rescale,
+                                      deprocess=deprocess)[0]
+                if u8 is not None:
+                    out["generation/gt_box_gt_mask"] = u8
+                boxes_pred = None
+                if model.has_graph:
+                    u8, boxes_pred, _ = sampler.generate(objs, triplets, triplet_type, rescale=rescale, deprocess=deprocess)
+                    if u8 is not None:
+                        out["generation/pred_box_pred_mask"] = u8
+                if imgs is not None:
+                    out["gt"] = ops.deprocess_u8(imgs.float().contiguous(memory_format=torch.channels_last), rescale, deprocess)
+                if draw_boxes:
+                    if "gt" in out:
+                        out["layout/gt"] = ops.draw_boxes_u8(out["gt"], boxes.float(), objs, image_id_obj, palette, thickness)
+                    if "generation/pred_box_pred_mask" in out:
+                        out["layout/pred"] = ops.draw_boxes_u8(out["generation/pred_box_pred_mask"], boxes_pred.detach().float(),
+                                                               objs, image_id_obj, palette, thickness)
+                if paths is None:
+                    out = {}                            # nothing to write: the pictures stay where they are
+                ids = image_ids if torch.is_tensor(image_ids) else torch.as_tensor(image_ids)
+                out.update({"image_id": ids.to(dev, non_blocking=True).reshape(-1).to(torch.int64), "objs": objs,
+                            "boxes": boxes.float()})
+                if boxes_pred is not None:
+                    iou, counted, _ = ops.box_iou(boxes_pred, boxes, objs, image_id_obj, totals)
+                    out.update({"boxes_pred": boxes_pred.detach().float(), "iou": iou, "counted": counted})
+                pictures.put(out, taker.take)
+                done += int(objs.shape[0])
+                if max_pictures and done >= max_pictures:
+                    break
+            pictures.flush()
+            metrics = {}
+            if model.has_graph and rows:
+                t = totals.cpu()                        # the one read of the totals, at the end
+                metrics = {"avg_iou": float(t[0] / t[3]), "total_iou_05": float(t[1] / t[3]), "total_iou_03": float(t[2] / t[3]),
+                           "num_boxes": float(t[3])}
+        raising = False
+    finally:
+        if files is not None:
+            files.close(reraise=not raising)            # an error already on its way is not replaced by the writer's
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "layouts.json"), "w") as f:
+            json.dump({"dataset": getattr(sampler.opt, "dataset", None), "split": split,
+                       "image_size": [int(v) for v in sampler.opt.image_size], "deprocess": deprocess, "rescale": bool(rescale),
+                       "metrics": metrics, "images": rows}, f)
+    return metrics, rows
+
+
+def generate_layouts(sampler, rows, which="pred", out_dir=None, *, deprocess, rescale=True, batch_size=None,
+                     image_format="png", num_writers=8):
+    """Pictures from layout rows with the generator alone (the reference's generation_dataframe.py --mode pred|gt): the
+    rows' objects go through the sampler's vocabulary, `batch_size` rows (default --batch_size) at a time in file order, and
+    `sampler.generate(objs, None, None, boxes_gt=boxes)` sees the tensors a dataset batch would give (`layout_batch`).
+    With `out_dir` the pictures go to generation/<which>_box_<which>_mask/<image_id>.<ext> and the number written is
+    returned; without it the pictures are returned, uint8 (N,3,H,W) on the host.  Every row is checked first
+    (`encode_layouts`): nothing is launched for a file with a bad row."""
+    from . import ops
+    from .sample import NO_CPU
+    if deprocess not in ops.DEPROCESS:
+        raise ValueError("generate_layouts: deprocess must be one of %s, got %r" % (
+            " or ".join(repr(k) for k in ops.DEPROCESS), deprocess))
+    samples = encode_layouts(rows, which, sampler.opt.vocab)
+    if sampler.device.type != "cuda":
+        raise RuntimeError(NO_CPU)
+    step = int(batch_size or sampler.opt.batch_size)
+    if step < 1:
+        raise ValueError("generate_layouts: batch_size must be positive")
+    name = "generation/%s_box_%s_mask" % (which, which)
+    files, pictures, paths = _open_writers(sampler, out_dir, image_format, num_writers)
+    kept = []
+
+    def on_host(host):
+        for i, image_id in enumerate(host["ids"]):
+            if paths is None:
+                kept.append(torch.from_numpy(host["u8"][i]).clone())
+            else:
+                files.submit(host["u8"][i], paths.of(name, image_id))
+
+    raising = True
+    try:
+        for first in range(0, len(samples), step):
+            if files is not None:
+                files.check()
+            chunk = samples[first:first + step]
+            objs, boxes = layout_batch(chunk, sampler.opt.vocab)
+            u8 = sampler.generate(objs.to(sampler.device), None, None, boxes_gt=boxes.to(sampler.device), rescale=rescale,
+                                  deprocess=deprocess)[0]
+            if u8 is None:
+                raise RuntimeError("generate_layouts needs a model that generates pictures (--skip_generation 0)")
+            ids = [s[0] for s in chunk]
+            pictures.put({"u8": u8}, lambda host, ids=ids: on_host(dict(host, ids=ids)))
+        pictures.flush()
+        raising = False
+    finally:
+        if files is not None:
+            files.close(reraise=not raising)
+    return len(samples) if paths is not None else torch.stack(kept)
