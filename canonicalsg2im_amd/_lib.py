@@ -222,6 +222,10 @@ SIGNATURES = {
     "csg_canon_general_converse": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "csg_canon_general_close": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_i32, c_p, c_i64, c_p, c_p]),
     "csg_canon_general_emit": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "csg_canon_small_workspace": (c_i64, [c_i64, c_i64]),
+    "csg_canon_small_build": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                      c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p]),
+    "csg_canon_small_emit": (c_i32, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
 }
 
 

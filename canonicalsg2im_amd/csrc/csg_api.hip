@@ -126,13 +126,14 @@ static const char* kNames[K_COUNT] = {
     "few_fwd",        "few_bwd_data",   "few_bwd_weight",
     "wino4_conv",     "wino4_wgrad",
     "gemm_nt",        "gemm_tn",
-    "norm_eval_stats", "deprocess_u8", "box_iou", "preprocess", "clevr_boxes", "vg_rows", "draw_boxes_u8"};
+    "norm_eval_stats", "deprocess_u8", "box_iou", "preprocess", "clevr_boxes", "vg_rows", "draw_boxes_u8",
+    "canon_small_build", "canon_small_emit"};
 
 }  // namespace csg
 
 extern "C" {
 
-int csg_version(void) { return 116; }
+int csg_version(void) { return 117; }
 const char* csg_last_error(void) { return csg::g_err; }
 
 int csg_prof_enable(int on) {

@@ -68,6 +68,8 @@ enum KernelId {
   K_CLEVR_BOXES,
   K_VG_ROWS,
   K_DRAW_BOXES,
+  K_CANON_SMALL_BUILD,
+  K_CANON_SMALL_EMIT,
   K_COUNT
 };
 

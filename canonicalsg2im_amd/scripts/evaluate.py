@@ -130,7 +130,7 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     val_set = folder_val_set(args)
-    if val_set is not None and args.dataset == "packed_vg":        # vocab.json is a file of its own: hold it to the checkpoint's
+    if val_set is not None and args.dataset in ("packed_vg", "vg"):   # vocab.json is a file of its own: hold it to the checkpoint's
         val_set = folder_val_set(args, torch.load(args.checkpoint_name, map_location="cpu").get("vocab"))
     args.vocab = val_set.vocab if val_set is not None else make_vocab(_vocab_kind(args.dataset))
     print("data: %s" % ("%d pictures of %s" % (len(val_set), val_set.image_dir) if val_set is not None

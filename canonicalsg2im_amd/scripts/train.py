@@ -23,7 +23,11 @@ and the annotated relationships join the canonical graph (sg2im/data/packed_vg.p
 a .h5 split needs h5py, a .npz split does not: tools/vg_h5_to_npz.py).  `--dataset coco`, the default, reads the COCO folder
 of `packed_coco` with the original sg2im graph: 3 to 8 objects, every object draws one partner on the host and the pair's
 predicate and the graph are made on the device (sg2im/data/coco.py of this package; `--mask_size` must be 0; `--coco_val_ids`
-names the val split's image ids).  Without the directory, and for every other dataset,
+names the val split's image ids).  `--dataset vg` reads the unpacked Visual Genome folder, <dataroot>/VisualGenome with the
+pictures, train.h5 or train.npz and vocab.json in it (or `--vg_image_dir`, `--train_h5`, `--vocab_json` where they exist), with
+`packed_vg`'s object choice and boxes and the reference's annotated-only graph: the annotated relationships and the dummies,
+no location relation, at most 63 objects per picture (sg2im/data/vg.py of this package; `--mask_size` must be 0).  Without
+the directory, and for every other dataset,
 the batches are seeded synthetic ones of the chosen dataset's shape.  One line says which of the two it is.
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as

@@ -1,14 +1,15 @@
 """Device-side pieces of the reference's data pipeline (sg2im/data/*): the canonical graph construction of the packed
 datasets — the O(O^3) numpy/python step that feeds the hot path — and the folder datasets that feed it pictures: the three
-packed ones and the default `coco` with its sampled-pair graph."""
+packed ones, the default `coco` with its sampled-pair graph and `vg` with its annotated-only graph."""
 from .base_dataset import (ANTI_SYMMETRIC_EDGE, ORIGINAL_EDGE, SYMMETRIC_EDGE, TRANSITIVE_EDGE,  # noqa: F401
-                           augmented_relations, canonical_triplets, meta_relations, register_augmented_relations)
+                           annotated_triplets, augmented_relations, canonical_triplets, meta_relations, register_augmented_relations)
 
 FOLDER_DATASETS = {        # --dataset -> (the module of this package that holds it, the module's build_*_dataset)
     "coco": ("coco", "build_coco_pairs_dataset"),
     "packed_coco": ("packed_coco", "build_coco_dataset"),
     "packed_clevr": ("packed_clevr", "build_clevr_dataset"),
     "packed_vg": ("packed_vg", "build_vg_dataset"),
+    "vg": ("vg", "build_vg_unpacked_dataset"),
 }
 
 
@@ -28,8 +29,11 @@ def looked_for(args, split):
     if args.dataset not in FOLDER_DATASETS:
         return "a folder dataset (--dataset %s names none: %s)" % (args.dataset, ", ".join(sorted(FOLDER_DATASETS)))
     import importlib
-    where = importlib.import_module("." + FOLDER_DATASETS[args.dataset][0], __name__).split_image_dir(args, split)
+    module = importlib.import_module("." + FOLDER_DATASETS[args.dataset][0], __name__)
+    where = module.split_image_dir(args, split)
     if args.dataset == "packed_vg":
         import os
         where = "%s with %s (.h5 or .npz)" % (where, getattr(args, "%s_h5" % split) or os.path.join(args.dataroot, "vg", "%s.h5" % split))
+    if args.dataset == "vg":
+        where = "%s with %s (.h5 or .npz)" % (where, module.split_path(args, split))
     return where

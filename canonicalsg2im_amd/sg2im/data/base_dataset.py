@@ -142,6 +142,82 @@ def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learn
     return out, conv_counts, triplet_type
 
 
+def annotated_triplets(objs, n_objs, vocab, rows, rows_host=None, learned_transitivity=False, include_dummies=True,
+                       learned_converse=False, converse_weights=None, uniforms=None):
+    """`add_dummy_triplets` + `add_learnt_triplets` + the collate's padding for graphs that are their annotated rows alone
+    (reference sg2im/data/vg.py:136-149 and vg_collate_fn): no geometry and no location relation, every predicate but
+    `__padding__` and `__in_image__` is an ordinary non-meta one — whether or not the vocabulary has location predicates.
+
+    objs (B,O) or (B,O,A) int64 on the device; n_objs (B,) = rows per sample with its `__image__` row, at most 64, on the host
+    (a device tensor is read back); rows (B,R,3) int64 in local indices, rows of `__padding__` are padding; `rows_host`:
+    their host copy, which spares the read-back when `rows` is on the device.  Returns (triplets (B,T,3), conv_counts
+    (B,P,P+1) float32, triplet_type (B,T)) as canonical_triplets does, equal to its general kernels' on the same rows.
+
+    Two launches (csrc/canon_small.hip) around the one 16-byte-per-sample read-back of the counts.  With `learned_converse`
+    the number of draws of a sample — its distinct rows of non-meta predicates — is counted here, on the host, from
+    `rows_host`; that many numbers are taken from numpy's GLOBAL stream, or from `uniforms`, as canonical_triplets does."""
+    objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
+    dev = objs0.device
+    B, O = objs0.shape
+    first = list(vocab["attributes"].keys())[0]
+    image_id = vocab["object_name_to_idx"]["__image__"]
+    if vocab["attributes"][first]["__image__"] != image_id:
+        raise ValueError("the __image__ id of the first attribute and of object_name_to_idx differ")
+    p2i = vocab["pred_name_to_idx"]
+    P, pad, in_image = len(p2i), p2i["__padding__"], p2i["__in_image__"]
+    rel_h = _host_int64(rows if rows_host is None else rows_host)
+    if rel_h.dim() != 3 or rel_h.shape[0] != B or rel_h.shape[2] != 3 or tuple(rows.shape) != tuple(rel_h.shape):
+        raise ValueError("rows must be (B, R, 3), and rows_host of the same shape; got %s and %s" % (
+            tuple(rows.shape), tuple(rel_h.shape)))
+    R = rel_h.shape[1]
+    rel_d = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous()
+    n_host = _host_int64(n_objs)
+    n_dev = (n_objs if torch.is_tensor(n_objs) and n_objs.device == dev else n_host).to(device=dev, dtype=torch.int64).contiguous()
+    nbytes = lib.csg_canon_small_workspace(B, P)
+    if nbytes < 0:
+        raise RuntimeError("annotated_triplets: at most 256 predicates (the vocabulary has %d)" % P)
+    ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    counts = torch.empty((B, 2), device=dev, dtype=torch.int64)
+    conv_counts = torch.zeros((B, P, P + 1), device=dev, dtype=torch.float32)        # base_dataset.py:93
+    cdf_d = u_d = off_d = None
+    total = 0
+    if learned_converse:
+        if converse_weights is None:
+            raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
+        w = converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
+        rel_np = rel_h.numpy()
+        draws = torch.zeros(B, dtype=torch.int64)
+        for b in range(B):                                            # np.unique of a sample's rows, meta predicates apart
+            r = rel_np[b]
+            r = r[(r[:, 1] != pad) & (r[:, 1] != in_image)]
+            draws[b] = len(np.unique(r, axis=0)) if len(r) else 0
+        u, u_off = _draw_numbers(draws, uniforms)
+        total = int(draws.sum())
+        non_meta = [p for p in range(P) if p not in (pad, in_image)]
+        cdf = np.zeros((P, len(non_meta)), np.float64)
+        for rel_id in non_meta:                                       # graphs_utils.py:126-140, candidates ascending
+            cdf[rel_id] = _choice_cdf(w, rel_id, [c for c in non_meta if c != rel_id])
+        cdf_d, u_d, off_d = torch.from_numpy(cdf).to(dev), torch.from_numpy(u).to(dev), u_off.to(dev)
+    check(lib.csg_canon_small_build(ptr(objs0), ptr(n_dev), ctypes.c_void_p(n_host.data_ptr()), B, O,
+                                    ptr(rel_d) if R else None, ctypes.c_void_p(rel_h.data_ptr()) if R else None, R, P, pad,
+                                    in_image, image_id, 1 if include_dummies else 0, 1 if learned_transitivity else 0,
+                                    ptr(cdf_d) if learned_converse else None, ptr(u_d) if learned_converse else None,
+                                    ptr(off_d) if learned_converse else None, total,
+                                    ptr(conv_counts) if learned_converse else None, ptr(ws), nbytes, ptr(counts), stream()),
+          "canon_small_build")
+    counts_host = counts.cpu()                       # the one read-back: vg_collate_fn pads to the longest sample
+    bad = (counts_host[:, 0] < 0).nonzero()
+    if bad.numel():
+        raise RuntimeError("annotated_triplets: the rows of sample %d on the device are not the rows the host holds: one lies "
+                           "outside [0, n_objs) or outside the vocabulary; no graph was written" % int(bad[0, 0]))
+    T = int(counts_host.sum(dim=1).max())
+    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
+    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
+    check(lib.csg_canon_small_emit(B, P, pad, ptr(ws), nbytes, ptr(counts), T, ptr(out), ptr(triplet_type), stream()),
+          "canon_small_emit")
+    return out, conv_counts, triplet_type
+
+
 def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transitivity=False, include_dummies=True,
                        learned_converse=False, converse_weights=None, uniforms=None, triplets=None, pairs=None,
                        use_converse=False, pairs_host=None):
@@ -164,7 +240,8 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     predicates are more than the six location relations (the converse candidates are then all other non-meta predicates,
     scripts/graphs_utils.py:126-152), the general kernels run (csg_canon_general_*, one (sample, predicate) bit matrix
     per block).  They read `triplets` and `n_objs` on the host: pass CPU tensors (or arrays) to spare a copy.
-    Otherwise the location-only kernels run, as before.
+    Otherwise the location-only kernels run, as before.  With `boxes=None` and a vocabulary that lacks any of the six location
+    predicates (the unpacked Visual Genome's), `triplets` go to `annotated_triplets`: at most 64 rows per sample.
 
     `boxes=None` (and `obj_centers=None`), with `triplets`: a graph without geometry (canonicalsg2im_amd/authored.py).  No
     location relation is derived; the given rows — which may carry location predicates and `__in_image__` — are the
@@ -177,13 +254,19 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     coco.py:404-421), the rows stay on the device (csg_canon_general_build_dev) and dummies, converse draws, transitive
     extras, order and padding follow as above.  The tensors may be on the host or the device; the host needs them
     (refusals): `pairs_host` = their CPU copies spares the read-back of device tensors."""
+    p2i = vocab["pred_name_to_idx"]
+    if boxes is None and obj_centers is None and triplets is not None and pairs is None \
+            and any(name not in p2i for name in augmented_relations):
+        # a vocabulary without the location predicates (the unpacked Visual Genome's): the rows alone, at most 64 per sample
+        return annotated_triplets(objs, n_objs, vocab, triplets, learned_transitivity=learned_transitivity,
+                                  include_dummies=include_dummies, learned_converse=learned_converse,
+                                  converse_weights=converse_weights, uniforms=uniforms)
     objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
     first = list(vocab["attributes"].keys())[0]
     image_id = vocab["object_name_to_idx"]["__image__"]
     if vocab["attributes"][first]["__image__"] != image_id:
         raise ValueError("the __image__ id of the first attribute and of object_name_to_idx differ")
     B, O = objs0.shape
-    p2i = vocab["pred_name_to_idx"]
     names = meta_relations + augmented_relations
     if (boxes is None) != (obj_centers is None) or (boxes is None and triplets is None):
         raise ValueError("canonical_triplets: boxes=None needs obj_centers=None and the graph's rows in `triplets`")

@@ -10,9 +10,19 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     (its objects live on the device: deriving the counts from them would be a read-back per batch); by default they are
     derived from the objects, as before.  The unpacked coco dataset hands over, in the triplet slot, the pairs its builder
     drew: (other, flip) on the device and their host copies (None with --include_relationships 0: the dummies alone,
-    sg2im/data/coco.py:374-375); its graph is the sampled rows, not the all-pairs relations of the geometry."""
-    from . import canonical_triplets
-    rel = pairs = None
+    sg2im/data/coco.py:374-375); its graph is the sampled rows, not the all-pairs relations of the geometry.  The unpacked vg
+    dataset hands over its annotated rows, on the device and on the host: they and the dummies are its whole graph
+    (sg2im/data/vg.py:136-149), built by annotated_triplets."""
+    from . import annotated_triplets, canonical_triplets
+    rel = pairs = rows = None
+    if args.dataset == "vg":
+        if counts is None:
+            raise ValueError("packed_batch: a vg batch comes from VGAnnotatedBatchBuilder, with the objects per sample")
+        batch = list(batch)
+        rows, batch[3] = batch[3], None
+        if not args.include_relationships:                 # vg.py:138-139
+            rows = tuple(t[:, :0] for t in rows)
+        n = counts + 1
     if args.dataset == "coco":
         if counts is None:
             raise ValueError("packed_batch: a coco batch comes from CocoPairsBatchBuilder, with the objects per sample")
@@ -27,7 +37,7 @@ def packed_batch(args, trainer, batch, dev, counts=None):
         n = n + 1                                           # real objects + the __image__ row appended below
     batch = [None if x is None else x.to(dev) for x in batch]
     objs, boxes = batch[1], batch[2]
-    if rel is None and pairs is None:
+    if rel is None and pairs is None and rows is None:
         n = ((objs[..., 0] != 0).sum(1) if counts is None else counts.to(dev)) + 1
     O = objs.shape[1] + 1
     objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
@@ -46,6 +56,14 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     if args.learned_converse:    # the data loader reads the model's converse weights back (scripts/train.py:274-276)
         from ..model import get_conv_converse
         conv_w = get_conv_converse(trainer.model).detach().cpu().numpy()
+    if rows is not None:
+        batch[3], batch[4], batch[5] = annotated_triplets(objs, n, args.vocab, rows[0].contiguous(),
+                                                          rows_host=rows[1].contiguous(),
+                                                          learned_transitivity=bool(args.learned_transitivity),
+                                                          learned_converse=bool(args.learned_converse),
+                                                          converse_weights=conv_w)
+        assert batch[3].shape[1] > 0 and objs.shape[1] == O
+        return batch
     batch[3], batch[4], batch[5] = canonical_triplets(objs, boxes, centers, n, args.vocab,
                                                       learned_transitivity=bool(args.learned_transitivity),
                                                       learned_converse=bool(args.learned_converse),

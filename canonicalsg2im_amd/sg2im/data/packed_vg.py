@@ -84,11 +84,7 @@ class PackedVGDataset:
     def __init__(self, split_path, image_dir, vocab_json, image_size=(64, 64), mask_size=0, normalize_images=True,
                  min_objects=0, max_objects=1000, max_samples=None, include_relationships=True, use_orphaned_objects=True,
                  use_transitivity=False, use_converse=False):
-        if use_transitivity or use_converse:
-            raise NotImplementedError("PackedVGDataset: use_transitivity / use_converse are not implemented, as in the "
-                                      "reference (sg2im/data/packed_vg.py:40-41)")
-        if mask_size:
-            raise NotImplementedError(_NO_MASKS % mask_size)
+        self.check_flags(use_transitivity, use_converse, mask_size, int(max_objects))
         self.image_dir = image_dir
         self.image_size = tuple(image_size)
         self.normalize_images = bool(normalize_images)
@@ -112,6 +108,18 @@ class PackedVGDataset:
         self.image_ids = [int(p.split("/")[-1].split(".")[0]) for p in self.image_paths]  # :78
         self.vocab["attributes"] = {"objects": self.vocab["object_name_to_idx"]}        # :60-64
         self.vocab["reverse_attributes"] = {a: {v: k for k, v in t.items()} for a, t in self.vocab["attributes"].items()}
+        self.add_predicates()
+
+    def check_flags(self, use_transitivity, use_converse, mask_size, max_objects):
+        """What the constructor refuses before it reads a file."""
+        if use_transitivity or use_converse:
+            raise NotImplementedError("PackedVGDataset: use_transitivity / use_converse are not implemented, as in the "
+                                      "reference (sg2im/data/packed_vg.py:40-41)")
+        if mask_size:
+            raise NotImplementedError(_NO_MASKS % mask_size)
+
+    def add_predicates(self):
+        """The predicates the constructor adds to vocab.json's."""
         register_augmented_relations(self.vocab)                                        # :65
 
     def __len__(self):

@@ -50,7 +50,8 @@ extern "C" {
  * 113: csg_preprocess_px_workspace, csg_preprocess_px, csg_clevr_boxes;
  * 114: csg_vg_rows;
  * 115: csg_draw_boxes_u8; csg_canon_general_build takes boxes = centers = NULL;
- * 116: csg_pair_relations, csg_canon_general_build_dev) */
+ * 116: csg_pair_relations, csg_canon_general_build_dev;
+ * 117: csg_canon_small_workspace, csg_canon_small_build, csg_canon_small_emit) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -790,6 +791,36 @@ int csg_canon_general_build_dev(const int64_t* objs0, const float* boxes, const 
                                 int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
                                 const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
                                 int64_t workspace_bytes, int64_t* counts, void* stream);
+
+/* ---- canonical graphs of at most 64 rows per sample from annotated rows alone (reference sg2im/data/vg.py:136-149) ------
+ * The unpacked Visual Genome dataset: the annotated rows and the __in_image__ dummies through add_learnt_triplets.  No
+ * role table and no geometry: every predicate but pid_padding and pid_in_image is an ordinary non-meta predicate (a
+ * vocabulary that has __left of__ is served the same way), and the output equals csg_canon_general_build(boxes = NULL) /
+ * [_converse] / _close / _emit on the same rows, bit for bit.  A sample is one block and a predicate's 64x64 bit matrix one
+ * 64-bit register per lane of a wave; csg_canon_small_build is ONE launch (scatter, draws, converse, closure, offsets),
+ * csg_canon_small_emit a second one after the caller has read counts back for T = max_b(counts[b][0] + counts[b][1]).
+ *   objs0 (B,O) int64 and n_objs (B,) int64 (rows per sample incl. __image__): device; n_objs_host: its host copy.
+ *   rel (B,R,3) int64 in local indices: device, 8-byte aligned; rel_host: its host copy.  Rows of __padding__ are padding.
+ *   cdf = NULL: no converse draws.  Otherwise cdf (P, K = P - 2) float64, uniforms, u_off (B,) int64 and conv_counts
+ *   (B, P, P + 1) float32 (zero-initialised by the caller) as for csg_canon_general_converse, all on the device, and
+ *   n_uniforms = the length of `uniforms`: the host counts a sample's draws itself, its distinct rows of non-meta
+ *   predicates, so nothing is read back between the phases.
+ *   counts (B,2) int64 (device) = {original triplets, transitive triplets}.
+ * Checked on the host before anything is enqueued: P <= 256 and n_objs_host[b] <= 64 (CSG_E_UNSUPPORTED); n_objs_host[b] in
+ * [0, O], every row of rel_host that is not padding with its predicate in [0, P) and both objects in [0, n_objs_host[b]),
+ * two distinct meta ids in [0, P), the workspace size (CSG_E_BADSHAPE).  The kernel reads the DEVICE copies; it indexes
+ * nothing with a row that fails those checks, nor `uniforms` past n_uniforms: counts[b][0] of such a sample is NEGATIVE
+ * (-1 - the count), and the caller must not call csg_canon_small_emit.
+ * No entry synchronises or copies: both launches can be captured.  Workspace: csg_canon_small_workspace(B, P) bytes
+ * (B * P * 1544, rounded up to 256 per sample).                                                                       */
+int64_t csg_canon_small_workspace(int64_t B, int64_t P);
+int csg_canon_small_build(const int64_t* objs0, const int64_t* n_objs, const int64_t* n_objs_host, int64_t B, int64_t O,
+                          const int64_t* rel, const int64_t* rel_host, int64_t R, int64_t P, int64_t pid_padding,
+                          int64_t pid_in_image, int64_t image_id, int include_dummies, int learned_transitivity,
+                          const double* cdf, const double* uniforms, const int64_t* u_off, int64_t n_uniforms,
+                          float* conv_counts, void* workspace, int64_t workspace_bytes, int64_t* counts, void* stream);
+int csg_canon_small_emit(int64_t B, int64_t P, int64_t pid_padding, const void* workspace, int64_t workspace_bytes,
+                         const int64_t* counts, int64_t T, int64_t* triplets, int64_t* triplet_type, void* stream);
 
 /* ---- sampled-pair relations of the unpacked COCO dataset (reference sg2im/data/coco.py:372-421) ---------------------
  * Every object `cur` of a sample drew ONE other object and a coin on the host; this gives the pair's predicate, one thread
