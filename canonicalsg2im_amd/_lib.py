@@ -226,6 +226,8 @@ SIGNATURES = {
     "csg_canon_small_build": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
                                       c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p]),
     "csg_canon_small_emit": (c_i32, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "csg_clevr_graph_count": (c_i32, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p]),
+    "csg_clevr_graph_emit": (c_i32, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_p, c_p, c_p]),
 }
 
 

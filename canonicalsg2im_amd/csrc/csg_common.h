@@ -70,6 +70,8 @@ enum KernelId {
   K_DRAW_BOXES,
   K_CANON_SMALL_BUILD,
   K_CANON_SMALL_EMIT,
+  K_CLEVR_GRAPH_COUNT,
+  K_CLEVR_GRAPH_EMIT,
   K_COUNT
 };
 

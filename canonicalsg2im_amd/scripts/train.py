@@ -26,8 +26,11 @@ predicate and the graph are made on the device (sg2im/data/coco.py of this packa
 names the val split's image ids).  `--dataset vg` reads the unpacked Visual Genome folder, <dataroot>/VisualGenome with the
 pictures, train.h5 or train.npz and vocab.json in it (or `--vg_image_dir`, `--train_h5`, `--vocab_json` where they exist), with
 `packed_vg`'s object choice and boxes and the reference's annotated-only graph: the annotated relationships and the dummies,
-no location relation, at most 63 objects per picture (sg2im/data/vg.py of this package; `--mask_size` must be 0).  Without
-the directory, and for every other dataset,
+no location relation, at most 63 objects per picture (sg2im/data/vg.py of this package; `--mask_size` must be 0).
+`--dataset clevr` reads the CLEVR folder of `packed_clevr` with the reference's CLEVR-Dialog graph: the scene file's own
+relationships, every predicate's reduced to its minimal graph on the device, and the dummies; six predicates, at most 63
+objects per scene (sg2im/data/clevr.py of this package; `--use_transitivity` is 0 or 1, the learned flags, `--use_converse` and
+`--mask_size` above 0 are refused).  Without the directory, and for `--dataset synthetic`,
 the batches are seeded synthetic ones of the chosen dataset's shape.  One line says which of the two it is.
 
 For packed datasets the scene graphs are built on the device from the boxes (`sg2im.data.canonical_triplets`), as

@@ -1,10 +1,13 @@
 """Device-side pieces of the reference's data pipeline (sg2im/data/*): the canonical graph construction of the packed
 datasets — the O(O^3) numpy/python step that feeds the hot path — and the folder datasets that feed it pictures: the three
-packed ones, the default `coco` with its sampled-pair graph and `vg` with its annotated-only graph."""
+packed ones, the default `coco` with its sampled-pair graph, `vg` with its annotated-only graph and `clevr` with the renderer's
+relations reduced to their minimal graphs."""
 from .base_dataset import (ANTI_SYMMETRIC_EDGE, ORIGINAL_EDGE, SYMMETRIC_EDGE, TRANSITIVE_EDGE,  # noqa: F401
-                           annotated_triplets, augmented_relations, canonical_triplets, meta_relations, register_augmented_relations)
+                           annotated_triplets, augmented_relations, canonical_triplets, clevr_triplets, meta_relations,
+                           register_augmented_relations)
 
 FOLDER_DATASETS = {        # --dataset -> (the module of this package that holds it, the module's build_*_dataset)
+    "clevr": ("clevr", "build_clevr_dialog_dataset"),
     "coco": ("coco", "build_coco_pairs_dataset"),
     "packed_coco": ("packed_coco", "build_coco_dataset"),
     "packed_clevr": ("packed_clevr", "build_clevr_dataset"),

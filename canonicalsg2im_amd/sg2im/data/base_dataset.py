@@ -218,6 +218,65 @@ def annotated_triplets(objs, n_objs, vocab, rows, rows_host=None, learned_transi
     return out, conv_counts, triplet_type
 
 
+def clevr_triplets(objs, n_objs, vocab, rows, rows_host=None, use_transitivity=0, n_objs_host=None):
+    """`extract_triplets` + the collate's padding of the unpacked CLEVR dataset (reference sg2im/data/clevr_dialog.py:289-307,
+    :447-451): the renderer's relation rows, every predicate's reduced to its minimal graph by `reduce_transitive_edges`
+    (scripts/graphs_utils.py:74-82), then the `__in_image__` dummies.  No `add_learnt_triplets`: no np.unique order, no
+    converse draws, no extras.
+
+    objs (B,O) or (B,O,A) int64 on the device (its shape and device are used); n_objs (B,) = rows per sample with its
+    `__image__` row, at most 64, on the host (a device tensor is read back, unless `n_objs_host` is its host copy); rows (B,R,3) int64 = [o2, pred, o1] in the
+    order extract_triplets lists them — the relationships' key order, then o1 ascending, then the list's order, duplicates
+    kept — rows of `__padding__` are padding; `rows_host`: their host copy, which spares the read-back when `rows` is on
+    the device.  Returns (triplets (B,T,3), conv_counts (B,P,P+1) float32 of zeros, triplet_type (B,T) of ORIGINAL_EDGE)
+    as canonical_triplets does.
+
+    `use_transitivity` is the reference's `p_keep`, 0 or 1: a predicate of 3 or more listed rows keeps its minimal graph
+    alone (0), or that and every listed edge (1).  The reference draws a uniform matrix per such predicate from numpy's
+    global stream and keeps a listed edge when `u * 1 > 1 - p_keep`: never for 0, always for 1 — but for a draw of exactly
+    0.0 — so the draws cannot change the result here and none is made; the reference's global numpy stream advances and
+    this one's does not.  Any other value is refused: its result would depend on those draws.
+
+    Two launches (csrc/clevr_graph.hip) around the one 8-byte-per-sample read-back of the counts."""
+    if use_transitivity not in (0, 1):
+        raise ValueError("clevr_triplets: use_transitivity must be 0 or 1 (got %r): between them the reference's graph depends "
+                         "on its uniform draws" % (use_transitivity,))
+    objs0 = objs[..., 0] if objs.dim() == 3 else objs
+    if objs0.dim() != 2:
+        raise ValueError("objs must be (B, O) or (B, O, A); got %s" % (tuple(objs.shape),))
+    dev = objs0.device
+    B, O = objs0.shape
+    p2i = vocab["pred_name_to_idx"]
+    P, pad, in_image = len(p2i), p2i["__padding__"], p2i["__in_image__"]
+    rel_h = _host_int64(rows if rows_host is None else rows_host)
+    if rel_h.dim() != 3 or rel_h.shape[0] != B or rel_h.shape[2] != 3 or tuple(rows.shape) != tuple(rel_h.shape):
+        raise ValueError("rows must be (B, R, 3), and rows_host of the same shape; got %s and %s" % (
+            tuple(rows.shape), tuple(rel_h.shape)))
+    R = rel_h.shape[1]
+    rel_d = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous()
+    n_host = _host_int64(n_objs if n_objs_host is None else n_objs_host)
+    if tuple(n_host.shape) != (B,) or tuple(np.shape(n_objs)) != (B,):
+        raise ValueError("n_objs, and n_objs_host, must be (B,) = (%d,); got %s and %s" % (
+            B, tuple(np.shape(n_objs)), tuple(n_host.shape)))
+    n_dev = (n_objs if torch.is_tensor(n_objs) and n_objs.device == dev else n_host).to(device=dev, dtype=torch.int64).contiguous()
+    counts = torch.empty((B,), device=dev, dtype=torch.int64)
+    check(lib.csg_clevr_graph_count(ptr(n_dev), ctypes.c_void_p(n_host.data_ptr()), B, O, ptr(rel_d) if R else None,
+                                    ctypes.c_void_p(rel_h.data_ptr()) if R else None, R, P, pad, in_image,
+                                    int(use_transitivity), ptr(counts), stream()), "clevr_graph_count")
+    counts_host = counts.cpu()                       # the one read-back: the collate pads to the longest sample
+    bad = (counts_host < 0).nonzero()
+    if bad.numel():
+        raise RuntimeError("clevr_triplets: the rows of sample %d on the device are not the rows the host holds: one lies "
+                           "outside [0, n_objs - 1) or outside the vocabulary; no graph was written" % int(bad[0, 0]))
+    T = int(counts_host.max())
+    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
+    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
+    check(lib.csg_clevr_graph_emit(ptr(n_dev), B, O, ptr(rel_d) if R else None, R, P, pad, in_image, int(use_transitivity), T,
+                                   ptr(out), ptr(triplet_type), stream()), "clevr_graph_emit")
+    conv_counts = torch.zeros((B, P, P + 1), device=dev, dtype=torch.float32)        # never drawn: clevr_dialog.py has no
+    return out, conv_counts, triplet_type                                            # add_learnt_triplets
+
+
 def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transitivity=False, include_dummies=True,
                        learned_converse=False, converse_weights=None, uniforms=None, triplets=None, pairs=None,
                        use_converse=False, pairs_host=None):

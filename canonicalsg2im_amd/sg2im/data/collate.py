@@ -12,9 +12,20 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     drew: (other, flip) on the device and their host copies (None with --include_relationships 0: the dummies alone,
     sg2im/data/coco.py:374-375); its graph is the sampled rows, not the all-pairs relations of the geometry.  The unpacked vg
     dataset hands over its annotated rows, on the device and on the host: they and the dummies are its whole graph
-    (sg2im/data/vg.py:136-149), built by annotated_triplets."""
-    from . import annotated_triplets, canonical_triplets
+    (sg2im/data/vg.py:136-149), built by annotated_triplets.  The unpacked clevr dataset hands over the renderer's relation
+    rows the same way, and the objects per sample on the device besides: clevr_triplets reduces them per predicate
+    (sg2im/data/clevr_dialog.py:289-307; the dummies alone with --include_relationships 0), and the `__image__` row, which
+    follows a sample's objects, has the box (0, 0, 1, 1) (clevr_dialog.py:176-179) where every other dataset's has -1."""
+    from . import annotated_triplets, canonical_triplets, clevr_triplets
     rel = pairs = rows = None
+    if args.dataset == "clevr":
+        if counts is None:
+            raise ValueError("packed_batch: a clevr batch comes from ClevrDialogBatchBuilder, with the objects per sample")
+        batch = list(batch)
+        (*rows, counts_dev), batch[3] = batch[3], None
+        if not args.include_relationships:
+            rows = tuple(t[:, :0] for t in rows)
+        n = counts + 1
     if args.dataset == "vg":
         if counts is None:
             raise ValueError("packed_batch: a vg batch comes from VGAnnotatedBatchBuilder, with the objects per sample")
@@ -42,8 +53,18 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     O = objs.shape[1] + 1
     objs = torch.cat([objs, objs.new_zeros(objs.shape[0], 1, objs.shape[2])], 1)
     boxes = torch.cat([boxes, boxes.new_full((boxes.shape[0], 1, 4), -1.0)], 1)
-    centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
     batch[1], batch[2] = objs, boxes
+    if args.dataset == "clevr":                            # row counts[b] of sample b is its __image__ row; -1 boxes after it
+        counts_dev = counts_dev.to(dev)
+        image_row = (torch.arange(O, device=dev)[None] == counts_dev[:, None])[..., None]
+        boxes[..., :2].masked_fill_(image_row, 0.0)
+        boxes[..., 2:].masked_fill_(image_row, 1.0)
+        batch[3], batch[4], batch[5] = clevr_triplets(objs, counts_dev + 1, args.vocab, rows[0].contiguous(),
+                                                      rows_host=rows[1].contiguous(), n_objs_host=n,
+                                                      use_transitivity=int(args.use_transitivity))
+        assert batch[3].shape[1] > 0 and objs.shape[1] == O
+        return batch
+    centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
     extra = {"triplets": rel}
     if args.dataset == "coco":
         if pairs is None:                                  # no geometry: the (empty) rows are the whole graph

@@ -38,10 +38,15 @@ _NO_MASKS = ("PackedClevrDataset: mask_size must be 0 (got %d): the reference re
              "(sg2im/data/packed_clevr_dialog.py:212)")
 
 
-def clevr_vocab():
-    """The vocabulary of packed_clevr_dialog.py:113-143."""
+def clevr_vocab(predicates=None):
+    """The vocabulary of packed_clevr_dialog.py:113-143; with `predicates` (names by id) those are its predicate table, in
+    place of the eight packed ones."""
     vocab = {"use_object_embedding": False}
-    register_augmented_relations(vocab)
+    if predicates is None:
+        register_augmented_relations(vocab)
+    else:
+        vocab["pred_name_to_idx"] = {name: i for i, name in enumerate(predicates)}
+        vocab["pred_idx_to_name"] = list(predicates)
     vocab["attributes"] = {attr: dict(table) for attr, table in ATTRIBUTES.items()}
     vocab["reverse_attributes"] = {attr: {v: k for k, v in table.items()} for attr, table in ATTRIBUTES.items()}
     vocab["object_name_to_idx"] = {}
@@ -60,14 +65,13 @@ class PackedClevrDataset:
         """`image_dir`: with split_dirs the reference's <base>/images, under which a picture is <split>/<image_filename>;
         without, the directory of the pictures themselves.  `dialog_json`: the reference's clevr_dialog_{mode}_raw.json,
         read when the file exists."""
-        if mask_size:
-            raise NotImplementedError(_NO_MASKS % mask_size)
+        self.check_flags(mask_size)
         self.image_dir = image_dir
         self.split_dirs = bool(split_dirs)
         self.image_size = tuple(image_size)
         self.normalize_images = bool(normalize_images)
         self.max_samples = max_samples
-        self.vocab = clevr_vocab()
+        self.vocab = self.make_vocab()
         with open(scenes_json, "r") as f:
             self.scenes = json.load(f)["scenes"]
         entries = self.scenes
@@ -75,7 +79,7 @@ class PackedClevrDataset:
             with open(dialog_json, "r") as f:
                 entries = json.load(f)
         if dense_scenes:                                   # keep_dense_scenes: scene and dialog entry by the same index
-            keep = [i for i, s in enumerate(self.scenes) if min_objects < len(s["objects"]) < max_objects]
+            keep = [i for i, s in enumerate(self.scenes) if self.is_dense(len(s["objects"]), min_objects, max_objects)]
             entries = [entries[i] for i in keep]
             self.scenes = [self.scenes[i] for i in keep]
         self.image_paths = [os.path.join(e["split"], e["image_filename"]) if self.split_dirs else e["image_filename"]
@@ -83,6 +87,18 @@ class PackedClevrDataset:
         if len(self.image_paths) != len(self.scenes):
             raise ValueError("the dialog file has %d entries for %d scenes" % (len(self.image_paths), len(self.scenes)))
         self.image_ids = [int(s["image_index"]) for s in self.scenes]
+
+    def check_flags(self, mask_size):
+        """What the constructor refuses before it reads a file."""
+        if mask_size:
+            raise NotImplementedError(_NO_MASKS % mask_size)
+
+    def make_vocab(self):
+        return clevr_vocab()
+
+    def is_dense(self, n, min_objects, max_objects):
+        """Whether `dense_scenes` keeps a scene of n objects (:226-240)."""
+        return min_objects < n < max_objects
 
     def __len__(self):
         return len(self.scenes) if self.max_samples is None else min(len(self.scenes), self.max_samples)
@@ -107,7 +123,7 @@ class PackedClevrDataset:
         """One sample on the host: (pixels uint8 (h,w,3), objs (n,4), geom (n,5), rot (2,), image id)."""
         with self.open(index) as im:
             pixels = np.asarray(im.convert("RGB"))
-        objs, geom, rot = self.annotations(index)
+        objs, geom, rot = self.annotations(index)[:3]
         return pixels, torch.from_numpy(objs), torch.from_numpy(geom), torch.from_numpy(rot), self.image_ids[index]
 
 
@@ -120,17 +136,20 @@ class ClevrBatchBuilder(BatchBuilder):
     mean, std = CLEVR_MEAN, CLEVR_STD
 
     def rows(self, indices, sizes, drawn):
-        ann = [self.ds.annotations(i) for i in indices]
+        return self.fields_of([self.ds.annotations(i) for i in indices]), {}
+
+    def fields_of(self, ann):
+        """The second buffer's fields from the samples' annotations (objs, geom, rot, ...), padded to the batch's O."""
         O = max(a[0].shape[0] for a in ann)
         if O < 1:
             raise ValueError("a batch of scenes without objects")
         objs = np.zeros((len(ann), O, 4), np.int64)
         geom = np.zeros((len(ann), O, 5), np.float64)
-        for b, (o, g, _) in enumerate(ann):
-            objs[b, :o.shape[0]] = o
-            geom[b, :g.shape[0]] = g
+        for b, a in enumerate(ann):
+            objs[b, :a[0].shape[0]] = a[0]
+            geom[b, :a[1].shape[0]] = a[1]
         return {"counts": np.asarray([a[0].shape[0] for a in ann], np.int64), "objs": objs, "geom": geom,
-                "rot": np.stack([a[2] for a in ann])}, {}
+                "rot": np.stack([a[2] for a in ann])}
 
     def assemble(self, dev, p):
         from ... import ops

@@ -51,7 +51,8 @@ extern "C" {
  * 114: csg_vg_rows;
  * 115: csg_draw_boxes_u8; csg_canon_general_build takes boxes = centers = NULL;
  * 116: csg_pair_relations, csg_canon_general_build_dev;
- * 117: csg_canon_small_workspace, csg_canon_small_build, csg_canon_small_emit) */
+ * 117: csg_canon_small_workspace, csg_canon_small_build, csg_canon_small_emit;
+ * 118: csg_clevr_graph_count, csg_clevr_graph_emit) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -821,6 +822,33 @@ int csg_canon_small_build(const int64_t* objs0, const int64_t* n_objs, const int
                           float* conv_counts, void* workspace, int64_t workspace_bytes, int64_t* counts, void* stream);
 int csg_canon_small_emit(int64_t B, int64_t P, int64_t pid_padding, const void* workspace, int64_t workspace_bytes,
                          const int64_t* counts, int64_t T, int64_t* triplets, int64_t* triplet_type, void* stream);
+
+/* ---- the graph of the unpacked CLEVR dataset (reference sg2im/data/clevr_dialog.py:289-307, extract_triplets) -----------
+ * The renderer's relation rows reduced per predicate to their minimal graph (scripts/graphs_utils.py:74-82,
+ * reduce_transitive_edges with p_keep = keep, 0 or 1), then the __in_image__ dummies, then the collate's padding.  A sample
+ * is one block, a predicate one wave, a row of its 64x64 bit matrix one lane.
+ *   n_rows (B,) int64: rows per sample incl. its __image__ row, i.e. objects + 1: device; n_rows_host: its host copy.
+ *   rel (B,R,3) int64 = [o2, pred, o1] as extract_triplets lists them (the relationships' key order, then o1 ascending,
+ *   then the list's order, duplicates kept): device, 8-byte aligned; rel_host: its host copy.  Rows of __padding__ are
+ *   padding and may stand anywhere.
+ * Per predicate, in the order of the predicates' first rows: fewer than 3 listed rows are emitted as listed; otherwise
+ * M = the rows as a matrix, H = hsu(path(M)) in the reference's in-place order (defined for cycles and self-relations
+ * too), and H (keep = 0) or H | M (keep = 1) is emitted row-major.  Then [i, pid_in_image, n] for the n = n_rows - 1
+ * objects, then [0, pid_padding, 0] up to T.  triplet_type is 0 (ORIGINAL_EDGE) everywhere.
+ * csg_clevr_graph_count writes counts (B,) int64 (device) = triplets per sample, dummies included; the caller reads them
+ * back for T = max_b counts[b] and calls csg_clevr_graph_emit with the same rows, which computes the same graphs again
+ * and stores them: there is no workspace.
+ * Checked on the host before anything is enqueued: P <= 16 and n_rows_host[b] <= 64 (CSG_E_UNSUPPORTED); n_rows_host[b] in
+ * [1, O], every row of rel_host that is not padding with its predicate in [0, P) and both objects in [0, n), two distinct
+ * meta ids in [0, P), keep in {0, 1} (CSG_E_BADSHAPE).  The kernels read the DEVICE copies and index nothing with a row
+ * that fails those checks: counts[b] of such a sample is NEGATIVE (-1 - the count) and the caller must not emit.
+ * No entry synchronises or copies: both launches can be captured.                                                     */
+int csg_clevr_graph_count(const int64_t* n_rows, const int64_t* n_rows_host, int64_t B, int64_t O, const int64_t* rel,
+                          const int64_t* rel_host, int64_t R, int64_t P, int64_t pid_padding, int64_t pid_in_image, int keep,
+                          int64_t* counts, void* stream);
+int csg_clevr_graph_emit(const int64_t* n_rows, int64_t B, int64_t O, const int64_t* rel, int64_t R, int64_t P,
+                         int64_t pid_padding, int64_t pid_in_image, int keep, int64_t T, int64_t* triplets,
+                         int64_t* triplet_type, void* stream);
 
 /* ---- sampled-pair relations of the unpacked COCO dataset (reference sg2im/data/coco.py:372-421) ---------------------
  * Every object `cur` of a sample drew ONE other object and a coin on the host; this gives the pair's predicate, one thread
