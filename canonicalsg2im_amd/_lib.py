@@ -219,6 +219,7 @@ SIGNATURES = {
                                             c_i64, c_i32, c_p, c_i64, c_p, c_p]),
     "csg_pair_relations": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, ctypes.POINTER(c_i32), c_i32, c_p,
                                    c_p]),
+    "csg_coco_masks": (c_i32, [c_p] * 16 + [c_i64] * 6 + [c_p, c_p, c_p]),
     "csg_canon_general_converse": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "csg_canon_general_close": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_i32, c_p, c_i64, c_p, c_p]),
     "csg_canon_general_emit": (c_i32, [c_i64, ctypes.POINTER(c_i32), c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),

@@ -72,6 +72,7 @@ enum KernelId {
   K_CANON_SMALL_EMIT,
   K_CLEVR_GRAPH_COUNT,
   K_CLEVR_GRAPH_EMIT,
+  K_COCO_MASKS,
   K_COUNT
 };
 

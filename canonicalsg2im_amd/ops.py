@@ -1746,6 +1746,61 @@ def pair_relations(boxes, centers, counts, other, flip, vocab, use_converse=Fals
     return out
 
 
+COCO_MASKS_MAX_M = 64
+
+
+def coco_masks(kind, crop, sizes, boxes, obj_poly, poly_off, poly_xy, obj_runs, toggles, mask_size, want_masks=True,
+               kind_host=None, crop_host=None, sizes_host=None, obj_poly_host=None, poly_off_host=None, poly_xy_host=None,
+               obj_runs_host=None, out_masks=None, out_centers=None):
+    """The per-object mask recipe of the reference's COCO __getitem__ (sg2im/data/packed_coco.py:305-351) for a padded batch,
+    on the device (csg_coco_masks): seg_to_mask, the crop to the rounded box, cv2.resize(INTER_NEAREST) to M x M and the mask's
+    centroid as the object's centre — pycocotools' and OpenCV's arithmetic restated (tests/mask_cases.py), evaluated only at
+    the M x M source pixels the resize reads.
+
+    kind: uint8 (B,O), 0 padding / 1 polygons / 2 runs; crop: int32 (B,O,4) = x0, y0, x1, y1, rounded and clamped on the
+    host; sizes: int64 (B,2) = (HH, WW); boxes: fp32 (B,O,4) xywh; obj_poly: int32 (B,O,2) = (first polygon, polygons);
+    poly_off: int32 (P+1,) vertex offsets; poly_xy: fp64 (V,2) pixels; obj_runs: int32 (B,O,2) = (first toggle, toggles);
+    toggles: int32 (T,) running sums of the run lengths.  All on the device; all but boxes and toggles are needed on the host
+    too (refusals): pass their CPU copies `*_host`, or they are read back, which synchronises.  `mask_size` M: a power of two,
+    2 .. 64.  Returns (masks int64 (B,O+1,M,M) with the all-ones `__image__` row collate.packed_batch expects, or None with
+    want_masks=False; centres fp32 (B,O,2), the box centre where a mask is empty or the row is padding).  `out_masks`,
+    `out_centers`: caller-owned buffers, for a captured graph.  The same bytes on every run.  No autograd."""
+    M = int(mask_size)
+    if M < 2 or M > COCO_MASKS_MAX_M or M & (M - 1):
+        raise RuntimeError("coco_masks: mask_size must be a power of two in 2 .. %d, got %d" % (COCO_MASKS_MAX_M, M))
+    _device_operands("coco_masks", (("kind", kind, torch.uint8, (None, None)), ("crop", crop, torch.int32, (None, None, 4)),
+                                    ("sizes", sizes, torch.int64, (None, 2)), ("boxes", boxes, torch.float32, (None, None, 4)),
+                                    ("obj_poly", obj_poly, torch.int32, (None, None, 2)),
+                                    ("poly_off", poly_off, torch.int32, (None,)), ("poly_xy", poly_xy, torch.float64, (None, 2)),
+                                    ("obj_runs", obj_runs, torch.int32, (None, None, 2)),
+                                    ("toggles", toggles, torch.int32, (None,))))
+    B, O = kind.shape
+    if any(tuple(t.shape[:2]) != (B, O) for t in (crop, boxes, obj_poly, obj_runs)) or sizes.shape[0] != B or \
+            poly_off.shape[0] < 1:
+        raise RuntimeError("coco_masks: crop %s, boxes %s, obj_poly %s, obj_runs %s, sizes %s and poly_off %s do not fit kind %s" % (
+            tuple(crop.shape), tuple(boxes.shape), tuple(obj_poly.shape), tuple(obj_runs.shape), tuple(sizes.shape),
+            tuple(poly_off.shape), tuple(kind.shape)))
+    hosts = _host_copies("coco_masks", (("kind", kind, kind_host), ("crop", crop, crop_host), ("sizes", sizes, sizes_host),
+                                        ("obj_poly", obj_poly, obj_poly_host), ("poly_off", poly_off, poly_off_host),
+                                        ("poly_xy", poly_xy, poly_xy_host), ("obj_runs", obj_runs, obj_runs_host)))
+    if want_masks and out_masks is None:
+        out_masks = torch.empty((B, O + 1, M, M), device=kind.device, dtype=torch.int64)
+    if want_masks and (tuple(out_masks.shape) != (B, O + 1, M, M) or out_masks.dtype != torch.int64 or
+                       not out_masks.is_contiguous() or not out_masks.is_cuda):
+        raise RuntimeError("coco_masks: out_masks must be contiguous int64 (B,O+1,M,M) on the device")
+    if out_centers is None:
+        out_centers = torch.empty((B, O, 2), device=kind.device, dtype=torch.float32)
+    if tuple(out_centers.shape) != (B, O, 2) or out_centers.dtype != torch.float32 or not out_centers.is_contiguous() or \
+            not out_centers.is_cuda:
+        raise RuntimeError("coco_masks: out_centers must be contiguous fp32 (B,O,2) on the device")
+    P, V, T = poly_off.shape[0] - 1, poly_xy.shape[0], toggles.shape[0]
+    check(lib.csg_coco_masks(ptr(kind), ptr(crop), ptr(sizes), ptr(boxes), ptr(obj_poly), ptr(poly_off),
+                             ptr(poly_xy) if V else None, ptr(obj_runs), ptr(toggles) if T else None,
+                             *[ctypes.c_void_p(h.data_ptr()) if h.numel() else None for h in hosts], B, O, P, V, T, M,
+                             ptr(out_masks) if want_masks else None, ptr(out_centers), stream()), "coco_masks")
+    return (out_masks if want_masks else None), out_centers
+
+
 # ------------------------------------------------------------------------------------ resampling
 class _Upsample2x(torch.autograd.Function):
     @staticmethod

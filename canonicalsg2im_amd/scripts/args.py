@@ -29,6 +29,9 @@ _OFF_PATH_FLAGS = {
     'coco_val_instances_json': (None, 'str'), 'coco_val_stuff_json': (None, 'str'),
     # --dataset coco (sg2im/data/coco.py of this package): a JSON list of image ids; the val split keeps the images on it
     'coco_val_ids': (None, 'str'),
+    # --dataset coco / packed_coco: 1 decodes the annotations' segmentations on the device (ops.coco_masks): --mask_size M
+    # is then served and object centres are mask centroids, as in the reference; 0: no masks, box centres
+    'coco_segmentations': (0, 'int'),
     # CLEVR from a folder (sg2im/data/packed_clevr.py of this package): unset, the reference's layout under --dataroot
     # (<dataroot>/CLEVR/CLEVR_Dialog/scenes/CLEVR_<split>_scenes.json, .../images/<split>/); an image dir given here holds the
     # split's pictures themselves

@@ -11,7 +11,8 @@ drives that iteration with the reference's flags, one process per GPU:
 Data.  `--dataset packed_coco` trains on real pictures when the train image directory exists (`--coco_train_image_dir`, by
 default <dataroot>/MSCoco/images/train2017 with the annotation files beside it, the reference's layout): the pictures are
 decoded on the host in `--loader_num_workers` threads and resized, converted and normalised on the device, one batch ahead of
-the step (sg2im/data/packed_coco.py of this package; `--mask_size` must be 0 there).  Every epoch is a permutation seeded by
+the step (sg2im/data/packed_coco.py of this package; `--mask_size` must be 0 there unless `--coco_segmentations 1` decodes
+the annotations' segmentations on the device: masks in the batch, mask centroids as centres).  Every epoch is a permutation seeded by
 the epoch number; with N ranks each takes every N-th sample of a global batch.  `--dataset packed_clevr` does the same when
 its train image directory exists (`--clevr_train_image_dir`, by default <dataroot>/CLEVR/CLEVR_Dialog/images/train with
 scenes/CLEVR_train_scenes.json beside `images`): the renders go up as decoded, RGBA included, and the boxes are computed on
@@ -22,7 +23,8 @@ chosen on the host as the reference chooses them, their pixel boxes are divided 
 and the annotated relationships join the canonical graph (sg2im/data/packed_vg.py of this package; `--mask_size` must be 0;
 a .h5 split needs h5py, a .npz split does not: tools/vg_h5_to_npz.py).  `--dataset coco`, the default, reads the COCO folder
 of `packed_coco` with the original sg2im graph: 3 to 8 objects, every object draws one partner on the host and the pair's
-predicate and the graph are made on the device (sg2im/data/coco.py of this package; `--mask_size` must be 0; `--coco_val_ids`
+predicate and the graph are made on the device (sg2im/data/coco.py of this package; `--mask_size` must be 0 unless
+`--coco_segmentations 1`, as for `packed_coco`; `--coco_val_ids`
 names the val split's image ids).  `--dataset vg` reads the unpacked Visual Genome folder, <dataroot>/VisualGenome with the
 pictures, train.h5 or train.npz and vocab.json in it (or `--vg_image_dir`, `--train_h5`, `--vocab_json` where they exist), with
 `packed_vg`'s object choice and boxes and the reference's annotated-only graph: the annotated relationships and the dummies,

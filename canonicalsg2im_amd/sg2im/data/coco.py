@@ -17,8 +17,12 @@ predicates (`ops.pair_relations`), the `__image__` row and the canonical graph o
 (csg_canon_general_build_dev, then the converse / close / emit entries packed_vg uses) run on the device, as do Pillow's
 resize, ToTensor and the ImageNet Normalize (`ops.preprocess_images`).
 
-MASKS ARE NOT SUPPORTED, as for packed_coco: `mask_size` must be 0 and object centres are BOX centres, x0 + 0.5 * w.  The
-reference takes the centroid of the decoded mask and falls back to exactly this expression when a mask is empty (:356-358).
+MASKS ARE OPT-IN, as for packed_coco (its docstring has the whole of it): without `segmentations=True`
+(`--coco_segmentations 1`) `mask_size` must be 0 and object centres are BOX centres, x0 + 0.5 * w — the reference takes the
+centroid of the decoded mask and falls back to exactly this expression when a mask is empty (:356-358).  With it the
+segmentations are decoded on the device (`ops.coco_masks`), the batch carries the masks, and the mask centroids are the
+centres `ops.pair_relations` compares; with mask_size == 0 they are decoded at the reference's working size for this dataset,
+32 (:152-154), for the centres alone.  Equality with pycocotools' and OpenCV's output has not been run.
 
 LIMIT: at most 255 objects per picture.  The canonical graph takes 256 rows per sample, one of which is `__image__`; an
 image that passes the filters with more objects is refused when the dataset is made (`--max_objects 1000`, the README's
@@ -34,7 +38,7 @@ import random
 import numpy as np
 
 from .loader import BatchBuilder
-from .packed_coco import _NO_MASKS, PackedCocoSceneGraphDataset, split_image_dir
+from .packed_coco import _NO_MASKS, PackedCocoSceneGraphDataset, device_masks, segmentation_fields, split_image_dir
 
 COCO_MIN_OBJECTS, COCO_MAX_OBJECTS = 3, 8                  # sg2im/data/dataset_params.py:132-133
 MAX_OBJECTS_PER_PICTURE = 255                              # csg_canon_general_*: 256 rows with __image__
@@ -44,14 +48,16 @@ _TOO_MANY = ("CocoSceneGraphDataset: image %s keeps %d objects; the canonical gr
 
 
 class CocoSceneGraphDataset(PackedCocoSceneGraphDataset):
+    default_mask_size = 32                                 # what the reference decodes at with mask_size == 0 (:152-154)
+
     def __init__(self, image_dir, instances_json, stuff_json, image_size=(64, 64), mask_size=0, normalize_images=True,
                  max_samples=None, include_relationships=True, min_object_size=0.02, min_objects=COCO_MIN_OBJECTS,
                  max_objects=COCO_MAX_OBJECTS, include_other=False, instance_whitelist=None, stuff_whitelist=None,
-                 use_converse=False, keep_image_ids=None):
+                 use_converse=False, keep_image_ids=None, segmentations=False):
         super().__init__(image_dir, instances_json, stuff_json, image_size=image_size, mask_size=mask_size,
                          normalize_images=normalize_images, max_samples=max_samples, min_object_size=min_object_size,
                          min_objects=min_objects, max_objects=max_objects, include_other=include_other,
-                         instance_whitelist=instance_whitelist, stuff_whitelist=stuff_whitelist)
+                         instance_whitelist=instance_whitelist, stuff_whitelist=stuff_whitelist, segmentations=segmentations)
         self.include_relationships = bool(include_relationships)
         self.use_converse = bool(use_converse)
         if keep_image_ids is not None:                     # dataset_params.py:187-189, in annotation order
@@ -84,7 +90,8 @@ class CocoPairsBatchBuilder(BatchBuilder):
     consumer's thread (the order decides what the random stream gives whom, so the workers do not do it).  The fields of
     its own are the category ids, the boxes over the decoded sizes, the counts, and the draws: other int32 (B,O), -1 where
     nothing was drawn, flip uint8 (B,O).  No kernel of its own runs in assemble: the pairs reach collate.packed_batch in
-    the batch's triplet slot, as device views with their host copies.
+    the batch's triplet slot, as device views with their host copies.  A dataset that reads segmentations adds their fields,
+    and assemble launches ops.coco_masks (packed_coco.device_masks).
 
     `rng`: where the draws come from; by default a random.Random of the builder's own, seeded from (0, rank).  A resumed
     run starts it afresh: its epoch order is the interrupted run's, its pairs are not."""
@@ -117,11 +124,14 @@ class CocoPairsBatchBuilder(BatchBuilder):
             if pairs:
                 other[b, :len(pairs)] = [j for j, _ in pairs]
                 flip[b, :len(pairs)] = [f for _, f in pairs]
+        seg = segmentation_fields(self, indices, sizes, O) if self.ds.segmentations else {}
         return {"objs": objs, "boxes": boxes, "counts": np.asarray([a[0].shape[0] for a in ann], np.int64), "other": other,
-                "flip": flip}, {}
+                "flip": flip, **seg}, {}
 
     def assemble(self, dev, p):
         pairs = (dev["other"], dev["flip"], p.other, p.flip) if self.ds.include_relationships else None
+        if self.ds.segmentations:
+            return dev["objs"], dev["boxes"], pairs, p.counts, device_masks(self.ds, dev, p)
         return dev["objs"], dev["boxes"], pairs, p.counts
 
 
@@ -137,7 +147,8 @@ def build_coco_pairs_dataset(args, split):
     image_dir = split_image_dir(args, split)
     if not os.path.isdir(image_dir):
         return None
-    if args.mask_size:
+    segmentations = bool(getattr(args, "coco_segmentations", 0))
+    if args.mask_size and not segmentations:
         raise NotImplementedError(_NO_MASKS % args.mask_size)
     inst = getattr(args, "coco_%s_instances_json" % split) or os.path.join(root, "annotations", "instances_%s2017.json" % split)
     stuff = getattr(args, "coco_%s_stuff_json" % split) or os.path.join(root, "annotations", "stuff_%s2017.json" % split)
@@ -152,4 +163,4 @@ def build_coco_pairs_dataset(args, split):
         max_samples=args.num_train_samples if split == "train" else args.num_val_samples,
         include_relationships=bool(args.include_relationships), min_object_size=args.min_object_size,
         min_objects=args.min_objects or COCO_MIN_OBJECTS, max_objects=args.max_objects or COCO_MAX_OBJECTS,
-        use_converse=bool(args.use_converse), keep_image_ids=keep)
+        use_converse=bool(args.use_converse), keep_image_ids=keep, segmentations=segmentations)

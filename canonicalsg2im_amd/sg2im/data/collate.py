@@ -2,7 +2,7 @@
 import torch
 
 
-def packed_batch(args, trainer, batch, dev, counts=None):
+def packed_batch(args, trainer, batch, dev, counts=None, centers=None):
     """A packed batch (the tensors of synth.make_batch or of a dataset's batch builder, on the host or on `dev`) on `dev`,
     with the canonical graph built on the device: the __image__ row appended to every sample, then canonical_triplets in
     place of the triplets.  packed_vg hands the batch's annotated relationships over, unless --include_relationships 0
@@ -15,7 +15,11 @@ def packed_batch(args, trainer, batch, dev, counts=None):
     (sg2im/data/vg.py:136-149), built by annotated_triplets.  The unpacked clevr dataset hands over the renderer's relation
     rows the same way, and the objects per sample on the device besides: clevr_triplets reduces them per predicate
     (sg2im/data/clevr_dialog.py:289-307; the dummies alone with --include_relationships 0), and the `__image__` row, which
-    follows a sample's objects, has the box (0, 0, 1, 1) (clevr_dialog.py:176-179) where every other dataset's has -1."""
+    follows a sample's objects, has the box (0, 0, 1, 1) (clevr_dialog.py:176-179) where every other dataset's has -1.
+    `centers`: fp32 (B,O,2) object centres of the rows handed over, from a builder that has better ones than the box centres
+    (the COCO datasets' mask centroids, ops.coco_masks); they replace x0 + 0.5 * w for those rows — the appended `__image__`
+    row keeps its value — and reach canonical_triplets and, for coco, ops.pair_relations.  The batch's masks, if any, come
+    with their `__image__` row already in place."""
     from . import annotated_triplets, canonical_triplets, clevr_triplets
     rel = pairs = rows = None
     if args.dataset == "clevr":
@@ -64,7 +68,13 @@ def packed_batch(args, trainer, batch, dev, counts=None):
                                                       use_transitivity=int(args.use_transitivity))
         assert batch[3].shape[1] > 0 and objs.shape[1] == O
         return batch
-    centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
+    if centers is None:
+        centers = boxes[..., :2] + 0.5 * boxes[..., 2:]
+    else:
+        if args.dataset in ("clevr", "vg") or tuple(centers.shape) != (objs.shape[0], O - 1, 2):
+            raise ValueError("packed_batch: centers must be (B, O, 2) for the %d x %d rows handed over, and the dataset one "
+                             "whose graph has location relations" % (objs.shape[0], O - 1))
+        centers = torch.cat([centers.to(dev), boxes[:, O - 1:, :2] + 0.5 * boxes[:, O - 1:, 2:]], 1)
     extra = {"triplets": rel}
     if args.dataset == "coco":
         if pairs is None:                                  # no geometry: the (empty) rows are the whole graph

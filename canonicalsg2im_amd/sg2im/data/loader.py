@@ -107,7 +107,9 @@ class BatchBuilder:
                    to the batch's O, which go into the second buffer, and what only the host needs.  `sizes`: int64 (B,2) =
                    (h, w) of the decoded pictures.  Both are kept, unmodified, as attributes of the pending batch.
       assemble(dev, pending)          the device hook -> (objs, boxes, rel, counts) for collate.packed_batch, from the device
-                   views `dev[name]` of the fields and their host copies `pending.<name>`.
+                   views `dev[name]` of the fields and their host copies `pending.<name>`.  A fifth value, optional, is a
+                   pair (masks or None, centres): the batch's mask slot and the object centres the graph is built from, in
+                   place of None and the box centres (the COCO datasets with segmentations).
     All of them run on the consumer's thread.
 
     batches(lists) runs the HOST half one batch ahead: the decode of batch k + 1 — the host-bound part of the loader — runs
@@ -178,12 +180,13 @@ class BatchBuilder:
         from .collate import packed_batch
         src, meta_dev = self._upload(p)
         dev = p.layout.views(meta_dev)
-        objs, boxes, rel, counts = self.assemble(dev, p)
+        objs, boxes, rel, counts, *more = self.assemble(dev, p)
+        masks, centers = more[0] if more else (None, None)
         H, W = self.ds.image_size
         imgs = ops.preprocess_images(src, dev["desc"], H, W, normalize=self.ds.normalize_images, desc_host=p.desc,
                                      **({} if self.mean is None else {"mean": self.mean, "std": self.std}))
-        raw = [imgs, objs, boxes, rel, None, None, None, dev["image_ids"]]
-        return packed_batch(self.args, self.trainer, raw, self.dev, counts=counts)
+        raw = [imgs, objs, boxes, rel, None, None, masks, dev["image_ids"]]
+        return packed_batch(self.args, self.trainer, raw, self.dev, counts=counts, centers=centers)
 
     def _upload(self, p):
         """Wait for the decode, then one copy of each staging buffer -> (packed bytes, second buffer) on the device."""

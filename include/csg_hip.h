@@ -52,7 +52,8 @@ extern "C" {
  * 115: csg_draw_boxes_u8; csg_canon_general_build takes boxes = centers = NULL;
  * 116: csg_pair_relations, csg_canon_general_build_dev;
  * 117: csg_canon_small_workspace, csg_canon_small_build, csg_canon_small_emit;
- * 118: csg_clevr_graph_count, csg_clevr_graph_emit) */
+ * 118: csg_clevr_graph_count, csg_clevr_graph_emit;
+ * 119: csg_coco_masks) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -871,6 +872,45 @@ int csg_clevr_graph_emit(const int64_t* n_rows, int64_t B, int64_t O, const int6
 int csg_pair_relations(const float* boxes, const float* centers, const int64_t* counts, const int32_t* other,
                        const uint8_t* flip, const int64_t* counts_host, const int32_t* other_host, const uint8_t* flip_host,
                        int64_t B, int64_t O, const int32_t* pred_ids, int use_converse, int64_t* rows, void* stream);
+
+/* ---- COCO segmentations -> M x M object masks and mask centroids (reference sg2im/data/packed_coco.py:305-351,
+ * sg2im/data/coco.py:317-363; csrc/coco_masks.hip) -----------------------------------------------------------------
+ * What the reference computes per object through pycocotools (frPyObjects / merge / decode) and OpenCV (cv2.resize,
+ * INTER_NEAREST), restated from their public sources; the restatement is tests/mask_cases.py.  One block per (sample,
+ * object) row; only the M source columns and M source rows the nearest-neighbour resize reads are evaluated.
+ *   kind (B,O) uint8: 0 padding row, 1 a list of polygons, 2 run lengths.
+ *   crop (B,O,4) int32 = x0, y0, x1, y1 of mask[y0:y1, x0:x1]: int(round(.)) of the annotation's box with ties to even,
+ *     max(lo + 1, hi), clamped as a slice clamps — made on the host, from the annotation's own floats.
+ *   sizes (B,2) int64 = (HH, WW) of the decoded pictures.   boxes (B,O,4) fp32 xywh over the picture's size.
+ *   obj_poly (B,O,2) int32 = (first polygon, polygons) of a kind-1 row; poly_off (P+1,) int32: polygon p has the vertices
+ *     poly_off[p] .. poly_off[p+1] of poly_xy (V,2) fp64 = (x, y) in pixels.  A polygon is rasterised as rleFrPoly does
+ *     (scale 5, C truncation, one toggle per crossing of a pixel column's middle); an object's polygons are ORed.
+ *   obj_runs (B,O,2) int32 = (first toggle, toggles) of a kind-2 row in toggles (T,) int32: the running sums of the
+ *     column-major run lengths; pixel (x, y) is parity(#{toggles <= x * HH + y}).
+ *   masks (B,O+1,M,M) int64, or NULL when only the centres are wanted: 0 / 1; rows of kind 0 are 0; row O of every sample,
+ *     the __image__ row the collate appends, is all ones (packed_coco.py:330).
+ *   centers (B,O,2) fp32: with count = sum of the mask, x0 + 0.5 w in fp32 for count == 0 (kind 0 included: the box centre),
+ *     else x0 + ((fp32)(x0 + w) - x0) * sum_col / ((M - 1) * count) in fp64, rounded once; y likewise.
+ * kind_host .. obj_runs_host: the host copies of the operands of those names.
+ * Limits (CSG_E_UNSUPPORTED): M a power of two in 2 .. CSG_COCO_MASKS_MAX_M.  Checked on the host before the launch
+ * (CSG_E_BADSHAPE): 1 <= B <= CSG_COCO_MASKS_MAX_BATCH, 1 <= O <= CSG_COCO_MASKS_MAX_OBJECTS; pictures of 1 ..
+ * CSG_COCO_MASKS_MAX_SIDE on a side and fewer than 2^31 pixels; P, V <= CSG_COCO_MASKS_MAX_VERTICES; kind in {0, 1, 2}; for
+ * every row that is not padding a non-empty crop inside the picture and its (first, count) inside [0, P] / [0, T];
+ * poly_off non-decreasing inside [0, V]; every coordinate within +-CSG_COCO_MASKS_MAX_COORD; null operands (poly_xy may be
+ * NULL with V == 0, toggles with T == 0); alignment (boxes 16, sizes / masks / centers / poly_xy 8, the int32 operands 4).
+ * The kernel reads the DEVICE copies and indexes nothing with a row that fails those checks: it becomes a padding row.
+ * No workspace, no synchronisation, no float atomics: capturable, and the same bytes on every run.                     */
+#define CSG_COCO_MASKS_MAX_M 64
+#define CSG_COCO_MASKS_MAX_BATCH 4096
+#define CSG_COCO_MASKS_MAX_OBJECTS 256
+#define CSG_COCO_MASKS_MAX_SIDE 16777216
+#define CSG_COCO_MASKS_MAX_VERTICES 16777216
+#define CSG_COCO_MASKS_MAX_COORD 1.0e6
+int csg_coco_masks(const uint8_t* kind, const int32_t* crop, const int64_t* sizes, const float* boxes, const int32_t* obj_poly,
+                   const int32_t* poly_off, const double* poly_xy, const int32_t* obj_runs, const int32_t* toggles,
+                   const uint8_t* kind_host, const int32_t* crop_host, const int64_t* sizes_host, const int32_t* obj_poly_host,
+                   const int32_t* poly_off_host, const double* poly_xy_host, const int32_t* obj_runs_host, int64_t B, int64_t O,
+                   int64_t P, int64_t V, int64_t T, int64_t M, int64_t* masks, float* centers, void* stream);
 
 /* ---- spectral normalisation of a conv weight (a13) ----------------------------------------------
  * torch.nn.utils.spectral_norm's forward pre-hook (reference call sites architecture.py:35-39,
