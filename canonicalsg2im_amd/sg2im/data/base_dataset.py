@@ -71,6 +71,16 @@ def _refuse_dropped_rows(first):
         raise RuntimeError(_BAD_DEVICE_ROW % int(bad[0, 0]))
 
 
+def _refuse_rows_beyond(n_host, O):
+    """The location-only kernels clamp a sample's rows to O; the host's count of dummies and draws would not.  One rule on
+    every path (csg_canon_general_build, csg_canon_small_build and csg_clevr_graph_count refuse it the same way): a
+    sample with more rows than `objs` has is an error, raised before any uniform number is drawn."""
+    bad = ((n_host < 0) | (n_host > O)).nonzero()
+    if bad.numel():
+        b = int(bad[0, 0])
+        raise RuntimeError("canonical_triplets: n_objs[%d] = %d outside [0, %d]" % (b, int(n_host[b]), O))
+
+
 def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity, include_dummies,
                        learned_converse, converse_weights, uniforms, triplets, rel_dev=None, rel_counts=None):
     """Annotated rows and any vocabulary (csrc/canon.hip, csg_canon_general_*): packed_vg.py:127-142 + vg_collate_fn.
@@ -283,7 +293,9 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     """Batched `add_location_triplets` + `add_dummy_triplets` + `add_learnt_triplets` + collate padding.
 
     objs (B,O) or (B,O,A) int64 (attribute 0 is used, as `objs['shape']` in packed_clevr_dialog.py:207),
-    boxes (B,O,4) xywh, obj_centers (B,O,2), n_objs (B,) = objects per sample incl. its `__image__` row.
+    boxes (B,O,4) xywh, obj_centers (B,O,2), n_objs (B,) = objects per sample incl. its `__image__` row, each in [0, O]:
+    a sample with more rows than `objs` has is refused on every path (RuntimeError "n_objs[b] = n outside [0, O]"), before
+    a uniform number is drawn — a host tensor before any launch, a device tensor with the read-back the call makes anyway.
     Returns (triplets (B,T,3) int64, conv_counts (B,P,P+1) float32, triplet_type (B,T) int64) —
     the collate layout of the trainer's batch tuple.
 
@@ -354,6 +366,12 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
         return _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learned_transitivity,
                                   include_dummies, learned_converse, converse_weights, uniforms, triplets)
     ids = (ctypes.c_int32 * 8)(*[p2i[n] for n in names])
+    n_objs = torch.as_tensor(n_objs)
+    if n_objs.device.type == "cpu":                  # a host tensor is checked here, before anything is enqueued
+        _refuse_rows_beyond(n_objs.to(torch.int64), O)
+        rows_checked = True
+    else:                                            # a device tensor: its extremes ride on the read-back below
+        rows_checked = False
     n_objs = n_objs.to(device=objs0.device, dtype=torch.int64).contiguous()
     dev = objs0.device
     nbytes = lib.csg_canon_workspace(B)
@@ -372,7 +390,13 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
         in_range = torch.arange(O, device=dev).unsqueeze(0) < n_objs.unsqueeze(1)
         has_img = ((objs0 == image_id) & in_range).any(dim=1)
         dummies = torch.where(has_img, n_objs - 1, torch.zeros_like(n_objs)) if include_dummies else torch.zeros_like(n_objs)
-        draws = (counts[:, 0] - dummies).cpu()                       # read-back: the uniforms are the HOST's random stream
+        if rows_checked:
+            draws = (counts[:, 0] - dummies).cpu()                   # read-back: the uniforms are the HOST's random stream
+        else:                                                        # the same read-back carries n_objs: refused before a draw
+            both = torch.cat([counts[:, 0] - dummies, n_objs]).cpu()
+            draws = both[:B]
+            _refuse_rows_beyond(both[B:], O)
+            rows_checked = True
         u_off = torch.cumsum(draws, 0) - draws
         total = int(draws.sum())
         if uniforms is None:
@@ -391,7 +415,12 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
         check(lib.csg_canon_converse(ptr(objs0), ptr(n_objs), B, O, ids, image_id, 1 if include_dummies else 0,
                                      1 if learned_transitivity else 0, ptr(ws), ptr(cdf_d), ptr(u_d), ptr(off_d), n_rel,
                                      ptr(conv_counts), ptr(counts), stream()), "canon_converse")
-    T = int(counts.sum(dim=1).max().item())          # the collate pads to the longest sample: one 8-byte read-back
+    if rows_checked:
+        T = int(counts.sum(dim=1).max().item())      # the collate pads to the longest sample: one 8-byte read-back
+    else:                                            # the same read-back carries n_objs
+        both = torch.cat([counts.sum(dim=1).max().view(1), n_objs]).cpu()
+        _refuse_rows_beyond(both[1:], O)
+        T = int(both[0])
     triplets = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
     triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
     check(lib.csg_canon_emit(ptr(objs0), ptr(n_objs), B, O, ids, image_id, 1 if include_dummies else 0,
