@@ -21,7 +21,7 @@
 // its predicate, and k_gen_pack, which takes such device rows into that pipeline (csg_canon_general_build_dev).
 // This file is NOT compiled with -ffp-contract=off; k_pair_relations, the one kernel here that adds to a product, turns
 // contraction off for itself.
-#include "csg_common.h"
+#include "csg_bitgraph.h"
 
 #include <vector>
 
@@ -68,6 +68,80 @@ __device__ int block_exscan(int v, int* sm, int* total) {
   return sm[tid] - v;
 }
 
+// objects of sample b: never more than the input tensors or a bit matrix hold
+__device__ __forceinline__ int canon_n(const CanonParams& P, const int64_t* __restrict__ n_objs, int b) {
+  int n = (int)n_objs[b];
+  if (n > P.O) n = P.O;
+  if (n > MAXN) n = MAXN;
+  return n;
+}
+
+// the index of the sample's first row that carries P.image_id among `ids` (objs0's row of the sample), or -1; every
+// thread of the block calls it
+__device__ __forceinline__ int image_row(const int64_t* __restrict__ ids, int64_t image_id, int n, int* sm) {
+  const int tid = threadIdx.x;
+  sm[tid] = (tid < n && ids[tid] == image_id) ? tid : MAXN;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sm[tid] = min(sm[tid], sm[tid + o]);
+    __syncthreads();
+  }
+  return sm[0] < MAXN ? sm[0] : -1;
+}
+
+// path(): Warshall closure of the six matrices, pivot i (graphs_utils.py:15-27); one barrier per pivot and one after
+__device__ __forceinline__ void close_relations(uint64_t (&adj)[NREL][MAXN][W], int n) {
+  const int tid = threadIdx.x, nw = (n + 63) >> 6, tasks = NREL * n;
+  for (int i = 0; i < n; ++i) {
+    __syncthreads();
+    for (int t = tid; t < tasks; t += 256) {
+      const int r = t / n, j = t - r * n;
+      if (j != i && ((adj[r][j][i >> 6] >> (i & 63)) & 1ull)) {
+        for (int w = 0; w < nw; ++w) adj[r][j][w] |= adj[r][i][w];
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// Per-row counts -> offsets, and the sample's two counts.  `cur` [NREL][MAXN][W]: the current graphs, in LDS or the
+// workspace's R; X: the workspace's extras.  Both as the whole block sees them.
+__device__ __forceinline__ void counts_and_offsets(const CanonParams& P, const int64_t* __restrict__ objs0, int b, int n,
+                                                   const uint64_t* cur, const uint64_t* X, int* off, int* scan,
+                                                   int64_t* __restrict__ counts) {
+  const int tid = threadIdx.x, nw = (n + 63) >> 6;
+  // the __image__ object's index (base_dataset.py:144)
+  const int img = P.include_dummies ? image_row(objs0 + (int64_t)b * P.O, (int64_t)P.image_id, n, scan) : -1;
+  int c = 0;
+  if (tid < n) {
+    for (int r = 0; r < NREL; ++r)
+      for (int w = 0; w < nw; ++w) c += __popcll(cur[((int64_t)r * MAXN + tid) * W + w]);
+    if (img >= 0 && tid != img) c += 1;
+  }
+  int total = 0;
+  int ex = block_exscan(c, scan, &total);
+  off[tid] = ex;
+  const int n_orig = total;
+  int n_trans = 0;
+  if (P.learned_transitivity) {
+    for (int q = 0; q < NREL + 1; ++q) {               // extras per relation, in predicate order
+      const int r = P.order[q];
+      if (r >= NREL) continue;
+      int cx = 0;
+      if (tid < n)
+        for (int w = 0; w < nw; ++w) cx += __popcll(X[((int64_t)r * MAXN + tid) * W + w]);
+      int tot = 0;
+      int e = block_exscan(cx, scan, &tot);
+      off[MAXN + r * MAXN + tid] = n_trans + e;
+      n_trans += tot;
+    }
+  }
+  if (tid == 0) {
+    counts[b * 2 + 0] = n_orig;
+    counts[b * 2 + 1] = n_trans;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_canon_build(CanonParams P, const int64_t* __restrict__ objs0,
                                                       const float* __restrict__ boxes,
                                                       const float* __restrict__ centers,
@@ -78,10 +152,7 @@ __global__ __launch_bounds__(256) void k_canon_build(CanonParams P, const int64_
   __shared__ int real[MAXN];
   __shared__ int scan[256];
   const int b = blockIdx.x, tid = threadIdx.x;
-  int n = (int)n_objs[b];
-  if (n > P.O) n = P.O;
-  if (n > MAXN) n = MAXN;
-  const int nw = (n + 63) >> 6;
+  const int n = canon_n(P, n_objs, b), nw = (n + 63) >> 6;
 
   for (int i = tid; i < NREL * MAXN * W; i += 256) (&adj[0][0][0])[i] = 0;
   if (tid < MAXN) {
@@ -129,18 +200,8 @@ __global__ __launch_bounds__(256) void k_canon_build(CanonParams P, const int64_
     }
   }
 
-  // ---- path(): Warshall closure, pivot i (graphs_utils.py:15-27)
+  close_relations(adj, n);
   const int tasks = NREL * n;
-  for (int i = 0; i < n; ++i) {
-    __syncthreads();
-    for (int t = tid; t < tasks; t += 256) {
-      const int r = t / n, j = t - r * n;
-      if (j != i && ((adj[r][j][i >> 6] >> (i & 63)) & 1ull)) {
-        for (int w = 0; w < nw; ++w) adj[r][j][w] |= adj[r][i][w];
-      }
-    }
-  }
-  __syncthreads();
   uint64_t* X = ws_X(ws, b);
   uint64_t* R = ws_R(ws, b);
   for (int t = tid; t < tasks * W; t += 256) {       // park the closure in X
@@ -170,53 +231,7 @@ __global__ __launch_bounds__(256) void k_canon_build(CanonParams P, const int64_
     X[at] = X[at] & ~red;                             // closure - current (graphs_utils.py:96-100)
   }
 
-  // ---- per-row counts -> offsets
-  int img = -1;
-  if (P.include_dummies) {                            // the __image__ object's index (base_dataset.py:144)
-    scan[tid] = (tid < n && objs0[(int64_t)b * P.O + tid] == (int64_t)P.image_id) ? tid : MAXN;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) scan[tid] = min(scan[tid], scan[tid + o]);
-      __syncthreads();
-    }
-    img = scan[0] < MAXN ? scan[0] : -1;
-  }
-  int c = 0;
-  if (tid < n) {
-    for (int r = 0; r < NREL; ++r)
-      for (int w = 0; w < nw; ++w) c += __popcll(adj[r][tid][w]);
-    if (img >= 0 && tid != img) c += 1;
-  }
-  int* off = ws_off(ws, b);
-  int total = 0;
-  int ex = block_exscan(c, scan, &total);
-  off[tid] = ex;
-  const int n_orig = total;
-  int n_trans = 0;
-  if (P.learned_transitivity) {
-    for (int q = 0; q < NREL + 1; ++q) {
-      const int r = P.order[q];
-      if (r >= NREL) continue;
-      int cx = 0;
-      if (tid < n)
-        for (int w = 0; w < nw; ++w) cx += __popcll(X[((int64_t)r * MAXN + tid) * W + w]);
-      int tot = 0;
-      int e = block_exscan(cx, scan, &tot);
-      off[MAXN + r * MAXN + tid] = n_trans + e;
-      n_trans += tot;
-    }
-  }
-  if (tid == 0) {
-    counts[b * 2 + 0] = n_orig;
-    counts[b * 2 + 1] = n_trans;
-  }
-}
-
-__device__ __forceinline__ void put(int64_t* trip, int64_t* tt, int64_t at, int s, int p, int o, int type) {
-  trip[at * 3 + 0] = s;
-  trip[at * 3 + 1] = p;
-  trip[at * 3 + 2] = o;
-  tt[at] = type;
+  counts_and_offsets(P, objs0, b, n, &adj[0][0][0], X, ws_off(ws, b), scan, counts);     // adj = R, still in LDS
 }
 
 __global__ __launch_bounds__(256) void k_canon_emit(CanonParams P, const int64_t* __restrict__ objs0,
@@ -226,10 +241,7 @@ __global__ __launch_bounds__(256) void k_canon_emit(CanonParams P, const int64_t
                                                      int64_t* __restrict__ ttype) {
   __shared__ int red[256];
   const int b = blockIdx.x, tid = threadIdx.x;
-  int n = (int)n_objs[b];
-  if (n > P.O) n = P.O;
-  if (n > MAXN) n = MAXN;
-  const int nw = (n + 63) >> 6;
+  const int n = canon_n(P, n_objs, b), nw = (n + 63) >> 6;
   const uint64_t* R = ws_R((void*)ws, b);
   const uint64_t* X = ws_X((void*)ws, b);
   const int* off = ws_off((void*)ws, b);
@@ -237,54 +249,29 @@ __global__ __launch_bounds__(256) void k_canon_emit(CanonParams P, const int64_t
   int64_t* tt = ttype + (int64_t)b * T;
   const int n_orig = (int)counts[b * 2 + 0], n_trans = (int)counts[b * 2 + 1];
 
-  int img = -1;
-  if (P.include_dummies) {
-    red[tid] = (tid < n && objs0[(int64_t)b * P.O + tid] == (int64_t)P.image_id) ? tid : MAXN;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) red[tid] = min(red[tid], red[tid + o]);
-      __syncthreads();
-    }
-    img = red[0] < MAXN ? red[0] : -1;
-  }
+  const int img = P.include_dummies ? image_row(objs0 + (int64_t)b * P.O, (int64_t)P.image_id, n, red) : -1;
   if (tid < n) {
     const int s = tid;
     int64_t at = off[s];
     for (int q = 0; q < NREL + 1; ++q) {               // ascending predicate id: np.unique's (s, p, o) order
       const int r = P.order[q];
       if (r >= NREL) {
-        if (img >= 0 && s != img && at < T) put(trip, tt, at++, s, P.pid_in_image, img, 0);
+        if (img >= 0 && s != img) put_triplet(trip, tt, at++, T, s, P.pid_in_image, img, 0);
         continue;
       }
-      for (int w = 0; w < nw; ++w) {
-        uint64_t m = R[((int64_t)r * MAXN + s) * W + w];
-        while (m) {
-          const int k = __ffsll((long long)m) - 1;
-          m &= m - 1;
-          if (at < T) put(trip, tt, at, s, P.pid[r], w * 64 + k, 0);
-          ++at;
-        }
-      }
+      for (int w = 0; w < nw; ++w) at = emit_bits(R[((int64_t)r * MAXN + s) * W + w], w * 64, at, T, trip, tt, s, P.pid[r], 0);
     }
     if (n_trans) {
       for (int q = 0; q < NREL + 1; ++q) {
         const int r = P.order[q];
         if (r >= NREL) continue;
         int64_t a2 = (int64_t)n_orig + off[MAXN + r * MAXN + s];
-        for (int w = 0; w < nw; ++w) {
-          uint64_t m = X[((int64_t)r * MAXN + s) * W + w];
-          while (m) {
-            const int k = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            if (a2 < T) put(trip, tt, a2, s, P.pid[r], w * 64 + k, 1);
-            ++a2;
-          }
-        }
+        for (int w = 0; w < nw; ++w) a2 = emit_bits(X[((int64_t)r * MAXN + s) * W + w], w * 64, a2, T, trip, tt, s, P.pid[r], 1);
       }
     }
   }
   for (int64_t t = (int64_t)n_orig + n_trans + tid; t < T; t += 256)      // packed_clevr_dialog.py:309-315
-    put(trip, tt, t, 0, P.pid_padding, 0, 0);
+    put_triplet(trip, tt, t, T, 0, P.pid_padding, 0, 0);
 }
 
 
@@ -308,10 +295,7 @@ __global__ __launch_bounds__(256) void k_canon_converse(CanonParams P, const int
   __shared__ int hist[NREL][NREL];             // [relation slot][choice 0..4 = candidate, 5 = none]
   __shared__ int cand[NREL][NREL - 1];         // candidate relation slots of a slot, ascending predicate id
   const int b = blockIdx.x, tid = threadIdx.x;
-  int n = (int)n_objs[b];
-  if (n > P.O) n = P.O;
-  if (n > MAXN) n = MAXN;
-  const int nw = (n + 63) >> 6;
+  const int n = canon_n(P, n_objs, b), nw = (n + 63) >> 6;
   uint64_t* R = ws_R(ws, b);
   uint64_t* X = ws_X(ws, b);
   for (int i = tid; i < NREL * MAXN * W; i += 256) (&adj[0][0][0])[i] = 0;
@@ -340,12 +324,10 @@ __global__ __launch_bounds__(256) void k_canon_converse(CanonParams P, const int
       for (int w = 0; w < nw; ++w) {
         uint64_t m = R[((int64_t)r * MAXN + s) * W + w];
         while (m) {
-          const int o = w * 64 + (__ffsll((long long)m) - 1);
-          m &= m - 1;
+          const int o = w * 64 + pop_bit(m);
           const double u = uniforms[u_off[b] + k];
           ++k;
-          int j = 0;
-          while (j < NREL - 1 && cd[j] <= u) ++j;            // searchsorted(cdf, u, side='right'); the last threshold is 1
+          const int j = choice_right(cd, NREL, u);
           atomicAdd(&hist[r][j], 1);
           if (j < NREL - 1)                                    // converse edge (o, cand, s)
             atomicOr((unsigned long long*)&adj[cand[r][j]][o][s >> 6], 1ull << (s & 63));
@@ -367,16 +349,7 @@ __global__ __launch_bounds__(256) void k_canon_converse(CanonParams P, const int
   }
   // ---- closure of the new graphs (path(): graphs_utils.py:15-27), X <- closure - current
   if (P.learned_transitivity) {
-    for (int i = 0; i < n; ++i) {
-      __syncthreads();
-      for (int t = tid; t < tasks; t += 256) {
-        const int r = t / n, j = t - r * n;
-        if (j != i && ((adj[r][j][i >> 6] >> (i & 63)) & 1ull)) {
-          for (int w = 0; w < nw; ++w) adj[r][j][w] |= adj[r][i][w];
-        }
-      }
-    }
-    __syncthreads();
+    close_relations(adj, n);
     for (int t = tid; t < tasks * W; t += 256) {
       const int w = t % W, rj = t / W;
       const int r = rj / n, j = rj - r * n;
@@ -385,46 +358,7 @@ __global__ __launch_bounds__(256) void k_canon_converse(CanonParams P, const int
     }
   }
   __syncthreads();
-  // ---- counts and offsets (as k_canon_build)
-  int img = -1;
-  if (P.include_dummies) {
-    scan[tid] = (tid < n && objs0[(int64_t)b * P.O + tid] == (int64_t)P.image_id) ? tid : MAXN;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) scan[tid] = min(scan[tid], scan[tid + o]);
-      __syncthreads();
-    }
-    img = scan[0] < MAXN ? scan[0] : -1;
-  }
-  int c = 0;
-  if (tid < n) {
-    for (int r = 0; r < NREL; ++r)
-      for (int w = 0; w < nw; ++w) c += __popcll(R[((int64_t)r * MAXN + tid) * W + w]);
-    if (img >= 0 && tid != img) c += 1;
-  }
-  int* off = ws_off(ws, b);
-  int total = 0;
-  int ex = block_exscan(c, scan, &total);
-  off[tid] = ex;
-  const int n_orig = total;
-  int n_trans = 0;
-  if (P.learned_transitivity) {
-    for (int q = 0; q < NREL + 1; ++q) {
-      const int r = P.order[q];
-      if (r >= NREL) continue;
-      int cx = 0;
-      if (tid < n)
-        for (int w = 0; w < nw; ++w) cx += __popcll(X[((int64_t)r * MAXN + tid) * W + w]);
-      int tot = 0;
-      int e = block_exscan(cx, scan, &tot);
-      off[MAXN + r * MAXN + tid] = n_trans + e;
-      n_trans += tot;
-    }
-  }
-  if (tid == 0) {
-    counts[b * 2 + 0] = n_orig;
-    counts[b * 2 + 1] = n_trans;
-  }
+  counts_and_offsets(P, objs0, b, n, R, X, ws_off(ws, b), scan, counts);
   // ---- conv_counts[b][rel][r] (base_dataset.py:93, graphs_utils.py:146): r = a relation id, or npred for "none"
   if (tid < NREL * NREL) {
     const int r = tid / NREL, j = tid - r * NREL;
@@ -553,16 +487,8 @@ __global__ __launch_bounds__(256) void k_gen_scatter(GenParams P, const int64_t*
   const int n = gen_n(w, P, b), nw = (n + 63) >> 6;
   const int role = P.role[p];
   for (int i = tid; i < n * W; i += 256) (&adj[0][0])[i] = 0;
-  int img = -1;
-  if (role == CSG_CANON_ROLE_IN_IMAGE && P.include_dummies) {      // base_dataset.py:141-151
-    scan[tid] = (tid < n && objs0[(int64_t)b * P.O + tid] == (int64_t)P.image_id) ? tid : MAXN;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) scan[tid] = min(scan[tid], scan[tid + o]);
-      __syncthreads();
-    }
-    img = scan[0] < MAXN ? scan[0] : -1;
-  }
+  const int img = (role == CSG_CANON_ROLE_IN_IMAGE && P.include_dummies)      // base_dataset.py:141-151
+                      ? image_row(objs0 + (int64_t)b * P.O, (int64_t)P.image_id, n, scan) : -1;
   __syncthreads();
   if (tid < n) {
     if (role >= 0 && geo != nullptr) {                                // base_dataset.py:83-87; no geometry: authored rows alone
@@ -637,14 +563,8 @@ __global__ __launch_bounds__(256) void k_gen_converse(GenParams P, GenWs w, cons
     for (int k = 0; k < nw; ++k) {
       uint64_t m = U[s * W + k];
       while (m) {
-        const int o = k * 64 + (__ffsll((long long)m) - 1);
-        m &= m - 1;
-        const double u = uniforms[k0++];
-        int lo = 0, hi = K - 1;                                // searchsorted(cdf, u, side='right'), at most K - 1
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (cd[mid] <= u) lo = mid + 1; else hi = mid;
-        }
+        const int o = k * 64 + pop_bit(m);
+        const int lo = choice_right(cd, K, uniforms[k0++]);
         atomicAdd(&hist[lo], 1);
         if (lo < K - 1) {                                      // converse edge (o, cand, s)
           const int cand = P.nm[lo + (lo >= q)];
@@ -773,32 +693,16 @@ __global__ __launch_bounds__(256) void k_gen_emit(GenParams P, GenWs w, const in
   if (tid < n && n_orig) {
     int64_t at = w.rc[bp * MAXN + tid];
     const uint64_t* U = w.U + (bp * MAXN + tid) * W;
-    for (int k = 0; k < nw; ++k) {
-      uint64_t m = U[k];
-      while (m) {
-        const int o = k * 64 + (__ffsll((long long)m) - 1);
-        m &= m - 1;
-        if (at < T) put(trip, tt, at, tid, p, o, 0);
-        ++at;
-      }
-    }
+    for (int k = 0; k < nw; ++k) at = emit_bits(U[k], k * 64, at, T, trip, tt, tid, p, 0);
   }
   if (tid < n && n_x) {
     int64_t at = w.xc[bp * MAXN + tid];
     const uint64_t* X = w.V + (bp * MAXN + tid) * W;
-    for (int k = 0; k < nw; ++k) {
-      uint64_t m = X[k];
-      while (m) {
-        const int o = k * 64 + (__ffsll((long long)m) - 1);
-        m &= m - 1;
-        if (at < T) put(trip, tt, at, tid, p, o, 1);
-        ++at;
-      }
-    }
+    for (int k = 0; k < nw; ++k) at = emit_bits(X[k], k * 64, at, T, trip, tt, tid, p, 1);
   }
   const int64_t used = counts[b * 2 + 0] + counts[b * 2 + 1];
   for (int64_t t = used + (int64_t)p * 256 + tid; t < T; t += (int64_t)P.P * 256)    // vg_collate_fn: packed_vg.py:207-212
-    put(trip, tt, t, 0, P.pid_padding, 0, 0);
+    put_triplet(trip, tt, t, T, 0, P.pid_padding, 0, 0);
 }
 
 // ---- pack: annotated rows that are already on the device -> the workspace's 4-byte form (csg_canon_general_build_dev).
@@ -929,6 +833,49 @@ int gen_params(GenParams* G, int32_t* pred_ids, const int32_t* roles, int64_t B,
   CSG_REQUIRE(roles && workspace, CSG_E_BADSHAPE, fn ": null argument");                                              \
   CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, 0, nullptr, nullptr), CSG_E_BADSHAPE,                               \
               fn ": workspace too small (%ld bytes)", (long)workspace_bytes)
+
+// What csg_canon_general_build and csg_canon_general_build_dev (`fn`) do alike, after GEN_CHECK_COMMON: the shapes, the
+// role table, and the head of the upload, which lies in `up` as in the workspace: bad[B] = 0 | nob[B] = n_objs |
+// rbeg[B + 1] = the first row of each sample when sample b has rel_counts[b] rows (R without rel_counts) | room for
+// B * row_room packed rows.
+struct GenUpload {
+  GenParams G;
+  int32_t ids[8];
+  std::vector<char> up;
+  int64_t head;                  // bytes before the rows
+  int64_t* nob;
+  int* rbeg;
+};
+
+int gen_build_prologue(const char* fn, bool no_null, const int64_t* n_objs, int64_t B, int64_t O, const int64_t* rel_counts,
+                       int64_t R, int64_t row_room, const int32_t* roles, int64_t P, int64_t image_id, int include_dummies,
+                       int64_t workspace_bytes, GenUpload* u) {
+  CSG_REQUIRE(O > 0 && R >= 0 && B * R < (1ll << 31), CSG_E_BADSHAPE, "%s: bad shape O=%ld R=%ld", fn, (long)O, (long)R);
+  CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "%s: at most %d objects per sample (got %ld)", fn, MAXN, (long)O);
+  CSG_REQUIRE(no_null, CSG_E_BADSHAPE, "%s: null argument", fn);
+  CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, R, nullptr, nullptr), CSG_E_BADSHAPE,
+              "%s: workspace too small (%ld bytes, need %ld)", fn, (long)workspace_bytes,
+              (long)gen_layout(B, P, R, nullptr, nullptr));
+  CSG_REQUIRE(gen_params(&u->G, u->ids, roles, B, P, O, image_id, include_dummies, 0), CSG_E_BADSHAPE,
+              "%s: the role table needs one __padding__, one __in_image__ and each location relation exactly once", fn);
+  u->head = gen_align(B * 4) + gen_align(B * 8) + gen_align((B + 1) * 4);
+  u->up.assign((size_t)(u->head + B * row_room * 4), 0);
+  u->nob = (int64_t*)(u->up.data() + gen_align(B * 4));
+  u->rbeg = (int*)(u->up.data() + gen_align(B * 4) + gen_align(B * 8));
+  int nr = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t n = n_objs[b];
+    CSG_REQUIRE(n >= 0 && n <= O, CSG_E_BADSHAPE, "%s: n_objs[%ld] = %ld outside [0, %ld]", fn, (long)b, (long)n, (long)O);
+    const int64_t cnt = rel_counts ? rel_counts[b] : R;
+    CSG_REQUIRE(cnt >= 0 && cnt <= R, CSG_E_BADSHAPE, "%s: rel_counts[%ld] = %ld outside [0, %ld]", fn, (long)b, (long)cnt,
+                (long)R);
+    u->nob[b] = n;
+    u->rbeg[b] = nr;
+    nr += (int)cnt;
+  }
+  u->rbeg[B] = nr;
+  return CSG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -999,59 +946,35 @@ int csg_canon_general_build(const int64_t* objs0, const float* boxes, const floa
                             int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
                             const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
                             int64_t workspace_bytes, int64_t* counts, void* stream) {
+  const char* fn = "csg_canon_general_build";
   GEN_CHECK_COMMON("csg_canon_general_build");
-  CSG_REQUIRE(O > 0 && R >= 0 && B * R < (1ll << 31), CSG_E_BADSHAPE, "csg_canon_general_build: bad shape O=%ld R=%ld", (long)O, (long)R);
-  CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "csg_canon_general_build: at most %d objects per sample (got %ld)", MAXN,
-              (long)O);
-  CSG_REQUIRE(objs0 && n_objs && counts && (R == 0 || rel) && (boxes != nullptr) == (centers != nullptr), CSG_E_BADSHAPE,
-              "csg_canon_general_build: null argument");
+  GenUpload u;
+  // every input is checked here, before anything is enqueued; `up` is zeros: `bad` stays 0
+  int rc = gen_build_prologue(fn, objs0 && n_objs && counts && (R == 0 || rel) && (boxes != nullptr) == (centers != nullptr),
+                              n_objs, B, O, rel_counts, R, R, roles, P, image_id, include_dummies, workspace_bytes, &u);
+  if (rc != CSG_OK) return rc;
   const bool geometry = boxes != nullptr;      // boxes = centers = NULL: the location relations are the given rows alone
-  CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, R, nullptr, nullptr), CSG_E_BADSHAPE,
-              "csg_canon_general_build: workspace too small (%ld bytes, need %ld)", (long)workspace_bytes,
-              (long)gen_layout(B, P, R, nullptr, nullptr));
-  GenParams G;
-  int32_t ids[8];
-  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, O, image_id, include_dummies, 0), CSG_E_BADSHAPE,
-              "csg_canon_general_build: the role table needs one __padding__, one __in_image__ and each location "
-              "relation exactly once");
-  // every input is checked here, before anything is enqueued
-  const int64_t head = gen_align(B * 4) + gen_align(B * 8) + gen_align((B + 1) * 4);
-  std::vector<char> up((size_t)(head + B * R * 4));          // zeros: `bad` stays 0, every row was checked here
-  int64_t* nob = (int64_t*)(up.data() + gen_align(B * 4));
-  int* rbeg = (int*)(up.data() + gen_align(B * 4) + gen_align(B * 8));
-  uint32_t* rows = (uint32_t*)(up.data() + head);
+  uint32_t* rows = (uint32_t*)(u.up.data() + u.head);
   int nr = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t n = n_objs[b];
-    CSG_REQUIRE(n >= 0 && n <= O, CSG_E_BADSHAPE, "csg_canon_general_build: n_objs[%ld] = %ld outside [0, %ld]", (long)b,
-                (long)n, (long)O);
-    nob[b] = n;
-    rbeg[b] = nr;
+  for (int64_t b = 0; b < B; ++b) {            // the rows are packed sample after sample, the skipped ones left out
     const int64_t cnt = rel_counts ? rel_counts[b] : R;
-    CSG_REQUIRE(cnt >= 0 && cnt <= R, CSG_E_BADSHAPE, "csg_canon_general_build: rel_counts[%ld] = %ld outside [0, %ld]",
-                (long)b, (long)cnt, (long)R);
+    u.rbeg[b] = nr;
     for (int64_t r = 0; r < cnt; ++r) {
       const int64_t* t = rel + (b * R + r) * 3;
-      const int64_t s = t[0], p = t[1], o = t[2];
-      if (!rel_counts && p == G.pid_padding) continue;
-      CSG_REQUIRE(p >= 0 && p < P && p != G.pid_padding, CSG_E_BADSHAPE,
-                  "csg_canon_general_build: sample %ld row %ld: predicate %ld outside [0, %ld) or __padding__", (long)b,
-                  (long)r, (long)p, (long)P);
-      CSG_REQUIRE(s >= 0 && s < n && o >= 0 && o < n, CSG_E_BADSHAPE,
-                  "csg_canon_general_build: sample %ld row %ld: object %ld or %ld outside [0, %ld)", (long)b, (long)r,
-                  (long)s, (long)o, (long)n);
-      rows[nr++] = (uint32_t)s | (uint32_t)o << 8 | (uint32_t)p << 16;
+      rc = check_host_row(fn, !rel_counts, " or __padding__", t, b, r, P, u.G.pid_padding, u.nob[b]);
+      if (rc < 0) return rc;
+      if (rc) rows[nr++] = (uint32_t)t[0] | (uint32_t)t[2] << 8 | (uint32_t)t[1] << 16;
     }
   }
-  rbeg[B] = nr;
+  u.rbeg[B] = nr;
   GenWs w;
   gen_layout(B, P, R, workspace, &w);
   hipStream_t st = (hipStream_t)stream;
   // bad, nob, rbeg and rows are adjacent in the workspace, as in `up`; a pageable source is copied before the call returns
-  CSG_REQUIRE(hipMemcpyAsync(w.bad, up.data(), (size_t)(head + (int64_t)nr * 4), hipMemcpyHostToDevice, st) == hipSuccess,
+  CSG_REQUIRE(hipMemcpyAsync(w.bad, u.up.data(), (size_t)(u.head + (int64_t)nr * 4), hipMemcpyHostToDevice, st) == hipSuccess,
               CSG_E_LAUNCH, "csg_canon_general_build: upload of the annotated rows failed");
   CanonParams C;
-  fill_params(&C, O, ids, image_id, 0, 0);
+  fill_params(&C, O, u.ids, image_id, 0, 0);
   if (geometry) {
     ProfScope pr(K_CANON_BUILD, (double)B * O * O, st);
     CSG_LAUNCH(k_canon_build, dim3((unsigned)B), dim3(256), 0, st, C, objs0, boxes, centers, (const int64_t*)w.nob,
@@ -1059,9 +982,9 @@ int csg_canon_general_build(const int64_t* objs0, const float* boxes, const floa
   }
   {
     ProfScope pr(K_CANON_BUILD, (double)B * P * O * W, st);
-    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, objs0, w,
+    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, u.G, objs0, w,
                geometry ? workspace : (void*)nullptr);
-    CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, G, w, counts);
+    CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, u.G, w, counts);
   }
   return check_launch("csg_canon_general_build");
 }
@@ -1121,52 +1044,27 @@ int csg_canon_general_build_dev(const int64_t* objs0, const float* boxes, const 
                                 int64_t B, int64_t O, const int64_t* rel, const int64_t* rel_counts, int64_t R,
                                 const int32_t* roles, int64_t P, int64_t image_id, int include_dummies, void* workspace,
                                 int64_t workspace_bytes, int64_t* counts, void* stream) {
+  const char* fn = "csg_canon_general_build_dev";
   GEN_CHECK_COMMON("csg_canon_general_build_dev");
-  CSG_REQUIRE(O > 0 && R >= 0 && B * R < (1ll << 31), CSG_E_BADSHAPE, "csg_canon_general_build_dev: bad shape O=%ld R=%ld",
-              (long)O, (long)R);
-  CSG_REQUIRE(O <= MAXN, CSG_E_UNSUPPORTED, "csg_canon_general_build_dev: at most %d objects per sample (got %ld)", MAXN,
-              (long)O);
-  CSG_REQUIRE(objs0 && n_objs && counts && rel_counts && (R == 0 || rel), CSG_E_BADSHAPE,
-              "csg_canon_general_build_dev: null argument");
   CSG_REQUIRE(boxes == nullptr && centers == nullptr, CSG_E_UNSUPPORTED,
               "csg_canon_general_build_dev: boxes and centers must be NULL (the given rows are the whole graph)");
   CSG_REQUIRE(((uintptr_t)rel & 7) == 0, CSG_E_BADSHAPE, "csg_canon_general_build_dev: rel must be 8-byte aligned");
-  CSG_REQUIRE(workspace_bytes >= gen_layout(B, P, R, nullptr, nullptr), CSG_E_BADSHAPE,
-              "csg_canon_general_build_dev: workspace too small (%ld bytes, need %ld)", (long)workspace_bytes,
-              (long)gen_layout(B, P, R, nullptr, nullptr));
-  GenParams G;
-  int32_t ids[8];
-  CSG_REQUIRE(gen_params(&G, ids, roles, B, P, O, image_id, include_dummies, 0), CSG_E_BADSHAPE,
-              "csg_canon_general_build_dev: the role table needs one __padding__, one __in_image__ and each location "
-              "relation exactly once");
+  GenUpload u;
   // what the host has is checked here, before anything is enqueued; the rows themselves by k_gen_pack
-  const int64_t head = gen_align(B * 4) + gen_align(B * 8) + gen_align((B + 1) * 4);
-  std::vector<char> up((size_t)head);                         // zeros: `bad` starts at 0
-  int64_t* nob = (int64_t*)(up.data() + gen_align(B * 4));
-  int* rbeg = (int*)(up.data() + gen_align(B * 4) + gen_align(B * 8));
-  int nr = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t n = n_objs[b];
-    CSG_REQUIRE(n >= 0 && n <= O, CSG_E_BADSHAPE, "csg_canon_general_build_dev: n_objs[%ld] = %ld outside [0, %ld]", (long)b,
-                (long)n, (long)O);
-    const int64_t cnt = rel_counts[b];
-    CSG_REQUIRE(cnt >= 0 && cnt <= R, CSG_E_BADSHAPE, "csg_canon_general_build_dev: rel_counts[%ld] = %ld outside [0, %ld]",
-                (long)b, (long)cnt, (long)R);
-    nob[b] = n;
-    rbeg[b] = nr;
-    nr += (int)cnt;
-  }
-  rbeg[B] = nr;
+  const int rc = gen_build_prologue(fn, objs0 && n_objs && counts && rel_counts && (R == 0 || rel), n_objs, B, O, rel_counts, R,
+                                    0, roles, P, image_id, include_dummies, workspace_bytes, &u);
+  if (rc != CSG_OK) return rc;
+  const int nr = u.rbeg[B];
   GenWs w;
   gen_layout(B, P, R, workspace, &w);
   hipStream_t st = (hipStream_t)stream;
-  CSG_REQUIRE(hipMemcpyAsync(w.bad, up.data(), (size_t)head, hipMemcpyHostToDevice, st) == hipSuccess, CSG_E_LAUNCH,
+  CSG_REQUIRE(hipMemcpyAsync(w.bad, u.up.data(), (size_t)u.head, hipMemcpyHostToDevice, st) == hipSuccess, CSG_E_LAUNCH,
               "csg_canon_general_build_dev: upload of the row offsets failed");
   {
     ProfScope pr(K_CANON_BUILD, (double)B * P * O * W, st);
-    if (nr > 0) CSG_LAUNCH(k_gen_pack, dim3((unsigned)cdiv(B * R, 256)), dim3(256), 0, st, G, w, rel, (int)R);
-    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, G, objs0, w, (void*)nullptr);
-    CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, G, w, counts);
+    if (nr > 0) CSG_LAUNCH(k_gen_pack, dim3((unsigned)cdiv(B * R, 256)), dim3(256), 0, st, u.G, w, rel, (int)R);
+    CSG_LAUNCH(k_gen_scatter, dim3((unsigned)P, (unsigned)B), dim3(256), 0, st, u.G, objs0, w, (void*)nullptr);
+    CSG_LAUNCH(k_gen_draws, dim3((unsigned)B), dim3(256), 0, st, u.G, w, counts);
   }
   return check_launch("csg_canon_general_build_dev");
 }

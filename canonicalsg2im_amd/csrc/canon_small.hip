@@ -15,7 +15,7 @@
 // P = 47 is 47 KiB, and it stays in L2.  The words that other waves of the block set with atomicOr (which act in L2) are
 // read back with agent-scope atomic loads after the barrier, never through a line the CU's L1 may still hold.
 // Integer atomics (OR, and counting draws) only: the bytes do not depend on the order in which waves run.
-#include "csg_common.h"
+#include "csg_bitgraph.h"
 
 using namespace csg;
 
@@ -65,23 +65,6 @@ __device__ __forceinline__ int nm_pred(const SmallParams& S, int j) {
 
 __device__ __forceinline__ uint64_t load_l2(const uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int wave_incscan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_total(int inc) { return __shfl(inc, 63, 64); }
-
-// row k of the matrix whose row `lane` is v; k is wave-uniform
-__device__ __forceinline__ uint64_t row_of(uint64_t v, int k) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, k);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), k);
-  return (uint64_t)hi << 32 | lo;
 }
 
 // exclusive scan of one int of each of the first 256 threads; every thread of the block calls it
@@ -177,19 +160,14 @@ __global__ __launch_bounds__(SNT) void k_canon_small_build(SmallParams S, const 
         int64_t k = u_off[b] + doff[rel_p] + (wave_incscan(c, lane) - c);
         const double* cd = cdf + (int64_t)rel_p * K;
         while (m) {
-          const int o = __ffsll((long long)m) - 1;
-          m &= m - 1;
+          const int o = pop_bit(m);
           const int64_t at = k++;
           if (at < 0 || at >= n_uniforms) {            // fewer numbers than rows: the host counted other rows than these
             bad = 1;
             continue;
           }
           const double u = uniforms[at];
-          int lo = 0, hi = K - 1;                      // searchsorted(cdf, u, side='right'), at most K - 1
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cd[mid] <= u) lo = mid + 1; else hi = mid;
-          }
+          const int lo = choice_right(cd, K, u);
           atomicAdd(&hist[wave][lo], 1);
           if (lo < K - 1) {                            // converse edge (o, cand, s)
             const int cand = nm_pred(S, lo + (lo >= q));
@@ -219,13 +197,7 @@ __global__ __launch_bounds__(SNT) void k_canon_small_build(SmallParams S, const 
     const int inc = wave_incscan(c, lane);
     if (lane == 63) tot_o[p] = inc;
     if (S.learned_transitivity && !is_meta(S, p)) {
-      uint64_t row = cur;
-      for (int i = 0; i < n; ++i) {                    // path(): row j takes row i when j -> i, pivots in order
-        const uint64_t ri = row_of(row, i);
-        if (ri == 0) continue;                         // wave-uniform: an empty row adds nothing
-        if (lane != i && ((row >> i) & 1ull)) row |= ri;
-      }
-      const uint64_t x = row & ~cur;
+      const uint64_t x = wave_close(cur, n, lane) & ~cur;
       w.V[p * SMAXN + lane] = x;
       const int cx = __popcll(x);
       cnt_x[p][lane] = (unsigned char)cx;
@@ -266,13 +238,6 @@ __global__ __launch_bounds__(SNT) void k_canon_small_build(SmallParams S, const 
   }
 }
 
-__device__ __forceinline__ void put(int64_t* trip, int64_t* tt, int64_t at, int s, int p, int o, int type) {
-  trip[at * 3 + 0] = s;
-  trip[at * 3 + 1] = p;
-  trip[at * 3 + 2] = o;
-  tt[at] = type;
-}
-
 // ---- emit: block b; a wave writes the originals and the extras of its predicates, every thread a share of the padding
 __global__ __launch_bounds__(SNT) void k_canon_small_emit(int P, int pid_padding, const void* __restrict__ ws,
                                                           const int64_t* __restrict__ counts, int64_t T,
@@ -282,30 +247,12 @@ __global__ __launch_bounds__(SNT) void k_canon_small_emit(int P, int pid_padding
   int64_t* trip = triplets + (int64_t)b * T * 3;
   int64_t* tt = ttype + (int64_t)b * T;
   for (int p = wave; p < P; p += SNW) {
-    if (w.tot[p * 2 + 0]) {
-      int64_t at = w.offo[p * SMAXN + lane];
-      uint64_t m = w.U[p * SMAXN + lane];
-      while (m) {
-        const int o = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (at >= 0 && at < T) put(trip, tt, at, lane, p, o, 0);
-        ++at;
-      }
-    }
-    if (w.tot[p * 2 + 1]) {
-      int64_t at = w.offx[p * SMAXN + lane];
-      uint64_t m = w.V[p * SMAXN + lane];
-      while (m) {
-        const int o = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (at >= 0 && at < T) put(trip, tt, at, lane, p, o, 1);
-        ++at;
-      }
-    }
+    if (w.tot[p * 2 + 0]) emit_bits(w.U[p * SMAXN + lane], 0, w.offo[p * SMAXN + lane], T, trip, tt, lane, p, 0);
+    if (w.tot[p * 2 + 1]) emit_bits(w.V[p * SMAXN + lane], 0, w.offx[p * SMAXN + lane], T, trip, tt, lane, p, 1);
   }
   int64_t used = counts[b * 2 + 0] + counts[b * 2 + 1];
   if (used < 0) used = 0;
-  for (int64_t t = used + tid; t < T; t += SNT) put(trip, tt, t, 0, pid_padding, 0, 0);    // vg_collate_fn: vg.py:214-219
+  for (int64_t t = used + tid; t < T; t += SNT) put_triplet(trip, tt, t, T, 0, pid_padding, 0, 0);    // vg_collate_fn: vg.py:214-219
 }
 
 #define SMALL_CHECK_COMMON(fn)                                                                                          \
@@ -335,9 +282,7 @@ int csg_canon_small_build(const int64_t* objs0, const int64_t* n_objs, const int
   CSG_REQUIRE(objs0 && n_objs && n_objs_host && counts && (R == 0 || (rel && rel_host)), CSG_E_BADSHAPE,
               "csg_canon_small_build: null argument");
   CSG_REQUIRE(((uintptr_t)rel & 7) == 0, CSG_E_BADSHAPE, "csg_canon_small_build: rel must be 8-byte aligned");
-  CSG_REQUIRE(pid_padding >= 0 && pid_padding < P && pid_in_image >= 0 && pid_in_image < P && pid_padding != pid_in_image,
-              CSG_E_BADSHAPE, "csg_canon_small_build: __padding__ = %ld and __in_image__ = %ld must be two ids of [0, %ld)",
-              (long)pid_padding, (long)pid_in_image, (long)P);
+  if (const int rc = check_meta_ids("csg_canon_small_build", P, pid_padding, pid_in_image)) return rc;
   const bool converse = cdf != nullptr;
   CSG_REQUIRE(!converse || (uniforms && u_off && conv_counts && n_uniforms >= 0 && P >= 3), CSG_E_BADSHAPE,
               "csg_canon_small_build: the converse draws need uniforms, u_off, conv_counts and a non-meta predicate");
@@ -350,14 +295,8 @@ int csg_canon_small_build(const int64_t* objs0, const int64_t* n_objs, const int
                 "csg_canon_small_build: at most %d rows per sample, the __image__ row included (sample %ld has %ld)", SMAXN,
                 (long)b, (long)n);
     for (int64_t r = 0; r < R; ++r) {
-      const int64_t* t = rel_host + (b * R + r) * 3;
-      const int64_t s = t[0], p = t[1], o = t[2];
-      if (p == pid_padding) continue;
-      CSG_REQUIRE(p >= 0 && p < P, CSG_E_BADSHAPE, "csg_canon_small_build: sample %ld row %ld: predicate %ld outside [0, %ld)",
-                  (long)b, (long)r, (long)p, (long)P);
-      CSG_REQUIRE(s >= 0 && s < n && o >= 0 && o < n, CSG_E_BADSHAPE,
-                  "csg_canon_small_build: sample %ld row %ld: object %ld or %ld outside [0, %ld)", (long)b, (long)r, (long)s,
-                  (long)o, (long)n);
+      const int rc = check_host_row("csg_canon_small_build", true, "", rel_host + (b * R + r) * 3, b, r, P, pid_padding, n);
+      if (rc < 0) return rc;
     }
   }
   SmallParams S;

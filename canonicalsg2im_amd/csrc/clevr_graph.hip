@@ -22,7 +22,7 @@
 // on the order in which waves run).  Both launches run this same computation from the rows — a few thousand integer
 // operations — and differ in what they store: the count launch the sample's number of triplets, the emit launch, after the
 // host has read the counts for T, the triplets.  Nothing is kept between them but the rows themselves.
-#include "csg_common.h"
+#include "csg_bitgraph.h"
 
 using namespace csg;
 
@@ -38,30 +38,6 @@ struct GraphParams {
   int pid_padding, pid_in_image;
   int keep;
 };
-
-__device__ __forceinline__ int wave_incscan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// row k of the matrix whose row `lane` is v; k is wave-uniform
-__device__ __forceinline__ uint64_t row_of(uint64_t v, int k) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, k);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), k);
-  return (uint64_t)hi << 32 | lo;
-}
-
-__device__ __forceinline__ void put(int64_t* trip, int64_t* tt, int64_t at, int64_t T, int64_t s, int64_t p, int64_t o) {
-  if (at < 0 || at >= T) return;
-  trip[at * 3 + 0] = s;
-  trip[at * 3 + 1] = p;
-  trip[at * 3 + 2] = o;
-  tt[at] = 0;                                          // ORIGINAL_EDGE; 0 on padding too
-}
 
 template <bool EMIT>
 __global__ __launch_bounds__(GNT) void k_clevr_graph(GraphParams G, const int64_t* __restrict__ n_rows,
@@ -111,12 +87,7 @@ __global__ __launch_bounds__(GNT) void k_clevr_graph(GraphParams G, const int64_
       continue;
     }
     const uint64_t m = M[p][lane];
-    uint64_t row = m;
-    for (int i = 0; i < n; ++i) {                      // path(): row j takes row i when j -> i, pivots in order
-      const uint64_t ri = row_of(row, i);
-      if (ri == 0) continue;                           // wave-uniform: an empty row adds nothing
-      if (lane != i && ((row >> i) & 1ull)) row |= ri;
-    }
+    uint64_t row = wave_close(m, n, lane);             // path()
     for (int j = 0; j < n; ++j) {                      // hsu(), in place
       const uint64_t old = row_of(row, j);
       if (old == 0) continue;                          // wave-uniform: nothing to clear
@@ -154,7 +125,7 @@ __global__ __launch_bounds__(GNT) void k_clevr_graph(GraphParams G, const int64_
     return;
   }
   int64_t* trip = triplets + (int64_t)b * T * 3;
-  int64_t* tt = ttype + (int64_t)b * T;
+  int64_t* tt = ttype + (int64_t)b * T;                // every row is an ORIGINAL_EDGE = 0, the padding too
   if (!bad) {
     for (int p = wave; p < P; p += GNW) {
       const int c = listed[p];
@@ -162,22 +133,17 @@ __global__ __launch_bounds__(GNT) void k_clevr_graph(GraphParams G, const int64_
       if (c < 3) {
         if (lane < c) {
           const int r = lane == 0 ? first[p] : last[p];
-          put(trip, tt, base[p] + lane, T, rows[r * 3 + 0], p, rows[r * 3 + 2]);
+          put_triplet(trip, tt, base[p] + lane, T, rows[r * 3 + 0], p, rows[r * 3 + 2], 0);
         }
         continue;
       }
-      uint64_t row = M[p][lane];
-      const int cnt = __popcll(row);
-      int64_t at = base[p] + (wave_incscan(cnt, lane) - cnt);
-      while (row) {                                    // matrix_to_triplets: np.where's row-major order
-        const int o = __ffsll((long long)row) - 1;
-        row &= row - 1;
-        put(trip, tt, at++, T, lane, p, o);
-      }
+      const uint64_t row = M[p][lane];
+      const int cnt = __popcll(row);                   // matrix_to_triplets: np.where's row-major order
+      emit_bits(row, 0, base[p] + (wave_incscan(cnt, lane) - cnt), T, trip, tt, lane, p, 0);
     }
-    if (tid < n) put(trip, tt, n_rel + tid, T, tid, G.pid_in_image, n);          // clevr_dialog.py:301-304
+    if (tid < n) put_triplet(trip, tt, n_rel + tid, T, tid, G.pid_in_image, n, 0);          // clevr_dialog.py:301-304
   }
-  for (int64_t t = (bad ? 0 : n_rel + n) + tid; t < T; t += GNT) put(trip, tt, t, T, 0, G.pid_padding, 0);   // :447-451
+  for (int64_t t = (bad ? 0 : n_rel + n) + tid; t < T; t += GNT) put_triplet(trip, tt, t, T, 0, G.pid_padding, 0, 0);   // :447-451
 }
 
 int check_common(const char* fn, int64_t B, int64_t O, int64_t R, int64_t P, int64_t pid_padding, int64_t pid_in_image,
@@ -185,9 +151,7 @@ int check_common(const char* fn, int64_t B, int64_t O, int64_t R, int64_t P, int
   CSG_REQUIRE(B > 0 && B < (1ll << 31) && O > 0 && O < (1ll << 31) && R >= 0 && R < (1ll << 31) / 3 && P > 0, CSG_E_BADSHAPE,
               "%s: bad shape B=%ld O=%ld R=%ld P=%ld", fn, (long)B, (long)O, (long)R, (long)P);
   CSG_REQUIRE(P <= GMAXP, CSG_E_UNSUPPORTED, "%s: at most %d predicates (got %ld)", fn, GMAXP, (long)P);
-  CSG_REQUIRE(pid_padding >= 0 && pid_padding < P && pid_in_image >= 0 && pid_in_image < P && pid_padding != pid_in_image,
-              CSG_E_BADSHAPE, "%s: __padding__ = %ld and __in_image__ = %ld must be two ids of [0, %ld)", fn, (long)pid_padding,
-              (long)pid_in_image, (long)P);
+  if (const int rc = check_meta_ids(fn, P, pid_padding, pid_in_image)) return rc;
   CSG_REQUIRE(keep == 0 || keep == 1, CSG_E_BADSHAPE, "%s: keep (use_transitivity) must be 0 or 1 (got %d)", fn, keep);
   return CSG_OK;
 }
@@ -226,14 +190,8 @@ int csg_clevr_graph_count(const int64_t* n_rows, const int64_t* n_rows_host, int
                 GMAXN - 1, GMAXN, (long)b, (long)rows);
     const int64_t n = rows - 1;
     for (int64_t r = 0; r < R; ++r) {
-      const int64_t* t = rel_host + (b * R + r) * 3;
-      const int64_t s = t[0], p = t[1], o = t[2];
-      if (p == pid_padding) continue;
-      CSG_REQUIRE(p >= 0 && p < P, CSG_E_BADSHAPE, "csg_clevr_graph_count: sample %ld row %ld: predicate %ld outside [0, %ld)",
-                  (long)b, (long)r, (long)p, (long)P);
-      CSG_REQUIRE(s >= 0 && s < n && o >= 0 && o < n, CSG_E_BADSHAPE,
-                  "csg_clevr_graph_count: sample %ld row %ld: object %ld or %ld outside [0, %ld)", (long)b, (long)r, (long)s,
-                  (long)o, (long)n);
+      const int rc = check_host_row("csg_clevr_graph_count", true, "", rel_host + (b * R + r) * 3, b, r, P, pid_padding, n);
+      if (rc < 0) return rc;
     }
   }
   hipStream_t st = (hipStream_t)stream;

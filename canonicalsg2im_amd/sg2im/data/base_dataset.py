@@ -62,13 +62,78 @@ def _host_int64(t):
 
 _BAD_DEVICE_ROW = ("canonical_triplets: sample %d has a sampled row whose objects lie outside [0, n_objs) or whose predicate "
                    "lies outside the vocabulary or is __padding__; the row was dropped on the device and no graph was written")
+_OTHER_ROWS = ("%s: the rows of sample %%d on the device are not the rows the host holds: one lies outside [0, %s) or outside "
+               "the vocabulary; no graph was written")
 
 
-def _refuse_dropped_rows(first):
-    """Raise when csg_canon_general_build_dev marked a sample: `first` is the host copy of counts[:, 0]."""
+def _refuse_negative(first, message):
+    """A kernel that met a row it could not index with reports a negative count for the sample: `first` is the host copy
+    of the samples' (first) counts, `message` the entry's text with a %d for the sample."""
     bad = (first < 0).nonzero()
     if bad.numel():
-        raise RuntimeError(_BAD_DEVICE_ROW % int(bad[0, 0]))
+        raise RuntimeError(message % int(bad[0, 0]))
+
+
+def _image_id(vocab):
+    """The id of the `__image__` object, which the first attribute and object_name_to_idx must give alike."""
+    first = list(vocab["attributes"].keys())[0]
+    image_id = vocab["object_name_to_idx"]["__image__"]
+    if vocab["attributes"][first]["__image__"] != image_id:
+        raise ValueError("the __image__ id of the first attribute and of object_name_to_idx differ")
+    return image_id
+
+
+def _meta_ids(vocab):
+    """(P, id of __padding__, id of __in_image__)"""
+    p2i = vocab["pred_name_to_idx"]
+    return len(p2i), p2i["__padding__"], p2i["__in_image__"]
+
+
+def _rows_both_sides(rows, rows_host, B, dev):
+    """(rows on the host, rows on the device, R) of (B,R,3) int64 rows given on either side; `rows_host`: their host copy,
+    which spares the read-back of device rows."""
+    rel_h = _host_int64(rows if rows_host is None else rows_host)
+    if rel_h.dim() != 3 or rel_h.shape[0] != B or rel_h.shape[2] != 3 or tuple(rows.shape) != tuple(rel_h.shape):
+        raise ValueError("rows must be (B, R, 3), and rows_host of the same shape; got %s and %s" % (
+            tuple(rows.shape), tuple(rel_h.shape)))
+    return rel_h, torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous(), rel_h.shape[1]
+
+
+def _n_objs_both_sides(n_objs, n_objs_host, dev):
+    """(n_objs on the host, n_objs on the device); a device tensor without its host copy is read back."""
+    n_host = _host_int64(n_objs if n_objs_host is None else n_objs_host)
+    n_dev = n_objs if torch.is_tensor(n_objs) and n_objs.device == dev else n_host
+    return n_host, n_dev.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def _weights(converse_weights):
+    if converse_weights is None:
+        raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
+    return converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
+
+
+def _converse_plan(w, relations, draws, uniforms, dev):
+    """What a converse launch reads, on the device: (cdf, uniforms, u_off, total).  relations[r] is the predicate whose
+    draws search row r of the cdf, None for a row without draws (a meta predicate); its candidates are the other relations
+    by ascending id (graphs_utils.py:126-140).  `draws` (B,) on the host: the numbers each sample takes, in this moment,
+    from numpy's GLOBAL stream or from `uniforms`; `total` is their sum."""
+    u, u_off = _draw_numbers(draws, uniforms)
+    drawn = sorted(c for c in relations if c is not None)
+    cdf = np.zeros((len(relations), len(drawn)), np.float64)
+    for r, rel in enumerate(relations):
+        if rel is not None:
+            cdf[r] = _choice_cdf(w, rel, [c for c in drawn if c != rel])
+    return torch.from_numpy(cdf).to(dev), torch.from_numpy(u).to(dev), u_off.to(dev), int(draws.sum())
+
+
+def _emit(totals, B, dev, entry, call):
+    """The collate pads to the longest sample: T = the largest of `totals` (host: the samples' triplets, or their maximum
+    alone), the two outputs, and the emit entry `call(T, triplets, triplet_type)`."""
+    T = int(totals.max())
+    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
+    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
+    check(call(T, ptr(out), ptr(triplet_type)), entry)
+    return out, triplet_type
 
 
 def _refuse_rows_beyond(n_host, O):
@@ -122,33 +187,22 @@ def _canonical_general(objs0, boxes, obj_centers, n_objs, vocab, image_id, learn
               "canon_general_build")
     conv_counts = torch.zeros((B, P, P + 1), device=dev, dtype=torch.float32)        # base_dataset.py:93
     if learned_converse:
-        if converse_weights is None:
-            raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
-        w = converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
+        w = _weights(converse_weights)
         draws = counts[:, 0].cpu()                                   # read-back: the uniforms are the HOST's random stream
-        _refuse_dropped_rows(draws)
-        u, u_off = _draw_numbers(draws, uniforms)
-        non_meta = [p for p in range(P) if roles[p] not in (-2, -3)]
-        cdf = np.zeros((P, len(non_meta)), np.float64)
-        for rel_id in non_meta:                                       # graphs_utils.py:126-140, candidates ascending
-            cdf[rel_id] = _choice_cdf(w, rel_id, [c for c in non_meta if c != rel_id])
-        cdf_d = torch.from_numpy(cdf).to(dev)
-        u_d = torch.from_numpy(u).to(dev)
-        off_d = u_off.to(dev)
+        _refuse_negative(draws, _BAD_DEVICE_ROW)
+        cdf_d, u_d, off_d, _ = _converse_plan(w, [None if roles[p] in (-2, -3) else p for p in range(P)], draws, uniforms, dev)
         check(lib.csg_canon_general_converse(B, roles_c, P, ptr(ws), nbytes, ptr(cdf_d), ptr(u_d), ptr(off_d),
                                              ptr(conv_counts), stream()), "canon_general_converse")
     check(lib.csg_canon_general_close(B, roles_c, P, 1 if learned_transitivity else 0, ptr(ws), nbytes, ptr(counts),
                                       stream()), "canon_general_close")
     if rel_dev is not None:                          # the same single read-back, of every count: a negative one is a refusal
         counts_host = counts.cpu()
-        _refuse_dropped_rows(counts_host[:, 0])
-        T = int(counts_host.sum(dim=1).max())
+        _refuse_negative(counts_host[:, 0], _BAD_DEVICE_ROW)
+        totals = counts_host.sum(dim=1)
     else:
-        T = int(counts.sum(dim=1).max().item())      # vg_collate_fn pads to the longest sample: one 8-byte read-back
-    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
-    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
-    check(lib.csg_canon_general_emit(B, roles_c, P, ptr(ws), nbytes, ptr(counts), T, ptr(out), ptr(triplet_type),
-                                     stream()), "canon_general_emit")
+        totals = counts.sum(dim=1).max().view(1).cpu()       # vg_collate_fn pads to the longest sample: one 8-byte read-back
+    out, triplet_type = _emit(totals, B, dev, "canon_general_emit", lambda T, trip, tt: lib.csg_canon_general_emit(
+        B, roles_c, P, ptr(ws), nbytes, ptr(counts), T, trip, tt, stream()))
     return out, conv_counts, triplet_type
 
 
@@ -169,20 +223,10 @@ def annotated_triplets(objs, n_objs, vocab, rows, rows_host=None, learned_transi
     objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
     dev = objs0.device
     B, O = objs0.shape
-    first = list(vocab["attributes"].keys())[0]
-    image_id = vocab["object_name_to_idx"]["__image__"]
-    if vocab["attributes"][first]["__image__"] != image_id:
-        raise ValueError("the __image__ id of the first attribute and of object_name_to_idx differ")
-    p2i = vocab["pred_name_to_idx"]
-    P, pad, in_image = len(p2i), p2i["__padding__"], p2i["__in_image__"]
-    rel_h = _host_int64(rows if rows_host is None else rows_host)
-    if rel_h.dim() != 3 or rel_h.shape[0] != B or rel_h.shape[2] != 3 or tuple(rows.shape) != tuple(rel_h.shape):
-        raise ValueError("rows must be (B, R, 3), and rows_host of the same shape; got %s and %s" % (
-            tuple(rows.shape), tuple(rel_h.shape)))
-    R = rel_h.shape[1]
-    rel_d = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous()
-    n_host = _host_int64(n_objs)
-    n_dev = (n_objs if torch.is_tensor(n_objs) and n_objs.device == dev else n_host).to(device=dev, dtype=torch.int64).contiguous()
+    image_id = _image_id(vocab)
+    P, pad, in_image = _meta_ids(vocab)
+    rel_h, rel_d, R = _rows_both_sides(rows, rows_host, B, dev)
+    n_host, n_dev = _n_objs_both_sides(n_objs, None, dev)
     nbytes = lib.csg_canon_small_workspace(B, P)
     if nbytes < 0:
         raise RuntimeError("annotated_triplets: at most 256 predicates (the vocabulary has %d)" % P)
@@ -192,22 +236,15 @@ def annotated_triplets(objs, n_objs, vocab, rows, rows_host=None, learned_transi
     cdf_d = u_d = off_d = None
     total = 0
     if learned_converse:
-        if converse_weights is None:
-            raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
-        w = converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
+        w = _weights(converse_weights)
         rel_np = rel_h.numpy()
         draws = torch.zeros(B, dtype=torch.int64)
         for b in range(B):                                            # np.unique of a sample's rows, meta predicates apart
             r = rel_np[b]
             r = r[(r[:, 1] != pad) & (r[:, 1] != in_image)]
             draws[b] = len(np.unique(r, axis=0)) if len(r) else 0
-        u, u_off = _draw_numbers(draws, uniforms)
-        total = int(draws.sum())
-        non_meta = [p for p in range(P) if p not in (pad, in_image)]
-        cdf = np.zeros((P, len(non_meta)), np.float64)
-        for rel_id in non_meta:                                       # graphs_utils.py:126-140, candidates ascending
-            cdf[rel_id] = _choice_cdf(w, rel_id, [c for c in non_meta if c != rel_id])
-        cdf_d, u_d, off_d = torch.from_numpy(cdf).to(dev), torch.from_numpy(u).to(dev), u_off.to(dev)
+        cdf_d, u_d, off_d, total = _converse_plan(w, [None if p in (pad, in_image) else p for p in range(P)], draws, uniforms,
+                                                  dev)
     check(lib.csg_canon_small_build(ptr(objs0), ptr(n_dev), ctypes.c_void_p(n_host.data_ptr()), B, O,
                                     ptr(rel_d) if R else None, ctypes.c_void_p(rel_h.data_ptr()) if R else None, R, P, pad,
                                     in_image, image_id, 1 if include_dummies else 0, 1 if learned_transitivity else 0,
@@ -216,15 +253,9 @@ def annotated_triplets(objs, n_objs, vocab, rows, rows_host=None, learned_transi
                                     ptr(conv_counts) if learned_converse else None, ptr(ws), nbytes, ptr(counts), stream()),
           "canon_small_build")
     counts_host = counts.cpu()                       # the one read-back: vg_collate_fn pads to the longest sample
-    bad = (counts_host[:, 0] < 0).nonzero()
-    if bad.numel():
-        raise RuntimeError("annotated_triplets: the rows of sample %d on the device are not the rows the host holds: one lies "
-                           "outside [0, n_objs) or outside the vocabulary; no graph was written" % int(bad[0, 0]))
-    T = int(counts_host.sum(dim=1).max())
-    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
-    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
-    check(lib.csg_canon_small_emit(B, P, pad, ptr(ws), nbytes, ptr(counts), T, ptr(out), ptr(triplet_type), stream()),
-          "canon_small_emit")
+    _refuse_negative(counts_host[:, 0], _OTHER_ROWS % ("annotated_triplets", "n_objs"))
+    out, triplet_type = _emit(counts_host.sum(dim=1), B, dev, "canon_small_emit", lambda T, trip, tt: lib.csg_canon_small_emit(
+        B, P, pad, ptr(ws), nbytes, ptr(counts), T, trip, tt, stream()))
     return out, conv_counts, triplet_type
 
 
@@ -256,33 +287,20 @@ def clevr_triplets(objs, n_objs, vocab, rows, rows_host=None, use_transitivity=0
         raise ValueError("objs must be (B, O) or (B, O, A); got %s" % (tuple(objs.shape),))
     dev = objs0.device
     B, O = objs0.shape
-    p2i = vocab["pred_name_to_idx"]
-    P, pad, in_image = len(p2i), p2i["__padding__"], p2i["__in_image__"]
-    rel_h = _host_int64(rows if rows_host is None else rows_host)
-    if rel_h.dim() != 3 or rel_h.shape[0] != B or rel_h.shape[2] != 3 or tuple(rows.shape) != tuple(rel_h.shape):
-        raise ValueError("rows must be (B, R, 3), and rows_host of the same shape; got %s and %s" % (
-            tuple(rows.shape), tuple(rel_h.shape)))
-    R = rel_h.shape[1]
-    rel_d = torch.as_tensor(rows).to(device=dev, dtype=torch.int64).contiguous()
-    n_host = _host_int64(n_objs if n_objs_host is None else n_objs_host)
+    P, pad, in_image = _meta_ids(vocab)
+    rel_h, rel_d, R = _rows_both_sides(rows, rows_host, B, dev)
+    n_host, n_dev = _n_objs_both_sides(n_objs, n_objs_host, dev)
     if tuple(n_host.shape) != (B,) or tuple(np.shape(n_objs)) != (B,):
         raise ValueError("n_objs, and n_objs_host, must be (B,) = (%d,); got %s and %s" % (
             B, tuple(np.shape(n_objs)), tuple(n_host.shape)))
-    n_dev = (n_objs if torch.is_tensor(n_objs) and n_objs.device == dev else n_host).to(device=dev, dtype=torch.int64).contiguous()
     counts = torch.empty((B,), device=dev, dtype=torch.int64)
     check(lib.csg_clevr_graph_count(ptr(n_dev), ctypes.c_void_p(n_host.data_ptr()), B, O, ptr(rel_d) if R else None,
                                     ctypes.c_void_p(rel_h.data_ptr()) if R else None, R, P, pad, in_image,
                                     int(use_transitivity), ptr(counts), stream()), "clevr_graph_count")
     counts_host = counts.cpu()                       # the one read-back: the collate pads to the longest sample
-    bad = (counts_host < 0).nonzero()
-    if bad.numel():
-        raise RuntimeError("clevr_triplets: the rows of sample %d on the device are not the rows the host holds: one lies "
-                           "outside [0, n_objs - 1) or outside the vocabulary; no graph was written" % int(bad[0, 0]))
-    T = int(counts_host.max())
-    out = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
-    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
-    check(lib.csg_clevr_graph_emit(ptr(n_dev), B, O, ptr(rel_d) if R else None, R, P, pad, in_image, int(use_transitivity), T,
-                                   ptr(out), ptr(triplet_type), stream()), "clevr_graph_emit")
+    _refuse_negative(counts_host, _OTHER_ROWS % ("clevr_triplets", "n_objs - 1"))
+    out, triplet_type = _emit(counts_host, B, dev, "clevr_graph_emit", lambda T, trip, tt: lib.csg_clevr_graph_emit(
+        ptr(n_dev), B, O, ptr(rel_d) if R else None, R, P, pad, in_image, int(use_transitivity), T, trip, tt, stream()))
     conv_counts = torch.zeros((B, P, P + 1), device=dev, dtype=torch.float32)        # never drawn: clevr_dialog.py has no
     return out, conv_counts, triplet_type                                            # add_learnt_triplets
 
@@ -333,10 +351,7 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
                                   include_dummies=include_dummies, learned_converse=learned_converse,
                                   converse_weights=converse_weights, uniforms=uniforms)
     objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
-    first = list(vocab["attributes"].keys())[0]
-    image_id = vocab["object_name_to_idx"]["__image__"]
-    if vocab["attributes"][first]["__image__"] != image_id:
-        raise ValueError("the __image__ id of the first attribute and of object_name_to_idx differ")
+    image_id = _image_id(vocab)
     B, O = objs0.shape
     names = meta_relations + augmented_relations
     if (boxes is None) != (obj_centers is None) or (boxes is None and triplets is None):
@@ -383,9 +398,7 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     n_rel = len(p2i)
     conv_counts = torch.zeros((B, n_rel, n_rel + 1), device=dev, dtype=torch.float32)     # base_dataset.py:93
     if learned_converse:
-        if converse_weights is None:
-            raise ValueError("learned_converse needs the data loader's converse_candidates_weights")
-        w = converse_weights.detach().cpu().numpy() if torch.is_tensor(converse_weights) else np.asarray(converse_weights)
+        w = _weights(converse_weights)
         # one draw per original triplet of the six location relations = originals minus the __in_image__ dummies
         in_range = torch.arange(O, device=dev).unsqueeze(0) < n_objs.unsqueeze(1)
         has_img = ((objs0 == image_id) & in_range).any(dim=1)
@@ -397,33 +410,18 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
             draws = both[:B]
             _refuse_rows_beyond(both[B:], O)
             rows_checked = True
-        u_off = torch.cumsum(draws, 0) - draws
-        total = int(draws.sum())
-        if uniforms is None:
-            u = np.random.random_sample(total)                       # the reference's np.random.choice draws, in its order
-        else:
-            u = np.asarray(uniforms, np.float64).reshape(-1)
-            if u.shape[0] < total:
-                raise ValueError("learned_converse: %d uniform numbers given, %d needed" % (u.shape[0], total))
-        loc = [p2i[n] for n in augmented_relations]
-        cdf = np.zeros((6, 6), np.float64)
-        for r, rel in enumerate(loc):
-            cdf[r] = _choice_cdf(w, rel, sorted(c for c in loc if c != rel))
-        cdf_d = torch.from_numpy(cdf).to(dev)
-        u_d = torch.from_numpy(np.ascontiguousarray(u[:max(total, 1)] if total else np.zeros(1))).to(dev)
-        off_d = u_off.to(dev)
+        cdf_d, u_d, off_d, _ = _converse_plan(w, [p2i[n] for n in augmented_relations], draws, uniforms, dev)
         check(lib.csg_canon_converse(ptr(objs0), ptr(n_objs), B, O, ids, image_id, 1 if include_dummies else 0,
                                      1 if learned_transitivity else 0, ptr(ws), ptr(cdf_d), ptr(u_d), ptr(off_d), n_rel,
                                      ptr(conv_counts), ptr(counts), stream()), "canon_converse")
+    longest = counts.sum(dim=1).max().view(1)        # the collate pads to the longest sample: one 8-byte read-back
     if rows_checked:
-        T = int(counts.sum(dim=1).max().item())      # the collate pads to the longest sample: one 8-byte read-back
+        longest = longest.cpu()
     else:                                            # the same read-back carries n_objs
-        both = torch.cat([counts.sum(dim=1).max().view(1), n_objs]).cpu()
+        both = torch.cat([longest, n_objs]).cpu()
         _refuse_rows_beyond(both[1:], O)
-        T = int(both[0])
-    triplets = torch.empty((B, T, 3), device=dev, dtype=torch.int64)
-    triplet_type = torch.empty((B, T), device=dev, dtype=torch.int64)
-    check(lib.csg_canon_emit(ptr(objs0), ptr(n_objs), B, O, ids, image_id, 1 if include_dummies else 0,
-                             1 if learned_transitivity else 0, ptr(ws), ptr(counts), T, ptr(triplets),
-                             ptr(triplet_type), stream()), "canon_emit")
+        longest = both[:1]
+    triplets, triplet_type = _emit(longest, B, dev, "canon_emit", lambda T, trip, tt: lib.csg_canon_emit(
+        ptr(objs0), ptr(n_objs), B, O, ids, image_id, 1 if include_dummies else 0, 1 if learned_transitivity else 0, ptr(ws),
+        ptr(counts), T, trip, tt, stream()))
     return triplets, conv_counts, triplet_type

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timing of the device-side canonical graph construction (csrc/canon.hip) at the C5 sizes, with the
 numpy oracle (oracle/canon.py — the checker, timed here only as the CPU baseline) beside it.
-Usage (GPU box): python tools/canon_bench.py [--batch 48] [--objects 128] [--reps 20]"""
+Usage (GPU box): python tests/dev/canon_bench.py [--batch 48] [--objects 128] [--reps 20]"""
 import argparse
 import json
 import os
