@@ -229,6 +229,15 @@ SIGNATURES = {
     "csg_canon_small_emit": (c_i32, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
     "csg_clevr_graph_count": (c_i32, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p]),
     "csg_clevr_graph_emit": (c_i32, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_p, c_p, c_p]),
+    "csg_resize_bilinear": (c_i32, [c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_i32, c_p, c_p]),
+    "csg_pool3": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_p, c_i64, c_i64, c_p]),
+    "csg_spatial_mean": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
+    "csg_bias_act": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i32, c_f32, c_p]),
+    "csg_feat_stats": (c_i32, [c_p, c_i64, c_i64, c_p, c_p, c_p]),
+    "csg_feat_stats_finalize": (c_i32, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p]),
+    "csg_softmax_rows": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p]),
+    "csg_inception_score_workspace": (c_i64, [c_i64, c_i64, c_i64]),
+    "csg_inception_score": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
 }
 
 

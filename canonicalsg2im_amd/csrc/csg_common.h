@@ -73,6 +73,12 @@ enum KernelId {
   K_CLEVR_GRAPH_COUNT,
   K_CLEVR_GRAPH_EMIT,
   K_COCO_MASKS,
+  K_RESIZE_BILINEAR,
+  K_POOL3,
+  K_SPATIAL_MEAN,
+  K_BIAS_ACT,
+  K_FEAT_STATS,
+  K_INCEPTION_SCORE,
   K_COUNT
 };
 

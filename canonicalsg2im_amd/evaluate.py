@@ -19,8 +19,10 @@ on the device and come to the host in ONE copy at the end.  (`gans_model` itself
 object discriminator's crops, as it does in a training step.)  The trainer's captured step graphs are not touched.
 
 Differences from the reference, on purpose:
-  * no `inception_mean` / `inception_std`: the Inception network's weights are not available, and a zero there would be a
-    false number;
+  * `inception_mean` / `inception_std` appear only when `check_model` is given an Inception network (`inception=`,
+    `scripts.evaluate --inception_weights FILE`): every generated batch is then fed to `quality.InceptionScore` as at :198 and
+    the score is computed with splits=5 (:262-268).  Without a network the two keys are absent — the reference's weights are a
+    download, and a zero there would be a false number;
   * the table's `iou05` is the share of boxes above 0.5; the reference appends `mean(iou03)` under that name (:221), a slip;
   * the table is a dict of host tensors, not a pandas frame (pandas is not a dependency); `predicted_boxes` / `gt_boxes`
     are the padded (N, O, 4) arrays with `counted` marking the rows the metric kept, not strings; no `class` column;
@@ -95,8 +97,11 @@ class Evaluator:
         return self.sampler._generator(objs, boxes.float().contiguous(), None if masks is None else masks.float().contiguous(),
                                        False, True)[0]
 
-    def check_model(self, batches, use_gt=True, num_val_samples=None, full_test=False):
+    def check_model(self, batches, use_gt=True, num_val_samples=None, full_test=False, inception=None):
         """-> (mean_losses, samples, table).  `batches`: an iterable of collated batches on the trainer's device.
+        `inception`: an `inception.InceptionV3("torchvision", ...)`; mean_losses then gains `inception_mean` /
+        `inception_std` of the generated images (splits=5), and `inception_stand_in` = 1.0 when the network is the seeded
+        stand-in, whose score means nothing.
         mean_losses: {name: 0-d host tensor} — every generator loss but `bbox_pred_all`, averaged per batch and then over
         the batches, plus `avg_iou`, `total_iou_05`, `total_iou_03` (totals / counted boxes, float64) with the graph model.
         samples: {key: uint8 (B,H,W,3) host tensor} of the LAST batch (keys and conditions of :242-255).
@@ -107,6 +112,10 @@ class Evaluator:
         dev = torch.device(tr.device)
         obj_d = None if opt.use_img_disc or opt.skip_generation else tr.discriminator.obj_discriminator
         losses, rows = {}, []
+        score = None
+        if inception is not None:
+            from .quality import InceptionScore
+            score = InceptionScore(inception)
         totals = torch.zeros(4, device=dev, dtype=torch.float64)
         num_samples, last = 0, None
         self._fresh_sampler()
@@ -132,6 +141,8 @@ class Evaluator:
                     G = tr.gans_model(batch, (img, boxes_pred, masks_pred), mode="compute_generator_loss")
                     if obj_d is not None:
                         obj_d.release_index()
+                    if score is not None and img is not None:
+                        score.update(img.float())            # scripts/train.py:198
                     for k, v in G.items():
                         if k != "bbox_pred_all":
                             losses.setdefault(k, []).append(v.mean())
@@ -149,6 +160,12 @@ class Evaluator:
                     raise ValueError("check_model: no validation batch was given")
                 samples = self._samples(last)
                 mean_losses, table = self._collect(losses, totals, rows, dev)
+                if score is not None and score.n:
+                    mean, std = score.compute(splits=5)     # scripts/train.py:266
+                    mean_losses.update({"inception_mean": torch.tensor(mean, dtype=torch.float64),
+                                        "inception_std": torch.tensor(std, dtype=torch.float64)})
+                    if score.stand_in:
+                        mean_losses["inception_stand_in"] = torch.tensor(1.0, dtype=torch.float64)
         finally:
             model.train()                               # scripts/train.py:270
         return mean_losses, samples, table

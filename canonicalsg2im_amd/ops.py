@@ -22,6 +22,7 @@ __all__ = [
     "nhwc", "empty_nhwc", "conv2d", "linear", "norm_act", "upsample2x", "nearest_resize", "avgpool3s2", "embed", "real_object_mask",
     "norm_act_pair", "graph_csr", "gather_concat", "segment_avg", "layout_pyramid", "layout_paint", "disc_input", "crop_objects", "maxpool2", "avgpool2", "l1_mean",
     "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "preprocess_images", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
+    "conv2d_forward", "pool3", "spatial_mean", "resize_bilinear", "feat_stats", "feat_stats_finalize", "softmax_rows", "inception_score", "POOL_MAX", "POOL_AVG9", "POOL_AVG_INSIDE",
 ]
 
 
@@ -2407,3 +2408,184 @@ class _CropObjects(torch.autograd.Function):
 def crop_objects(img, boxes, img_idx, HH):
     """img (B,C,H,W); boxes (N,4) xywh of the real objects in (image, object) order; img_idx (N,) int64."""
     return _CropObjects.apply(img, boxes, img_idx.contiguous(), int(HH))
+
+
+# ------------------------------------------------------------------------------------ Inception forward, FID, Inception score
+# Forward-only entry points (csrc/inception.hip and csg_conv_fwd): inference of a frozen network, no autograd Function.
+def _nhwc_whole(t, what):
+    """(B, C, H, W) of a logical NCHW fp32 HIP tensor whose memory is dense NHWC (its own buffer, no channel slice)."""
+    if t.dim() != 4 or not t.permute(0, 2, 3, 1).is_contiguous():
+        raise RuntimeError("%s: needs a (B,C,H,W) tensor with dense NHWC memory (ops.nhwc / ops.empty_nhwc)" % what)
+    _f32(t)
+    return t.shape[0], t.shape[1], t.shape[2], t.shape[3]
+
+
+def _no_grad_only(what, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError("%s is forward only: it has no backward pass; call it under torch.no_grad() or on detached "
+                           "tensors" % what)
+
+
+def _out_slice(out, out_off, B, C, OH, OW, dev, what):
+    """The destination of a pass that writes channels [out_off, out_off + C) of `out` (a fresh (B,C,OH,OW) map if None)."""
+    if out is None:
+        if out_off:
+            raise RuntimeError("%s: out_off needs out=" % what)
+        return empty_nhwc(B, C, OH, OW, dev), C
+    ob, oc, oh, ow = _nhwc_whole(out, what + " out=")
+    if (ob, oh, ow) != (B, OH, OW) or out_off < 0 or out_off % 4 or out_off + C > oc or oc % 4 or out.device != dev:
+        raise RuntimeError("%s: out= is %s, the pass writes channels [%d, %d) of a (%d, *, %d, %d) map" % (
+            what, tuple(out.shape), out_off, out_off + C, B, OH, OW))
+    return out, oc
+
+
+def conv2d_taps_desc(B, IH, IW, Cin, Cout, KH, KW, stride, pad_h, pad_w, first, count, act=ACT_NONE, slope=0.0, y_cs=None,
+                     accumulate=0):
+    """The csg_conv_fwd descriptor of taps [first, first + count) (row-major over (ky, kx)) of a KH x KW convolution with
+    separate paddings — a rectangular filter, or one launch of a filter with more than MAX_TAPS taps.  The weight is
+    [Cout][KH*KW][Cin] whole (wtaps = KH*KW).  Host only."""
+    if not 1 <= count <= _lib.MAX_TAPS or first < 0 or first + count > KH * KW:
+        raise RuntimeError("conv2d_taps_desc: taps [%d, %d) of a %d x %d filter" % (first, first + count, KH, KW))
+    d = ConvDesc()
+    d.B, d.IHp, d.IWp, d.Cin, d.x_cs = B, IH, IW, Cin, Cin
+    d.IHv, d.IWv, d.in_up = IH, IW, 0
+    OH = (IH + 2 * pad_h - KH) // stride + 1
+    OW = (IW + 2 * pad_w - KW) // stride + 1
+    d.OHg, d.OWg, d.OHf, d.OWf, d.os, d.ooy, d.oox = OH, OW, OH, OW, 1, 0, 0
+    d.Cout, d.y_cs = Cout, (Cout if y_cs is None else y_cs)
+    d.istride, d.ntaps, d.wtaps = stride, count, KH * KW
+    for n in range(count):
+        s = first + n
+        d.tap_dy[n], d.tap_dx[n], d.tap_w[n] = s // KW - pad_h, s % KW - pad_w, s
+    d.act, d.slope, d.accumulate = act, slope, accumulate
+    return d, OH, OW
+
+
+def conv2d_forward(x, wp, bias, KH, KW, stride=1, padding=(0, 0), act=ACT_NONE, slope=0.0, out=None, out_off=0):
+    """y = act(conv(x, w) + bias), forward only, written into channels [out_off, out_off + Cout) of `out` (no concatenation
+    copy behind the branches of a block).  wp: the frozen weight as [Cout][KH][KW][Cin] dense; padding = (pad_h, pad_w), so
+    (1,7), (7,1), (1,3), (3,1) filters are tap tables like any other.  A filter with more than MAX_TAPS taps (5x5: 25) runs
+    as ceil(taps / MAX_TAPS) launches over the one weight — the first writes, the others accumulate, all without bias and
+    activation — and csg_bias_act applies both to the SUM."""
+    B, Cin, IH, IW = _nhwc_whole(x, "conv2d_forward")
+    _no_grad_only("conv2d_forward", x, wp, bias)
+    pad_h, pad_w = (padding, padding) if isinstance(padding, int) else padding
+    Cout = wp.shape[0]
+    if tuple(wp.shape) != (Cout, KH, KW, Cin) or not wp.is_contiguous() or Cout % 4 or Cin % 4:
+        raise RuntimeError("conv2d_forward: weight %s is not a dense [Cout][%d][%d][%d] with channel counts that are "
+                           "multiples of 4" % (tuple(wp.shape), KH, KW, Cin))
+    OH, OW = (IH + 2 * pad_h - KH) // stride + 1, (IW + 2 * pad_w - KW) // stride + 1
+    if OH < 1 or OW < 1:
+        raise RuntimeError("conv2d_forward: a %dx%d map is too small for a %dx%d filter" % (IH, IW, KH, KW))
+    y, y_cs = _out_slice(out, out_off, B, Cout, OH, OW, x.device, "conv2d_forward")
+    yp = ctypes_ptr_off(y, out_off)
+    taps = KH * KW
+    single = taps <= _lib.MAX_TAPS
+    for first in range(0, taps, _lib.MAX_TAPS):
+        d, _, _ = conv2d_taps_desc(B, IH, IW, Cin, Cout, KH, KW, stride, pad_h, pad_w, first, min(_lib.MAX_TAPS, taps - first),
+                                   act if single else ACT_NONE, slope if single else 0.0, y_cs, 1 if first else 0)
+        nbytes = lib.csg_conv_fwd_workspace(d)
+        if nbytes < 0:
+            raise RuntimeError("conv_fwd_workspace: " + _lib.last_error())
+        ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes > 0 else None
+        check(lib.csg_conv_fwd(d, ptr(x), ptr(wp), ptr(bias) if single else None, None, yp, ptr(ws), nbytes, stream()),
+              "conv2d_forward")
+    if not single and (bias is not None or act != ACT_NONE):
+        check(lib.csg_bias_act(yp, B * OH * OW, Cout, y_cs, 0, ptr(bias), act, slope, stream()), "bias_act")
+    return y if out is None else out
+
+
+POOL_MAX, POOL_AVG9, POOL_AVG_INSIDE = 0, 1, 2
+
+
+def pool3(x, kind, stride, pad, out=None, out_off=0):
+    """3x3 pool (csg_pool3): kind POOL_MAX / POOL_AVG9 (count_include_pad=True) / POOL_AVG_INSIDE (=False); (stride, pad) in
+    {(1, 1), (2, 0)}; written into channels [out_off, out_off + C) of `out` when given."""
+    B, C, H, W = _nhwc_whole(x, "pool3")
+    _no_grad_only("pool3", x)
+    OH, OW = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
+    if OH < 1 or OW < 1:
+        raise RuntimeError("pool3: a %dx%d map is too small" % (H, W))
+    y, y_cs = _out_slice(out, out_off, B, C, OH, OW, x.device, "pool3")
+    check(lib.csg_pool3(ptr(x), B, H, W, C, C, int(kind), int(stride), int(pad), ptr(y), y_cs, out_off, stream()), "pool3")
+    return y
+
+
+def spatial_mean(x):
+    """(B,C,H,W) NHWC -> (B,C): the mean over the pixels (csg_spatial_mean)."""
+    B, C, H, W = _nhwc_whole(x, "spatial_mean")
+    _no_grad_only("spatial_mean", x)
+    y = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    check(lib.csg_spatial_mean(ptr(x), B, H * W, C, C, ptr(y), stream()), "spatial_mean")
+    return y
+
+
+def resize_bilinear(src, size, a=1.0, b=0.0, reverse=False):
+    """F.interpolate(mode='bilinear', align_corners=False) to `size` = (OH, OW), then a * x + b (csg_resize_bilinear).
+    src: uint8 (B,H,W,3) — bytes, divided by 255 first — or fp32 logical (B,3,H,W) / (B,4,H,W) with NHWC memory (a generated
+    image).  Returns logical (B,4,OH,OW) with NHWC memory, channel 3 zero; reverse=True swaps channels 0 and 2."""
+    OH, OW = int(size[0]), int(size[1])
+    if src.dtype == torch.uint8:
+        if src.dim() != 4 or src.shape[3] != 3 or not src.is_contiguous():
+            raise RuntimeError("resize_bilinear: uint8 pictures must be a dense (B,H,W,3) tensor, got %s" % (tuple(src.shape),))
+        B, IH, IW, cs, u8 = src.shape[0], src.shape[1], src.shape[2], 3, 1
+    else:
+        _f32(src)
+        _no_grad_only("resize_bilinear", src)
+        if src.dim() != 4 or src.shape[1] not in (3, 4):
+            raise RuntimeError("resize_bilinear: fp32 images must be (B,3,H,W) or (B,4,H,W), got %s" % (tuple(src.shape),))
+        src = nhwc(src.detach())
+        B, IH, IW, cs, u8 = src.shape[0], src.shape[2], src.shape[3], src.shape[1], 0
+    out = empty_nhwc(B, 4, OH, OW, src.device)
+    check(lib.csg_resize_bilinear(ptr(src), u8, B, IH, IW, cs, OH, OW, float(a), float(b), int(bool(reverse)), ptr(out),
+                                  stream()), "resize_bilinear")
+    return out
+
+
+def feat_stats(x, total, outer):
+    """total (D) += sum_n x[n]; outer (D,D) += sum_n x[n] x[n]^T — fp64 accumulators on the device, x (n,D) fp32, D a
+    multiple of 64 (csg_feat_stats; rows in order, no atomics)."""
+    _f32(x)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError("feat_stats: features must be a dense (n,D) fp32 tensor")
+    n, D = x.shape
+    for t, shape in ((total, (D,)), (outer, (D, D))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise RuntimeError("feat_stats: the accumulators must be dense float64 (D,) and (D,D) on the features' device")
+    check(lib.csg_feat_stats(ptr(x.detach()), n, D, ptr(total), ptr(outer), stream()), "feat_stats")
+
+
+def feat_stats_finalize(total, outer, N):
+    """(mu (D), sigma (D,D)) fp64 on the device: np.mean(axis=0) and np.cov(rowvar=False) of the N accumulated rows."""
+    D = total.shape[0]
+    mu = torch.empty((D,), device=total.device, dtype=torch.float64)
+    sigma = torch.empty((D, D), device=total.device, dtype=torch.float64)
+    check(lib.csg_feat_stats_finalize(ptr(total), ptr(outer), int(N), D, ptr(mu), ptr(sigma), stream()), "feat_stats_finalize")
+    return mu, sigma
+
+
+def softmax_rows(logits):
+    """(N,K) fp32 logits -> (N,K) float64: the fp32 row softmax, widened (csg_softmax_rows)."""
+    _f32(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("softmax_rows: logits must be (N,K) fp32 with unit column stride")
+    N, K = logits.shape
+    probs = torch.empty((N, K), device=logits.device, dtype=torch.float64)
+    check(lib.csg_softmax_rows(ptr(logits.detach()), N, K, logits.stride(0), ptr(probs), stream()), "softmax_rows")
+    return probs
+
+
+def inception_score(probs, splits):
+    """float64 device vector [mean, population std, split scores...] of compute_score(splits) over probs (N,K) float64
+    (csg_inception_score)."""
+    if probs.dtype != torch.float64 or probs.dim() != 2 or not probs.is_contiguous():
+        raise RuntimeError("inception_score: probabilities must be a dense (N,K) float64 tensor")
+    N, K = probs.shape
+    splits = int(splits)
+    if not 1 <= splits <= N:
+        raise RuntimeError("inception_score: %d splits of %d rows" % (splits, N))
+    nbytes = lib.csg_inception_score_workspace(N, K, splits)
+    ws = torch.empty(nbytes // 8, device=probs.device, dtype=torch.float64)
+    out = torch.empty((2 + splits,), device=probs.device, dtype=torch.float64)
+    check(lib.csg_inception_score(ptr(probs), N, K, splits, ptr(ws), nbytes, ptr(out), stream()), "inception_score")
+    return out

@@ -13,6 +13,10 @@ of them:
     --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (required)
     --output_dir DIR         where <pass>_<key>_%03d.png, metrics.json and table.json go (default: nothing is written)
     --num_val_samples N      images to validate (default 1024, the reference's), in batches of --batch_size
+    --inception_weights FILE torchvision's inception_v3_google-*.pth: both passes also report `inception_mean` /
+                             `inception_std` of the generated images (splits=5, scripts/train.py:198,262-268).  `random` is the
+                             seeded stand-in (throughput only; the lines then carry inception_stand_in 1).  Loading the real
+                             file and the numbers it gives are unchecked here.  Without the flag nothing changes.
 
     python -m canonicalsg2im_amd.scripts.evaluate --dataset packed_coco --image_size 256,256 --batch_size 16 \\
         --checkpoint_name out/itr_100000.pt --output_dir val --num_val_samples 1024
@@ -38,7 +42,9 @@ _NO_CHECKPOINT = "checkpoint"           # the reference's default of --checkpoin
 
 def build_parser():
     from .args import build_parser as train_parser
-    return train_parser()
+    p = train_parser()
+    p.add_argument("--inception_weights", default=None)
+    return p
 
 
 def parse_args(argv=None):
@@ -93,13 +99,14 @@ def log_results(losses, t, prefix):
     print(head + ("  " + rest if rest else ""), flush=True)
 
 
-def validate(args, evaluator, dev, t, world=1, val_set=None):
+def validate(args, evaluator, dev, t, world=1, val_set=None, inception=None):
     """The two passes of scripts/train.py:410-424 -> (gt_val_losses, val_losses, val_samples, val_table)."""
     tr = evaluator.trainer
-    gt_losses, _, _ = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=True)
+    extra = {} if inception is None else {"inception": inception}
+    gt_losses, _, _ = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=True, **extra)
     log_results(gt_losses, t, "GT VAL")
     use_gt = bool(args.skip_graph_model)                                          # :419
-    losses, samples, table = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=use_gt)
+    losses, samples, table = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=use_gt, **extra)
     log_results(losses, t, "VAL")
     return gt_losses, losses, samples, table
 
@@ -139,7 +146,11 @@ def main(argv=None):
     torch.manual_seed(0)
     trainer = T.Trainer(args, dev)
     t, _ = trainer.load_checkpoint(args.checkpoint_name)
-    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t, val_set=val_set)
+    net = None
+    if getattr(args, "inception_weights", None):
+        from ..inception import InceptionV3
+        net = InceptionV3("torchvision", args.inception_weights).to(dev)
+    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t, val_set=val_set, inception=net)
     if args.output_dir:
         write_outputs(args.output_dir, gt_losses, losses, samples, table)
     torch.cuda.synchronize()

@@ -53,7 +53,9 @@ extern "C" {
  * 116: csg_pair_relations, csg_canon_general_build_dev;
  * 117: csg_canon_small_workspace, csg_canon_small_build, csg_canon_small_emit;
  * 118: csg_clevr_graph_count, csg_clevr_graph_emit;
- * 119: csg_coco_masks) */
+ * 119: csg_coco_masks;
+ * 120: csg_resize_bilinear, csg_pool3, csg_spatial_mean, csg_bias_act, csg_feat_stats, csg_feat_stats_finalize,
+ *      csg_softmax_rows, csg_inception_score_workspace, csg_inception_score) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -962,6 +964,48 @@ typedef struct csg_sn_bwd_item {
   int64_t workspace_bytes;
 } csg_sn_bwd_item;
 int csg_spectral_norm_bwd_multi(const csg_sn_bwd_item* items, int32_t n, void* stream);
+
+/* ---- Inception-v3 forward and the statistics behind FID and the Inception score (csrc/inception.hip) ----------------
+ * The network of evaluation/fid/inception.py:166-310 and torchvision's inception_v3 (evaluation/inception.py:16) runs its 94
+ * convolutions through csg_conv_fwd; these are the passes around them.  All stream ordered and capturable, no atomics, every
+ * sum in one fixed order.  Maps are NHWC fp32; channel counts, pixel strides and channel offsets are multiples of 4.
+ *
+ * csg_resize_bilinear: F.interpolate(mode='bilinear', align_corners=False), no antialiasing (fid/inception.py:146-150,
+ * evaluation/inception.py:26), then a * x + b (fid/inception.py:153).  src: fp32 (B,IH,IW,src_cs) with src_cs 3 or 4 (src_u8 = 0)
+ * or uint8 (B,IH,IW,3) (src_u8 = 1; a byte is first divided by 255 in fp32, fid_score.py:115).  out: fp32 (B,OH,OW,4), the
+ * fourth channel 0; reverse = 1 writes the three channels in the opposite order (a BGR reader, fid_score.py:111).        */
+int csg_resize_bilinear(const void* src, int32_t src_u8, int64_t B, int64_t IH, int64_t IW, int64_t src_cs, int64_t OH,
+                        int64_t OW, float a, float b, int32_t reverse, float* out, void* stream);
+/* 3x3 pool with (stride, pad) = (1, 1) or (2, 0).  kind 0: max, padding -inf (F.max_pool2d); 1: the sum divided by 9
+ * (F.avg_pool2d, count_include_pad=True); 2: divided by the number of taps inside the picture (count_include_pad=False,
+ * fid/inception.py:210).  The taps inside the picture are visited row by row, left to right, the averages start from 0 and
+ * divide once: torch's host arithmetic, bit for bit.  x (B,H,W,x_cs), C channels read; y (B,OH,OW,y_cs), written at channels
+ * [y_off, y_off + C) only.                                                                                            */
+int csg_pool3(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, int64_t x_cs, int32_t kind, int32_t stride,
+              int32_t pad, float* y, int64_t y_cs, int64_t y_off, void* stream);
+/* y (B,C) = mean over the P pixels of x (B,P,x_cs): adaptive_avg_pool2d(1) (fid_score.py:125-126).  B <= 65535. */
+int csg_spatial_mean(const float* x, int64_t B, int64_t P, int64_t C, int64_t x_cs, float* y, void* stream);
+/* y[p, y_off + c] = act(y[p, y_off + c] + bias[c]) in place, bias nullable: the epilogue of a convolution whose taps exceed
+ * CSG_MAX_TAPS and which therefore is the SUM of two csg_conv_fwd launches over one weight (the second with accumulate = 1,
+ * both without bias and activation) — InceptionA's 5x5 layers.                                                        */
+int csg_bias_act(float* y, int64_t P, int64_t C, int64_t y_cs, int64_t y_off, const float* bias, int32_t act, float slope,
+                 void* stream);
+/* sum (D) += sum_n x[n], outer (D,D) += sum_n x[n] x[n]^T in fp64 from fp32 features x (n,D), rows in order; the caller zeroes
+ * both before the first call.  D a multiple of 64.  A block owns a 64 x 64 tile of the upper triangle and mirrors it.
+ * csg_feat_stats_finalize: mu = sum / N, sigma = (outer - N mu mu^T) / (N - 1) — np.mean(axis=0) and np.cov(rowvar=False)
+ * (fid_score.py:213-214); N = 1 gives a NaN covariance, as numpy does.                                                */
+int csg_feat_stats(const float* x, int64_t n, int64_t D, double* sum, double* outer, void* stream);
+int csg_feat_stats_finalize(const double* sum, const double* outer, int64_t N, int64_t D, double* mu, double* sigma,
+                            void* stream);
+/* probs (N,K) fp64 = the fp32 row softmax of logits (N rows of ld floats): F.softmax of an fp32 model appended to a float64
+ * array (evaluation/inception.py:28,33).                                                                               */
+int csg_softmax_rows(const float* logits, int64_t N, int64_t K, int64_t ld, double* probs, void* stream);
+/* compute_score (evaluation/inception.py:35-49) in fp64 over probs (N,K): split k is rows [k * (N / splits), (k + 1) * (N /
+ * splits)); its score is exp(mean_i entropy(p_i, mean_i p_i)) with scipy.stats.entropy's renormalisation of both arguments.
+ * out = [mean, population std, score of split 0, 1, ...] (2 + splits doubles).  1 <= splits <= N.                     */
+int64_t csg_inception_score_workspace(int64_t N, int64_t K, int64_t splits);
+int csg_inception_score(const double* probs, int64_t N, int64_t K, int64_t splits, double* workspace, int64_t workspace_bytes,
+                        double* out, void* stream);
 
 #ifdef __cplusplus
 }
