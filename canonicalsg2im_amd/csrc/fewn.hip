@@ -275,14 +275,18 @@ __global__ __launch_bounds__(256) void k_few_bwd_weight(FewParams p, const float
     for (int n = NR; n < 4; ++n)
       for (int t = 0; t < T; ++t) *(float4*)(slab + ((int64_t)n * T + t) * p.Cin + c4 * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  // bias gradient: this block's share of the OUTPUT pixels, summed in a fixed order
+  // bias gradient: this block's share of the OUTPUT pixels, summed in a fixed order; the pad channels of dy are the
+  // caller's and take no part (db holds zeros beyond the real outputs, like dw)
   if (dbslabs != nullptr) {
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     const int64_t o0 = (int64_t)blockIdx.x * opb;
     const int64_t o1 = o0 + opb < nout ? o0 + opb : nout;
     for (int64_t o = o0 + threadIdx.x; o < o1; o += 256) {
       const float4 g = *(const float4*)(dy + o * 4);
-      s.x += g.x; s.y += g.y; s.z += g.z; s.w += g.w;
+      s.x += g.x;
+      if (NR > 1) s.y += g.y;
+      if (NR > 2) s.z += g.z;
+      if (NR > 3) s.w += g.w;
     }
     part[0][threadIdx.x] = s;
     __syncthreads();
