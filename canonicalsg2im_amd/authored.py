@@ -136,6 +136,47 @@ def object_names(rows, vocab):
     return out
 
 
+def object_labels(graphs):
+    """Authored graphs -> the labels of their layout pictures, B lists of O `str` or None in the rows of `encode_graphs`: an
+    object of the reference's form is named ', '.join(obj.values()), as scripts/run_model.py hands it to
+    draw_reversed_item; one of the flat form by its name.  None for the appended `__image__` row and for padding rows."""
+    O = max(len(graph["objects"]) for graph in graphs) + 1
+    out = []
+    for graph in graphs:
+        names = [obj if isinstance(obj, str) else ", ".join(obj.values()) for obj in graph["objects"]]
+        out.append(names + [None] * (O - len(names)))
+    return out
+
+
+def labels_from_objs(objs_host, vocab):
+    """A dataset batch's object ids (B,O,A) on the host -> B lists of O `str` or None: object_idx_to_name[id] for a
+    vocabulary with one attribute, otherwise the attributes' names in the vocabulary's attribute order joined by ', '
+    (CLEVR: "cube, red, metal, large").  None for rows of id 0 (padding) and for `__image__`."""
+    attrs = vocab["attributes"]
+    back = []
+    for a in attrs:
+        names = {}
+        for name, idx in attrs[a].items():
+            names.setdefault(int(idx), name)
+        back.append(names)
+    image = int(vocab["object_name_to_idx"]["__image__"])
+    single = len(back) == 1
+    out = []
+    for sample in (objs_host.tolist() if hasattr(objs_host, "tolist") else objs_host):
+        row = []
+        for ids in sample:
+            if ids[0] == 0 or ids[0] == image:
+                row.append(None)
+            elif single:
+                row.append(vocab["object_idx_to_name"][ids[0]])
+            else:
+                if len(ids) != len(back) or any(i not in names for i, names in zip(ids, back)):
+                    raise ValueError("object ids %r name no object of the attributes %s" % (ids, list(attrs)))
+                row.append(", ".join(names[i] for i, names in zip(ids, back)))
+        out.append(row)
+    return out
+
+
 def _encode_one(g, graph, vocab):
     """-> (object rows [n + 1][A], triplets [[s, p, o], ...]) of graph number g."""
     if not isinstance(graph, dict) or "objects" not in graph or "relationships" not in graph:

@@ -79,6 +79,7 @@ enum KernelId {
   K_BIAS_ACT,
   K_FEAT_STATS,
   K_INCEPTION_SCORE,
+  K_DRAW_LABELS,
   K_COUNT
 };
 

@@ -1,6 +1,7 @@
 // Box outlines on a uint8 picture: the layout picture of the reference's scripts/run_model.py (img_%06d_layout.png:
-// the generated image with the predicted boxes on it, sg2im/vis.py:128-146), without matplotlib and without its text
-// labels.  The rule is defined to the byte and restated in numpy by tests/overlay_cases.py:
+// the generated image with the predicted boxes on it, sg2im/vis.py:128-146), without matplotlib; the boxes' text labels are
+// a launch of their own on the outlined picture, csg_draw_labels_u8 below.
+// The rule is defined to the byte and restated in numpy by tests/overlay_cases.py:
 //   row o of sample b is SKIPPED when objs[b,o,0] == image_id, or all four box values are -1, or one of them is NaN, or
 //   w <= 0 or h <= 0;  otherwise, in fp32 and in this order (this file is compiled with -ffp-contract=off):
 //     x0 = clamp(x, 0, 1), x1 = clamp(x + w, 0, 1)                        (y likewise; clamp of a NaN sum is 0)
@@ -18,6 +19,25 @@ constexpr int kOverlayMaxColours = 256;
 
 __device__ __forceinline__ float clamp01(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }
 
+// (px0, py0, px1, py1) of row `row` = b * O + o, or px0 < 0 for a row that is not drawn: the one statement of the pixel
+// rule's fp32 part, read by the outline kernel and by the label kernel
+__device__ __forceinline__ int4 pixel_rect(const float* __restrict__ boxes, const int64_t* __restrict__ objs, int64_t row, int A,
+                                           int H, int W, int64_t image_id) {
+  const float4 q = *(const float4*)(boxes + row * 4);
+  const bool pad = q.x == -1.f && q.y == -1.f && q.z == -1.f && q.w == -1.f;
+  const bool nan = q.x != q.x || q.y != q.y || q.z != q.z || q.w != q.w;
+  int4 r = make_int4(-1, -1, -1, -1);
+  if (objs[row * A] != image_id && !pad && !nan && q.z > 0.f && q.w > 0.f) {
+    const float x0 = clamp01(q.x), x1 = clamp01(q.x + q.z);
+    const float y0 = clamp01(q.y), y1 = clamp01(q.y + q.w);
+    r.x = min(W - 1, (int)(x0 * (float)W));
+    r.z = max(r.x, min(W - 1, (int)(x1 * (float)W) - 1));
+    r.y = min(H - 1, (int)(y0 * (float)H));
+    r.w = max(r.y, min(H - 1, (int)(y1 * (float)H) - 1));
+  }
+  return r;
+}
+
 // out (B,3,H,W) uint8 planar, W % 4 == 0: a lane owns four consecutive pixels of one row and writes one dword per plane,
 // so a wave stores 256 contiguous bytes per plane
 __global__ __launch_bounds__(256) void k_draw_boxes_u8(const uint8_t* __restrict__ img, const float* __restrict__ boxes,
@@ -27,21 +47,7 @@ __global__ __launch_bounds__(256) void k_draw_boxes_u8(const uint8_t* __restrict
   __shared__ int4 s_rect[kOverlayMaxRows];          // px0, py0, px1, py1; px0 < 0: skipped
   __shared__ uint32_t s_rgb[kOverlayMaxColours];
   const int b = blockIdx.y, tid = threadIdx.x;
-  for (int o = tid; o < O; o += 256) {
-    const float4 q = *(const float4*)(boxes + ((int64_t)b * O + o) * 4);
-    const bool pad = q.x == -1.f && q.y == -1.f && q.z == -1.f && q.w == -1.f;
-    const bool nan = q.x != q.x || q.y != q.y || q.z != q.z || q.w != q.w;
-    int4 r = make_int4(-1, -1, -1, -1);
-    if (objs[((int64_t)b * O + o) * A] != image_id && !pad && !nan && q.z > 0.f && q.w > 0.f) {
-      const float x0 = clamp01(q.x), x1 = clamp01(q.x + q.z);
-      const float y0 = clamp01(q.y), y1 = clamp01(q.y + q.w);
-      r.x = min(W - 1, (int)(x0 * (float)W));
-      r.z = max(r.x, min(W - 1, (int)(x1 * (float)W) - 1));
-      r.y = min(H - 1, (int)(y0 * (float)H));
-      r.w = max(r.y, min(H - 1, (int)(y1 * (float)H) - 1));
-    }
-    s_rect[o] = r;
-  }
+  for (int o = tid; o < O; o += 256) s_rect[o] = pixel_rect(boxes, objs, (int64_t)b * O + o, A, H, W, image_id);
   for (int p = tid; p < P; p += 256)
     s_rgb[p] = (uint32_t)palette[p * 3] | (uint32_t)palette[p * 3 + 1] << 8 | (uint32_t)palette[p * 3 + 2] << 16;
   __syncthreads();
@@ -81,6 +87,89 @@ __global__ __launch_bounds__(256) void k_draw_boxes_u8(const uint8_t* __restrict
   }
 }
 
+// ---- the boxes' names (csg_draw_labels_u8) --------------------------------------------------------------------------
+// A strip of at most nine lines across the top of each box, blended half and half with palette[o % P], with the label in a
+// 5 x 7 font on its lines 1..7 (include/csg_hip.h states the rule; tests/label_cases.py restates it in numpy).  The same
+// walk as the outlines: a lane owns four pixels of one line, the highest row whose strip holds a pixel decides it.
+constexpr int kFontRows = 7;
+constexpr int kFontBytes = 95 * kFontRows;          // glyphs of the bytes 32 .. 126
+constexpr int kFontUnknown = '?' - 32;
+
+__global__ __launch_bounds__(256) void k_draw_labels_u8(const uint8_t* __restrict__ img, const float* __restrict__ boxes,
+                                                         const int64_t* __restrict__ objs, int O, int A, int H, int W,
+                                                         int64_t image_id, const uint8_t* __restrict__ palette, int P,
+                                                         const uint8_t* __restrict__ text, const int32_t* __restrict__ text_off,
+                                                         const uint8_t* __restrict__ font, uint8_t* __restrict__ out) {
+  __shared__ int4 s_strip[kOverlayMaxRows];         // px0, py0, px1, the strip's last line; px0 < 0: no strip
+  __shared__ int4 s_label[kOverlayMaxRows];         // the label's first byte in `text`, its bytes n, tx
+  __shared__ uint32_t s_rgb[kOverlayMaxColours];
+  __shared__ uint8_t s_font[(kFontBytes + 3) & ~3];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  for (int o = tid; o < O; o += 256) {
+    const int64_t row = (int64_t)b * O + o;
+    int4 r = pixel_rect(boxes, objs, row, A, H, W, image_id);
+    const int first = text_off[row], n = text_off[row + 1] - first;
+    int4 l = make_int4(first, n, 0, 0);
+    if (first < 0 || n <= 0) r.x = -1;              // no label: no strip either
+    if (r.x >= 0) {
+      r.w = min(r.w, r.y + 8);
+      const int64_t slack = (int64_t)(r.z - r.x + 1) - (6ll * n - 1);           // rw - tw
+      l.z = r.x + (slack > 0 ? (int)(slack / 2) : 0);
+    }
+    s_strip[o] = r;
+    s_label[o] = l;
+  }
+  for (int p = tid; p < P; p += 256)
+    s_rgb[p] = (uint32_t)palette[p * 3] | (uint32_t)palette[p * 3 + 1] << 8 | (uint32_t)palette[p * 3 + 2] << 16;
+  for (int i = tid; i < kFontBytes; i += 256) s_font[i] = font[i];
+  __syncthreads();
+  const int64_t npix = (int64_t)H * W, nquad = npix >> 2;
+  const uint8_t* ib = img + (int64_t)b * 3 * npix;
+  uint8_t* ob = out + (int64_t)b * 3 * npix;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + tid; q < nquad; q += (int64_t)gridDim.x * 256) {
+    const int y = (int)((q * 4) / W), x = (int)((q * 4) % W);
+    int win[4] = {-1, -1, -1, -1};
+    int open = 4;
+    for (int o = O - 1; o >= 0 && open; --o) {      // the LDS reads are wave-uniform (one broadcast each)
+      const int4 r = s_strip[o];
+      if (r.x < 0 || y < r.y || y > r.w) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int xx = x + j;
+        if (win[j] >= 0 || xx < r.x || xx > r.z) continue;
+        win[j] = o;
+        --open;
+      }
+    }
+    uint32_t word[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) word[c] = *(const uint32_t*)(ib + (int64_t)c * npix + q * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (win[j] < 0) continue;
+      const int4 r = s_strip[win[j]], l = s_label[win[j]];
+      const int line = y - r.y - 1, col = x + j - l.z;
+      bool ink = false;
+      if (line >= 0 && line < kFontRows && col >= 0) {
+        const int k = col / 6, bit = col - 6 * k;   // k < n and bit < 5  <=>  col < tw = 6 n - 1 and col % 6 < 5
+        if (k < l.y && bit < 5) {
+          const int byte = text[l.x + k];
+          const int g = byte >= 32 && byte <= 126 ? byte - 32 : kFontUnknown;
+          ink = (s_font[g * kFontRows + line] >> (4 - bit)) & 1;
+        }
+      }
+      const uint32_t rgb = s_rgb[win[j] % P];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint32_t half = (((word[c] >> (8 * j)) & 0xffu) + ((rgb >> (8 * c)) & 0xffu) + 1u) >> 1;
+        word[c] = (word[c] & ~(0xffu << (8 * j))) | (ink ? 0u : half) << (8 * j);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *(uint32_t*)(ob + (int64_t)c * npix + q * 4) = word[c];
+  }
+}
+
 }  // namespace csg
 
 using namespace csg;
@@ -110,6 +199,34 @@ int csg_draw_boxes_u8(const uint8_t* img, const float* boxes, const int64_t* obj
   CSG_LAUNCH(k_draw_boxes_u8, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, s, img, boxes, objs, (int)O, (int)A, (int)H,
              (int)W, image_id, palette, (int)P, (int)thickness, out);
   return check_launch("csg_draw_boxes_u8");
+}
+
+int csg_draw_labels_u8(const uint8_t* img, const float* boxes, const int64_t* objs, int64_t B, int64_t O, int64_t A, int64_t H,
+                       int64_t W, int64_t image_id, const uint8_t* palette, int64_t P, const uint8_t* text,
+                       const int32_t* text_off, const uint8_t* font, uint8_t* out, void* stream) {
+  CSG_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && W % 4 == 0 && H * W < (1ll << 31), CSG_E_BADSHAPE,
+              "csg_draw_labels_u8: bad shape B=%ld H=%ld W=%ld (W a multiple of 4)", (long)B, (long)H, (long)W);
+  CSG_REQUIRE(O > 0 && A > 0 && P > 0, CSG_E_BADSHAPE, "csg_draw_labels_u8: bad shape O=%ld A=%ld P=%ld", (long)O, (long)A,
+              (long)P);
+  CSG_REQUIRE(O <= kOverlayMaxRows && P <= kOverlayMaxColours, CSG_E_UNSUPPORTED,
+              "csg_draw_labels_u8: at most %d rows per sample and %d colours (got %ld, %ld)", kOverlayMaxRows,
+              kOverlayMaxColours, (long)O, (long)P);
+  CSG_REQUIRE(img != nullptr && boxes != nullptr && objs != nullptr && palette != nullptr && text != nullptr &&
+                  text_off != nullptr && font != nullptr && out != nullptr,
+              CSG_E_BADSHAPE, "csg_draw_labels_u8: null operand");
+  CSG_REQUIRE(img != out, CSG_E_BADSHAPE, "csg_draw_labels_u8: out must not be img");
+  CSG_REQUIRE(((uintptr_t)img & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)boxes & 15) == 0 &&
+                  ((uintptr_t)text_off & 3) == 0,
+              CSG_E_BADSHAPE,
+              "csg_draw_labels_u8: img, out and text_off must start on a 4-byte boundary, boxes on a 16-byte one");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t npix = H * W;
+  ProfScope p(K_DRAW_LABELS, (double)B * npix * 6, s);
+  int64_t blocks = cdiv(npix / 4, 256);
+  if (blocks > 256) blocks = 256;
+  CSG_LAUNCH(k_draw_labels_u8, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, s, img, boxes, objs, (int)O, (int)A, (int)H,
+             (int)W, image_id, palette, (int)P, text, text_off, font, out);
+  return check_launch("csg_draw_labels_u8");
 }
 
 }  // extern "C"

@@ -1555,6 +1555,72 @@ def draw_boxes_u8(img, boxes, objs, image_id, palette, thickness=2):
     return out
 
 
+_FONTS = {}     # device -> font5x7.FONT on it, uploaded once and kept
+
+
+def pack_labels(labels, B, O):
+    """B sequences of O `str` or None -> (one host uint8 tensor, the first text byte in it): the int32 offsets text_off
+    (B*O + 1 of them) and behind them every label's bytes back to back, encoded as ASCII with errors="replace" (None and
+    "" give no byte; a `bytes` label goes in as it is), then four bytes of padding so that the text has an address even
+    when it is empty."""
+    if isinstance(labels, (str, bytes)) or not hasattr(labels, "__len__") or len(labels) != B or any(
+            isinstance(row, (str, bytes)) or not hasattr(row, "__len__") or len(row) != O for row in labels):
+        raise RuntimeError("draw_labels_u8: labels must be %d sequences of %d names (str or None)" % (B, O))
+    offsets, chunks, end = [0], [], 0
+    for row in labels:
+        for name in row:
+            if name is not None and not isinstance(name, (str, bytes)):
+                raise RuntimeError("draw_labels_u8: a label is a str or None, got %r" % (name,))
+            data = b"" if not name else name if isinstance(name, bytes) else name.encode("ascii", errors="replace")
+            chunks.append(data)
+            end += len(data)
+            offsets.append(end)
+    if end >= 1 << 31:
+        raise RuntimeError("draw_labels_u8: %d label bytes; the offsets are int32" % end)
+    head = torch.tensor(offsets, dtype=torch.int32).view(torch.uint8)
+    text = torch.frombuffer(bytearray(b"".join(chunks) + b"\0" * 4), dtype=torch.uint8)
+    return torch.cat([head, text]), head.numel()
+
+
+def draw_labels_u8(img, boxes, objs, image_id, palette, labels, font=None):
+    """The boxes' names on a uint8 picture (csg_draw_labels_u8; the pixel rule is DESIGN 4.10b and include/csg_hip.h): a
+    strip of nine lines across the top of each box, half picture and half palette[o % P], with the label in the 5 x 7 font on
+    it.  img, boxes, objs, image_id, palette: as `draw_boxes_u8`, whose result this is usually called on; rows it does not
+    draw get no label either.  labels: B sequences of O `str` or None (None and "": no label, no strip), encoded as ASCII
+    with errors="replace"; they are packed on the host with their offsets, uploaded in one copy, then one launch.  font: a
+    uint8 (95, 7) device tensor, by default font5x7.FONT, uploaded once per device and kept.  Returns a new uint8
+    (B,3,H,W); img is not written.  Nothing read back.  No autograd."""
+    for name, t, dt in (("img", img, torch.uint8), ("objs", objs, torch.int64), ("palette", palette, torch.uint8)):
+        if t.dtype != dt:
+            raise RuntimeError("draw_labels_u8: %s must be %s, got %s" % (name, dt, t.dtype))
+    boxes = _f32(boxes)
+    if img.dim() != 4 or img.shape[1] != 3 or boxes.dim() != 3 or boxes.shape[2] != 4 or objs.dim() != 3 \
+            or tuple(objs.shape[:2]) != tuple(boxes.shape[:2]) or boxes.shape[0] != img.shape[0] \
+            or palette.dim() != 2 or palette.shape[1] != 3:
+        raise RuntimeError("draw_labels_u8: img (B,3,H,W), boxes (B,O,4), objs (B,O,A), palette (P,3); got %s %s %s %s" % (
+            tuple(img.shape), tuple(boxes.shape), tuple(objs.shape), tuple(palette.shape)))
+    if font is not None and (font.dtype != torch.uint8 or tuple(font.shape) != (95, 7)):
+        raise RuntimeError("draw_labels_u8: font must be uint8 (95, 7), got %s %s" % (font.dtype, tuple(font.shape)))
+    B, _, H, W = img.shape
+    O = objs.shape[1]
+    packed, head = pack_labels(labels, B, O)
+    if not img.is_cuda:
+        raise RuntimeError("canonicalsg2im_amd ops need HIP (cuda) tensors; there is no CPU path")
+    if font is None:
+        font = _FONTS.get(img.device)
+        if font is None:
+            from .font5x7 import FONT
+            font = _FONTS[img.device] = torch.from_numpy(FONT.copy()).to(img.device)
+    img, boxes, objs, palette, font = img.contiguous(), boxes.contiguous(), objs.contiguous(), palette.contiguous(), \
+        font.contiguous()
+    packed = packed.to(img.device, non_blocking=True)
+    out = torch.empty_like(img)
+    check(lib.csg_draw_labels_u8(ptr(img), ptr(boxes), ptr(objs), B, O, objs.shape[2], H, W, int(image_id), ptr(palette),
+                                 palette.shape[0], ctypes_ptr_off(packed, head), ptr(packed), ptr(font), ptr(out), stream()),
+          "draw_labels_u8")
+    return out
+
+
 def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_host=None, out=None, out_u8=None,
                       workspace=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """The loader's per-sample transform (sg2im/data/packed_coco.py:269-272: T.Resize, T.ToTensor, T.Normalize) for a batch

@@ -263,7 +263,7 @@ class Sampler:
                                       uint8, rescale, deprocess)
         return (u8 if uint8 else img), boxes_pred, masks_pred
 
-    def generate_from_graphs(self, graphs, overlay=False, thickness=2, palette=None):
+    def generate_from_graphs(self, graphs, overlay=False, thickness=2, palette=None, labels=False):
         """Authored scene graphs (authored.py: a list of graphs or the path of a JSON file) -> (images uint8 (B,3,H,W),
         boxes_pred (B,O,4), overlays uint8 (B,3,H,W) or None).  The graphs are encoded and checked on the host, uploaded
         once, and made canonical without boxes (`canonical_triplets(boxes=None)`: the authored rows are the location
@@ -271,13 +271,17 @@ class Sampler:
         settings make them in training, converse draws from numpy's global stream as the data loader's).  The pictures come
         from `generate` on the predicted boxes, under its replay keys.  `overlay`: the pictures with the outlines of the
         predicted boxes, `thickness` pixels wide, row o in palette[o % P] — `palette` a sequence of RGB
-        triples, by default authored.DEFAULT_PALETTE."""
+        triples, by default authored.DEFAULT_PALETTE.  `labels` (needs `overlay`): the objects' names on the overlays as
+        well (`ops.draw_labels_u8` on the outlined pictures, names by `authored.object_labels`)."""
         from . import authored
         from .sg2im.data import canonical_triplets
+        if labels and not overlay:
+            raise ValueError("generate_from_graphs(labels=True) needs overlay=True: the names go on the layout pictures")
         if self.device.type != "cuda":
             raise RuntimeError(NO_CPU)
         vocab = self.opt.vocab
-        objs, rows, counts = authored.encode_graphs(authored.load_graphs(graphs, vocab), vocab)
+        graphs = authored.load_graphs(graphs, vocab)
+        objs, rows, counts = authored.encode_graphs(graphs, vocab)
         conv_w = None
         if getattr(self.opt, "learned_converse", False):
             from .sg2im.model import get_conv_converse
@@ -292,6 +296,9 @@ class Sampler:
             if imgs is None or boxes_pred is None:
                 raise RuntimeError("generate_from_graphs(overlay=True) needs a model that predicts boxes and pictures")
             pal = torch.tensor(authored.DEFAULT_PALETTE if palette is None else palette, dtype=torch.uint8).reshape(-1, 3)
-            overlays = ops.draw_boxes_u8(imgs, boxes_pred.detach().float(), objs, vocab["object_name_to_idx"]["__image__"],
-                                         pal.to(self.device), thickness)
+            pal, image_id = pal.to(self.device), vocab["object_name_to_idx"]["__image__"]
+            overlays = ops.draw_boxes_u8(imgs, boxes_pred.detach().float(), objs, image_id, pal, thickness)
+            if labels:
+                overlays = ops.draw_labels_u8(overlays, boxes_pred.detach().float(), objs, image_id, pal,
+                                              authored.object_labels(graphs))
         return imgs, boxes_pred, overlays

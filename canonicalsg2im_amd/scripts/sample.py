@@ -15,8 +15,13 @@ model; on top of them:
     --scene_graphs FILE      authored scene graphs (JSON), drawn in batches of --batch_size; the vocabulary is the one the
                              checkpoint carries, --num_samples is ignored.  Writes img_%06d_generated.png, with
                              --draw_boxes 1 (the default) img_%06d_layout.png — the picture with the outlines of the
-                             predicted boxes, no text labels — and graphs.json, the encoded triplets with their
-                             predicates' names (in place of the reference's GraphViz picture)
+                             predicted boxes — and graphs.json, the encoded triplets with their predicates' names (in
+                             place of the reference's GraphViz picture)
+    --draw_labels 0|1        with --draw_boxes 1 (refused without): the objects' names on the layout pictures, a coloured
+                             strip with the name across the top of each box as the reference's sg2im/vis.py draws it
+                             (default 0).  --scene_graphs: on img_%06d_layout.png; --split: on layout/gt/ and
+                             layout/pred/; --layouts: writes layout/<which>/<image id>.<ext> besides, the picture under
+                             its boxes' outlines and names
     --split train|val        the split's folder (the paths of scripts/train.py; --num_train_samples / --num_val_samples cap
                              it, --coco_val_ids narrows coco's val) in file order, batches of --batch_size decoded in
                              --loader_num_workers threads.  Needs --checkpoint_name; the folder's vocabulary is held to the
@@ -56,6 +61,7 @@ def build_parser():
     p.add_argument('--num_samples', default=16, type=int)
     p.add_argument('--scene_graphs', default=None, type=str)
     p.add_argument('--draw_boxes', default=1, type=int)
+    p.add_argument('--draw_labels', default=0, type=int)
     p.add_argument('--split', default=None, choices=["train", "val"])
     p.add_argument('--max_pictures', default=0, type=int)
     p.add_argument('--image_format', default="png", choices=["png", "jpg"])
@@ -71,6 +77,9 @@ def parse_args(argv=None):
         raise SystemExit("--num_samples and --batch_size must be positive")
     if args.checkpoint_name != _NO_CHECKPOINT and not os.path.isfile(args.checkpoint_name):
         raise SystemExit("--checkpoint_name %s: no such file" % args.checkpoint_name)
+    if args.draw_labels and not args.draw_boxes:
+        raise SystemExit("--draw_labels 1 needs --draw_boxes 1: the names go on the layout pictures, which --draw_boxes 0 "
+                         "leaves out")
     if args.scene_graphs is not None and not os.path.isfile(args.scene_graphs):
         raise SystemExit("--scene_graphs %s: no such file" % args.scene_graphs)
     given = [flag for flag, v in (("--split", args.split), ("--layouts", args.layouts), ("--scene_graphs", args.scene_graphs))
@@ -134,7 +143,8 @@ def sample_split(args, dev, dataset):
     try:
         metrics, rows = generate_split(
             sampler, builder.batches(file_order_batches(len(dataset), args.batch_size)), args.output_dir,
-            deprocess=args.img_deprocess, draw_boxes=bool(args.draw_boxes), image_format=args.image_format,
+            deprocess=args.img_deprocess, draw_boxes=bool(args.draw_boxes), draw_labels=bool(args.draw_labels),
+            image_format=args.image_format,
             num_writers=args.num_writers, max_pictures=args.max_pictures, split=args.split)
     finally:
         builder.close()
@@ -168,7 +178,8 @@ def sample_layouts(args, dev):
     sampler = Sampler(args, dev, ckpt)
     tic = time.time()
     done = generate_layouts(sampler, rows, args.layout_boxes, args.output_dir, deprocess=args.img_deprocess,
-                            batch_size=args.batch_size, image_format=args.image_format, num_writers=args.num_writers)
+                            batch_size=args.batch_size, image_format=args.image_format, num_writers=args.num_writers,
+                            draw_labels=bool(args.draw_labels))
     torch.cuda.synchronize()
     _rate_line(done, tic, sampler)
 
@@ -202,7 +213,7 @@ def sample_scene_graphs(args, dev):
     tic = time.time()
     for first in range(0, len(graphs), args.batch_size):
         chunk = graphs[first:first + args.batch_size]
-        imgs, _, overlays = sampler.generate_from_graphs(chunk, overlay=bool(args.draw_boxes))
+        imgs, _, overlays = sampler.generate_from_graphs(chunk, overlay=bool(args.draw_boxes), labels=bool(args.draw_labels))
         if Image is not None:
             kinds = [("generated", imgs)] + ([("layout", overlays)] if overlays is not None else [])
             for kind, t in kinds:

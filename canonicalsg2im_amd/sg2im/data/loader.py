@@ -67,6 +67,16 @@ class MetaLayout:
             view.copy_(self.host[name])
 
 
+class HostBatch(list):
+    """The trainer's 8-tuple with `objs_host`: the batch's object ids (B,O,A) as the host already holds them, in the rows
+    of the device tensor batch[1] (its `__image__` row included).  For what names the objects without reading them back
+    (split.generate_split(draw_labels=True))."""
+
+    def __init__(self, batch, objs_host):
+        super().__init__(batch)
+        self.objs_host = objs_host
+
+
 class _Pending:
     """A batch whose host half is under way: the decode futures and what the device half needs (slot, stage, meta, layout),
     and as attributes of their own names the host copies of the second buffer's fields (`desc` among them) and the
@@ -151,6 +161,10 @@ class BatchBuilder:
     def assemble(self, dev, pending):
         raise NotImplementedError
 
+    def host_objs(self, pending):
+        """The object ids int64 (B,O,A) of the rows `assemble` hands over, from the host copies of the fields."""
+        return pending.objs.to(torch.int64)
+
     def start(self, indices):
         """The host half.  Called by the consumer's thread between two steps: the one HIP call it can make, the pinned
         allocation when a staging buffer has to grow, is made here and not by a worker."""
@@ -186,7 +200,9 @@ class BatchBuilder:
         imgs = ops.preprocess_images(src, dev["desc"], H, W, normalize=self.ds.normalize_images, desc_host=p.desc,
                                      **({} if self.mean is None else {"mean": self.mean, "std": self.std}))
         raw = [imgs, objs, boxes, rel, None, None, masks, dev["image_ids"]]
-        return packed_batch(self.args, self.trainer, raw, self.dev, counts=counts, centers=centers)
+        batch = packed_batch(self.args, self.trainer, raw, self.dev, counts=counts, centers=centers)
+        ids = self.host_objs(p)                                           # packed_batch appends one row of 0 per sample
+        return HostBatch(batch, torch.cat([ids, ids.new_zeros((ids.shape[0], 1, ids.shape[2]))], 1))
 
     def _upload(self, p):
         """Wait for the decode, then one copy of each staging buffer -> (packed bytes, second buffer) on the device."""

@@ -220,6 +220,10 @@ class VGBatchBuilder(BatchBuilder):
                                   sizes_host=p.sizes, counts_host=p.counts)
         return objs, boxes, p.rel, p.counts
 
+    def host_objs(self, p):
+        names = p.rows[..., :1].to(torch.int64)                            # -1 at and beyond a sample's count: 0, as vg_rows
+        return names.clamp_(min=0)
+
 
 PackedVGDataset.builder_class = VGBatchBuilder
 

@@ -12,7 +12,8 @@ yields) through calls this package already has, in this order per batch and unde
                                   normalised, through the same deprocess (generation_attspade.py:47,71)
     layout/gt, layout/pred        with draw_boxes: `gt` under the ground-truth boxes, the predicted-layout picture under the
                                   predicted ones (ops.draw_boxes_u8, palette and thickness of generate_from_graphs); outlines
-                                  never go into gt/ or generation/, which feed the metrics
+                                  never go into gt/ or generation/, which feed the metrics; with draw_labels the objects'
+                                  names as well (ops.draw_labels_u8), from the ids the batch holds on the host
     ops.box_iou                   the per-object IoU and the running totals of Evaluator.check_model
 
 Nothing is read back inside the loop.  The uint8 pictures stay planar and leave, with the batch's ids, objects, boxes and
@@ -292,14 +293,28 @@ def _open_writers(sampler, out_dir, image_format, num_writers):
     return files, PictureWriter(sampler.device, files), (_Paths(out_dir, image_format) if out_dir else None)
 
 
+def _host_ids(batch):
+    """The object ids a batch carries on the host (loader.HostBatch), for the labels: they are never read back here."""
+    ids = getattr(batch, "objs_host", None)
+    if ids is None or tuple(ids.shape) != tuple(batch[1].shape):
+        raise ValueError("draw_labels needs batches that carry their object ids on the host as `objs_host`, in the shape of "
+                         "their objects (sg2im.data.loader.HostBatch, what a BatchBuilder yields): the ids are not read back")
+    return ids
+
+
 def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, draw_boxes=False, thickness=2,
-                   image_format="png", num_writers=8, max_pictures=0, split=None):
+                   image_format="png", num_writers=8, max_pictures=0, split=None, draw_labels=False):
     """Walk `batches` (see the module docstring) -> (metrics, rows).  metrics: avg_iou, total_iou_05, total_iou_03 (the
     totals / counted boxes, float64, as Evaluator.check_model forms them) and num_boxes; empty for a model without a graph
     part.  With `out_dir` the pictures and layouts.json are written; without it only metrics and rows are made.
-    `max_pictures`: stop after that many images (a batch may be cut; 0: all).  `split`: the name layouts.json records."""
+    `max_pictures`: stop after that many images (a batch may be cut; 0: all).  `split`: the name layouts.json records.
+    `draw_labels` (needs `draw_boxes`): the objects' names on layout/gt and layout/pred (ops.draw_labels_u8, names by
+    authored.labels_from_objs from the ids the batch holds on the host)."""
     from . import ops
     from .sample import NO_CPU
+    from .sg2im.data.loader import HostBatch
+    if draw_labels and not draw_boxes:
+        raise ValueError("generate_split(draw_labels=True) needs draw_boxes=True: the names go on the layout pictures")
     if sampler.device.type != "cuda":
         raise RuntimeError(NO_CPU)
     if deprocess not in ops.DEPROCESS:
@@ -319,10 +334,12 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                 if files is not None:
                     files.check()
                 if max_pictures and done + int(batch[1].shape[0]) > max_pictures:
-                    batch = _cut(batch, max_pictures - done)
+                    n = max_pictures - done
+                    batch = HostBatch(_cut(batch, n), batch.objs_host[:n]) if hasattr(batch, "objs_host") else _cut(batch, n)
                 imgs, objs, boxes, triplets, _, triplet_type, masks, image_ids = batch
                 if not objs.is_cuda:
                     raise RuntimeError(NO_CPU)
+                names = authored.labels_from_objs(_host_ids(batch), vocab) if draw_labels else None
                 out = {}
                 u8 = sampler.generate(objs, triplets, triplet_type, boxes_gt=boxes, masks_gt=masks, rescale=rescale,
                                       deprocess=deprocess)[0]
@@ -341,6 +358,9 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                     if "generation/pred_box_pred_mask" in out:
                         out["layout/pred"] = ops.draw_boxes_u8(out["generation/pred_box_pred_mask"], boxes_pred.detach().float(),
                                                                objs, image_id_obj, palette, thickness)
+                    for name, bx in (("layout/gt", boxes), ("layout/pred", boxes_pred)):
+                        if draw_labels and name in out:
+                            out[name] = ops.draw_labels_u8(out[name], bx.detach().float(), objs, image_id_obj, palette, names)
                 if paths is None:
                     out = {}                            # nothing to write: the pictures stay where they are
                 ids = image_ids if torch.is_tensor(image_ids) else torch.as_tensor(image_ids)
@@ -373,13 +393,17 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
 
 
 def generate_layouts(sampler, rows, which="pred", out_dir=None, *, deprocess, rescale=True, batch_size=None,
-                     image_format="png", num_writers=8):
+                     image_format="png", num_writers=8, draw_labels=False, thickness=2):
     """Pictures from layout rows with the generator alone (the reference's generation_dataframe.py --mode pred|gt): the
     rows' objects go through the sampler's vocabulary, `batch_size` rows (default --batch_size) at a time in file order, and
     `sampler.generate(objs, None, None, boxes_gt=boxes)` sees the tensors a dataset batch would give (`layout_batch`).
     With `out_dir` the pictures go to generation/<which>_box_<which>_mask/<image_id>.<ext> and the number written is
     returned; without it the pictures are returned, uint8 (N,3,H,W) on the host.  Every row is checked first
-    (`encode_layouts`): nothing is launched for a file with a bad row."""
+    (`encode_layouts`): nothing is launched for a file with a bad row.
+    `draw_labels`: besides, every picture under the outlines and the names of its boxes (ops.draw_boxes_u8, then
+    ops.draw_labels_u8; palette and thickness of generate_split; the names are the rows' own, authored.object_labels) in
+    layout/<which>/<image_id>.<ext>, as generate_split's layout/gt and layout/pred; without `out_dir` the pair (pictures,
+    labelled pictures) is returned."""
     from . import ops
     from .sample import NO_CPU
     if deprocess not in ops.DEPROCESS:
@@ -393,14 +417,20 @@ def generate_layouts(sampler, rows, which="pred", out_dir=None, *, deprocess, re
         raise ValueError("generate_layouts: batch_size must be positive")
     name = "generation/%s_box_%s_mask" % (which, which)
     files, pictures, paths = _open_writers(sampler, out_dir, image_format, num_writers)
-    kept = []
+    kept, kept_layouts = [], []
+    vocab = sampler.opt.vocab
+    palette = torch.tensor(authored.DEFAULT_PALETTE, dtype=torch.uint8).reshape(-1, 3).to(sampler.device) if draw_labels else None
 
     def on_host(host):
         for i, image_id in enumerate(host["ids"]):
             if paths is None:
                 kept.append(torch.from_numpy(host["u8"][i]).clone())
+                if "layout" in host:
+                    kept_layouts.append(torch.from_numpy(host["layout"][i]).clone())
             else:
                 files.submit(host["u8"][i], paths.of(name, image_id))
+                if "layout" in host:
+                    files.submit(host["layout"][i], paths.of("layout/%s" % which, image_id))
 
     raising = True
     try:
@@ -408,16 +438,23 @@ def generate_layouts(sampler, rows, which="pred", out_dir=None, *, deprocess, re
             if files is not None:
                 files.check()
             chunk = samples[first:first + step]
-            objs, boxes = layout_batch(chunk, sampler.opt.vocab)
-            u8 = sampler.generate(objs.to(sampler.device), None, None, boxes_gt=boxes.to(sampler.device), rescale=rescale,
-                                  deprocess=deprocess)[0]
+            objs, boxes = layout_batch(chunk, vocab)
+            objs, boxes = objs.to(sampler.device), boxes.to(sampler.device)
+            u8 = sampler.generate(objs, None, None, boxes_gt=boxes, rescale=rescale, deprocess=deprocess)[0]
             if u8 is None:
                 raise RuntimeError("generate_layouts needs a model that generates pictures (--skip_generation 0)")
             ids = [s[0] for s in chunk]
-            pictures.put({"u8": u8}, lambda host, ids=ids: on_host(dict(host, ids=ids)))
+            out = {"u8": u8}
+            if draw_labels:
+                image_id_obj = vocab["object_name_to_idx"]["__image__"]
+                out["layout"] = ops.draw_labels_u8(ops.draw_boxes_u8(u8, boxes, objs, image_id_obj, palette, thickness), boxes,
+                                                   objs, image_id_obj, palette, authored.object_labels(rows[first:first + step]))
+            pictures.put(out, lambda host, ids=ids: on_host(dict(host, ids=ids)))
         pictures.flush()
         raising = False
     finally:
         if files is not None:
             files.close(reraise=not raising)
-    return len(samples) if paths is not None else torch.stack(kept)
+    if paths is not None:
+        return len(samples)
+    return (torch.stack(kept), torch.stack(kept_layouts)) if draw_labels else torch.stack(kept)

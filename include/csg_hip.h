@@ -55,7 +55,8 @@ extern "C" {
  * 118: csg_clevr_graph_count, csg_clevr_graph_emit;
  * 119: csg_coco_masks;
  * 120: csg_resize_bilinear, csg_pool3, csg_spatial_mean, csg_bias_act, csg_feat_stats, csg_feat_stats_finalize,
- *      csg_softmax_rows, csg_inception_score_workspace, csg_inception_score) */
+ *      csg_softmax_rows, csg_inception_score_workspace, csg_inception_score;
+ * 121: csg_draw_labels_u8) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -511,10 +512,34 @@ int csg_deprocess_u8(const float* img, int64_t B, int64_t H, int64_t W, int64_t 
  * HIGHEST such o.  One launch, capturable, nothing is read back; each lane decides its own pixels, so the bytes are the
  * same on every run.
  * LIMITS: 1 <= B <= 65535; O <= 256 and P <= 256 (CSG_E_UNSUPPORTED beyond); H * W < 2^31; img and out on a 4-byte
- * boundary, boxes on a 16-byte one.                                                                                */
+ * boundary, boxes on a 16-byte one.
+ * The boxes' names are drawn by csg_draw_labels_u8 below, on the picture this entry point returns.                  */
 int csg_draw_boxes_u8(const uint8_t* img, const float* boxes, const int64_t* objs, int64_t B, int64_t O, int64_t A, int64_t H,
                       int64_t W, int64_t image_id, const uint8_t* palette, int64_t P, int32_t thickness, uint8_t* out,
                       void* stream);
+
+/* ---- the boxes' names on a uint8 picture (csrc/overlay.hip) ---------------------------------------------
+ * The coloured strip with the object's name that sg2im/vis.py:16-41 puts across the top of each box, in a 5 x 7 font.
+ * img, boxes, objs, B, O, A, H, W, image_id, palette, P, out: as csg_draw_boxes_u8, with its layouts, limits and alignment.
+ * text: uint8, every label's bytes back to back; text_off: int32, B*O + 1 ascending offsets into it, text_off[0] == 0, on a
+ * 4-byte boundary: row (b, o) owns the bytes [text_off[b*O+o], text_off[b*O+o+1]).  font: uint8 (95, 7): glyph g serves
+ * byte 32 + g, row r (0 = top) is one byte whose bits 4..0 are the five columns from left to right.  All device memory.
+ * Row o of sample b is skipped under csg_draw_boxes_u8's conditions, and when its label is empty.  For the others
+ * (px0, py0, px1, py1) is that entry point's pixel rectangle, by the same fp32 statements, and with n label bytes
+ *   the strip is [px0, px1] x [py0, min(py1, py0 + 8)]: nine lines, clipped to the box;
+ *   tw = 6 n - 1, rw = px1 - px0 + 1, tx = px0 + max(0, (rw - tw) / 2) in integer division: the text is centred when it
+ *   fits, and otherwise starts at the left side and is cut at px1;
+ *   a strip pixel (x, y) is INK when r = y - py0 - 1 lies in [0, 6], c = x - tx lies in [0, tw), c % 6 < 5 and bit
+ *   4 - c % 6 of font[g][r] is set, g being the glyph of the label's byte c / 6: the byte - 32 for a byte in [32, 126],
+ *   otherwise the glyph of '?'.
+ * Among the rows whose strip holds a pixel the HIGHEST o decides: an ink pixel becomes (0, 0, 0), another strip pixel
+ * (img + palette[o % P] + 1) >> 1 per channel (the reference's alpha 0.5 in integers, from the INPUT byte, not from another
+ * row's result); a pixel in no strip keeps its byte.  One launch, capturable, no atomics, nothing is read back; each lane
+ * decides its own pixels, so the bytes are the same on every run.
+ * LIMITS: those of csg_draw_boxes_u8; no null pointer (an empty text still needs an address); text_off[B*O] < 2^31.  */
+int csg_draw_labels_u8(const uint8_t* img, const float* boxes, const int64_t* objs, int64_t B, int64_t O, int64_t A,
+                       int64_t H, int64_t W, int64_t image_id, const uint8_t* palette, int64_t P, const uint8_t* text,
+                       const int32_t* text_off, const uint8_t* font, uint8_t* out, void* stream);
 
 /* ---- decoded pictures -> the trainer's image tensor (csrc/preprocess.hip) ------------------------------
  * The per-sample transform of the reference's loader (sg2im/data/packed_coco.py:269-272: T.Resize(image_size), T.ToTensor(),

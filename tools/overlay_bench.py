@@ -2,11 +2,13 @@
 """Timing of the box-outline launch (csg_draw_boxes_u8) against the only way to the same picture without it: copy the
 uint8 batch to the host and paint there with the numpy restatement of the rule (tests/overlay_cases.py).
 
-    python tools/overlay_bench.py device|host [--batch 16] [--size 256] [--objects 31] [--calls 20] [--warmup 5]
+    python tools/overlay_bench.py device|host|labels [--batch 16] [--size 256] [--objects 31] [--calls 20] [--warmup 5]
 
-One mode per process (run the two alternately, several rounds); prints one JSON line: the synchronised median, minimum and
-maximum per call in milliseconds.  Both modes start from the same seeded device tensors and the host mode's result is
-checked against the device's bytes once, outside the timed window."""
+One mode per process (run them alternately, several rounds); prints one JSON line: the synchronised median, minimum and
+maximum per call in milliseconds.  All modes start from the same seeded device tensors and the host mode's result is
+checked against the device's bytes once, outside the timed window.  `labels` is the outline launch followed by the label
+launch (csg_draw_labels_u8: seeded names of 6 to 12 small letters, packed and uploaded inside the timed call, as a caller
+pays for them), to be set beside `device`, the outlines alone."""
 import argparse
 import json
 import os
@@ -23,7 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("device", "host"))
+    ap.add_argument("mode", choices=("device", "host", "labels"))
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--objects", type=int, default=31)
@@ -57,7 +59,15 @@ def main():
     def host_call():
         return oc.draw_boxes(img.cpu().numpy(), boxes.cpu().numpy(), objs.cpu().numpy(), 0, pal_host, 2)
 
-    call = device_call if a.mode == "device" else host_call
+    names = [["".join(chr(97 + int(c)) for c in torch.randint(0, 26, (int(torch.randint(6, 13, (1,), generator=g)),), generator=g))
+              for _ in range(O)] + [None] for _ in range(B)]
+
+    def labels_call():
+        out = ops.draw_labels_u8(ops.draw_boxes_u8(img, boxes, objs, 0, pal, 2), boxes, objs, 0, pal, names)
+        torch.cuda.synchronize()
+        return out
+
+    call = {"device": device_call, "host": host_call, "labels": labels_call}[a.mode]
     times = []
     for k in range(a.warmup + a.calls):
         torch.cuda.synchronize()
@@ -65,7 +75,7 @@ def main():
         out = call()
         if k >= a.warmup:
             times.append((time.perf_counter() - t0) * 1e3)
-    want = device_call().cpu().numpy()
+    want = (labels_call() if a.mode == "labels" else device_call()).cpu().numpy()
     got = out.cpu().numpy() if torch.is_tensor(out) else out
     assert np.array_equal(got, want), "the two ways disagree"
     times.sort()
