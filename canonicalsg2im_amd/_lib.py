@@ -201,10 +201,6 @@ SIGNATURES = {
     "csg_hinge_mean_fwd": (c_i32, [ctypes.POINTER(HingeItem), c_i32, c_i32, c_p, c_p]),
     "csg_hinge_mean_bwd": (c_i32, [ctypes.POINTER(HingeItem), c_i32, c_i32, c_p, c_p]),
     "csg_spectral_norm_workspace": (c_i64, [c_i64, c_i64]),
-    "csg_spectral_norm_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_f32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                      c_p]),
-    "csg_spectral_norm_bwd": (c_i32, [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p,
-                                      c_p, c_p, c_i64, c_p]),
     "csg_spectral_norm_fwd_multi": (c_i32, [ctypes.POINTER(SnFwdItem), c_i32, c_i32, c_f32, c_p]),
     "csg_spectral_norm_bwd_multi": (c_i32, [ctypes.POINTER(SnBwdItem), c_i32, c_p]),
     "csg_canon_workspace": (c_i64, [c_i64]),

@@ -59,11 +59,6 @@ __device__ __forceinline__ void d_sn_wtu_partial(const float* __restrict__ w, co
   *(float4*)(part + (int64_t)r * K + k) = a;
 }
 
-__global__ __launch_bounds__(256) void k_sn_wtu_partial(const float* __restrict__ w, const float* __restrict__ u,
-                                                         int Cout, int K, int R, float* __restrict__ part) {
-  d_sn_wtu_partial(w, u, Cout, K, R, part, blockIdx.x, blockIdx.y);
-}
-
 // t[k] = sum_r part[r][k]
 __device__ __forceinline__ void d_sn_wtu_reduce(const float* __restrict__ part, int K, int R, float* __restrict__ t, int bx) {
   const int k = (bx * blockDim.x + threadIdx.x) * 4;
@@ -75,10 +70,6 @@ __device__ __forceinline__ void d_sn_wtu_reduce(const float* __restrict__ part, 
     a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
   }
   *(float4*)(t + k) = a;
-}
-
-__global__ void k_sn_wtu_reduce(const float* __restrict__ part, int K, int R, float* __restrict__ t) {
-  d_sn_wtu_reduce(part, K, R, t, blockIdx.x);
 }
 
 // s[i] = W[i] . v with v = t / max(||t||, eps) formed on the fly (training) or v = the stored buffer (eval).
@@ -116,13 +107,6 @@ __device__ __forceinline__ void d_sn_rowdot(const float* __restrict__ w, const f
   }
   const double tot = block_sum((double)(acc0 + acc1), sm);
   if (tid == 0) s[row] = (float)tot;
-}
-
-__global__ __launch_bounds__(256) void k_sn_rowdot(const float* __restrict__ w, const float* __restrict__ t,
-                                                    int Cout, int K, float eps, int iterate, float* __restrict__ v,
-                                                    float* __restrict__ v_used, float* __restrict__ s) {
-  __shared__ double sm[16];
-  d_sn_rowdot(w, t, Cout, K, eps, iterate, v, v_used, s, blockIdx.x, sm);
 }
 
 // W_eff = W / sigma.  Every block derives sigma from s (Cout floats) in the same order:
@@ -179,15 +163,6 @@ __device__ __forceinline__ void d_sn_scale(const float* __restrict__ w, const fl
   }
 }
 
-__global__ __launch_bounds__(256) void k_sn_scale(const float* __restrict__ w, const float* __restrict__ s, int Cout,
-                                                   float eps, int iterate, float* __restrict__ u,
-                                                   float* __restrict__ u_used, float* __restrict__ sigma, int64_t n4,
-                                                   float* __restrict__ w_eff, int Cin, int khw) {
-  __shared__ double sm[16];
-  extern __shared__ __attribute__((aligned(16))) float row[];          // [khw][Cin + 4]
-  d_sn_scale(w, s, Cout, eps, iterate, u, u_used, sigma, n4, w_eff, Cin, khw, blockIdx.x, gridDim.x, sm, row);
-}
-
 struct SnGeom {
   int Cout, Cin, KH, KW;
   int64_t s0, s1, s2, s3;   // element strides of dW_eff along (Cout, Cin, KH, KW)
@@ -217,14 +192,6 @@ __device__ __forceinline__ void d_sn_bwd_dot(const SnGeom& g, const float* __res
   if (threadIdx.x == 0) partial[co] = acc;
 }
 
-__global__ __launch_bounds__(256) void k_sn_bwd_dot(SnGeom g, const float* __restrict__ dweff,
-                                                     const float* __restrict__ w, int K,
-                                                     double* __restrict__ partial) {
-  extern __shared__ float row[];
-  __shared__ double sm[16];
-  d_sn_bwd_dot(g, dweff, w, K, partial, blockIdx.x, sm, row);
-}
-
 // dW = (dW_eff - c u v^T) / sigma,  c = sum dW_eff . W_eff = (sum dW_eff . W) / sigma
 __device__ __forceinline__ void d_sn_bwd_dw(const SnGeom& g, const float* __restrict__ dweff, const float* __restrict__ u,
                                             const float* __restrict__ v, const float* __restrict__ sigma,
@@ -241,18 +208,10 @@ __device__ __forceinline__ void d_sn_bwd_dw(const SnGeom& g, const float* __rest
   for (int k = threadIdx.x; k < K; k += 256) dr[k] = (row[row_off(g, k)] - cu * v[k]) / sg;
 }
 
-__global__ __launch_bounds__(256) void k_sn_bwd_dw(SnGeom g, const float* __restrict__ dweff,
-                                                    const float* __restrict__ u, const float* __restrict__ v,
-                                                    const float* __restrict__ sigma, const double* __restrict__ partial,
-                                                    int K, float* __restrict__ dw) {
-  extern __shared__ float row[];
-  __shared__ double sm[16];
-  d_sn_bwd_dw(g, dweff, u, v, sigma, partial, K, dw, blockIdx.x, sm, row);
-}
-
-// ---- multi-tensor forms: every spectrally normalised weight of a network in ONE launch per stage (blockIdx.z = tensor).
-// A generator forward calls the hook on 18 convolutions and a PatchGAN pass on 3 per scale; one by one that is 4 launches
-// of a few microseconds each per weight — ~200 launches per training step that individually cannot fill the chip.
+// ---- the kernels: every spectrally normalised weight of a network in ONE launch per stage (blockIdx.z = tensor; a single
+// weight is a list of one).  A generator forward calls the hook on 18 convolutions and a PatchGAN pass on 3 per scale; one
+// by one that is 4 launches of a few microseconds each per weight — ~200 launches per training step that individually
+// cannot fill the chip.  The grid of a stage is the largest any of its weights needs; blocks beyond a weight's own return.
 #define SN_MAXT 12
 struct SnFwdItem {
   const float* w;
@@ -332,85 +291,9 @@ int64_t csg_spectral_norm_workspace(int64_t Cout, int64_t K) {
   return fwd > bwd ? fwd : bwd;
 }
 
-int csg_spectral_norm_fwd(const float* w, float* u, float* v, int64_t Cout, int64_t K, int iterate, float eps,
-                          float* w_eff, int64_t cl_Cin, float* sigma, float* u_used, float* v_used, void* workspace,
-                          int64_t workspace_bytes, void* stream) {
-  CSG_REQUIRE(cl_Cin == 0 || (cl_Cin % 4 == 0 && K % cl_Cin == 0), CSG_E_BADSHAPE,
-              "csg_spectral_norm_fwd: channels-last output needs Cin %% 4 == 0 dividing K");
-  CSG_REQUIRE(Cout > 0 && K > 0 && K % 4 == 0, CSG_E_BADSHAPE,
-              "csg_spectral_norm_fwd: bad shape Cout=%ld K=%ld (K must be a multiple of 4)", (long)Cout, (long)K);
-  CSG_REQUIRE(workspace && workspace_bytes >= csg_spectral_norm_workspace(Cout, K), CSG_E_BADSHAPE,
-              "csg_spectral_norm_fwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope p(K_SPECTRAL_FWD, (double)Cout * K * 4 * (iterate ? 4 : 3), s);
-  const int R = sn_R(Cout, K);
-  float* part = (float*)workspace;
-  float* t = part + (int64_t)R * K;
-  float* sv = t + K;
-  if (iterate) {
-    CSG_LAUNCH(k_sn_wtu_partial, dim3((unsigned)cdiv(K, 1024), (unsigned)R), dim3(256), 0, s, w, u, (int)Cout,
-                       (int)K, R, part);
-    CSG_LAUNCH(k_sn_wtu_reduce, dim3((unsigned)cdiv(K, 256)), dim3(64), 0, s, part, (int)K, R, t);
-  }
-  CSG_LAUNCH(k_sn_rowdot, dim3((unsigned)Cout), dim3(256), 0, s, w, t, (int)Cout, (int)K, eps, iterate,
-                     v, v_used, sv);
-  const int64_t n4 = Cout * K / 4;
-  int64_t grid = cdiv(n4, 256 * 4);
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) grid = 1;
-  size_t shm = 0;
-  if (cl_Cin) {
-    const int khw = (int)(K / cl_Cin);
-    shm = (size_t)khw * (cl_Cin + 4) * sizeof(float);
-    CSG_REQUIRE(shm <= 64 * 1024, CSG_E_UNSUPPORTED, "csg_spectral_norm_fwd: a %ld-element row does not fit the transpose buffer",
-                (long)K);
-    grid = Cout < 2048 ? Cout : 2048;
-  }
-  CSG_LAUNCH(k_sn_scale, dim3((unsigned)grid), dim3(256), shm, s, w, sv, (int)Cout, eps, iterate, u, u_used, sigma,
-                     n4, w_eff, (int)cl_Cin, cl_Cin ? (int)(K / cl_Cin) : 1);
-  return check_launch("csg_spectral_norm_fwd");
-}
-
-int csg_spectral_norm_bwd(const float* dweff, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, int64_t s0,
-                          int64_t s1, int64_t s2, int64_t s3, const float* w, const float* u_used,
-                          const float* v_used, const float* sigma, float* dw, void* workspace,
-                          int64_t workspace_bytes, void* stream) {
-  CSG_REQUIRE(Cout > 0 && Cin > 0 && KH > 0 && KW > 0, CSG_E_BADSHAPE, "csg_spectral_norm_bwd: bad shape");
-  const int64_t K = Cin * KH * KW;
-  CSG_REQUIRE(K % 4 == 0 && K <= 15360, CSG_E_UNSUPPORTED,
-              "csg_spectral_norm_bwd: K=%ld must be a multiple of 4 and at most 15360 (one LDS row)", (long)K);
-  // rows of dW_eff must be dense: s0 == K and (s1,s2,s3) a dense permutation of (Cin,KH,KW)
-  {
-    int64_t d[3] = {Cin, KH, KW}, st[3] = {s1, s2, s3};
-    for (int a = 0; a < 3; ++a)
-      for (int c = a + 1; c < 3; ++c)
-        if (st[c] < st[a]) {
-          int64_t t = st[a]; st[a] = st[c]; st[c] = t;
-          t = d[a]; d[a] = d[c]; d[c] = t;
-        }
-    int64_t run = 1;
-    bool dense = s0 == K;
-    for (int a = 0; a < 3; ++a) {
-      if (d[a] > 1 && st[a] != run) dense = false;
-      run *= d[a];
-    }
-    CSG_REQUIRE(dense, CSG_E_BADSHAPE, "csg_spectral_norm_bwd: dW_eff rows must be dense (strides %ld %ld %ld %ld)",
-                (long)s0, (long)s1, (long)s2, (long)s3);
-  }
-  CSG_REQUIRE(workspace && workspace_bytes >= Cout * (int64_t)sizeof(double), CSG_E_BADSHAPE,
-              "csg_spectral_norm_bwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope p(K_SPECTRAL_BWD, (double)Cout * K * 4 * 4, s);
-  SnGeom g{(int)Cout, (int)Cin, (int)KH, (int)KW, s0, s1, s2, s3};
-  const size_t shm = (size_t)K * sizeof(float);
-  CSG_LAUNCH(k_sn_bwd_dot, dim3((unsigned)Cout), dim3(256), shm, s, g, dweff, w, (int)K, (double*)workspace);
-  CSG_LAUNCH(k_sn_bwd_dw, dim3((unsigned)Cout), dim3(256), shm, s, g, dweff, u_used, v_used, sigma,
-                     (const double*)workspace, (int)K, dw);
-  return check_launch("csg_spectral_norm_bwd");
-}
-
-// ---- multi-tensor entry points (see SnFwdMulti above): the same arithmetic, kernel by kernel, for up to SN_MAXT weights
-// per launch (longer lists go out in chunks); every weight's results are bit-identical to the single-tensor calls.
+// ---- entry points (see SnFwdMulti above): up to SN_MAXT weights per launch, longer lists go out in chunks.  A weight's
+// workspace split, grids and LDS size depend on its own shape alone, so its results do not depend on what shares its launch
+// or on the chunk it falls in (bit for bit).
 int csg_spectral_norm_fwd_multi(const csg_sn_fwd_item* items, int32_t n, int32_t iterate, float eps, void* stream) {
   CSG_REQUIRE(items != nullptr && n > 0, CSG_E_BADSHAPE, "csg_spectral_norm_fwd_multi: empty list");
   hipStream_t s = (hipStream_t)stream;

@@ -257,7 +257,6 @@ def wino_pack(weight, backward_data, sigma=None, variant=2):
 # happens to the registry between a forward and its backward (another network's optimiser step bumps the epoch), the
 # backward uses the operand of the weights its forward saw.  What a pass asks for that was not parked is packed on the spot
 # (as before) and noted on the owning module for the next pass.
-PREPACK = os.environ.get("CSG_PREPACK", "1") != "0"
 _PREPACKED = {}          # (data_ptr, backward_data, variant) -> (packed, shape, strides, epoch)
 _PACK_OWNER = {}         # data_ptr -> (weakref to module, attribute): who to note a request on
 
@@ -326,8 +325,6 @@ def _prepack_weight_of(m, attr):
 
 def prepack_weights(root):
     """Pack, in one launch per 24 weights, every Winograd operand the previous passes through `root` asked for."""
-    if not PREPACK:
-        return
     import weakref
     mine = root.__dict__.setdefault("_pp_keys", [])
     for k in mine:                                    # operands of the previous pass nobody took
@@ -873,60 +870,11 @@ def linear(x, weight, bias=None, act=ACT_NONE, slope=0.0, in_act=None, grad_is_p
 
 
 class _SpectralWeight(torch.autograd.Function):
-    """W_eff = W / sigma(W, u, v) with torch.nn.utils.spectral_norm's power iteration (one step, in place on
-    the u / v buffers) — csrc/spectral.hip.  u and v are constants of the graph, as in PyTorch."""
-
-    @staticmethod
-    def forward(ctx, w, u, v, iterate, eps):
-        w = _f32(w).contiguous()
-        Cout = w.shape[0]
-        K = w.numel() // Cout
-        nbytes = lib.csg_spectral_norm_workspace(Cout, K)
-        if nbytes < 0:
-            raise RuntimeError("spectral_weight: weight (%d x %d) needs K %% 4 == 0" % (Cout, K))
-        dev = w.device
-        ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
-        # 4-D weights come out in channels-last memory: the convolution kernels' forward operand, no repack per call
-        cl = w.shape[1] if (w.dim() == 4 and w.shape[1] % 4 == 0 and w.shape[2] * w.shape[3] > 1
-                           and w.shape[2] * w.shape[3] * (w.shape[1] + 4) * 4 <= 65536) else 0
-        w_eff = torch.empty_like(w, memory_format=torch.channels_last) if cl else torch.empty_like(w)
-        small = torch.empty(1 + Cout + K, device=dev, dtype=torch.float32)      # sigma | u_used | v_used
-        sigma, u_used, v_used = small[:1], small[1:1 + Cout], small[1 + Cout:]
-        check(lib.csg_spectral_norm_fwd(ptr(w), ptr(u), ptr(v), Cout, K, 1 if iterate else 0, eps, ptr(w_eff), cl,
-                                        ptr(sigma), ptr(u_used), ptr(v_used), ptr(ws), nbytes, stream()),
-              "spectral_norm_fwd")
-        ctx.save_for_backward(w, small)                 # u, v are buffers (no grad): updated in place by the kernel
-        return w_eff
-
-    @staticmethod
-    def backward(ctx, dweff):
-        w, small = ctx.saved_tensors
-        Cout = w.shape[0]
-        K = w.numel() // Cout
-        Cin, KH, KW = (w.shape[1], w.shape[2], w.shape[3]) if w.dim() == 4 else (K, 1, 1)
-        dweff = _f32(dweff)
-        if dweff.dim() != 4:                            # (a 2-D gradient may arrive transposed: the kernel reads it row-major)
-            dweff = dweff.contiguous()
-        st = dweff.stride() if dweff.dim() == 4 else (K, 1, 1, 1)
-        if not _rows_dense(st, (Cin, KH, KW), K):       # e.g. a slice of a channel-padded gradient
-            dweff = dweff.contiguous()
-            st = dweff.stride() if dweff.dim() == 4 else (K, 1, 1, 1)
-        sigma, u_used, v_used = small[:1], small[1:1 + Cout], small[1 + Cout:]
-        nbytes = lib.csg_spectral_norm_workspace(Cout, K)
-        ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-        dw = _grad_dest(w, tuple(w.shape))           # w is contiguous (rows of W.view(Cout, -1)): the slot has its order
-        if dw is None:
-            dw = torch.empty_like(w)
-        check(lib.csg_spectral_norm_bwd(ptr(dweff), Cout, Cin, KH, KW, st[0], st[1], st[2], st[3], ptr(w), ptr(u_used),
-                                        ptr(v_used), ptr(sigma), ptr(dw), ptr(ws), nbytes, stream()),
-              "spectral_norm_bwd")
-        return dw, None, None, None, None
-
-
-class _SpectralWeightMulti(torch.autograd.Function):
-    """`_SpectralWeight` for every spectrally normalised weight of a network pass at once (csg_spectral_norm_*_multi): one
-    launch per stage instead of one per weight and stage — a generator forward has 18 such weights, a PatchGAN pass 3 per
-    scale, ~200 launches of a few microseconds each per training step.  Same arithmetic, bit-identical per weight."""
+    """W_eff = W / sigma(W, u, v) with torch.nn.utils.spectral_norm's power iteration (one step, in place on the u / v
+    buffers) — csrc/spectral.hip.  u and v are constants of the graph, as in PyTorch.  Takes every spectrally normalised
+    weight of a network pass at once (csg_spectral_norm_*_multi): one launch per stage instead of one per weight and stage —
+    a generator forward has 18 such weights, a PatchGAN pass 3 per scale, ~200 launches of a few microseconds each per
+    training step.  A weight's result does not depend on what shares its launch (bit for bit); one weight is a list of one."""
 
     @staticmethod
     def forward(ctx, iterate, eps, *wuv):
@@ -942,6 +890,7 @@ class _SpectralWeightMulti(torch.autograd.Function):
             if nbytes < 0:
                 raise RuntimeError("spectral_weight: weight (%d x %d) needs K %% 4 == 0" % (Cout, K))
             wsb = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+            # 4-D weights come out in channels-last memory: the convolution kernels' forward operand, no repack per call
             cl = w.shape[1] if (w.dim() == 4 and w.shape[1] % 4 == 0 and w.shape[2] * w.shape[3] > 1
                                and w.shape[2] * w.shape[3] * (w.shape[1] + 4) * 4 <= 65536) else 0
             w_eff = torch.empty_like(w, memory_format=torch.channels_last) if cl else torch.empty_like(w)
@@ -957,7 +906,7 @@ class _SpectralWeightMulti(torch.autograd.Function):
         check(lib.csg_spectral_norm_fwd_multi(items, n, 1 if iterate else 0, eps, stream()), "spectral_norm_fwd_multi")
         ctx.n = n
         ctx.set_materialize_grads(False)          # an output left out of the backward arrives as None, not as zeros to push through
-        ctx.save_for_backward(*ws, *smalls)
+        ctx.save_for_backward(*ws, *smalls)          # u, v are buffers (no grad): updated in place by the kernel
         return tuple(outs)
 
     @staticmethod
@@ -976,15 +925,15 @@ class _SpectralWeightMulti(torch.autograd.Function):
             K = w.numel() // Cout
             Cin, KH, KW = (w.shape[1], w.shape[2], w.shape[3]) if w.dim() == 4 else (K, 1, 1)
             dweff = _f32(dweffs[i])
-            if dweff.dim() != 4:
+            if dweff.dim() != 4:                        # (a 2-D gradient may arrive transposed: the kernel reads it row-major)
                 dweff = dweff.contiguous()
             st = dweff.stride() if dweff.dim() == 4 else (K, 1, 1, 1)
-            if not _rows_dense(st, (Cin, KH, KW), K):
+            if not _rows_dense(st, (Cin, KH, KW), K):   # e.g. a slice of a channel-padded gradient
                 dweff = dweff.contiguous()
                 st = dweff.stride() if dweff.dim() == 4 else (K, 1, 1, 1)
             nbytes = lib.csg_spectral_norm_workspace(Cout, K)
             wsb = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-            dw = _grad_dest(w, tuple(w.shape))
+            dw = _grad_dest(w, tuple(w.shape))       # w is contiguous (rows of W.view(Cout, -1)): the slot has its order
             if dw is None:
                 dw = torch.empty_like(w)
             it = items[j]
@@ -1000,12 +949,12 @@ class _SpectralWeightMulti(torch.autograd.Function):
 
 
 def spectral_weights(wuv, iterate, eps=1e-12):
-    """[(weight_orig, u, v), ...] -> [W / sigma, ...] (see _SpectralWeightMulti)."""
+    """[(weight_orig, u, v), ...] -> [W / sigma, ...] (see _SpectralWeight)."""
     flat = [t for triple in wuv for t in triple]
     for t in flat:
         if not t.is_cuda:
             raise RuntimeError("canonicalsg2im_amd ops need HIP (cuda) tensors; there is no CPU path")
-    return list(_SpectralWeightMulti.apply(bool(iterate), float(eps), *flat))
+    return list(_SpectralWeight.apply(bool(iterate), float(eps), *flat))
 
 
 def _rows_dense(st, dims, K):
@@ -1020,7 +969,8 @@ def _rows_dense(st, dims, K):
 
 
 def spectral_weight(w, u, v, iterate, eps=1e-12):
-    return _SpectralWeight.apply(w, u, v, bool(iterate), float(eps))
+    """W / sigma of one weight: `spectral_weights` over a list of one."""
+    return spectral_weights([(w, u, v)], iterate, eps)[0]
 
 
 # ------------------------------------------------------------------------------------ normalisation
@@ -1976,17 +1926,9 @@ class _PoolFanout(torch.autograd.Function):
         return dx
 
 
-POOL_FANOUT = os.environ.get("CSG_POOL_FANOUT", "1") != "0"       # 0: plain avgpool3s2 + autograd's own addition (A/B)
-
-
 def pool_fanout(x):
     """(x, avgpool3s2(x)) with the two gradients of x summed inside the pooling backward (ops._PoolFanout)."""
-    if not POOL_FANOUT:
-        return x, avgpool3s2(x)
     return _PoolFanout.apply(x)
-
-
-HINGE_FUSED = os.environ.get("CSG_HINGE_FUSED", "1") != "0"       # 0: the GAN terms as torch's sub / clamp / mean / neg chain (A/B)
 
 
 class _HingeMean(torch.autograd.Function):
@@ -2025,7 +1967,7 @@ class _HingeMean(torch.autograd.Function):
 
 def hinge_mean(preds, kind):
     """None when the fused form does not apply (CPU tensors, more than four scales, maps with more than one channel)."""
-    if not HINGE_FUSED or not (1 <= len(preds) <= 4):
+    if not (1 <= len(preds) <= 4):
         return None
     if any((not p.is_cuda) or p.dim() != 4 or p.shape[1] != 1 or p.dtype != torch.float32 for p in preds):
         return None

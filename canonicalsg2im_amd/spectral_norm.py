@@ -4,15 +4,10 @@ state_dict hooks) whose per-call arithmetic runs on the HIP kernels of csrc/spec
 
 Registration is torch's own (`SpectralNorm.apply`), so checkpoints, `remove_spectral_norm` and the
 state-dict version hooks behave exactly as in the reference; only `compute_weight` is replaced."""
-import os
-
 from torch.nn.utils.spectral_norm import SpectralNorm
 from torch.nn.utils.spectral_norm import spectral_norm as _torch_spectral_norm
 
 from . import ops
-
-
-BATCHED = os.environ.get("CSG_SN_BATCHED", "1") != "0"
 
 
 def prepare(root):
@@ -21,8 +16,6 @@ def prepare(root):
     forward, picks it up instead of computing.  Call at the top of a network's forward whose spectrally normalised layers
     are each called exactly once per forward (the generator, a PatchGAN scale): the power iterations, u / v updates and
     W / sigma are then exactly those of the per-module calls, in one launch per stage instead of one per weight."""
-    if not BATCHED:
-        return
     plan = root.__dict__.get("_sn_plan")
     if plan is None:
         plan = []

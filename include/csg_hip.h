@@ -948,21 +948,14 @@ int csg_coco_masks(const uint8_t* kind, const int32_t* crop, const int64_t* size
  * graph keeps for backward (PyTorch clones them for the same reason).
  * Backward: dw = (dweff - (sum dweff.w_eff) u v^T) / sigma; dweff is given with its element strides
  * along (Cout, Cin, KH, KW) — rows must be dense, e.g. contiguous or the [Cout][KH][KW][Cin] layout of
- * csg_conv_bwd_weight.  One workspace size serves both calls. */
+ * csg_conv_bwd_weight.  One workspace size serves both calls.
+ * The calls take a list of weights — every spectrally normalised weight of a network pass in ONE launch per stage (a
+ * generator forward calls the hook of architecture.py:35-39 on 18 convolutions, a PatchGAN pass on 3 per scale); one
+ * weight is a list of one.  A weight's results do not depend on what shares its launch (bit for bit).  Per item:
+ * `workspace` as csg_spectral_norm_workspace; cl_Cin = 0: W_eff in W's memory order; cl_Cin = Cin (a multiple of 4): W is
+ * (Cout,Cin,KH,KW) row-major and W_eff is written in channels-last memory [Cout][KH][KW][Cin], the convolution kernels'
+ * forward operand (no repack).                                                                                          */
 int64_t csg_spectral_norm_workspace(int64_t Cout, int64_t K);
-/* cl_Cin = 0: W_eff in W's memory order; cl_Cin = Cin (a multiple of 4): W is (Cout,Cin,KH,KW) row-major and W_eff is
- * written in channels-last memory [Cout][KH][KW][Cin], the convolution kernels' forward operand (no repack).      */
-int csg_spectral_norm_fwd(const float* w, float* u, float* v, int64_t Cout, int64_t K, int iterate, float eps,
-                          float* w_eff, int64_t cl_Cin, float* sigma, float* u_used, float* v_used, void* workspace,
-                          int64_t workspace_bytes, void* stream);
-int csg_spectral_norm_bwd(const float* dweff, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, int64_t s0,
-                          int64_t s1, int64_t s2, int64_t s3, const float* w, const float* u_used,
-                          const float* v_used, const float* sigma, float* dw, void* workspace,
-                          int64_t workspace_bytes, void* stream);
-
-/* Multi-tensor forms: every spectrally normalised weight of a network pass in ONE launch per stage (a generator forward
- * calls the hook of architecture.py:35-39 on 18 convolutions, a PatchGAN pass on 3 per scale).  Same arithmetic and
- * bit-identical results per weight as the single-tensor calls; `workspace` per item as csg_spectral_norm_workspace. */
 typedef struct csg_sn_fwd_item {
   const float* w;
   float* u;

@@ -38,12 +38,12 @@ import torch
 
 # ------------------------------------------------------------------------------------------------- the launch rules
 EW_BLOCK, EW_CAP = 256, 256 * 16     # ew_grid: csrc/perceptual.hip:123-128 and csrc/norm.hip:544-549
-SN_MAXT = 12                         # csrc/spectral.hip:256: weights per multi-tensor launch
-SN_BWD_MAXK = 15360                  # csrc/spectral.hip:380,484: one LDS row of the backward
-SN_T_BYTES = 64 * 1024               # csrc/spectral.hip:365,445 and ops.py:889-890: the channels-last transpose buffer
-SN_SCALE_CAP = 2048                  # csrc/spectral.hip:358-367: blocks of k_sn_scale
-SN_EPS = 1e-12                       # ops.py:1016: spectral_weight's default, torch.nn.utils.spectral_norm's too
-HINGE_MAX_SCALES = 4                 # ops.py:1848
+SN_MAXT = 12                         # csrc/spectral.hip:215: weights per launch
+SN_BWD_MAXK = 15360                  # csrc/spectral.hip:367: one LDS row of the backward
+SN_T_BYTES = 64 * 1024               # csrc/spectral.hip:328 and ops.py:894-895: the channels-last transpose buffer
+SN_SCALE_CAP = 2048                  # csrc/spectral.hip:323-333: blocks of k_sn_scale_m per weight
+SN_EPS = 1e-12                       # ops.py:971: spectral_weight's default, torch.nn.utils.spectral_norm's too
+HINGE_MAX_SCALES = 4                 # ops.py:1970
 COTS = ("contig", "ohwi", "ohiw", "padslice", "colmajor")
 
 
@@ -62,7 +62,7 @@ def ew_capped(n):
 
 
 def sn_dims(shape):
-    """(Cout, Cin, KH, KW, K) as _SpectralWeight.backward sees a weight (ops.py:903-905)."""
+    """(Cout, Cin, KH, KW, K) as _SpectralWeight.backward sees a weight (ops.py:924-926)."""
     Cout = shape[0]
     K = int(np.prod(shape[1:]))
     Cin, KH, KW = (shape[1], shape[2], shape[3]) if len(shape) == 4 else (K, 1, 1)
@@ -70,7 +70,7 @@ def sn_dims(shape):
 
 
 def sn_R(Cout, K):
-    """Row chunks of the first stage of W^T u (csrc/spectral.hip:315-322)."""
+    """Row chunks of the first stage of W^T u (csrc/spectral.hip:274-281)."""
     return max(min(512 // cdiv(K, 1024), Cout, 32), 1)
 
 
@@ -82,24 +82,24 @@ def sn_empty_chunks(Cout, K):
 
 
 def sn_channels_last(shape):
-    """Cin if W_eff comes out in channels-last memory, else 0 (_SpectralWeight.forward, ops.py:889-890)."""
+    """Cin if W_eff comes out in channels-last memory, else 0 (_SpectralWeight.forward, ops.py:894-895)."""
     if len(shape) == 4 and shape[1] % 4 == 0 and shape[2] * shape[3] > 1 and shape[2] * shape[3] * (shape[1] + 4) * 4 <= SN_T_BYTES:
         return shape[1]
     return 0
 
 
 def sn_scale_rule(shape):
-    """k_sn_scale's launch (csrc/spectral.hip:357-370): path, grid, whether the cap makes the loop go round again, LDS."""
+    """A weight in k_sn_scale_m's launch (csrc/spectral.hip:322-333): path, grid, whether the cap makes the loop go round again, LDS."""
     Cout, Cin, KH, KW, K = sn_dims(shape)
     cl = sn_channels_last(shape)
-    if cl:                                                                   # :362-368: one block per output channel
+    if cl:                                                                   # :326-332: one block per output channel
         return dict(path="cl", grid=min(Cout, SN_SCALE_CAP), capped=Cout > SN_SCALE_CAP, lds=KH * KW * (cl + 4) * 4)
     n4 = Cout * K // 4
     return dict(path="plain", grid=min(max(cdiv(n4, 1024), 1), SN_SCALE_CAP), capped=cdiv(n4, 1024) > SN_SCALE_CAP, lds=0)
 
 
 def rows_dense(st, dims, K):
-    """ops._rows_dense (ops.py:1005-1013; csrc/spectral.hip:383-399): every Cout-row a dense permutation of its K elements."""
+    """ops._rows_dense (ops.py:960-968; csrc/spectral.hip:369-385): every Cout-row a dense permutation of its K elements."""
     run = 1
     for i in sorted(range(3), key=lambda i: st[1 + i]):
         if dims[i] > 1 and st[1 + i] != run:
@@ -125,7 +125,7 @@ def cot_strides(shape, cot):
 
 
 def cot_goes_through_contiguous(shape, cot):
-    """The `.contiguous()` fallback of _SpectralWeight.backward (ops.py:906-910)."""
+    """The `.contiguous()` fallback of _SpectralWeight.backward (ops.py:927-933)."""
     Cout, Cin, KH, KW, K = sn_dims(shape)
     return len(shape) != 4 and cot != "contig" or not rows_dense(cot_strides(shape, cot), (Cin, KH, KW), K)
 
@@ -178,7 +178,7 @@ def describe(c):
 
 
 def hinge_fused(c):
-    """ops.hinge_mean serves the call (ops.py:1846-1852): 1..4 scales of one-channel maps."""
+    """ops.hinge_mean serves the call (ops.py:1968-1974): 1..4 scales of one-channel maps."""
     return 1 <= len(c["maps"]) <= HINGE_MAX_SCALES and all(s[1] == 1 for s, _ in c["maps"])
 
 

@@ -65,6 +65,12 @@ def test_library_reads_only_the_family_switches_from_the_environment():
         if f.endswith((".hip", ".h")):
             names |= set(re.findall(r'getenv\("([A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
     assert names == {"CSG_WINO4", "CSG_WINO34", "CSG_WINO4_PERSIST"}, names
+    # the settled A/B switches are gone from the package, Python and HIP alike (their results: profiles/README.md)
+    retired = re.compile("CSG_SN_BATCHED|CSG_POOL_FANOUT|CSG_HINGE_FUSED|CSG_PREPACK")
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "canonicalsg2im_amd")):
+        for f in files:
+            if f.endswith((".py", ".hip", ".h")):
+                assert not retired.search(open(os.path.join(dirpath, f), errors="replace").read()), os.path.join(dirpath, f)
 
 
 def test_conv_descriptor_struct_matches_header(built):

@@ -581,9 +581,10 @@ def test_spectral_norm_vs_torch(ops, shape):
 
 
 def test_spectral_norm_multi_is_bit_identical_to_single(ops):
-    """The multi-tensor spectral normalisation (csg_spectral_norm_*_multi: every weight of a network pass in one launch
-    per stage) against the per-weight calls: W / sigma, the updated u / v buffers and d weight_orig bit for bit — 14
-    weights (more than one chunk of 12) of mixed shapes, two training-mode calls and an eval call."""
+    """A weight's spectral normalisation does not depend on what shares its launch or on the chunk it falls in: one
+    ops.spectral_weights call over 14 weights of mixed shapes (more than one chunk of 12) against 14 ops.spectral_weight
+    calls (lists of one, through the same kernels): W / sigma, the updated u / v buffers and d weight_orig bit for bit —
+    two training-mode calls and an eval call."""
     shapes = [(64, 32, 3, 3), (128, 64, 4, 4), (256, 128, 4, 4), (20, 12, 1, 1), (512, 256, 3, 3), (1024, 1024, 3, 3),
               (64, 64, 3, 3), (32, 16, 1, 1), (128, 128, 3, 3), (512, 256, 4, 4), (96, 48, 3, 3), (256, 256, 1, 1),
               (40, 8, 3, 3), (128, 32, 3, 3)]
@@ -687,20 +688,15 @@ def test_pool_fanout_sums_both_gradients_in_the_pooling_backward():
     w_full, w_pool = torch.randn(3, 36, 33, 47, generator=g), torch.randn(3, 36, 17, 24, generator=g)
 
     def run(fused, use_full=True, use_pool=True):
-        saved = ops.POOL_FANOUT
-        ops.POOL_FANOUT = fused
-        try:
-            x = ops.nhwc(x0.clone().cuda()).requires_grad_(True)
-            a, b = ops.pool_fanout(x)
-            loss = 0
-            if use_full:
-                loss = loss + (a * a * w_full.cuda()).sum()
-            if use_pool:
-                loss = loss + (b * w_pool.cuda()).sum()
-            loss.backward()
-            return a.detach(), b.detach(), x.grad.detach()
-        finally:
-            ops.POOL_FANOUT = saved
+        x = ops.nhwc(x0.clone().cuda()).requires_grad_(True)
+        a, b = ops.pool_fanout(x) if fused else (x, ops.avgpool3s2(x))
+        loss = 0
+        if use_full:
+            loss = loss + (a * a * w_full.cuda()).sum()
+        if use_pool:
+            loss = loss + (b * w_pool.cuda()).sum()
+        loss.backward()
+        return a.detach(), b.detach(), x.grad.detach()
 
     for use_full, use_pool in ((True, True), (True, False), (False, True)):
         a1, b1, g1 = run(True, use_full, use_pool)
@@ -712,7 +708,7 @@ def test_pool_fanout_sums_both_gradients_in_the_pooling_backward():
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2])
-def test_hinge_mean_over_scales_vs_torch(kind):
+def test_hinge_mean_over_scales_vs_torch(kind, monkeypatch):
     """ops.hinge_mean: the PatchGAN's GAN term over both scales in one launch (reference loss.py:60-93) against the torch chain
     it replaces — value and d/d(prediction) — on predictions that are the one real channel of padded NHWC buffers."""
     from canonicalsg2im_amd import ops
@@ -723,16 +719,14 @@ def test_hinge_mean_over_scales_vs_torch(kind):
     real, for_d = {0: (True, False), 1: (True, True), 2: (False, True)}[kind]
 
     def run(fused):
-        saved = ops.HINGE_FUSED
-        ops.HINGE_FUSED = fused
-        try:
+        with monkeypatch.context() as mp:
+            if not fused:
+                mp.setattr(ops, "hinge_mean", lambda preds, kind: None)   # GANLoss then runs its torch chain
             leaves = [b.clone().requires_grad_(True) for b in bufs]
             preds = [[l.permute(0, 3, 1, 2)[:, :1]] for l in leaves]      # (B,1,h,w) views, element stride 4
             out = crit(preds, real, for_discriminator=for_d)
             (out * 3.0).sum().backward()
             return out.detach(), [l.grad.detach() for l in leaves]
-        finally:
-            ops.HINGE_FUSED = saved
 
     o1, g1 = run(True)
     o0, g0 = run(False)

@@ -113,8 +113,8 @@ def _run_spectral(ops, c, d):
                 assert o.stride() == (K, 1, KW * Cin, Cin), "%s: W_eff is not channels-last" % rows[i]["name"]
             else:
                 assert o.is_contiguous(), "%s: W_eff is not in the weight's own order" % rows[i]["name"]
-            saved = o.grad_fn.saved_tensors
-            sigma = saved[1][:1] if single else saved[n + i][:1]
+            saved = o.grad_fn.saved_tensors                # (the n weights, then sigma | u_used | v_used of each)
+            sigma = saved[n + i][:1]
             res[pre(i, "weff" + tag)], res[pre(i, "sigma" + tag)] = _keep(o), _keep(sigma)
             if iterate:
                 res[pre(i, "u" + tag)], res[pre(i, "v" + tag)] = _keep(us[i]), _keep(vs[i])

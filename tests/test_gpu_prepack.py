@@ -38,12 +38,8 @@ def test_multi_pack_is_bit_identical_to_single_packs(ops):
         items.append(it)
         outs.append(out)
         ws.append(w)
-        saved = ops.PREPACK
-        ops.PREPACK = False
-        try:
-            want.append(ops.wino_pack(w, bd, None, var))
-        finally:
-            ops.PREPACK = saved
+        assert (w.data_ptr(), bd, var) not in ops._PREPACKED                # nothing parked: packed by its own launch
+        want.append(ops.wino_pack(w, bd, None, var))
     arr = (WinoPackItem * len(items))(*items)
     check(lib.csg_wino_pack_weights_multi(arr, len(items), stream()), "multi")
     torch.cuda.synchronize()
@@ -75,8 +71,10 @@ def test_training_steps_with_and_without_the_registry_are_bit_identical(ops, mon
     out of the registry (the one-weight pack is not called for them)."""
     import copy
     results = {}
+    real_prepack = ops.prepack_weights
     for on in (True, False):
-        monkeypatch.setattr(ops, "PREPACK", on)
+        # off: nothing is parked, every wino_pack packs on the spot (the networks call ops.prepack_weights by that name)
+        monkeypatch.setattr(ops, "prepack_weights", real_prepack if on else (lambda root: None))
         ops._PREPACKED.clear()
         ops._PACK_OWNER.clear()
         tr, batches = _trainer(on)
@@ -132,12 +130,8 @@ def test_registry_refuses_stale_operands(ops):
     invalidate_weight_caches) or for a tensor of another shape at the same address."""
     base = torch.randn(64 * 32 * 9, device="cuda")
     w = base.view(64, 32, 3, 3)
-    saved = ops.PREPACK
-    ops.PREPACK = False
-    try:
-        good = ops.wino_pack(w, False, None, 4)
-    finally:
-        ops.PREPACK = saved
+    assert (w.data_ptr(), False, 4) not in ops._PREPACKED                   # nothing parked: packed by its own launch
+    good = ops.wino_pack(w, False, None, 4)
     key = (w.data_ptr(), False, 4)
     marker = torch.zeros_like(good)
     ops._PREPACKED[key] = (marker,) + ops._pack_tag(w)

@@ -251,7 +251,7 @@ def test_table_covers_every_kernel_branch_and_corner():
     # ---- column blocks of 1024: exactly one, several, a ragged last one
     assert dims["sn_128x64x4x4"][4] == 1024 and dims["sn_64x512x3x3"][4] == 4608
     assert [n for n in dims if dims[n][4] < 1024] and [n for n in dims if dims[n][4] > 1024 and dims[n][4] % 1024]
-    # ---- both k_sn_scale paths, each with and without the capped loop; the transpose buffer's limit; the plain fallbacks
+    # ---- both d_sn_scale paths, each with and without the capped loop; the transpose buffer's limit; the plain fallbacks
     rules = {c["name"]: lc.sn_scale_rule(c["shape"]) for c in runs}
     for path in ("cl", "plain"):
         for capped in (False, True):
