@@ -1,4 +1,4 @@
-// Shared host-side plumbing of libcsg_hip.so: error text, launch checking, per-kernel timing.
+// Shared host-side plumbing of libcsg_hip.so: error text, launch checking, per-kernel timing, the dynamic-LDS rule (csg::lds_limit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -147,6 +147,14 @@ static inline void launch(void (*kernel)(KArgs...), dim3 g, dim3 b, size_t shm, 
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// blocks of 256 threads for a grid-stride elementwise kernel over n items
+static inline unsigned ew_grid(int64_t n) {
+  int64_t g = cdiv(n, 256);
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
 }  // namespace csg
 
 #define CSG_LAUNCH(kernel, grid, block, shm, stream, ...) csg::launch(kernel, grid, block, shm, stream, __VA_ARGS__)
@@ -159,7 +167,7 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
     }                                 \
   } while (0)
 
-// Per-device "already done" flags for idempotent one-time host setup (hipFuncSetAttribute on a kernel): lock-free and
+// Per-device "already done" flags for idempotent one-time host setup (csg::lds_limit below): lock-free and
 // re-entrant — two threads racing on a device's first launch both do the setup (harmless), a device id beyond the table does
 // it on every launch (correct, a few microseconds slower).
 struct DeviceOnce {
@@ -169,3 +177,31 @@ struct DeviceOnce {
     if (dev >= 0 && dev < 32) done[dev].store(true, std::memory_order_release);
   }
 };
+
+namespace csg {
+
+// The ONE rule for dynamic LDS: a launch may ask for up to 48 KB as it is; above that the kernel's limit has to be raised
+// first, per kernel and per device.  Every launch whose rule can ask for more calls this right before CSG_LAUNCH.
+// Cap = the largest request the kernel's launch rule can make (never this call's `bytes`: two threads with different sizes
+// could then leave the limit below a size already recorded as granted); a CU has 160 KB.  A request beyond Cap is refused;
+// a Cap of 48 KB or less costs nothing (no hipGetDevice); otherwise the limit is raised to Cap on the first launch of
+// (Kernel, device) and never again, so a captured or replayed step makes no such call.
+template <auto Kernel, size_t Cap>
+static inline int lds_limit(size_t bytes, const char* who) {
+  static_assert(Cap <= 160 * 1024, "a CU has 160 KB of LDS");
+  CSG_REQUIRE(bytes <= Cap, CSG_E_UNSUPPORTED, "%s: %zu bytes of LDS", who, bytes);
+  if constexpr (Cap > 48 * 1024) {
+    static DeviceOnce once;              // one table per kernel instantiation
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (once.pending(dev)) {
+      const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cap);
+      CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "%s: cannot raise the dynamic LDS limit to %zu bytes: %s", who, Cap,
+                  hipGetErrorString(e));
+      once.mark(dev);
+    }
+  }
+  return CSG_OK;
+}
+
+}  // namespace csg

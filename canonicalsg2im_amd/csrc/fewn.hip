@@ -354,16 +354,20 @@ static FewFwdPlan few_fwd_plan(const FewParams& p, int KH, int KW) {
   return f;
 }
 
+// the larger of few_fwd_plan's two patches, 16 x 16 and 8 x 32 outputs: 30 800 bytes for 4x4 taps, 27 200 for 3x3
+static constexpr size_t few_fwd_lds_cap(int KH, int KW) {
+  const size_t sq = (size_t)(16 + KH - 1) * (16 + KW - 1), wide = (size_t)(8 + KH - 1) * (32 + KW - 1);
+  return (sq > wide ? sq : wide) * FW_LD * 4;
+}
+
 template <int KH, int KW, int NR>
-static void few_launch_fwd(const FewParams& p, const FewFwdPlan& f, const float* x, const float* w, const float* bias,
-                           float* out, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)k_few_fwd<KH, KW, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    attr_set = true;
-  }
+static int few_launch_fwd(const FewParams& p, const FewFwdPlan& f, const float* x, const float* w, const float* bias,
+                          float* out, hipStream_t s) {
+  const int rc = lds_limit<k_few_fwd<KH, KW, NR>, few_fwd_lds_cap(KH, KW)>(f.shm, "csg_conv_few_fwd");
+  if (rc) return rc;
   CSG_LAUNCH((k_few_fwd<KH, KW, NR>), dim3((unsigned)f.grid), dim3(256), f.shm, s, p, x, w, bias, out, f.TX, f.ksplit,
                      f.cps, f.slab);
+  return check_launch("csg_conv_few_fwd");
 }
 
 extern "C" {
@@ -398,15 +402,14 @@ int csg_conv_few_fwd(const csg_few_desc* d, const float* x, const float* w, cons
   ProfScope ps(K_FEW_FWD, ((double)p.B * p.IH * p.IW * p.Cin + (double)p.B * p.OH * p.OW * 4) * 4, s);
   float* out = f.ksplit > 1 ? workspace : y;
   if (d->KH == 3) {
-    if (p.nreal == 1) few_launch_fwd<3, 3, 1>(p, f, x, w, bias, out, s);
-    else if (p.nreal == 2) few_launch_fwd<3, 3, 2>(p, f, x, w, bias, out, s);
-    else if (p.nreal == 3) few_launch_fwd<3, 3, 3>(p, f, x, w, bias, out, s);
-    else few_launch_fwd<3, 3, 4>(p, f, x, w, bias, out, s);
+    if (p.nreal == 1) rc = few_launch_fwd<3, 3, 1>(p, f, x, w, bias, out, s);
+    else if (p.nreal == 2) rc = few_launch_fwd<3, 3, 2>(p, f, x, w, bias, out, s);
+    else if (p.nreal == 3) rc = few_launch_fwd<3, 3, 3>(p, f, x, w, bias, out, s);
+    else rc = few_launch_fwd<3, 3, 4>(p, f, x, w, bias, out, s);
   } else {
-    if (p.nreal == 1) few_launch_fwd<4, 4, 1>(p, f, x, w, bias, out, s);
-    else few_launch_fwd<4, 4, 2>(p, f, x, w, bias, out, s);
+    if (p.nreal == 1) rc = few_launch_fwd<4, 4, 1>(p, f, x, w, bias, out, s);
+    else rc = few_launch_fwd<4, 4, 2>(p, f, x, w, bias, out, s);
   }
-  rc = check_launch("csg_conv_few_fwd");
   if (rc == CSG_OK && f.ksplit > 1) {
     const int64_t npix = (int64_t)p.B * p.OH * p.OW;
     CSG_LAUNCH(k_few_finish, dim3((unsigned)cdiv(npix, 256)), dim3(256), 0, s, p, (const float4*)workspace, f.ksplit,

@@ -461,6 +461,7 @@ int csg_gemm_nt(const csg_gemm_desc* d, const float* a, const float* bw, const f
   // latency is not what is exposed.  The 64-wide tiles of N <= 64 prefer the long stages (84 vs 72 TFLOP/s at K = 128).
   const int bk = narrow ? 32 : 16, nbuf = 2;
   p.nstage = (int)cdiv(d->K, bk);
+  // dynamic LDS: 2 x (128 + 128) x 16 x 4 = 32 KB, narrow 2 x (128 + 64) x 32 x 4 = 48 KB exactly — what any launch may ask for
   const size_t shm = (size_t)nbuf * (128 + (narrow ? 64 : 128)) * bk * 4;
 #define GM_NT(NTW, BK, NBUF)                                                                                     \
   do {                                                                                                           \
@@ -506,6 +507,7 @@ int csg_gemm_tn(int64_t M, int64_t N, int64_t K, const float* dy, int64_t ldy, c
   float* slabs = ns > 1 ? workspace : dw;
   float* dbs = db == nullptr ? nullptr : (ns > 1 ? workspace + (int64_t)ns * N * K : db);
   ProfScope ps(K_GEMM_TN, 2.0 * (double)M * (double)N * (double)K, s);
+  static_assert(GM_LDS_BYTES / 2 <= 48 * 1024, "k_gemm_tn: 32 KB of dynamic LDS, below what any launch may ask for");
   CSG_LAUNCH(k_gemm_tn<16>, dim3((unsigned)(p.nnb * p.nkb * ns)), dim3(256), GM_LDS_BYTES / 2, s, p, dy, x, slabs, dbs);
   if (ns > 1) launch_slab_reduce(slabs, N * K, dw, dbs, db != nullptr ? N : 0, db, ns, s);
   return check_launch("k_gemm_tn");

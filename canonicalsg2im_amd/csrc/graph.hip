@@ -618,6 +618,8 @@ int csg_embed_bwd(const int64_t* idx, int64_t rows, int64_t idx_stride, const fl
   const int64_t chunks = cdiv(rows, chunk), n = num_emb * dim;
   CSG_REQUIRE(chunks < (1ll << 31) && cdiv(n, 256) < 65536, CSG_E_UNSUPPORTED, "csg_embed_bwd: too many rows / entries");
   const dim3 grid((unsigned)chunks, (unsigned)cdiv(n, 256));
+  // dynamic LDS: chunk * dim <= EMB_TILE_FLOATS (dim <= 256, so the floor of 32 rows never binds) and chunk <= 1024, at most
+  // (8192 + 1024) * 4 = 36 864 bytes — below the 48 KB any launch may ask for
   const size_t shm = ((size_t)chunk * dim + chunk) * sizeof(float);
   if (chunks == 1) {
     CSG_LAUNCH(k_embed_bwd, grid, dim3(256), shm, s, idx, rows, idx_stride, dout, out_stride, out_off, (int)num_emb, (int)dim,
@@ -644,11 +646,13 @@ int csg_real_object_mask(const int64_t* objs, int64_t B, int64_t O, int64_t A, i
   return check_launch("csg_real_object_mask");
 }
 
+constexpr size_t CSR_SORTED_LDS_MAX = 150 * 1024;   // larger graphs go to the plain builder: the cap of k_csr_build_sorted
+
 // which builder serves (T, O): the counting sort's dynamic LDS in bytes, 0 = the plain builder, -1 = refused
 int64_t csg_graph_csr_lds(int64_t T, int64_t O) {
   if (T < 0 || O <= 0 || O > 256 * CSR_MAXJ || T >= (1 << 29)) return -1;
   const size_t shm = csr_sorted_lds(T, O);
-  return (O <= 254 && T >= 512 && T <= 65535 && shm <= 150 * 1024) ? (int64_t)shm : 0;   // dense graphs: counting sort
+  return (O <= 254 && T >= 512 && T <= 65535 && shm <= CSR_SORTED_LDS_MAX) ? (int64_t)shm : 0;   // dense graphs: counting sort
 }
 
 int csg_graph_csr_build(const int64_t* triplets, int64_t B, int64_t T, int64_t O, int32_t* row_ptr, int32_t* col,
@@ -662,11 +666,8 @@ int csg_graph_csr_build(const int64_t* triplets, int64_t B, int64_t T, int64_t O
   ProfScope p(K_CSR_BUILD, (double)B * T * (24 + 8), s);
   const size_t shm = (size_t)csg_graph_csr_lds(T, O);
   if (shm > 0) {
-    static size_t attr = 0;
-    if (shm > attr) {
-      (void)hipFuncSetAttribute((const void*)k_csr_build_sorted, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      attr = shm;
-    }
+    const int rc = lds_limit<k_csr_build_sorted, CSR_SORTED_LDS_MAX>(shm, "csg_graph_csr_build");
+    if (rc) return rc;
     CSG_LAUNCH(k_csr_build_sorted, dim3((unsigned)B), dim3(256), shm, s, triplets, (int)T, (int)O, row_ptr,
                        col);
   } else {

@@ -845,16 +845,15 @@ static int64_t fwd_grid(const IgemmParams& p) {
   return (int64_t)p.mtiles * p.ntiles * p.ksplit;
 }
 
+// dynamic LDS of k_igemm_fwd<BN>, fixed per BN (so the size is its own cap): 46 272 / 55 488 / 73 920 bytes for 32 / 64 / 128
+static constexpr size_t igemm_fwd_lds(int bn) { return (size_t)(2 * IG_BM * IG_LD + 2 * bn * IG_LD) * 4 + 48 * 4; }
+
 template <int BN>
 static int launch_fwd(IgemmParams& p, const float* x, const float* w, const float* bias, const float* res, float* y,
                       float* ws, hipStream_t s) {
-  static bool attr_set = false;
-  size_t shm = (size_t)(2 * IG_BM * IG_LD + 2 * BN * IG_LD) * 4 + 48 * 4;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_igemm_fwd<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_conv_fwd: hipFuncSetAttribute(%zu bytes of LDS): %s", shm, hipGetErrorString(e));
-    attr_set = true;
-  }
+  constexpr size_t shm = igemm_fwd_lds(BN);
+  const int rc = lds_limit<k_igemm_fwd<BN>, shm>(shm, "csg_conv_fwd");
+  if (rc) return rc;
   CSG_LAUNCH(k_igemm_fwd<BN>, dim3((unsigned)fwd_grid(p)), dim3(256), shm, s, p, x, w, bias, res, y, ws);
   return check_launch("csg_conv_fwd");
 }
@@ -871,13 +870,9 @@ static void wgrad_plan(const IgemmParams& p, int bi, int& itiles, int& jtiles, i
 template <int BI>
 static int launch_wgrad(IgemmParams& p, const float* x, const float* dy, float* out, int itiles, int jtiles,
                         int nsplit, int cps, float* dbp, hipStream_t s) {
-  static bool attr_set = false;
-  size_t shm = (size_t)(2 * 32 * BI + 2 * 32 * WG_LDB) * 4 + 48 * 4;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_igemm_wgrad<BI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_conv_bwd_weight: hipFuncSetAttribute(%zu bytes of LDS): %s", shm, hipGetErrorString(e));
-    attr_set = true;
-  }
+  constexpr size_t shm = (size_t)(2 * 32 * BI + 2 * 32 * WG_LDB) * 4 + 48 * 4;   // fixed per BI: the size is its own cap
+  const int rc = lds_limit<k_igemm_wgrad<BI>, shm>(shm, "csg_conv_bwd_weight");
+  if (rc) return rc;
   CSG_LAUNCH(k_igemm_wgrad<BI>, dim3((unsigned)(itiles * jtiles * nsplit)), dim3(256), shm, s, p, x, dy, out,
                      itiles, jtiles, nsplit, cps, dbp);
   return check_launch("csg_conv_bwd_weight");
@@ -924,13 +919,9 @@ static int multi_plan(const csg_conv_desc* descs, int n, IgemmMulti& mp, int64_t
 template <int BN>
 static int launch_fwd_multi(IgemmMulti& mp, int n, int max_blocks, const float* x, const float* w, const float* bias,
                             const float* res, float* y, float* ws, hipStream_t s) {
-  static bool attr_set = false;
-  size_t shm = (size_t)(2 * IG_BM * IG_LD + 2 * BN * IG_LD) * 4 + 48 * 4;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_igemm_fwd<BN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_conv_fwd_multi: hipFuncSetAttribute(%zu bytes of LDS): %s", shm, hipGetErrorString(e));
-    attr_set = true;
-  }
+  constexpr size_t shm = igemm_fwd_lds(BN);
+  const int rc = lds_limit<k_igemm_fwd<BN, true>, shm>(shm, "csg_conv_fwd_multi");
+  if (rc) return rc;
   CSG_LAUNCH((k_igemm_fwd<BN, true>), dim3((unsigned)max_blocks, (unsigned)n), dim3(256), shm, s, mp, x, w, bias, res,
                      y, ws);
   return check_launch("csg_conv_fwd_multi");

@@ -954,16 +954,24 @@ static int layout_fwd_launch(const float* vecs, const float* boxes, const uint8_
   if (pxc > OW) pxc = (int)OW;
   CSG_REQUIRE(pxc >= 1, CSG_E_UNSUPPORTED, "csg_layout_fwd: S too large for one chunk");
   size_t shm = (size_t)(LAY_OB * pxc + LAY_OB * S) * 4 + (size_t)4 * LAY_CULL * 4 + 16;
-  ProfScope p(K_LAYOUT_FWD, (double)B * OH * OW * S * 4, s);  // algorithmic bytes: the output, once
+  // LDS caps: pxc <= min(LAY_PXC, LAY_EPT * 1024 / S), so pxc + S is largest at the entry's S = 1024 (8 + 1024; 256 + 32 at the
+  // other end, and pxc + S is convex between them): 132 096 bytes of staged coverage and vectors, 136 208 / 137 232 with the lists
+  constexpr size_t stage_max = (size_t)LAY_OB * (LAY_EPT * 1024 / 1024 + 1024) * 4;
   if (masks == nullptr && (256 % qpp) == 0 && (pxc % LAY_EPT) == 0 && OH >= 32) {
     // boxes_to_layout on maps from 32 rows up: four rows per block share the staged x coverage and object vectors
     constexpr int ROWS = 4;
     const size_t shm4 = (size_t)(LAY_OB * pxc + LAY_OB * S) * 4 + (size_t)LAY_CULL * ROWS * 4 + (size_t)LAY_CULL * 4 + 16;
+    const int rc = lds_limit<k_layout_fwd_rows<ROWS>, stage_max + LAY_CULL * ROWS * 4 + LAY_CULL * 4 + 16>(shm4, "csg_layout_fwd");
+    if (rc) return rc;
+    ProfScope p(K_LAYOUT_FWD, (double)B * OH * OW * S * 4, s);  // algorithmic bytes: the output, once
     dim3 grid4((unsigned)cdiv(OW, pxc), (unsigned)cdiv(OH, ROWS), (unsigned)B);
     CSG_LAUNCH(k_layout_fwd_rows<ROWS>, grid4, dim3(256), shm4, s, vecs, boxes, valid, (int)O, (int)S, (int)H, (int)W,
                        (int)OH, (int)OW, pxc, out, (int)out_cs, (int)out_off, tail);
     return check_launch("csg_layout_fwd");
   }
+  const int rc = lds_limit<k_layout_fwd, stage_max + 4 * LAY_CULL * 4 + 16>(shm, "csg_layout_fwd");
+  if (rc) return rc;
+  ProfScope p(K_LAYOUT_FWD, (double)B * OH * OW * S * 4, s);
   dim3 grid((unsigned)cdiv(OW, pxc), (unsigned)OH, (unsigned)B);
   CSG_LAUNCH(k_layout_fwd, grid, dim3(256), shm, s, vecs, boxes, valid, masks, (int)M, (int)O, (int)S, (int)H,
                      (int)W, (int)OH, (int)OW, pxc, out, (int)out_cs, (int)out_off, tail);
@@ -1007,6 +1015,9 @@ int csg_layout_bwd_masks(const float* dout, int64_t out_cs, int64_t out_off, con
   if (O == 0) return CSG_OK;
   hipStream_t s = (hipStream_t)stream;
   const size_t shm = (size_t)(3 * (OH + OW) + S) * 4;
+  // at OH = OW = 4096, S = 1024, the limits checked above: 102 400 bytes
+  const int rc = lds_limit<k_layout_bwd_masks, (3 * (4096 + 4096) + 1024) * 4>(shm, "csg_layout_bwd_masks");
+  if (rc) return rc;
   ProfScope p(K_LAYOUT_BWD, (double)B * OH * OW * S * 4, s);
   CSG_LAUNCH(k_layout_bwd_masks, dim3((unsigned)O, (unsigned)B), dim3(256), shm, s, dout, (int)out_cs, (int)out_off, boxes,
              valid, (int)M, (int)O, (int)S, (int)H, (int)W, (int)OH, (int)OW, vecs, dmasks, accumulate);
@@ -1029,11 +1040,15 @@ int csg_layout_bwd(const float* dout, int64_t out_cs, int64_t out_off, const flo
       uint8_t* flags = (uint8_t*)workspace + B * ntiles * O * S * 4;
       const size_t shm = (size_t)LAY_BB * 256 * 16 + (size_t)LAY_BB * pxc * 4 + (size_t)LAY_CULL * ROWS * 4 +
                          (size_t)LAY_CULL * 4 + 16;
+      // at pxc = LAY_PXC: 46 096 bytes, below the 48 KB any launch may ask for
+      int rc = lds_limit<k_layout_bwd_tiles<ROWS>, LAY_BB * 256 * 16 + LAY_BB * LAY_PXC * 4 + LAY_CULL * ROWS * 4 + LAY_CULL * 4 + 16>(
+          shm, "csg_layout_bwd(tiles)");
+      if (rc) return rc;
       ProfScope p(K_LAYOUT_BWD, (double)B * OH * OW * S * 4, s);
       dim3 grid((unsigned)cdiv(OW, pxc), (unsigned)cdiv(OH, ROWS), (unsigned)B);
       CSG_LAUNCH(k_layout_bwd_tiles<ROWS>, grid, dim3(256), shm, s, dout, (int)out_cs, (int)out_off, boxes, valid,
                          (int)O, (int)S, (int)H, (int)W, (int)OH, (int)OW, pxc, partial, flags);
-      int rc = check_launch("csg_layout_bwd(tiles)");
+      rc = check_launch("csg_layout_bwd(tiles)");
       if (rc) return rc;
       CSG_LAUNCH(k_layout_bwd_gather, dim3((unsigned)O, (unsigned)B), dim3(256), 0, s, partial, flags, valid, (int)O,
                          (int)S, ntiles, dvecs, accumulate);
@@ -1055,6 +1070,9 @@ int csg_layout_bwd(const float* dout, int64_t out_cs, int64_t out_off, const flo
   CSG_REQUIRE(dboxes == nullptr || vecs != nullptr, CSG_E_BADSHAPE, "csg_layout_bwd: box gradients need vecs");
   const size_t red = (size_t)npl * S > (size_t)bd * 4 ? (size_t)npl * S : (size_t)bd * 4;
   size_t shm = (size_t)(((OH + OW + 4) + 3) & ~3) * 4 + red * 4 + (dboxes != nullptr ? (size_t)(OH + OW) * 4 : 0);
+  // at OH = OW = 4096 with box gradients; red <= 4096 floats (npl * S <= 4 * bd, bd <= 1024): 81 936 bytes
+  const int rc = lds_limit<k_layout_bwd, (8192 + 4) * 4 + 4096 * 4 + 8192 * 4>(shm, "csg_layout_bwd");
+  if (rc) return rc;
   ProfScope p(K_LAYOUT_BWD, (double)B * OH * OW * S * 4, s);
   CSG_LAUNCH(k_layout_bwd, dim3((unsigned)O, (unsigned)B), dim3((unsigned)bd), shm, s, dout, (int)out_cs, (int)out_off,
                      boxes, valid, masks, (int)M, (int)O, (int)S, (int)H, (int)W, (int)OH, (int)OW, dvecs, accumulate,

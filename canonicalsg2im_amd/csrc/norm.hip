@@ -9,12 +9,11 @@
 // discriminator.py:181-185 (InstanceNorm + LeakyReLU), generator.py:48 (nearest 2x),
 // discriminator.py:92-93 (avg_pool2d 3/2/1 without pad count).
 #include "csg_common.h"
+#include "csg_vec4.h"
 
 using namespace csg;
 
 __device__ __forceinline__ float4 f4(float v) { return make_float4(v, v, v, v); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ void st4(float* p, float4 v) { *(float4*)p = v; }
 __device__ __forceinline__ float lrelu(float v, float s) { return v > 0.f ? v : v * s; }
 __device__ __forceinline__ float lrelu_g(float pre, float s) { return pre > 0.f ? 1.f : s; }
 
@@ -541,12 +540,9 @@ __global__ void k_avgpool3s2_bwd(const float* __restrict__ dy, int H, int W, int
 }
 
 // --------------------------------------------------------------------------------- C ABI
-static inline unsigned ew_grid(int64_t n) {
-  int64_t g = cdiv(n, 256);
-  if (g > 256 * 16) g = 256 * 16;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
+// dynamic LDS of k_norm_stats_partial and k_norm_bwd_reduce: 16 KB, below the 48 KB any launch may ask for
+constexpr size_t NORM_PARTIAL_LDS = 256 * 8 * 8;
+static_assert(NORM_PARTIAL_LDS <= 48 * 1024, "above 48 KB these launches would have to go through csg::lds_limit");
 
 extern "C" {
 
@@ -558,7 +554,7 @@ int csg_norm_stats(const float* x, int64_t G, int64_t P, int64_t C, double* sums
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope p(K_NORM_STATS, (double)G * P * C * 4, s);
-    CSG_LAUNCH(k_norm_stats_partial, dim3((unsigned)nchunk, (unsigned)G), dim3(256), 256 * 8 * 8, s, x, P,
+    CSG_LAUNCH(k_norm_stats_partial, dim3((unsigned)nchunk, (unsigned)G), dim3(256), NORM_PARTIAL_LDS, s, x, P,
                        (int)C, C, (int)nchunk, partial);
   }
   CSG_LAUNCH(k_partial_reduce<double>, dim3((unsigned)cdiv(2 * C, 32), (unsigned)G), dim3(256), 0, s, partial,
@@ -579,7 +575,7 @@ int csg_norm_stats_finalize(const float* x, int64_t G, int64_t P, int64_t C, dou
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope p(K_NORM_STATS, (double)G * P * C * 4, s);
-    CSG_LAUNCH(k_norm_stats_partial, dim3((unsigned)nchunk, (unsigned)G), dim3(256), 256 * 8 * 8, s, x, P, (int)C, C,
+    CSG_LAUNCH(k_norm_stats_partial, dim3((unsigned)nchunk, (unsigned)G), dim3(256), NORM_PARTIAL_LDS, s, x, P, (int)C, C,
                (int)nchunk, partial);
   }
   ProfScope p(K_NORM_FINALIZE, (double)G * C * 24, s);
@@ -653,7 +649,7 @@ int csg_norm_apply_bwd_reduce(const float* dy, const float* x, const float* mean
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope p(K_NORM_BWD_REDUCE, (double)G * P * C * 4 * (gb ? 6 : 2), s);
-    CSG_LAUNCH(k_norm_bwd_reduce, dim3((unsigned)nchunk, (unsigned)G), dim3(256), 256 * 8 * 8, s, dy, x, mean,
+    CSG_LAUNCH(k_norm_bwd_reduce, dim3((unsigned)nchunk, (unsigned)G), dim3(256), NORM_PARTIAL_LDS, s, dy, x, mean,
                        invstd, gb, yact, slope, P, (int)C, (int)nchunk, dgb, partial, (int)gb_cs);
   }
   CSG_LAUNCH(k_partial_reduce<double>, dim3((unsigned)cdiv(2 * C, 32), (unsigned)G), dim3(256), 0, s, partial,
@@ -692,7 +688,7 @@ int csg_colsum(const float* x, int64_t rows, int64_t C, int64_t x_cs, float* out
   CSG_REQUIRE(nchunk >= 1 && nchunk <= 65535, CSG_E_BADSHAPE, "csg_colsum: bad nchunk");
   hipStream_t s = (hipStream_t)stream;
   ProfScope p(K_COLSUM, (double)rows * C * 4, s);
-  CSG_LAUNCH(k_norm_stats_partial, dim3((unsigned)nchunk, 1), dim3(256), 256 * 8 * 8, s, x, rows, (int)C, x_cs,
+  CSG_LAUNCH(k_norm_stats_partial, dim3((unsigned)nchunk, 1), dim3(256), NORM_PARTIAL_LDS, s, x, rows, (int)C, x_cs,
                      (int)nchunk, partial);
   CSG_LAUNCH(k_partial_reduce<float>, dim3((unsigned)cdiv(C, 32), 1), dim3(256), 0, s, partial, (int)(2 * C),
                      (int)nchunk, (int)C, out);

@@ -7,11 +7,9 @@
 // vgg19().features: conv3x3+ReLU blocks separated by MaxPool2d(kernel 2, stride 2)),
 // spade/models/networks/loss.py:102-117 (VGGLoss: sum_i w_i * L1Loss(x_vgg[i], y_vgg[i].detach())).
 #include "csg_common.h"
+#include "csg_vec4.h"
 
 using namespace csg;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ void st4(float* p, float4 v) { *(float4*)p = v; }
 
 // ---- MaxPool2d(2,2), floor mode: y[b,i,j,c] = max over x[b,2i+{0,1},2j+{0,1},c] ----------------
 __global__ void k_maxpool2_fwd(const float* __restrict__ x, int H, int W, int OH, int OW, int Q, int64_t n4,
@@ -118,13 +116,6 @@ __global__ void k_l1_bwd(const float* __restrict__ a, const float* __restrict__ 
     float4 u = ld4(a + e * 4), v = ld4(b + e * 4);
     st4(da + e * 4, make_float4(sg(u.x - v.x), sg(u.y - v.y), sg(u.z - v.z), sg(u.w - v.w)));
   }
-}
-
-static inline unsigned ew_grid(int64_t n) {
-  int64_t g = cdiv(n, 256);
-  if (g > 256 * 16) g = 256 * 16;
-  if (g < 1) g = 1;
-  return (unsigned)g;
 }
 
 // ---- AvgPool2d(2,2), floor mode (sg2im/layers.py:88-90, `build_cnn(pooling='avg')`): mean of the 2 x 2 window; backward

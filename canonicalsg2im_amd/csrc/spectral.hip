@@ -13,12 +13,11 @@
 // HBM bound: W is read three times forward (37.7 MB for the 1024x1024x3x3 layers) and twice backward.
 // All reductions are two-stage with a fixed combination order (bit-reproducible).
 #include "csg_common.h"
+#include "csg_vec4.h"
 
 using namespace csg;
 
 namespace {
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
 
 // block-wide sum of doubles, 1024 threads max; result valid in every thread
 __device__ double block_sum(double v, double* sm) {
@@ -338,6 +337,8 @@ int csg_spectral_norm_fwd_multi(const csg_sn_fwd_item* items, int32_t n, int32_t
       if ((unsigned)grid > g_scale) g_scale = (unsigned)grid;
       bytes += (double)a.Cout * a.K * 4 * (iterate ? 4 : 3);
     }
+    int rc = lds_limit<k_sn_scale_m, 64 * 1024>(shm, "csg_spectral_norm_fwd_multi");    // the transpose buffer's refusal above
+    if (rc) return rc;
     ProfScope p(K_SPECTRAL_FWD, bytes, s);
     if (iterate) {
       CSG_LAUNCH(k_sn_wtu_partial_m, dim3(g_part_x, g_part_y, (unsigned)cnt), dim3(256), 0, s, m);
@@ -345,7 +346,7 @@ int csg_spectral_norm_fwd_multi(const csg_sn_fwd_item* items, int32_t n, int32_t
     }
     CSG_LAUNCH(k_sn_rowdot_m, dim3(g_row, 1, (unsigned)cnt), dim3(256), 0, s, m, eps, (int)iterate);
     CSG_LAUNCH(k_sn_scale_m, dim3(g_scale, 1, (unsigned)cnt), dim3(256), shm, s, m, eps, (int)iterate);
-    const int rc = check_launch("csg_spectral_norm_fwd_multi");
+    rc = check_launch("csg_spectral_norm_fwd_multi");
     if (rc != CSG_OK) return rc;
   }
   return CSG_OK;
@@ -395,10 +396,14 @@ int csg_spectral_norm_bwd_multi(const csg_sn_bwd_item* items, int32_t n, void* s
       if ((size_t)K * sizeof(float) > shm) shm = (size_t)K * sizeof(float);
       bytes += (double)a.Cout * K * 4 * 4;
     }
+    constexpr size_t row_max = 15360 * sizeof(float);            // one row of K <= 15360 floats, refused above: 60 KB
+    int rc = lds_limit<k_sn_bwd_dot_m, row_max>(shm, "csg_spectral_norm_bwd_multi");
+    if (rc == CSG_OK) rc = lds_limit<k_sn_bwd_dw_m, row_max>(shm, "csg_spectral_norm_bwd_multi");
+    if (rc) return rc;
     ProfScope p(K_SPECTRAL_BWD, bytes, s);
     CSG_LAUNCH(k_sn_bwd_dot_m, dim3(g_row, 1, (unsigned)cnt), dim3(256), shm, s, m);
     CSG_LAUNCH(k_sn_bwd_dw_m, dim3(g_row, 1, (unsigned)cnt), dim3(256), shm, s, m);
-    const int rc = check_launch("csg_spectral_norm_bwd_multi");
+    rc = check_launch("csg_spectral_norm_bwd_multi");
     if (rc != CSG_OK) return rc;
   }
   return CSG_OK;

@@ -406,6 +406,13 @@ __global__ __launch_bounds__(256, 2) void k_wino_conv2(WinoParams p, const float
 }
 
 // ------------------------------------------------------------------------------------ host side
+// dynamic LDS of k_wino_conv2<TW, *>: the two input buffers of a TW x 32/TW tile block, or the epilogue exchange buffer
+constexpr size_t wn_conv_lds(int TW) {
+  const size_t in_bytes = (size_t)2 * ((2 * (32 / TW) + 2) * wn_row_stride(TW) + 16) * 4;   // + the dump slots of idle staging lanes
+  const size_t ep_bytes = (size_t)4 * 2 * 32 * WN_RSE * 4;
+  return in_bytes > ep_bytes ? in_bytes : ep_bytes;
+}
+
 static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const char* who) {
   CSG_REQUIRE(d != nullptr, CSG_E_BADSHAPE, "%s: null descriptor", who);
   CSG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, CSG_E_BADSHAPE, "%s: non-positive dimension", who);
@@ -434,10 +441,20 @@ static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const cha
   p.ksplit = 1;
   p.sps = p.nstage;
   p.slab = (long long)d->B * d->H * d->W * d->y_cs;
-  const size_t in_bytes = (size_t)2 * ((2 * p.TH + 2) * p.RS + 16) * 4;        // + the dump slots of idle staging lanes
-  const size_t ep_bytes = (size_t)4 * 2 * 32 * WN_RSE * 4;
-  shm = in_bytes > ep_bytes ? in_bytes : ep_bytes;
+  shm = wn_conv_lds(p.TW);
   return CSG_OK;
+}
+
+// one instantiation's launch (inside the caller's ProfScope, which also covers the slab sum of a split launch)
+template <int TW, int NTB>
+static int wn_conv_launch(const WinoParams& p, int64_t grid, const float* x, const float4* up, const float* bias,
+                          const float* residual, const float* gate, float* y, hipStream_t s) {
+  constexpr size_t shm = wn_conv_lds(TW);        // fixed per tile width: the size is its own cap
+  static_assert(shm <= 96 * 1024, "k_wino_conv2: two blocks per CU");
+  const int rc = lds_limit<k_wino_conv2<TW, NTB>, shm>(shm, "csg_wino_conv");
+  if (rc) return rc;
+  CSG_LAUNCH((k_wino_conv2<TW, NTB>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
+  return check_launch("csg_wino_conv");
 }
 
 extern "C" {
@@ -512,19 +529,6 @@ int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, c
   }
   CSG_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)packed % 16) == 0 && ((uintptr_t)y % 16) == 0, CSG_E_UNSUPPORTED,
               "csg_wino_conv: pointers must be 16-byte aligned");
-  static DeviceOnce attr_once;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (attr_once.pending(dev)) {
-    const void* fns[6] = {(const void*)k_wino_conv2<16, 2>, (const void*)k_wino_conv2<8, 2>, (const void*)k_wino_conv2<4, 2>,
-                          (const void*)k_wino_conv2<16, 1>, (const void*)k_wino_conv2<8, 1>, (const void*)k_wino_conv2<4, 1>};
-    for (const void* fn : fns) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_wino_conv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    }
-    attr_once.mark(dev);
-  }
-  CSG_REQUIRE(shm <= 96 * 1024, CSG_E_UNSUPPORTED, "csg_wino_conv: %zu bytes of LDS", shm);
   hipStream_t s = (hipStream_t)stream;
   const int64_t grid = (int64_t)p.B * p.tby * p.tbx * p.nblocks * p.ksplit;
   CSG_REQUIRE(grid < (1ll << 31), CSG_E_UNSUPPORTED, "csg_wino_conv: grid too large");
@@ -532,19 +536,12 @@ int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, c
   ProfScope ps(K_WINO_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
   const float4* up = (const float4*)packed;
   if (p.ntb == 1) {
-    if (p.TW == 16)
-      CSG_LAUNCH((k_wino_conv2<16, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-    else if (p.TW == 8)
-      CSG_LAUNCH((k_wino_conv2<8, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-    else
-      CSG_LAUNCH((k_wino_conv2<4, 1>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-  } else if (p.TW == 16)
-    CSG_LAUNCH((k_wino_conv2<16, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-  else if (p.TW == 8)
-    CSG_LAUNCH((k_wino_conv2<8, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-  else
-    CSG_LAUNCH((k_wino_conv2<4, 2>), dim3((unsigned)grid), dim3(256), shm, s, p, x, up, bias, residual, gate, y);
-  rc = check_launch("csg_wino_conv");
+    if (p.TW == 16) rc = wn_conv_launch<16, 1>(p, grid, x, up, bias, residual, gate, y, s);
+    else if (p.TW == 8) rc = wn_conv_launch<8, 1>(p, grid, x, up, bias, residual, gate, y, s);
+    else rc = wn_conv_launch<4, 1>(p, grid, x, up, bias, residual, gate, y, s);
+  } else if (p.TW == 16) rc = wn_conv_launch<16, 2>(p, grid, x, up, bias, residual, gate, y, s);
+  else if (p.TW == 8) rc = wn_conv_launch<8, 2>(p, grid, x, up, bias, residual, gate, y, s);
+  else rc = wn_conv_launch<4, 2>(p, grid, x, up, bias, residual, gate, y, s);
   if (rc == CSG_OK && p.ksplit > 1) {
     launch_slab_reduce(workspace, p.slab, y_final, nullptr, 0, nullptr, p.ksplit, s);
     rc = check_launch("csg_wino_conv(slab sum)");
@@ -851,6 +848,23 @@ static int wn_wg_plan(const csg_wino_desc* d, WinoWgParams& p, const char* who) 
   return CSG_OK;
 }
 
+// one tile shape's launch (TSX x 16/TSX tiles per region)
+template <int TSX>
+static int wn_wg_launch(const WinoWgParams& p, const float* x, const float* dy, float* slabs, float* dbslabs, hipStream_t s) {
+  constexpr int tsx = TSX, tsy = 16 / TSX;
+  // per buffer: the X patch (32 channels) padded to whole 256-lane DMAs + the dY pixels (64 channels)
+  constexpr size_t x_f4 = (size_t)(((2 * tsy + 2) * (2 * tsx + 2) * 8 + 255) / 256) * 256;
+  constexpr size_t stage_bytes = 2 * (x_f4 * 16 + (size_t)(2 * tsy) * (2 * tsx) * 64 * 4);
+  constexpr size_t ep_bytes = (size_t)4 * 3 * 32 * WG_EPS * 4;
+  constexpr size_t shm = stage_bytes > ep_bytes ? stage_bytes : ep_bytes;      // fixed per tile shape: its own cap
+  const int rc = lds_limit<k_wino_wgrad<TSX, 1>, shm>(shm, "csg_wino_bwd_weight");
+  if (rc) return rc;
+  ProfScope ps(K_WINO_WGRAD, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
+  CSG_LAUNCH((k_wino_wgrad<TSX, 1>), dim3((unsigned)(p.cblocks * p.kblocks * p.nsplit)), dim3(256), shm, s, p, x, dy, slabs,
+             dbslabs);
+  return check_launch("csg_wino_bwd_weight");
+}
+
 extern "C" {
 
 int64_t csg_wino_bwd_weight_workspace(const csg_wino_desc* d) {
@@ -868,42 +882,17 @@ int csg_wino_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy,
   const int64_t need = (int64_t)p.nsplit * (wsize + d->Cout) * 4;
   CSG_REQUIRE(workspace != nullptr && workspace_bytes >= need, CSG_E_WORKSPACE, "csg_wino_bwd_weight: workspace %ld < %ld bytes",
               (long)workspace_bytes, (long)need);
-  static DeviceOnce attr_once;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const int tsx = wn_wg_tsx(d->W), tsy = 16 / tsx;
-  // per buffer: the X patch (32 channels) padded to whole 256-lane DMAs + the dY pixels (64 channels)
-  const size_t x_f4 = (size_t)(((2 * tsy + 2) * (2 * tsx + 2) * 8 + 255) / 256) * 256;
-  const size_t stage_bytes = 2 * (x_f4 * 16 + (size_t)(2 * tsy) * (2 * tsx) * 64 * 4);
-  const size_t ep_bytes = (size_t)4 * 3 * 32 * WG_EPS * 4;
-  const size_t shm = stage_bytes > ep_bytes ? stage_bytes : ep_bytes;
-  if (attr_once.pending(dev)) {
-    const void* fns[3] = {(const void*)k_wino_wgrad<16, 1>, (const void*)k_wino_wgrad<8, 1>, (const void*)k_wino_wgrad<4, 1>};
-    for (const void* fn : fns) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "csg_wino_bwd_weight: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    }
-    attr_once.mark(dev);
-  }
-  CSG_REQUIRE(shm <= 128 * 1024, CSG_E_UNSUPPORTED, "csg_wino_bwd_weight: %zu bytes of LDS", shm);
+  const int tsx = wn_wg_tsx(d->W);
   hipStream_t s = (hipStream_t)stream;
   float* dbslabs = db != nullptr ? workspace + (int64_t)p.nsplit * wsize : nullptr;
   if (p.nsplit == 1) {          // a single slice: the block results ARE the gradient
     workspace = dw;
     dbslabs = db;
   }
-  {
-    ProfScope ps(K_WINO_WGRAD, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
-    const dim3 grid((unsigned)(p.cblocks * p.kblocks * p.nsplit));
-    if (tsx == 16)
-      CSG_LAUNCH((k_wino_wgrad<16, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-    else if (tsx == 8)
-      CSG_LAUNCH((k_wino_wgrad<8, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-    else
-      CSG_LAUNCH((k_wino_wgrad<4, 1>), grid, dim3(256), shm, s, p, x, dy, workspace, dbslabs);
-    rc = check_launch("csg_wino_bwd_weight");
-    if (rc) return rc;
-  }
+  if (tsx == 16) rc = wn_wg_launch<16>(p, x, dy, workspace, dbslabs, s);
+  else if (tsx == 8) rc = wn_wg_launch<8>(p, x, dy, workspace, dbslabs, s);
+  else rc = wn_wg_launch<4>(p, x, dy, workspace, dbslabs, s);
+  if (rc) return rc;
   if (p.nsplit > 1) {
     ProfScope ps(K_WGRAD_REDUCE, (double)(p.nsplit + 1) * wsize * 4, s);
     launch_slab_reduce(workspace, wsize, dw, dbslabs, db != nullptr ? d->Cout : 0, db, p.nsplit, s);

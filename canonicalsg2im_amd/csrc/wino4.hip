@@ -927,6 +927,10 @@ __global__ __launch_bounds__(W4_THREADS, 3) void k_wino4_conv_v(Wino4Params p, c
 }
 
 // ------------------------------------------------------------------------------------ host side
+// dynamic LDS of k_wino4_conv_v<T, false>, fixed per tile size: the buffers up to OFFTAB + one offset table
+template <int T>
+constexpr size_t w4_lds = (size_t)(W4Geo<T>::OFFTAB + W4_THREADS * 4) * 4;
+
 // T = 4: F(4x4,3x3), pad 1, output = input size.  T = 3: F(3x3,4x4), pad 1 or 2, output = input + 2 pad - 3.
 static int w4_plan(const csg_wino_desc* d, int T, int pad, Wino4Params& p, size_t& shm, const char* who) {
   CSG_REQUIRE(d != nullptr, CSG_E_BADSHAPE, "%s: null descriptor", who);
@@ -959,22 +963,7 @@ static int w4_plan(const csg_wino_desc* d, int T, int pad, Wino4Params& p, size_
   p.sps = p.nstage;
   p.slab = (long long)d->B * Ho * Wo * d->y_cs;
   p.nitems = 0;
-  shm = (size_t)((T == 4 ? W4Geo<4>::OFFTAB : W4Geo<3>::OFFTAB) + W4_THREADS * 4) * 4;
-  return CSG_OK;
-}
-
-// the launch shared by both tile sizes
-template <int T, bool P>
-static int w4_set_lds_limit(const char* who) {
-  static DeviceOnce attr_once;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (attr_once.pending(dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_wino4_conv_v<T, P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (P ? 160 : 128) * 1024);
-    CSG_REQUIRE(e == hipSuccess, CSG_E_LAUNCH, "%s: cannot raise the dynamic LDS limit: %s", who, hipGetErrorString(e));
-    attr_once.mark(dev);
-  }
+  shm = T == 4 ? w4_lds<4> : w4_lds<3>;
   return CSG_OK;
 }
 
@@ -1007,12 +996,14 @@ template <int T>
 static int w4_launch(Wino4Params& p, size_t shm, int kid, double flops, const float* x, const float* packed,
                      const float* bias, const float* residual, const float* gate, float* y, float* workspace,
                      float* y_final, hipStream_t s, const char* who) {
-  CSG_REQUIRE(shm <= 128 * 1024, CSG_E_UNSUPPORTED, "%s: %zu bytes of LDS", who, shm);
   const int64_t grid = (int64_t)p.B * p.tby * p.tbx * p.nblocks * p.ksplit;
   CSG_REQUIRE(grid < (1ll << 31), CSG_E_UNSUPPORTED, "%s: grid too large", who);
   p.nitems = (int)grid;
   const int pblocks = T == 4 ? w4_persistent_blocks(p, grid) : 0;
-  int rc = pblocks ? w4_set_lds_limit<4, true>(who) : w4_set_lds_limit<T, false>(who);
+  // the sizes are fixed per T, so each is its own cap; the persistent form adds a second offset table (12 KB)
+  static_assert(w4_lds<T> <= 128 * 1024, "k_wino4_conv_v: one block per CU with room for the persistent form's table");
+  int rc = pblocks ? lds_limit<k_wino4_conv_v<4, true>, w4_lds<4> + W4_THREADS * 16>(shm + W4_THREADS * 16, who)
+                   : lds_limit<k_wino4_conv_v<T, false>, w4_lds<T>>(shm, who);
   if (rc) return rc;
   ProfScope ps(kid, flops, s);
   if (pblocks)

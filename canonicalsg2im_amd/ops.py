@@ -105,30 +105,25 @@ def _descs_backward_data(B, IH, IW, Cin, Cout, KH, KW, stride, pad, OH, OW):
 
 
 def _conv_launch(d, x, w, bias, res, y, what):
-    """csg_conv_fwd with the split-K slabs it asks for."""
+    """csg_conv_fwd with the split-K slabs it asks for.  y: the output tensor, or a raw pointer into it (a channel slice)."""
     nbytes = lib.csg_conv_fwd_workspace(d)
     if nbytes < 0:
         raise RuntimeError("conv_fwd_workspace: " + _lib.last_error())
-    ws = torch.empty(nbytes // 4, device=y.device, dtype=torch.float32) if nbytes > 0 else None
-    check(lib.csg_conv_fwd(d, ptr(x), ptr(w), ptr(bias), ptr(res), ptr(y), ptr(ws), nbytes, stream()), what)
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes > 0 else None
+    y_ptr = y if isinstance(y, ctypes.c_void_p) else ptr(y)
+    check(lib.csg_conv_fwd(d, ptr(x), ptr(w), ptr(bias), ptr(res), y_ptr, ptr(ws), nbytes, stream()), what)
 
 
-def _conv_launch_classes(descs, x, w, y_ptr, dev, what):
+def _conv_launch_classes(descs, x, w, y_ptr, what):
     """The parity-class descriptors of a strided backward-data pass (same weights, input and output tensor): one
     launch for all of them (csg_conv_fwd_multi) — each class alone is a quarter of the pixels and cannot fill the chip."""
     if len(descs) == 1:
-        d = descs[0]
-        nbytes = lib.csg_conv_fwd_workspace(d)
-        if nbytes < 0:
-            raise RuntimeError("conv_fwd_workspace: " + _lib.last_error())
-        ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32) if nbytes > 0 else None
-        check(lib.csg_conv_fwd(d, ptr(x), ptr(w), None, None, y_ptr, ptr(ws), nbytes, stream()), what)
-        return
+        return _conv_launch(descs[0], x, w, None, None, y_ptr, what)
     arr = (ConvDesc * len(descs))(*descs)
     nbytes = lib.csg_conv_fwd_multi_workspace(arr, len(descs))
     if nbytes < 0:
         raise RuntimeError("conv_fwd_multi_workspace: " + _lib.last_error())
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32) if nbytes > 0 else None
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes > 0 else None
     check(lib.csg_conv_fwd_multi(arr, len(descs), ptr(x), ptr(w), None, None, y_ptr, ptr(ws), nbytes, stream()), what)
 
 
@@ -653,7 +648,7 @@ def _conv_bwd(plan, dy, x, w, y, need, packs, ut_pre):
         descs = _descs_backward_data(B, IH, IW, hi - lo, Cout, KH, KW, stride, pad, OH, OW)
         for d in descs:
             d.y_cs = Cin
-        _conv_launch_classes(descs, dpre, wt, ctypes_ptr_off(dx, lo), dev, "conv_bwd_data")
+        _conv_launch_classes(descs, dpre, wt, ctypes_ptr_off(dx, lo), "conv_bwd_data")
     elif fam == "wino":
         # dX = conv3x3(dY, flipped W^T): the same Winograd kernel with the roles of the channel counts swapped
         var = plan.dx_var
@@ -696,7 +691,7 @@ def _conv_bwd(plan, dy, x, w, y, need, packs, ut_pre):
             _conv_launch(d, dpre, wt, None, x, dx, "conv_bwd_data")
             gated = True
         else:
-            _conv_launch_classes(descs, dpre, wt, ptr(dx), dev, "conv_bwd_data")
+            _conv_launch_classes(descs, dpre, wt, ptr(dx), "conv_bwd_data")
     if dx is not None and not gated:              # the producer's activation derivative as a separate pass
         check(lib.csg_act_bwd(ptr(dx), ptr(x), dx.numel(), in_act[0], in_act[1], ptr(dx), stream()), "act_bwd")
     want_db = plan.has_bias and need[2]
@@ -2492,12 +2487,7 @@ def conv2d_forward(x, wp, bias, KH, KW, stride=1, padding=(0, 0), act=ACT_NONE, 
     for first in range(0, taps, _lib.MAX_TAPS):
         d, _, _ = conv2d_taps_desc(B, IH, IW, Cin, Cout, KH, KW, stride, pad_h, pad_w, first, min(_lib.MAX_TAPS, taps - first),
                                    act if single else ACT_NONE, slope if single else 0.0, y_cs, 1 if first else 0)
-        nbytes = lib.csg_conv_fwd_workspace(d)
-        if nbytes < 0:
-            raise RuntimeError("conv_fwd_workspace: " + _lib.last_error())
-        ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes > 0 else None
-        check(lib.csg_conv_fwd(d, ptr(x), ptr(wp), ptr(bias) if single else None, None, yp, ptr(ws), nbytes, stream()),
-              "conv2d_forward")
+        _conv_launch(d, x, wp, bias if single else None, None, yp, "conv2d_forward")
     if not single and (bias is not None or act != ACT_NONE):
         check(lib.csg_bias_act(yp, B * OH * OW, Cout, y_cs, 0, ptr(bias), act, slope, stream()), "bias_act")
     return y if out is None else out

@@ -73,6 +73,59 @@ def test_library_reads_only_the_family_switches_from_the_environment():
                 assert not retired.search(open(os.path.join(dirpath, f), errors="replace").read()), os.path.join(dirpath, f)
 
 
+def _call_args(text, start):
+    """The top-level arguments of the call whose opening parenthesis is at text[start]."""
+    args, depth, cur = [], 0, ""
+    for ch in text[start:]:
+        if ch == "(":
+            depth += 1
+            if depth == 1:
+                continue
+        elif ch == ")":
+            depth -= 1
+            if depth == 0:
+                return args + [cur.strip()]
+        if ch == "," and depth == 1:
+            args.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    raise AssertionError("unbalanced call")
+
+
+def test_dynamic_lds_limits_are_raised_in_one_place():
+    """Above 48 KB of dynamic LDS a kernel's limit has to be raised before the launch: csg::lds_limit (csg_common.h) is the
+    one place that does it, per kernel and device, checked.  A file that launches with dynamic LDS and never calls it
+    says so here, with the arithmetic beside its launches — a new kernel file has to decide on purpose."""
+    csrc = os.path.join(ROOT, "canonicalsg2im_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert len(text) >= 30
+    assert [f for f, t in text.items() if "hipFuncSetAttribute" in t] == ["csg_common.h"]
+    assert [f for f, t in text.items() if "attr_set" in t] == []
+    never_above_48k = {"gemm.hip",       # 32 KB, and exactly 48 KB for the 64-wide tile
+                       "norm.hip"}       # 16 KB
+    launches = 0
+    for f, t in text.items():
+        # a macro that hands its arguments on to CSG_LAUNCH (FEW_DISPATCH) is a launch too: same argument positions
+        macros = ["CSG_LAUNCH"] + re.findall(r"#define (\w+)\(KERNEL, \.\.\.\)", t)
+        dynamic = []
+        for m in re.finditer(r"\b(%s)\(" % "|".join(macros), t):
+            if t[:m.start()].endswith("#define "):
+                continue
+            args = _call_args(t, m.end() - 1)
+            if "__VA_ARGS__" in args:
+                continue                                       # inside such a macro's body: its uses are checked
+            assert len(args) >= 6, (f, args)
+            launches += 1
+            if args[3] != "0":
+                dynamic.append(args[3])
+        if dynamic and "lds_limit<" not in t:
+            assert f in never_above_48k, (f, dynamic)
+        else:
+            assert f not in never_above_48k, f
+    assert launches >= 100, launches
+
+
 def test_conv_descriptor_struct_matches_header(built):
     import ctypes
     hdr = open(os.path.join(ROOT, "include", "csg_hip.h")).read()
