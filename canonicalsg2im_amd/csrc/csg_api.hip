@@ -129,13 +129,13 @@ static const char* kNames[K_COUNT] = {
     "norm_eval_stats", "deprocess_u8", "box_iou", "preprocess", "clevr_boxes", "vg_rows", "draw_boxes_u8",
     "canon_small_build", "canon_small_emit", "clevr_graph_count", "clevr_graph_emit", "coco_masks",
     "resize_bilinear", "pool3", "spatial_mean", "bias_act", "feat_stats", "inception_score",
-    "draw_labels_u8"};
+    "draw_labels_u8", "draw_graph_u8"};
 
 }  // namespace csg
 
 extern "C" {
 
-int csg_version(void) { return 121; }
+int csg_version(void) { return 122; }
 const char* csg_last_error(void) { return csg::g_err; }
 
 int csg_prof_enable(int on) {

@@ -80,6 +80,7 @@ enum KernelId {
   K_FEAT_STATS,
   K_INCEPTION_SCORE,
   K_DRAW_LABELS,
+  K_DRAW_GRAPH,
   K_COUNT
 };
 

@@ -1566,6 +1566,133 @@ def draw_labels_u8(img, boxes, objs, image_id, palette, labels, font=None):
     return out
 
 
+GRAPH_SEGMENT, GRAPH_TRIANGLE, GRAPH_NODE = 0, 1, 2      # the record kinds of csg_draw_graph_u8 (include/csg_hip.h)
+GRAPH_MAX_PRIMS = 4096            # records per picture
+GRAPH_MAX_COORD = 4096            # |coordinate|: with canvases of at most 2048 it keeps 4 cross^2 of the segment rule in int64
+
+
+def _rgb(colour):
+    """(r, g, b) or an already packed integer -> r | g << 8 | b << 16."""
+    if isinstance(colour, int):
+        return colour & 0xffffff
+    r, g, b = (int(v) for v in colour)
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError("draw_graph_u8: a colour is three bytes, got %r" % (colour,))
+    return r | g << 8 | b << 16
+
+
+def _graph_record(kind, param, ink, geometry, colour):
+    w0 = kind | int(param) << 4 | _rgb(ink) << 8
+    return [w0 - (1 << 32) if w0 >= 1 << 31 else w0] + [int(v) for v in geometry] + [_rgb(colour)]
+
+
+def graph_segment(ax, ay, bx, by, colour, t=1):
+    """One csg_draw_graph_u8 record, eight int32 words: the segment A -> B, `t` pixels thick."""
+    return _graph_record(GRAPH_SEGMENT, t, 0, (ax, ay, bx, by, 0, 0), colour)
+
+
+def graph_triangle(x0, y0, x1, y1, x2, y2, colour):
+    """One csg_draw_graph_u8 record: the filled triangle V0 V1 V2, either winding, border included."""
+    return _graph_record(GRAPH_TRIANGLE, 0, 0, (x0, y0, x1, y1, x2, y2), colour)
+
+
+def graph_node(x0, y0, x1, y1, fill, ink, r, text_off, n):
+    """One csg_draw_graph_u8 record: the inclusive rectangle [x0, x1] x [y0, y1] with corner radius `r`, filled with `fill`,
+    carrying the `n` label bytes from `text_off` on in `ink`."""
+    return _graph_record(GRAPH_NODE, r, ink, (x0, y0, x1, y1, text_off, n), fill)
+
+
+def check_graph_records(primitives, prim_off, text_bytes):
+    """The host refusals of `draw_graph_u8`, before any device is touched: -> (records int32 (N,8), offsets int32 (B+1,))
+    as CPU tensors, or ValueError naming the picture and the figure that is out of range."""
+    rec = torch.as_tensor(primitives, dtype=torch.int64).reshape(-1, 8) if len(primitives) else torch.zeros((0, 8), dtype=torch.int64)
+    off = torch.as_tensor(prim_off, dtype=torch.int64).reshape(-1)
+    N = rec.shape[0]
+    if off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != N or bool((off[1:] < off[:-1]).any()):
+        raise ValueError("draw_graph_u8: prim_off must be B + 1 ascending offsets from 0 to the %d records, got %s" % (
+            N, off.tolist()[:8]))
+    if bool((rec.abs() >= 1 << 31).any()):
+        raise ValueError("draw_graph_u8: a record word does not fit int32")
+    counts = off[1:] - off[:-1]
+    if int(counts.max()) > GRAPH_MAX_PRIMS:
+        b = int(counts.argmax())
+        raise ValueError("draw_graph_u8: picture %d has %d primitives, at most %d" % (b, int(counts[b]), GRAPH_MAX_PRIMS))
+    picture = torch.repeat_interleave(torch.arange(counts.numel()), counts)
+
+    def refuse(bad, what):
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError("draw_graph_u8: picture %d, primitive %d: %s (record %s)" % (
+                int(picture[i]), i - int(off[picture[i]]), what, rec[i].tolist()))
+
+    kind, param = rec[:, 0] & 15, (rec[:, 0] >> 4) & 15
+    refuse(kind > GRAPH_NODE, "unknown kind")
+    words = torch.where(kind == GRAPH_TRIANGLE, 6, 4)              # how many of w1 .. w6 are coordinates
+    coord = rec[:, 1:7] * (torch.arange(6)[None, :] < words[:, None])
+    refuse((coord.abs() > GRAPH_MAX_COORD).any(1), "a coordinate outside [-%d, %d]" % (GRAPH_MAX_COORD, GRAPH_MAX_COORD))
+    refuse((kind == GRAPH_SEGMENT) & ((param < 1) | (param > 8)), "thickness t outside 1 .. 8")
+    refuse((kind == GRAPH_NODE) & (param > 8), "corner radius r outside 0 .. 8")
+    refuse((kind == GRAPH_NODE) & ((rec[:, 5] < 0) | (rec[:, 6] < 0) | (rec[:, 5] + rec[:, 6] > text_bytes)),
+           "label range outside the %d bytes of text" % text_bytes)
+    return rec.to(torch.int32), off.to(torch.int32)
+
+
+def draw_graph_u8(primitives, prim_off, text, H, W, background, font=None, out=None, device=None):
+    """Pictures of scene graphs (csg_draw_graph_u8; record and pixel rule: include/csg_hip.h): B blank canvases
+    painted from per-picture lists of segments, triangles and labelled nodes; the highest record covering a pixel decides
+    it.  primitives: N records of eight integers on the host (`graph_segment`, `graph_triangle`, `graph_node`: a list, an
+    array or a CPU tensor); prim_off: B + 1 ascending offsets, picture b owns [prim_off[b], prim_off[b+1]); text: the
+    nodes' label bytes; background: (r, g, b).  Refused here with ValueError, before any device is touched: more than
+    4096 primitives in a picture, a coordinate outside [-4096, 4096] (the bound that keeps the segment rule inside int64),
+    t outside 1 .. 8, r outside 0 .. 8, a label range outside `text`.  Offsets, records and text are packed into one host
+    buffer: one copy, one launch.  font: a uint8 (95, 7) device tensor, by default font5x7.FONT, uploaded once per device
+    and kept (the cache of `draw_labels_u8`).  out: a uint8 (B,3,H,W) device tensor to paint, by default a new one on
+    `device` (default: the current HIP device).  Every byte of it is written.  Nothing read back.  No autograd."""
+    text = bytes(text)
+    rec, off = check_graph_records(primitives, prim_off, len(text))
+    B, H, W = off.numel() - 1, int(H), int(W)
+    background = _rgb(background)
+    if font is not None and (font.dtype != torch.uint8 or tuple(font.shape) != (95, 7)):
+        raise RuntimeError("draw_graph_u8: font must be uint8 (95, 7), got %s %s" % (font.dtype, tuple(font.shape)))
+    if out is not None:
+        if out.dtype != torch.uint8 or tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous():
+            raise RuntimeError("draw_graph_u8: out must be a contiguous uint8 %s, got %s %s" % (
+                (B, 3, H, W), out.dtype, tuple(out.shape)))
+        device = out.device
+    elif device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("canonicalsg2im_amd ops need HIP (cuda) tensors; there is no CPU path")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("canonicalsg2im_amd ops need HIP (cuda) tensors; there is no CPU path")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if font is None:
+        font = _FONTS.get(device)
+        if font is None:
+            from .font5x7 import FONT
+            font = _FONTS[device] = torch.from_numpy(FONT.copy()).to(device)
+    font = font.contiguous()
+    # [offsets, padded to 16 bytes][records, 32 bytes each][text and four bytes, so that an empty text has an address]
+    head = (off.numel() * 4 + 15) // 16 * 16
+    packed = torch.zeros(head + rec.numel() * 4 + len(text) + 4, dtype=torch.uint8)
+    packed[:off.numel() * 4] = off.view(torch.uint8)
+    packed[head:head + rec.numel() * 4] = rec.contiguous().view(torch.uint8).reshape(-1)
+    if text:
+        packed[head + rec.numel() * 4:-4] = torch.frombuffer(bytearray(text), dtype=torch.uint8)
+    packed = packed.to(device, non_blocking=True)
+    if out is None:
+        if not (1 <= H <= 2048 and 1 <= W <= 2048):      # the entry point refuses it too: here before the allocation
+            raise RuntimeError("draw_graph_u8: H and W must lie in [1, 2048], got %d %d" % (H, W))
+        out = torch.empty((B, 3, H, W), device=device, dtype=torch.uint8)
+    with torch.cuda.device(device):
+        check(lib.csg_draw_graph_u8(ctypes_ptr_off(packed, head), rec.shape[0], ptr(packed),
+                                    ctypes_ptr_off(packed, head + rec.numel() * 4), len(text), ptr(font), B, H, W, background,
+                                    ptr(out), stream()), "draw_graph_u8")
+    return out
+
+
 def preprocess_images(src_u8, desc, H, W, normalize=True, want_u8=False, desc_host=None, out=None, out_u8=None,
                       workspace=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """The loader's per-sample transform (sg2im/data/packed_coco.py:269-272: T.Resize, T.ToTensor, T.Normalize) for a batch

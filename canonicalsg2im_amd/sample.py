@@ -263,7 +263,7 @@ class Sampler:
                                       uint8, rescale, deprocess)
         return (u8 if uint8 else img), boxes_pred, masks_pred
 
-    def generate_from_graphs(self, graphs, overlay=False, thickness=2, palette=None, labels=False):
+    def generate_from_graphs(self, graphs, overlay=False, thickness=2, palette=None, labels=False, return_graph=False):
         """Authored scene graphs (authored.py: a list of graphs or the path of a JSON file) -> (images uint8 (B,3,H,W),
         boxes_pred (B,O,4), overlays uint8 (B,3,H,W) or None).  The graphs are encoded and checked on the host, uploaded
         once, and made canonical without boxes (`canonical_triplets(boxes=None)`: the authored rows are the location
@@ -272,7 +272,9 @@ class Sampler:
         from `generate` on the predicted boxes, under its replay keys.  `overlay`: the pictures with the outlines of the
         predicted boxes, `thickness` pixels wide, row o in palette[o % P] — `palette` a sequence of RGB
         triples, by default authored.DEFAULT_PALETTE.  `labels` (needs `overlay`): the objects' names on the overlays as
-        well (`ops.draw_labels_u8` on the outlined pictures, names by `authored.object_labels`)."""
+        well (`ops.draw_labels_u8` on the outlined pictures, names by `authored.object_labels`).  `return_graph`: a fourth
+        element (triplets (B,T,3), triplet_type (B,T)), the device tensors of the canonical graph the model was given —
+        what `sgdraw.draw_scene_graphs` draws; the converse draws cannot be repeated afterwards."""
         from . import authored
         from .sg2im.data import canonical_triplets
         if labels and not overlay:
@@ -301,4 +303,6 @@ class Sampler:
             if labels:
                 overlays = ops.draw_labels_u8(overlays, boxes_pred.detach().float(), objs, image_id, pal,
                                               authored.object_labels(graphs))
+        if return_graph:
+            return imgs, boxes_pred, overlays, (triplets, triplet_type)
         return imgs, boxes_pred, overlays

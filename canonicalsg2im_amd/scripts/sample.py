@@ -15,13 +15,19 @@ model; on top of them:
     --scene_graphs FILE      authored scene graphs (JSON), drawn in batches of --batch_size; the vocabulary is the one the
                              checkpoint carries, --num_samples is ignored.  Writes img_%06d_generated.png, with
                              --draw_boxes 1 (the default) img_%06d_layout.png — the picture with the outlines of the
-                             predicted boxes — and graphs.json, the encoded triplets with their predicates' names (in
-                             place of the reference's GraphViz picture)
+                             predicted boxes — and graphs.json, the encoded triplets with their predicates' names (the
+                             graph as a picture: --draw_scene_graphs)
     --draw_labels 0|1        with --draw_boxes 1 (refused without): the objects' names on the layout pictures, a coloured
                              strip with the name across the top of each box as the reference's sg2im/vis.py draws it
                              (default 0).  --scene_graphs: on img_%06d_layout.png; --split: on layout/gt/ and
                              layout/pred/; --layouts: writes layout/<which>/<image id>.<ext> besides, the picture under
                              its boxes' outlines and names
+    --draw_scene_graphs 0|1|2  with --scene_graphs (refused without; for --split and --layouts it is out of scope): the
+                             picture of each graph itself as img_%06d_sg.png, at the graph's own size — objects and
+                             predicates as nodes, two arrows per triplet (canonicalsg2im_amd/sgdraw.py; the reference's
+                             flag, drawn there by GraphViz).  0 (default): none.  1: the host-encoded graph, what
+                             graphs.json lists.  2: the canonical graph the model was given, with transitive and converse
+                             edges in colours of their own; one read-back of the triplets per batch
     --split train|val        the split's folder (the paths of scripts/train.py; --num_train_samples / --num_val_samples cap
                              it, --coco_val_ids narrows coco's val) in file order, batches of --batch_size decoded in
                              --loader_num_workers threads.  Needs --checkpoint_name; the folder's vocabulary is held to the
@@ -62,6 +68,9 @@ def build_parser():
     p.add_argument('--scene_graphs', default=None, type=str)
     p.add_argument('--draw_boxes', default=1, type=int)
     p.add_argument('--draw_labels', default=0, type=int)
+    p.add_argument('--draw_scene_graphs', default=0, type=int, choices=[0, 1, 2],
+                   help="with --scene_graphs: img_%%06d_sg.png, the picture of each graph (1: as encoded on the host, 2: the "
+                        "canonical graph with edge types coloured); not available with --split or --layouts")
     p.add_argument('--split', default=None, choices=["train", "val"])
     p.add_argument('--max_pictures', default=0, type=int)
     p.add_argument('--image_format', default="png", choices=["png", "jpg"])
@@ -80,6 +89,9 @@ def parse_args(argv=None):
     if args.draw_labels and not args.draw_boxes:
         raise SystemExit("--draw_labels 1 needs --draw_boxes 1: the names go on the layout pictures, which --draw_boxes 0 "
                          "leaves out")
+    if args.draw_scene_graphs and args.scene_graphs is None:
+        raise SystemExit("--draw_scene_graphs %d needs --scene_graphs: only authored graphs get a picture of the graph "
+                         "(--split and --layouts are out of its scope)" % args.draw_scene_graphs)
     if args.scene_graphs is not None and not os.path.isfile(args.scene_graphs):
         raise SystemExit("--scene_graphs %s: no such file" % args.scene_graphs)
     given = [flag for flag, v in (("--split", args.split), ("--layouts", args.layouts), ("--scene_graphs", args.scene_graphs))
@@ -213,7 +225,15 @@ def sample_scene_graphs(args, dev):
     tic = time.time()
     for first in range(0, len(graphs), args.batch_size):
         chunk = graphs[first:first + args.batch_size]
-        imgs, _, overlays = sampler.generate_from_graphs(chunk, overlay=bool(args.draw_boxes), labels=bool(args.draw_labels))
+        drawn = sampler.generate_from_graphs(chunk, overlay=bool(args.draw_boxes), labels=bool(args.draw_labels),
+                                             **({"return_graph": True} if args.draw_scene_graphs == 2 else {}))
+        imgs, _, overlays = drawn[:3]
+        if Image is not None and args.draw_scene_graphs:
+            from .. import sgdraw
+            canvas, sizes = sgdraw.draw_canvas(chunk, args.vocab, dev, *(drawn[3] if args.draw_scene_graphs == 2 else ()))
+            host = canvas.permute(0, 2, 3, 1).contiguous().cpu().numpy()
+            for i, (w, h) in enumerate(sizes):
+                Image.fromarray(host[i, :h, :w]).save(os.path.join(args.output_dir, "img_%06d_sg.png" % (first + i)))
         if Image is not None:
             kinds = [("generated", imgs)] + ([("layout", overlays)] if overlays is not None else [])
             for kind, t in kinds:

@@ -56,7 +56,8 @@ extern "C" {
  * 119: csg_coco_masks;
  * 120: csg_resize_bilinear, csg_pool3, csg_spatial_mean, csg_bias_act, csg_feat_stats, csg_feat_stats_finalize,
  *      csg_softmax_rows, csg_inception_score_workspace, csg_inception_score;
- * 121: csg_draw_labels_u8) */
+ * 121: csg_draw_labels_u8;
+ * 122: csg_draw_graph_u8) */
 int csg_version(void);
 const char* csg_last_error(void);
 
@@ -540,6 +541,44 @@ int csg_draw_boxes_u8(const uint8_t* img, const float* boxes, const int64_t* obj
 int csg_draw_labels_u8(const uint8_t* img, const float* boxes, const int64_t* objs, int64_t B, int64_t O, int64_t A,
                        int64_t H, int64_t W, int64_t image_id, const uint8_t* palette, int64_t P, const uint8_t* text,
                        const int32_t* text_off, const uint8_t* font, uint8_t* out, void* stream);
+
+/* ---- scene-graph pictures: segments, arrowheads and labelled nodes on a blank canvas (csrc/overlay.hip) --------
+ * The picture of the graph itself that scripts/run_model.py writes beside each generated one (img_%06d_sg.png, there by
+ * GraphViz through sg2im/vis.py:draw_scene_graph): here the caller lays the graph out (canonicalsg2im_amd/sgdraw.py) and
+ * this entry point paints B canvases, out (B,3,H,W) uint8 planar, from per-picture lists of primitives.  There is no input
+ * picture: every byte of out is written.  All geometry is integer and exact; the kernel uses no floating point.
+ *   prims     int32 (n_prims, 8), 16-byte aligned: one record per primitive, see below;
+ *   prim_off  int32, B + 1 ascending offsets, prim_off[0] == 0: picture b owns the records [prim_off[b], prim_off[b+1]);
+ *   text      uint8 (text_bytes): the nodes' labels; font: uint8 (95, 7) as for csg_draw_labels_u8;
+ *   background, and every colour of a record: r | g << 8 | b << 16.                         All device memory.
+ * RECORD, words w0 .. w7:  w0 = kind | param << 4 | ink << 8,  w1 .. w6 geometry,  w7 = colour.
+ *   kind 0, SEGMENT:  w1 .. w4 = ax, ay, bx, by; param = thickness t in 1 .. 8.  With d = B - A, v = p - A, L2 = d.d,
+ *     dot = v.d, cross = vx dy - vy dx, the pixel p = (x, y) is covered when
+ *       L2 == 0 or dot <= 0:  4 |p - A|^2 <= t^2;      dot >= L2:  4 |p - B|^2 <= t^2;      otherwise:  4 cross^2 <= t^2 L2.
+ *   kind 1, TRIANGLE: w1 .. w6 = x0, y0, x1, y1, x2, y2.  With area2 = cross(V1 - V0, V2 - V0) and the edge functions
+ *     e0 = cross(V1 - V0, p - V0), e1 = cross(V2 - V1, p - V1), e2 = cross(V0 - V2, p - V2): covered when area2 != 0 and
+ *     (all e_i >= 0 or all e_i <= 0) - both windings, the border included; a degenerate triangle covers nothing.
+ *   kind 2, NODE:     w1 .. w4 = x0, y0, x1, y1, the inclusive rectangle; w5 = the label's first byte in text, w6 = its
+ *     bytes n; param = corner radius r in 0 .. 8; colour = fill, ink = the label's colour.  With re = min(r, (x1 - x0) / 2,
+ *     (y1 - y0) / 2) in integer division, a pixel of the rectangle is covered unless it lies in a corner square and
+ *     outside the corner circle (top left: x < x0 + re, y < y0 + re and (x0+re-x)^2 + (y0+re-y)^2 > re^2; the others
+ *     mirrored).  A covered pixel is INK when, with tw = 6 n - 1, tx = x0 + max(0, (x1-x0+1 - tw) / 2) and
+ *     ty = y0 + max(0, (y1-y0+1 - 7) / 2):  c = x - tx lies in [0, tw), l = y - ty in [0, 7), c % 6 < 5 and bit 4 - c % 6
+ *     of font[g][l] is set, g being csg_draw_labels_u8's glyph of the label's byte c / 6 (bytes outside [32, 126]: '?').
+ *     Text wider or taller than the node is cut at the node's border.
+ * Among a picture's records that cover a pixel the one with the HIGHEST index decides: the pixel takes its ink colour
+ * where it is label ink, else its colour; no blending.  A pixel no record covers is `background`.  Records may lie partly
+ * or wholly outside the canvas.  One launch, capturable, no atomics, nothing read back; each lane decides its own pixels, so
+ * the bytes are the same on every run.
+ * LIMITS (CSG_E_BADSHAPE): 1 <= B <= 65535; H and W in [1, 2048]; W % 4 == 0; no null pointer (empty prims and text still
+ * need an address); prims on a 16-byte boundary, prim_off and out on a 4-byte one.  The caller builds the records and
+ * holds them to: coordinates in [-4096, 4096], at most 4096 records per picture, t and r as above, label ranges inside
+ * text (ops.draw_graph_u8 refuses the rest with ValueError).  The coordinate bound is what keeps the rule inside int64:
+ * |v| <= 6143 and |d| <= 8192 per axis give |cross| < 2^28, so 4 cross^2 < 2^58; cross^2 alone does not fit int32.
+ * Offsets beyond n_prims and label bytes beyond text_bytes are not read (the record range is cut, the byte draws '?'). */
+int csg_draw_graph_u8(const int32_t* prims, int64_t n_prims, const int32_t* prim_off, const uint8_t* text,
+                      int64_t text_bytes, const uint8_t* font, int64_t B, int64_t H, int64_t W, uint32_t background,
+                      uint8_t* out, void* stream);
 
 /* ---- decoded pictures -> the trainer's image tensor (csrc/preprocess.hip) ------------------------------
  * The per-sample transform of the reference's loader (sg2im/data/packed_coco.py:269-272: T.Resize(image_size), T.ToTensor(),
