@@ -1,3 +1,4 @@
+// The device metrics of a padded batch: box IoU (below) and relation agreement (further down).
 // Box IoU of a padded validation batch: the reference's jaccard (sg2im/metrics.py:4-36) behind
 // remove_dummies_and_padding (sg2im/utils.py:66-71) and the clamp of scripts/train.py:196, per object, with the sums
 // check_model keeps (scripts/train.py:211-217).
@@ -84,6 +85,121 @@ __global__ __launch_bounds__(64) void k_box_iou_fold(const double* __restrict__ 
   }
 }
 
+// ---- relation agreement: do predicted boxes obey the triplets they were laid out from? -------------------------------
+// The datasets' location rule (base_dataset.py:42-81, canon.hip's pair loop) asked of one pair per triplet.  A row is
+// TESTED when its predicate is one of the six location ids, its type is 0..3 and s, o are rows of the batch; it AGREES
+// when the rule, on the clamped boxes and the centres, yields that predicate.  The counts are integers: two 32-bit halves
+// of one 64-bit accumulator per (type, relation), {agreeing << 32 | tested}, summed by fixed trees (lanes strided over
+// the rows, a shuffle tree per wave, the waves in order); no atomics.
+constexpr int kAgreeThreads = 256;
+constexpr int kAgreeSlots = 4 * 6;             // (triplet type, location relation)
+
+struct AgreeIds {
+  int pid[6];                                  // __below__ __above__ __left of__ __right of__ __inside__ __surrounding__
+};
+
+__device__ __forceinline__ bool agrees_one(int slot, float4 sb, float4 ob, float2 sc, float2 oc, bool own_centres) {
+  const float sx0 = clamp01(sb.x), sy0 = clamp01(sb.y), sw = clamp01(sb.z), sh = clamp01(sb.w);
+  const float ox0 = clamp01(ob.x), oy0 = clamp01(ob.y), ow = clamp01(ob.z), oh = clamp01(ob.w);
+  const float sxc = __fadd_rn(sx0, 0.5f * sw), syc = __fadd_rn(sy0, 0.5f * sh);
+  const float oxc = __fadd_rn(ox0, 0.5f * ow), oyc = __fadd_rn(oy0, 0.5f * oh);
+  const float scx = own_centres ? sc.x : sxc, scy = own_centres ? sc.y : syc;
+  const float ocx = own_centres ? oc.x : oxc, ocy = own_centres ? oc.y : oyc;
+  // a NaN anywhere in the pair: tested, never agreeing (the clamped values are finite or NaN: sxc is NaN iff x0 or w is)
+  if (sxc != sxc || syc != syc || oxc != oxc || oyc != oyc || scx != scx || scy != scy || ocx != ocx || ocy != ocy) return false;
+  const bool sur = sx0 < ox0 && sxc > oxc && sy0 < oy0 && syc > oyc;
+  const bool ins = sx0 > ox0 && sxc < oxc && sy0 > oy0 && syc < oyc;
+  if (slot == 5) return sur;
+  if (slot == 4) return !sur && ins;
+  if (sur || ins) return false;
+  return slot == 3 ? scx > ocx : slot == 2 ? scx < ocx : slot == 0 ? scy > ocy : scy < ocy;
+}
+
+// one block per sample, lanes strided over the T rows.  per_sample[b][type] = {agreeing, tested};
+// by_rel[b][type][relation] = {agreeing, tested} for the fold
+__global__ __launch_bounds__(kAgreeThreads) void k_relation_agreement(
+    const float4* __restrict__ boxes, const float2* __restrict__ centers, const int64_t* __restrict__ triplets,
+    const int64_t* __restrict__ triplet_type, int O, int T, AgreeIds ids, uint8_t* __restrict__ tested,
+    uint8_t* __restrict__ agrees, int64_t* __restrict__ per_sample, int64_t* __restrict__ by_rel) {
+  __shared__ unsigned long long part[kAgreeThreads / 64][kAgreeSlots];
+  const int b = blockIdx.x;
+  const int64_t row = (int64_t)b * T, obj = (int64_t)b * O;
+  unsigned long long acc[kAgreeSlots];
+#pragma unroll
+  for (int q = 0; q < kAgreeSlots; ++q) acc[q] = 0ull;
+  for (int t = threadIdx.x; t < T; t += kAgreeThreads) {
+    const int64_t* tr = triplets + (row + t) * 3;
+    const int64_t s = tr[0], p = tr[1], o = tr[2], ty = triplet_type[row + t];
+    int rel = -1;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) rel = p == (int64_t)ids.pid[r] ? r : rel;
+    const bool on = rel >= 0 && ty >= 0 && ty < 4 && s >= 0 && s < O && o >= 0 && o < O;
+    bool ok = false;
+    if (on) {
+      const bool own = centers != nullptr;
+      const float2 none = make_float2(0.f, 0.f);
+      ok = agrees_one(rel, boxes[obj + s], boxes[obj + o], own ? centers[obj + s] : none, own ? centers[obj + o] : none, own);
+    }
+    tested[row + t] = on ? 1 : 0;
+    agrees[row + t] = ok ? 1 : 0;
+    const int slot = on ? (int)ty * 6 + rel : -1;
+    const unsigned long long v = (ok ? (1ull << 32) : 0ull) | 1ull;
+#pragma unroll
+    for (int q = 0; q < kAgreeSlots; ++q) acc[q] += slot == q ? v : 0ull;      // no indexed register: no scratch
+  }
+#pragma unroll
+  for (int q = 0; q < kAgreeSlots; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < kAgreeSlots; ++q) part[w][q] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < kAgreeSlots) {
+    const int q = threadIdx.x;
+    unsigned long long v = part[0][q];
+    for (int k = 1; k < kAgreeThreads / 64; ++k) v += part[k][q];
+    by_rel[((int64_t)b * kAgreeSlots + q) * 2 + 0] = (int64_t)(v >> 32);
+    by_rel[((int64_t)b * kAgreeSlots + q) * 2 + 1] = (int64_t)(v & 0xffffffffull);
+    part[0][q] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    unsigned long long v = 0ull;
+    for (int r = 0; r < 6; ++r) v += part[0][threadIdx.x * 6 + r];
+    per_sample[((int64_t)b * 4 + threadIdx.x) * 2 + 0] = (int64_t)(v >> 32);
+    per_sample[((int64_t)b * 4 + threadIdx.x) * 2 + 1] = (int64_t)(v & 0xffffffffull);
+  }
+}
+
+// totals[type][pid[relation]][k] += sum_b by_rel[b][type][relation][k]: one wave per (type, relation), lanes strided over
+// the samples, the same tree.  The six ids are distinct: no two blocks write one cell.
+__global__ __launch_bounds__(64) void k_relation_agreement_fold(const int64_t* __restrict__ by_rel, int B, int P, AgreeIds ids,
+                                                                int64_t* __restrict__ totals) {
+  const int q = blockIdx.x, ty = q / 6, rel = q - ty * 6;
+  int64_t a = 0, n = 0;
+  for (int b = threadIdx.x; b < B; b += 64) {
+    a += by_rel[((int64_t)b * kAgreeSlots + q) * 2 + 0];
+    n += by_rel[((int64_t)b * kAgreeSlots + q) * 2 + 1];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_down(a, off, 64);
+    n += __shfl_down(n, off, 64);
+  }
+  if (threadIdx.x == 0) {
+    int pid = ids.pid[0];
+#pragma unroll
+    for (int r = 1; r < 6; ++r) pid = rel == r ? ids.pid[r] : pid;
+    int64_t* cell = totals + ((int64_t)ty * P + pid) * 2;
+    cell[0] = cell[0] + a;
+    cell[1] = cell[1] + n;
+  }
+}
+
 }  // namespace csg
 
 using namespace csg;
@@ -105,6 +221,60 @@ int csg_box_iou(const float* boxes_pred, const float* boxes_gt, const int64_t* o
              (int)O, (int)A, image_id, iou, counted, per_sample);
   CSG_LAUNCH(k_box_iou_fold, dim3(1), dim3(64), 0, s, (const double*)per_sample, (int)B, totals);
   return check_launch("csg_box_iou");
+}
+
+int64_t csg_relation_agreement_workspace(int64_t B) {
+  if (B <= 0 || B > 65535) return 0;
+  return B * kAgreeSlots * 2 * (int64_t)sizeof(int64_t);
+}
+
+int csg_relation_agreement(const float* boxes, const float* centers, const int64_t* triplets, const int64_t* triplet_type,
+                           const int64_t* triplets_host, const int64_t* triplet_type_host, int64_t B, int64_t O, int64_t T,
+                           int64_t P, const int32_t* pred_ids, uint8_t* tested, uint8_t* agrees, int64_t* per_sample,
+                           int64_t* totals, void* workspace, int64_t workspace_bytes, void* stream) {
+  CSG_REQUIRE(B > 0 && B <= 65535 && O > 0 && O <= (1 << 20) && T > 0 && T <= (1 << 20) && P > 0 && P <= 4096, CSG_E_BADSHAPE,
+              "csg_relation_agreement: bad shape B=%ld O=%ld T=%ld P=%ld (B <= 65535, O <= 2^20, T <= 2^20, P <= 4096)",
+              (long)B, (long)O, (long)T, (long)P);
+  CSG_REQUIRE(boxes != nullptr && triplets != nullptr && triplet_type != nullptr && pred_ids != nullptr && tested != nullptr &&
+                  agrees != nullptr && per_sample != nullptr && totals != nullptr && workspace != nullptr,
+              CSG_E_BADSHAPE, "csg_relation_agreement: null operand");
+  CSG_REQUIRE((triplets_host == nullptr) == (triplet_type_host == nullptr), CSG_E_BADSHAPE,
+              "csg_relation_agreement: triplets_host and triplet_type_host come together or not at all");
+  CSG_REQUIRE((uintptr_t)boxes % 16 == 0 && (uintptr_t)centers % 8 == 0 &&
+                  ((uintptr_t)triplets | (uintptr_t)triplet_type | (uintptr_t)per_sample | (uintptr_t)totals |
+                   (uintptr_t)workspace) % 8 == 0,
+              CSG_E_BADSHAPE,
+              "csg_relation_agreement: boxes must be 16-byte aligned, centers, the int64 operands and the workspace 8-byte aligned");
+  CSG_REQUIRE(workspace_bytes >= csg_relation_agreement_workspace(B), CSG_E_WORKSPACE,
+              "csg_relation_agreement: workspace of %ld bytes, %ld needed", (long)workspace_bytes,
+              (long)csg_relation_agreement_workspace(B));
+  AgreeIds ids;
+  for (int a = 0; a < 8; ++a) {
+    CSG_REQUIRE(pred_ids[a] >= 0 && pred_ids[a] < P, CSG_E_BADSHAPE,
+                "csg_relation_agreement: predicate id %d outside [0, P = %ld)", (int)pred_ids[a], (long)P);
+    for (int c = 0; c < a; ++c)
+      CSG_REQUIRE(pred_ids[a] != pred_ids[c], CSG_E_BADSHAPE, "csg_relation_agreement: the eight predicate ids must be distinct");
+    if (a >= 2) ids.pid[a - 2] = pred_ids[a];
+  }
+  if (triplets_host != nullptr) {                 // the rows' host copy: every tested row is checked before the first launch
+    for (int64_t i = 0; i < B * T; ++i) {
+      const int64_t s = triplets_host[i * 3], p = triplets_host[i * 3 + 1], o = triplets_host[i * 3 + 2];
+      bool location = false;
+      for (int r = 0; r < 6; ++r) location = location || p == (int64_t)ids.pid[r];
+      if (!location) continue;
+      CSG_REQUIRE(s >= 0 && s < O && o >= 0 && o < O, CSG_E_BADSHAPE,
+                  "csg_relation_agreement: triplet %ld of sample %ld = (%ld, %ld, %ld) names an object outside [0, O = %ld)",
+                  (long)(i % T), (long)(i / T), (long)s, (long)p, (long)o, (long)O);
+      CSG_REQUIRE(triplet_type_host[i] >= 0 && triplet_type_host[i] < 4, CSG_E_BADSHAPE,
+                  "csg_relation_agreement: triplet %ld of sample %ld has type %ld outside [0, 4)", (long)(i % T), (long)(i / T),
+                  (long)triplet_type_host[i]);
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  CSG_LAUNCH(k_relation_agreement, dim3((unsigned)B), dim3(kAgreeThreads), 0, s, (const float4*)boxes, (const float2*)centers,
+             triplets, triplet_type, (int)O, (int)T, ids, tested, agrees, per_sample, (int64_t*)workspace);
+  CSG_LAUNCH(k_relation_agreement_fold, dim3(kAgreeSlots), dim3(64), 0, s, (const int64_t*)workspace, (int)B, (int)P, ids, totals);
+  return check_launch("csg_relation_agreement");
 }
 
 }  // extern "C"

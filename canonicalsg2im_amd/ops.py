@@ -2270,6 +2270,56 @@ def box_iou(boxes_pred, boxes_gt, objs, image_id, totals):
     return iou, counted, per_sample
 
 
+def relation_agreement(boxes, triplets, triplet_type, vocab, totals, centers=None, triplets_host=None,
+                       triplet_type_host=None):
+    """Whether a layout obeys the triplets it was made from (csg_relation_agreement): the datasets' location rule
+    (sg2im/data/base_dataset.py:42-81) on clamp(boxes, 0, 1) for the pair of every triplet whose predicate is one of the six
+    location relations.  boxes (B,O,4) fp32 xywh; centers (B,O,2) fp32 or None (the box centres); triplets (B,T,3) and
+    triplet_type (B,T) int64; `vocab`: its pred_name_to_idx gives the eight ids and P; `totals` a dense int64 (4,P,2) on the
+    device that the call ADDS to in place: {agreeing, tested} by triplet type and predicate.
+    Returns (tested (B,T) uint8, agrees (B,T) uint8, per_sample (B,4,2) int64 = {agreeing, tested} by triplet type).
+    Nothing is read back and nothing synchronises.  `triplets_host` / `triplet_type_host`: CPU copies of the two; with
+    them a tested row that names an object outside [0, O) or a type outside [0, 4) is refused before any launch; without
+    them such a row is never dereferenced and is written as not tested."""
+    if triplets.dtype != torch.int64 or triplets.dim() != 3 or triplets.shape[2] != 3:
+        raise RuntimeError("relation_agreement: triplets must be (B,T,3) int64 (collate contract)")
+    B, T, _ = triplets.shape
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4:
+        raise RuntimeError("relation_agreement: boxes must be (B,O,4) with B = %d, got %s" % (B, tuple(boxes.shape)))
+    O = boxes.shape[1]
+    if triplet_type.dtype != torch.int64 or tuple(triplet_type.shape) != (B, T):
+        raise RuntimeError("relation_agreement: triplet_type must be (B,T) = %s int64, got %s" % ((B, T), tuple(triplet_type.shape)))
+    if centers is not None and tuple(centers.shape) != (B, O, 2):
+        raise RuntimeError("relation_agreement: centers must be (B,O,2) = %s, got %s" % ((B, O, 2), tuple(centers.shape)))
+    P = len(vocab["pred_name_to_idx"])
+    if totals.dtype != torch.int64 or tuple(totals.shape) != (4, P, 2) or not totals.is_contiguous() or \
+            totals.device != triplets.device:
+        raise RuntimeError("relation_agreement: totals must be a dense int64 (4,%d,2) on the batch's device" % P)
+    if (triplets_host is None) != (triplet_type_host is None):
+        raise RuntimeError("relation_agreement: triplets_host and triplet_type_host come together or not at all")
+    host = [None, None]
+    if triplets_host is not None:
+        host = [torch.as_tensor(t).detach().to(device="cpu", dtype=torch.int64).contiguous()
+                for t in (triplets_host, triplet_type_host)]
+        if tuple(host[0].shape) != (B, T, 3) or tuple(host[1].shape) != (B, T):
+            raise RuntimeError("relation_agreement: the host copies must have the shapes of triplets and triplet_type")
+    bx, tr, tt = _f32(boxes.detach()).contiguous(), triplets.contiguous(), triplet_type.contiguous()
+    ce = None if centers is None else _f32(centers.detach()).contiguous()
+    dev = tr.device
+    tested = torch.empty((B, T), device=dev, dtype=torch.uint8)
+    agrees = torch.empty((B, T), device=dev, dtype=torch.uint8)
+    per_sample = torch.empty((B, 4, 2), device=dev, dtype=torch.int64)
+    nbytes = lib.csg_relation_agreement_workspace(B)
+    ws = torch.empty(max(nbytes // 8, 1), device=dev, dtype=torch.int64)
+    ids = (ctypes.c_int32 * 8)(*[vocab["pred_name_to_idx"][n] for n in PAIR_PREDICATES])
+    check(lib.csg_relation_agreement(ptr(bx), ptr(ce), ptr(tr), ptr(tt),
+                                     None if host[0] is None else ctypes.c_void_p(host[0].data_ptr()),
+                                     None if host[1] is None else ctypes.c_void_p(host[1].data_ptr()), B, O, T, P, ids,
+                                     ptr(tested), ptr(agrees), ptr(per_sample), ptr(totals), ptr(ws), nbytes, stream()),
+          "relation_agreement")
+    return tested, agrees, per_sample
+
+
 def graph_csr(triplets, O):
     """(row_ptr (B,O+1) int32, col (B,2T) int32) — incident triplets per object, reference order."""
     B, T, _ = triplets.shape

@@ -65,7 +65,7 @@ _OFF_PATH_FLAGS = {
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument('--dataset', default='coco',
-                   choices=['vg', 'clevr', 'coco', 'synthetic', 'packed_coco', 'packed_vg', 'packed_clevr'])
+                   choices=['vg', 'clevr', 'coco', 'synthetic', 'packed_coco', 'packed_vg', 'packed_clevr', 'packed_clevr_syn'])
     # optimisation
     p.add_argument('--batch_size', default=4, type=int)
     p.add_argument('--num_iterations', default=1000000, type=int)

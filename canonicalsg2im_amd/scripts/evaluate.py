@@ -88,6 +88,9 @@ def folder_val_set(args, vocab=None):
     with; a val split whose categories, attribute tables or predicates differ from it is refused here, on the host — its
     ids would index the model's embedding tables."""
     from .train import folder_dataset, hold_to_vocab
+    if args.dataset == "packed_clevr_syn":              # no pictures: check_model's losses have nothing to compare with
+        from ..sg2im.data.packed_clevr_syn import NO_VALIDATION
+        raise SystemExit(NO_VALIDATION)
     return hold_to_vocab(folder_dataset(args, "val"), vocab, "val")
 
 

@@ -44,6 +44,17 @@ model; on top of them:
                              --output_dir; the vocabulary is the checkpoint's.  Writes
                              generation/<which>_box_<which>_mask/<image id>.<ext>; the scene-graph encoder is not run
     --layout_boxes pred|gt   with --layouts: which boxes of the rows to draw (default pred)
+    --dataset packed_clevr_syn   the large-graph generalisation run (the reference's scripts/generate_clevr.py): synthetic
+                             CLEVR scenes of --min_objects .. --max_objects objects (15 .. 30), --max_samples of them
+                             (1000), drawn from --seed (0) as the reference draws them, in batches of --batch_size (10
+                             for this dataset).  --scenes FILE.json: the scenes are read from the file when it exists and
+                             written to it otherwise, so that two checkpoints see the same scenes.  Needs
+                             --checkpoint_name and --output_dir; excludes the three flags above.  Writes
+                             generation/pred_box_pred_mask/ and generation/gt_box_gt_mask/ (<image id>.<ext>),
+                             layouts.json and generalisation.json: the IoU figures, the share of the graph's location
+                             triplets that the predicted layout obeys (ops.relation_agreement) by triplet type and by
+                             predicate, and both by the number of objects in the graph.  --inception_weights FILE: the
+                             Inception score of the predicted-layout pictures over 5 splits as well
 
 The two modes without --split / --layouts deprocess with imagenet_deprocess whatever --img_deprocess says.
 
@@ -59,6 +70,7 @@ import time
 import torch
 
 _NO_CHECKPOINT = "checkpoint"           # the reference's default of --checkpoint_name: no file was named
+SYN = "packed_clevr_syn"
 
 
 def build_parser():
@@ -77,11 +89,21 @@ def build_parser():
     p.add_argument('--num_writers', default=8, type=int)
     p.add_argument('--layouts', default=None, type=str)
     p.add_argument('--layout_boxes', default="pred", choices=["pred", "gt"])
+    p.add_argument('--max_samples', default=1000, type=int, help="--dataset packed_clevr_syn: the number of scenes")
+    p.add_argument('--seed', default=0, type=int, help="--dataset packed_clevr_syn: the seed the scenes are drawn from")
+    p.add_argument('--scenes', default=None, type=str,
+                   help="--dataset packed_clevr_syn: a JSON file of scenes, read when it exists and written otherwise")
+    p.add_argument('--inception_weights', default=None, type=str,
+                   help="--dataset packed_clevr_syn: inception_v3_google-*.pth (or 'random', a stand-in)")
     return p
 
 
 def parse_args(argv=None):
-    args = build_parser().parse_args(argv)
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.dataset == SYN:                 # scripts/generate_clevr.py's defaults where this dataset has its own
+        p.set_defaults(batch_size=10, min_objects=15, max_objects=30)
+        args = p.parse_args(argv)
     if args.num_samples < 1 or args.batch_size < 1:
         raise SystemExit("--num_samples and --batch_size must be positive")
     if args.checkpoint_name != _NO_CHECKPOINT and not os.path.isfile(args.checkpoint_name):
@@ -99,6 +121,18 @@ def parse_args(argv=None):
     if len(given) > 1:
         raise SystemExit("%s exclude each other: a run draws a dataset split, a file of layouts or authored graphs" % (
             " and ".join(given)))
+    if args.dataset == SYN:
+        if given:
+            raise SystemExit("--dataset %s is a run of its own: %s does not go with it" % (SYN, given[0]))
+        if args.checkpoint_name == _NO_CHECKPOINT or not args.output_dir:
+            raise SystemExit("--dataset %s needs --checkpoint_name and --output_dir: the run measures a trained model and "
+                             "its files are its result" % SYN)
+        if args.img_deprocess not in ("decode_img", "imagenet"):
+            raise SystemExit("--img_deprocess %s: --dataset %s draws through decode_img or imagenet" % (args.img_deprocess, SYN))
+        if args.max_pictures < 0 or not 1 <= args.num_writers <= 16:
+            raise SystemExit("--max_pictures must be >= 0 and --num_writers within 1 .. 16")
+        if args.inception_weights not in (None, "random") and not os.path.isfile(args.inception_weights):
+            raise SystemExit("--inception_weights %s: no such file" % args.inception_weights)
     if args.split is not None or args.layouts is not None:
         flag = given[0]
         if args.checkpoint_name == _NO_CHECKPOINT:
@@ -163,6 +197,69 @@ def sample_split(args, dev, dataset):
     torch.cuda.synchronize()
     if metrics:
         log_results(metrics, ckpt.get("counters", {}).get("t", 0), "SPLIT %s" % args.split)
+    _rate_line(len(rows), tic, sampler)
+
+
+def syn_dataset(args):
+    """--dataset packed_clevr_syn: the scenes, or the end of the run — host only, before any device call."""
+    from ..sg2im.data import build_folder_dataset
+    try:
+        return build_folder_dataset(args, "val")
+    except (ValueError, NotImplementedError) as e:
+        raise SystemExit(str(e))
+
+
+def sample_generalisation(args, dev, dataset):
+    """--dataset packed_clevr_syn: the scenes through `split.generate_split(relations=True)`; generalisation.json."""
+    import json
+
+    from ..sample import Sampler
+    from ..sg2im.data.loader import file_order_batches
+    from ..split import generalisation_report, generate_split
+    from .args import init_args
+    from .train import folder_builder, hold_to_vocab
+    ckpt = torch.load(args.checkpoint_name, map_location="cpu")
+    hold_to_vocab(dataset, ckpt.get("vocab") if isinstance(ckpt, dict) else None, "synthetic")
+    args.vocab = dataset.vocab
+    init_args(args)
+    print("data: %d scenes, %s" % (len(dataset), dataset.image_dir), flush=True)
+    torch.manual_seed(0)
+    sampler = Sampler(args, dev, ckpt)
+    builder = folder_builder(dataset, args, sampler, dev)
+    tic = time.time()
+    try:
+        metrics, rows = generate_split(
+            sampler, builder.batches(file_order_batches(len(dataset), args.batch_size)), args.output_dir,
+            deprocess=args.img_deprocess, image_format=args.image_format, num_writers=args.num_writers,
+            max_pictures=args.max_pictures, split="synthetic", relations=True)
+    finally:
+        builder.close()
+    torch.cuda.synchronize()
+    report = generalisation_report(
+        metrics, rows, dataset=SYN, checkpoint=args.checkpoint_name, seed=None if dataset.loaded else dataset.seed,
+        scenes=args.scenes, min_objects=min(len(s["objects"]) for s in dataset.scenes),
+        max_objects=max(len(s["objects"]) for s in dataset.scenes))
+    for k in ("avg_iou", "total_iou_05", "total_iou_03"):         # generate_clevr.py's three lines
+        if k in metrics:
+            print("%s: %s" % (k, metrics[k]), flush=True)
+    agreement = metrics.get("relation_agreement")
+    if agreement:
+        print("relation_agreement: %s of %s tested triplets (%s)" % (agreement["agreeing"], agreement["tested"], agreement["rate"]))
+    if args.inception_weights:
+        from .. import quality
+        from ..inception import InceptionV3
+        from .quality import batches, list_files
+        net = InceptionV3("torchvision", args.inception_weights).to(dev)
+        scorer = quality.InceptionScore(net, channel_order="rgb")
+        folder = os.path.join(args.output_dir, "generation", "pred_box_pred_mask")
+        for pics in batches(list_files(folder), min(50, len(rows)), dev):
+            scorer.update(pics)
+        mean, std = scorer.compute(5)
+        label = "  [stand-in weights: the number means nothing]" if net.stand_in else ""
+        print("inception_mean: %s%s\ninception_std: %s%s" % (mean, label, std, label), flush=True)
+        report["inception_score"] = {"mean": mean, "std": std, "splits": 5, "stand_in": bool(net.stand_in)}
+    with open(os.path.join(args.output_dir, "generalisation.json"), "w") as f:
+        json.dump(report, f, indent=1)
     _rate_line(len(rows), tic, sampler)
 
 
@@ -253,7 +350,7 @@ def sample_scene_graphs(args, dev):
 
 def main(argv=None):
     args = parse_args(argv)
-    dataset = split_dataset(args) if args.split is not None else None
+    dataset = split_dataset(args) if args.split is not None else (syn_dataset(args) if args.dataset == SYN else None)
     if not torch.cuda.is_available():
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")
     from ..sample import Sampler
@@ -268,6 +365,8 @@ def main(argv=None):
         return sample_split(args, dev, dataset)
     if args.layouts is not None:
         return sample_layouts(args, dev)
+    if args.dataset == SYN:
+        return sample_generalisation(args, dev, dataset)
     args.vocab = make_vocab(_vocab_kind(args.dataset))
     init_args(args)
     torch.manual_seed(0)

@@ -52,7 +52,7 @@ import torch
 
 
 def _vocab_kind(dataset):
-    return {"vg": "vg", "packed_vg": "vg", "clevr": "clevr", "packed_clevr": "clevr"}.get(dataset, "coco")
+    return {"vg": "vg", "packed_vg": "vg", "clevr": "clevr", "packed_clevr": "clevr", "packed_clevr_syn": "clevr"}.get(dataset, "coco")
 
 
 def packed_batch(args, trainer, batch, dev):
@@ -129,6 +129,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.val_every < 0:
         raise SystemExit("--val_every must be >= 0 (0: no validation)")
+    if args.dataset == "packed_clevr_syn":
+        from ..sg2im.data.packed_clevr_syn import NO_TRAINING
+        raise SystemExit(NO_TRAINING)
     rank, world, local = csg_dist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("canonicalsg2im_amd needs a HIP device: there is no CPU path")

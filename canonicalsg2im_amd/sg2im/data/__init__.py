@@ -1,7 +1,7 @@
 """Device-side pieces of the reference's data pipeline (sg2im/data/*): the canonical graph construction of the packed
 datasets — the O(O^3) numpy/python step that feeds the hot path — and the folder datasets that feed it pictures: the three
 packed ones, the default `coco` with its sampled-pair graph, `vg` with its annotated-only graph and `clevr` with the renderer's
-relations reduced to their minimal graphs."""
+relations reduced to their minimal graphs; and `packed_clevr_syn`, synthetic CLEVR scenes without pictures, for the large-graph run."""
 from .base_dataset import (ANTI_SYMMETRIC_EDGE, ORIGINAL_EDGE, SYMMETRIC_EDGE, TRANSITIVE_EDGE,  # noqa: F401
                            annotated_triplets, augmented_relations, canonical_triplets, clevr_triplets, meta_relations,
                            register_augmented_relations)
@@ -11,6 +11,7 @@ FOLDER_DATASETS = {        # --dataset -> (the module of this package that holds
     "coco": ("coco", "build_coco_pairs_dataset"),
     "packed_coco": ("packed_coco", "build_coco_dataset"),
     "packed_clevr": ("packed_clevr", "build_clevr_dataset"),
+    "packed_clevr_syn": ("packed_clevr_syn", "build_clevr_syn_dataset"),      # no folder: scenes drawn from a seed
     "packed_vg": ("packed_vg", "build_vg_dataset"),
     "vg": ("vg", "build_vg_unpacked_dataset"),
 }

@@ -15,6 +15,9 @@ yields) through calls this package already has, in this order per batch and unde
                                   never go into gt/ or generation/, which feed the metrics; with draw_labels the objects'
                                   names as well (ops.draw_labels_u8), from the ids the batch holds on the host
     ops.box_iou                   the per-object IoU and the running totals of Evaluator.check_model
+    ops.relation_agreement        with relations=True only: whether the predicted layout obeys the batch's triplets, per image
+                                  by triplet type and as running totals by type and predicate (`generalisation_report`
+                                  makes the large-graph run's generalisation.json of them, on the host)
 
 Nothing is read back inside the loop.  The uint8 pictures stay planar and leave, with the batch's ids, objects, boxes and
 IoU, in non-blocking copies to one of two pinned host buffers on a side stream (`PictureWriter`); a buffer whose copy has
@@ -275,6 +278,9 @@ class SplitRows:
             if "boxes_pred" in host:
                 row["predicted_boxes"] = host["boxes_pred"][i][keep].tolist()
                 row["iou"] = host["iou"][i][keep].tolist()
+            if "relations" in host:                     # generate_split(relations=True): {agreeing, tested} by triplet type
+                row["relation_agreement"] = {"agreeing": host["relations"][i, :, 0].tolist(),
+                                             "tested": host["relations"][i, :, 1].tolist()}
             self.rows.append(row)
             if self.paths is not None:
                 for name in SETS:
@@ -303,13 +309,17 @@ def _host_ids(batch):
 
 
 def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, draw_boxes=False, thickness=2,
-                   image_format="png", num_writers=8, max_pictures=0, split=None, draw_labels=False):
+                   image_format="png", num_writers=8, max_pictures=0, split=None, draw_labels=False, relations=False):
     """Walk `batches` (see the module docstring) -> (metrics, rows).  metrics: avg_iou, total_iou_05, total_iou_03 (the
     totals / counted boxes, float64, as Evaluator.check_model forms them) and num_boxes; empty for a model without a graph
     part.  With `out_dir` the pictures and layouts.json are written; without it only metrics and rows are made.
     `max_pictures`: stop after that many images (a batch may be cut; 0: all).  `split`: the name layouts.json records.
     `draw_labels` (needs `draw_boxes`): the objects' names on layout/gt and layout/pred (ops.draw_labels_u8, names by
-    authored.labels_from_objs from the ids the batch holds on the host)."""
+    authored.labels_from_objs from the ids the batch holds on the host).
+    `relations` (opt-in; without it nothing below is made and every output is as before): whether the PREDICTED layout
+    obeys the triplets it was made from (ops.relation_agreement on boxes_pred, box centres, in the loop and without a
+    read-back): every row gets `relation_agreement` = {agreeing, tested} by triplet type, and metrics gets
+    `relation_agreement` (`relation_summary`) from one int64 (4,P,2) buffer of totals read once at the end."""
     from . import ops
     from .sample import NO_CPU
     from .sg2im.data.loader import HostBatch
@@ -324,6 +334,8 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
     image_id_obj = vocab["object_name_to_idx"]["__image__"]
     files, pictures, paths = _open_writers(sampler, out_dir, image_format, num_writers)
     totals = torch.zeros(4, device=dev, dtype=torch.float64)
+    relations = bool(relations) and model.has_graph
+    rel_totals = torch.zeros((4, len(vocab["pred_name_to_idx"]), 2), device=dev, dtype=torch.int64) if relations else None
     palette = torch.tensor(authored.DEFAULT_PALETTE, dtype=torch.uint8).reshape(-1, 3).to(dev) if draw_boxes else None
     taker = SplitRows(vocab, files, paths)
     rows, done = taker.rows, 0
@@ -369,6 +381,9 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                 if boxes_pred is not None:
                     iou, counted, _ = ops.box_iou(boxes_pred, boxes, objs, image_id_obj, totals)
                     out.update({"boxes_pred": boxes_pred.detach().float(), "iou": iou, "counted": counted})
+                    if relations:
+                        out["relations"] = ops.relation_agreement(boxes_pred.detach().float(), triplets, triplet_type, vocab,
+                                                                  rel_totals)[2]
                 pictures.put(out, taker.take)
                 done += int(objs.shape[0])
                 if max_pictures and done >= max_pictures:
@@ -379,6 +394,8 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                 t = totals.cpu()                        # the one read of the totals, at the end
                 metrics = {"avg_iou": float(t[0] / t[3]), "total_iou_05": float(t[1] / t[3]), "total_iou_03": float(t[2] / t[3]),
                            "num_boxes": float(t[3])}
+                if relations:
+                    metrics["relation_agreement"] = relation_summary(rel_totals.cpu().tolist(), vocab)
         raising = False
     finally:
         if files is not None:
@@ -390,6 +407,52 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                        "image_size": [int(v) for v in sampler.opt.image_size], "deprocess": deprocess, "rescale": bool(rescale),
                        "metrics": metrics, "images": rows}, f)
     return metrics, rows
+
+
+EDGE_TYPES = ("original", "transitive", "symmetric", "anti_symmetric")      # triplet types 0..3 (sg2im/data/base_dataset.py)
+
+
+def _rate(agreeing, tested):
+    return {"agreeing": int(agreeing), "tested": int(tested), "rate": (agreeing / tested) if tested else None}
+
+
+def relation_summary(totals, vocab):
+    """The (4,P,2) totals of ops.relation_agreement as nested lists -> {agreeing, tested, rate, by_type: {name: ...},
+    by_predicate: {name: ...}} (the predicates that were tested at least once; `rate` is None where nothing was)."""
+    names = vocab["pred_idx_to_name"]
+    by_type = {EDGE_TYPES[k]: _rate(sum(c[0] for c in totals[k]), sum(c[1] for c in totals[k])) for k in range(4)}
+    by_pred = {names[p]: _rate(sum(totals[k][p][0] for k in range(4)), sum(totals[k][p][1] for k in range(4)))
+               for p in range(len(names))}
+    return dict(_rate(sum(v["agreeing"] for v in by_type.values()), sum(v["tested"] for v in by_type.values())),
+                by_type=by_type, by_predicate={k: v for k, v in by_pred.items() if v["tested"]})
+
+
+def generalisation_report(metrics, rows, **run):
+    """What the large-graph run reports (generalisation.json), on the host from `generate_split(relations=True)`'s two
+    results: the overall figures, relation agreement by triplet type and by predicate, and both again by the number of
+    objects in the graph — `by_num_objects`, the curve the experiment is about — summed from the per-image rows.  `run`:
+    what identifies the run (seed or scenes file, checkpoint), recorded as given."""
+    sizes = {}
+    for row in rows:
+        sizes.setdefault(len(row["objects"]), []).append(row)
+    by_size = {}
+    for n in sorted(sizes):
+        ious = [v for row in sizes[n] for v in row.get("iou", [])]
+        entry = {"images": len(sizes[n]), "num_boxes": len(ious)}
+        if ious:
+            entry.update({"avg_iou": sum(ious) / len(ious), "total_iou_05": sum(v > 0.5 for v in ious) / len(ious),
+                          "total_iou_03": sum(v > 0.3 for v in ious) / len(ious)})
+        if any("relation_agreement" in row for row in sizes[n]):
+            per = [row["relation_agreement"] for row in sizes[n]]
+            by_type = {EDGE_TYPES[k]: _rate(sum(r["agreeing"][k] for r in per), sum(r["tested"][k] for r in per))
+                       for k in range(4)}
+            entry["relation_agreement"] = dict(_rate(sum(v["agreeing"] for v in by_type.values()),
+                                                     sum(v["tested"] for v in by_type.values())), by_type=by_type)
+        by_size[str(n)] = entry
+    out = dict(run)
+    out.update({"images": len(rows), "metrics": {k: v for k, v in metrics.items() if k != "relation_agreement"},
+                "relation_agreement": metrics.get("relation_agreement"), "by_num_objects": by_size})
+    return out
 
 
 def generate_layouts(sampler, rows, which="pred", out_dir=None, *, deprocess, rescale=True, batch_size=None,

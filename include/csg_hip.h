@@ -693,6 +693,35 @@ int csg_vg_rows(const int32_t* rows, const int64_t* sizes, const int64_t* counts
 int csg_box_iou(const float* boxes_pred, const float* boxes_gt, const int64_t* objs, int64_t B, int64_t O, int64_t A,
                 int64_t image_id, float* iou, uint8_t* counted, double* per_sample, double* totals, void* stream);
 
+/* ---- layout metric: relation agreement of a padded batch (csrc/metrics.hip) --------------------------
+ * Does a layout obey the triplets it was made from?  The datasets' location rule (sg2im/data/base_dataset.py:42-81) asked
+ * of the pair (s, o) of every triplet (s, p, o), on predicted boxes.  (Added after revision 122 without a new revision
+ * number: callers detect it by its symbol.)
+ * boxes (B,O,4) fp32 xywh, 16-byte aligned, clamped to [0,1] as xywh as csg_box_iou clamps boxes_pred (a NaN stays NaN);
+ * xc = x0 + 0.5f * w and yc = y0 + 0.5f * h are one correctly rounded fp32 addition each.  centers (B,O,2) fp32, 8-byte
+ * aligned, or NULL: the centre (cx, cy) of a row is its row of centers, else (xc, yc).  triplets (B,T,3) and triplet_type
+ * (B,T) int64.  pred_ids (host, 8 int32, distinct, each in [0, P)): __padding__ __in_image__ __below__ __above__
+ * __left of__ __right of__ __inside__ __surrounding__, as csg_canon_build takes them.
+ * A row is TESTED when p is one of the six location ids (not __padding__, __in_image__ or any other id).  A tested row
+ * AGREES when the rule yields p:  __surrounding__ iff sx0 < ox0 && sxc > oxc && sy0 < oy0 && syc > oyc;  __inside__ iff
+ * the four mirrored comparisons hold;  otherwise __right of__ / __left of__ by scx > ocx / scx < ocx and __below__ /
+ * __above__ by scy > ocy / scy < ocy (one of each axis can hold at once).  A pair with a NaN in a clamped box value or in
+ * a centre is tested and does not agree.
+ * tested, agrees (B,T) uint8; per_sample (B,4,2) int64 = {agreeing, tested} by triplet type 0..3; totals (4,P,2) int64 +=
+ * the same by type and predicate (a running buffer the caller zeroes once).  Integer sums by fixed trees, no atomics:
+ * bit-reproducible.  Two launches (one block per sample; one wave per (type, relation)), stream ordered and capturable;
+ * nothing is read back.  workspace: csg_relation_agreement_workspace(B) bytes, 8-byte aligned.
+ * triplets_host / triplet_type_host (host copies of the two, both or neither): with them every tested row is checked
+ * before the first launch — s or o outside [0, O), or a type outside [0, 4), is CSG_E_BADSHAPE.  Without them the rows
+ * are known on the device alone: such a row is never dereferenced, and is written as not tested.
+ * LIMITS: 1 <= B <= 65535, 1 <= O <= 2^20, 1 <= T <= 2^20, 1 <= P <= 4096 (CSG_E_BADSHAPE otherwise, before the first
+ * launch; a short workspace is CSG_E_WORKSPACE).                                                                   */
+int64_t csg_relation_agreement_workspace(int64_t B);
+int csg_relation_agreement(const float* boxes, const float* centers, const int64_t* triplets, const int64_t* triplet_type,
+                           const int64_t* triplets_host, const int64_t* triplet_type_host, int64_t B, int64_t O, int64_t T,
+                           int64_t P, const int32_t* pred_ids, uint8_t* tested, uint8_t* agrees, int64_t* per_sample,
+                           int64_t* totals, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- K7 / pooling ------------------------------------------------------------------------------
  * nearest 2x upsample (generator.py:48,102-121) and its adjoint */
 /* F.interpolate(x, size=(OH, OW), mode='nearest') of an NHWC map (B,IH,IW,C), C a multiple of 4 — the resize of the
