@@ -34,6 +34,7 @@
 #include "csg_common.h"
 #include "csg_pack.h"
 #include "csg_reduce.h"
+#include "csg_wino_host.h"
 
 using namespace csg;
 
@@ -414,17 +415,11 @@ constexpr size_t wn_conv_lds(int TW) {
 }
 
 static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const char* who) {
-  CSG_REQUIRE(d != nullptr, CSG_E_BADSHAPE, "%s: null descriptor", who);
-  CSG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, CSG_E_BADSHAPE, "%s: non-positive dimension", who);
+  const int rc = wino_desc_check(d, who, 16, [](const csg_wino_desc& d) { return (int64_t)d.B * d.H * d.W; });
+  if (rc) return rc;
   CSG_REQUIRE(d->H % 2 == 0 && d->W % 2 == 0 && d->W >= 8, CSG_E_UNSUPPORTED, "%s: H=%d, W=%d must be even, W >= 8", who,
               d->H, d->W);
-  CSG_REQUIRE(d->Cin % 4 == 0 && d->x_cs % 4 == 0 && d->x_cs >= d->Cin && d->Cout % 4 == 0 && d->y_cs % 4 == 0 &&
-                  d->y_cs >= d->Cout,
-              CSG_E_UNSUPPORTED, "%s: channel counts and strides must be multiples of 4", who);
-  CSG_REQUIRE((int64_t)d->B * d->H * d->W * (int64_t)(d->x_cs > d->y_cs ? d->x_cs : d->y_cs) * 4 < CSG_MAX_RECORDS, CSG_E_UNSUPPORTED,
-              "%s: tensor too large for 32-bit byte offsets", who);
-  CSG_REQUIRE((int64_t)16 * ((d->Cout + 31) / 32) * ((d->Cin + 7) / 8) * 1024 < CSG_MAX_RECORDS, CSG_E_UNSUPPORTED,
-              "%s: packed weights too large for 32-bit byte offsets", who);
+  CSG_REQUIRE(d->Cin % 16 == 0, CSG_E_UNSUPPORTED, "%s: Cin must be a multiple of 16 (one LDS stage)", who);
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_cs = d->x_cs; p.Cout = d->Cout; p.y_cs = d->y_cs;
   p.TW = d->W >= 32 ? 16 : (d->W >= 16 ? 8 : 4);
   p.TH = 32 / p.TW;
@@ -433,7 +428,6 @@ static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const cha
   p.ntb = d->Cout <= 32 ? 1 : 2;                 // 32-wide blocks for layers with <= 32 output channels
   p.nblocks = (d->Cout + 32 * p.ntb - 1) / (32 * p.ntb);
   p.RS = wn_row_stride(p.TW);
-  CSG_REQUIRE(d->Cin % 16 == 0, CSG_E_UNSUPPORTED, "%s: Cin must be a multiple of 16 (one LDS stage)", who);
   p.NT32 = (d->Cout + 31) / 32;
   p.Q8 = (d->Cin + 7) / 8;
   p.act = d->act; p.slope = d->slope;
@@ -445,7 +439,7 @@ static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const cha
   return CSG_OK;
 }
 
-// one instantiation's launch (inside the caller's ProfScope, which also covers the slab sum of a split launch)
+// one instantiation's launch (inside the entry's ProfScope, which also covers the slab sum of a split launch)
 template <int TW, int NTB>
 static int wn_conv_launch(const WinoParams& p, int64_t grid, const float* x, const float4* up, const float* bias,
                           const float* residual, const float* gate, float* y, hipStream_t s) {
@@ -457,28 +451,32 @@ static int wn_conv_launch(const WinoParams& p, int64_t grid, const float* x, con
   return check_launch("csg_wino_conv");
 }
 
+// the instantiation of a plan; y: a.y, or the slabs of a split launch
+static int wn_conv_dispatch(const WinoParams& p, const WinoConvArgs& a, float* y) {
+  const int64_t grid = (int64_t)p.B * p.tby * p.tbx * p.nblocks * p.ksplit;
+  CSG_REQUIRE(grid < (1ll << 31), CSG_E_UNSUPPORTED, "csg_wino_conv: grid too large");
+  const float4* up = (const float4*)a.packed;
+  if (p.ntb == 1) {
+    if (p.TW == 16) return wn_conv_launch<16, 1>(p, grid, a.x, up, a.bias, a.residual, a.gate, y, a.s);
+    if (p.TW == 8) return wn_conv_launch<8, 1>(p, grid, a.x, up, a.bias, a.residual, a.gate, y, a.s);
+    return wn_conv_launch<4, 1>(p, grid, a.x, up, a.bias, a.residual, a.gate, y, a.s);
+  }
+  if (p.TW == 16) return wn_conv_launch<16, 2>(p, grid, a.x, up, a.bias, a.residual, a.gate, y, a.s);
+  if (p.TW == 8) return wn_conv_launch<8, 2>(p, grid, a.x, up, a.bias, a.residual, a.gate, y, a.s);
+  return wn_conv_launch<4, 2>(p, grid, a.x, up, a.bias, a.residual, a.gate, y, a.s);
+}
+
+// a split needs at least 16 stages of 16 channels and leaves at least 8 to a range (wino_split_plan)
+#define WN_SPLIT 16, 8
+
 extern "C" {
 
-int64_t csg_wino_pack_bytes(int64_t N, int64_t K) {
-  if (N <= 0 || K <= 0) return -1;
-  return (int64_t)16 * cdiv(N, 32) * cdiv(K, 8) * 64 * 16;
-}
+int64_t csg_wino_pack_bytes(int64_t N, int64_t K) { return wino_pack_bytes(16, N, K); }
 
 int csg_wino_pack_weights(const float* w, int64_t s_o, int64_t s_i, int64_t s_h, int64_t s_w, int64_t Cout, int64_t Cin,
                           int32_t backward_data, const float* sigma, float* packed, void* stream) {
-  CSG_REQUIRE(w != nullptr && packed != nullptr && Cout > 0 && Cin > 0, CSG_E_BADSHAPE, "csg_wino_pack_weights: bad arguments");
-  CSG_REQUIRE(((uintptr_t)packed % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino_pack_weights: packed must be 16-byte aligned");
-  // w is the (Cout, Cin, 3, 3) weight with element strides (s_o, s_i, s_h, s_w) — contiguous or channels-last.
-  // forward: n = cout, k = cin;  backward-data: n = cin, k = cout, taps flipped
-  const int64_t N = backward_data ? Cin : Cout, K = backward_data ? Cout : Cin;
-  const int64_t s_n = backward_data ? s_i : s_o, s_k = backward_data ? s_o : s_i;
-  const int NT32 = (int)cdiv(N, 32), Q8 = (int)cdiv(K, 8);
-  const int64_t total = (int64_t)16 * NT32 * Q8 * 64;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(K_WINO_PACK, (double)Cout * Cin * 9 * 4 + (double)total * 16, s);
-  CSG_LAUNCH(k_wino_pack, dim3((unsigned)cdiv(Q8, 4), (unsigned)NT32), dim3(256), 0, s, w, s_n, s_k, s_h, s_w,
-                     backward_data ? 1 : 0, (int)N, (int)K, sigma, NT32, Q8, (float4*)packed);
-  return check_launch("csg_wino_pack_weights");
+  return wino_pack_entry("csg_wino_pack_weights", 16, 9, w, s_o, s_i, s_h, s_w, Cout, Cin, backward_data, sigma, packed, stream,
+                         [](dim3 grid, hipStream_t s, auto... a) { CSG_LAUNCH(k_wino_pack, grid, dim3(256), 0, s, a...); });
 }
 
 int csg_wino2_pack_multi_launch(const PackMulti* pm, int blocks, double bytes, hipStream_t s) {
@@ -487,66 +485,18 @@ int csg_wino2_pack_multi_launch(const PackMulti* pm, int blocks, double bytes, h
   return check_launch("csg_wino_pack_weights_multi(F(2x2,3x3))");
 }
 
-// Split over the input channels when the tile grid alone cannot fill the chip (backward-data of the gamma/beta
-// convolutions: 128 output channels, 2048 input channels): only without an epilogue (bias / activation / residual)
-// and with a dense output, the slabs are summed in a fixed order by k_slab_reduce.
-static void wn_split_plan(WinoParams& p, bool plain) {
-  if (!plain || p.y_cs != p.Cout) return;
-  const int64_t blocks = (int64_t)p.B * p.tby * p.tbx * p.nblocks;
-  if (blocks >= 384 || p.nstage < 16) return;
-  int ks = (int)((512 + blocks - 1) / blocks);
-  if (ks > p.nstage / 8) ks = p.nstage / 8;
-  if (ks < 2) return;
-  p.sps = (p.nstage + ks - 1) / ks;
-  p.ksplit = (p.nstage + p.sps - 1) / p.sps;
-}
-
 int64_t csg_wino_conv_workspace(const csg_wino_desc* d) {
-  WinoParams p;
-  size_t shm = 0;
-  if (wn_plan(d, p, shm, "csg_wino_conv_workspace")) return -1;
-  wn_split_plan(p, d->act == CSG_ACT_NONE);
-  return p.ksplit > 1 ? (int64_t)p.ksplit * p.slab * 4 : 0;
+  return wino_conv_workspace<WinoParams>(
+      d, WN_SPLIT, [&](WinoParams& p, size_t& shm) { return wn_plan(d, p, shm, "csg_wino_conv_workspace"); });
 }
 
 int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, const float* bias, const float* residual,
                   const float* gate, float gate_slope, float* y, float* workspace, int64_t workspace_bytes, void* stream) {
-  WinoParams p;
-  size_t shm = 0;
-  int rc = wn_plan(d, p, shm, "csg_wino_conv");
-  if (rc) return rc;
-  wn_split_plan(p, d->act == CSG_ACT_NONE && bias == nullptr && residual == nullptr && gate == nullptr);
-  p.gate_slope = gate_slope;
-  CSG_REQUIRE(gate == nullptr || ((uintptr_t)gate % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino_conv: gate must be 16-byte aligned");
-  if (p.ksplit > 1 && (workspace == nullptr || workspace_bytes < (int64_t)p.ksplit * p.slab * 4)) {   // no slabs: unsplit
-    p.ksplit = 1;
-    p.sps = p.nstage;
-  }
-  float* const y_final = y;
-  if (p.ksplit > 1) {
-    CSG_REQUIRE(((uintptr_t)workspace % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino_conv: workspace must be 16-byte aligned");
-    y = workspace;
-  }
-  CSG_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)packed % 16) == 0 && ((uintptr_t)y % 16) == 0, CSG_E_UNSUPPORTED,
-              "csg_wino_conv: pointers must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t grid = (int64_t)p.B * p.tby * p.tbx * p.nblocks * p.ksplit;
-  CSG_REQUIRE(grid < (1ll << 31), CSG_E_UNSUPPORTED, "csg_wino_conv: grid too large");
-  // algorithmic FLOPs of the DIRECT convolution this replaces (2 * M * 9*Cin * Cout): what FlopCounterMode counts
-  ProfScope ps(K_WINO_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
-  const float4* up = (const float4*)packed;
-  if (p.ntb == 1) {
-    if (p.TW == 16) rc = wn_conv_launch<16, 1>(p, grid, x, up, bias, residual, gate, y, s);
-    else if (p.TW == 8) rc = wn_conv_launch<8, 1>(p, grid, x, up, bias, residual, gate, y, s);
-    else rc = wn_conv_launch<4, 1>(p, grid, x, up, bias, residual, gate, y, s);
-  } else if (p.TW == 16) rc = wn_conv_launch<16, 2>(p, grid, x, up, bias, residual, gate, y, s);
-  else if (p.TW == 8) rc = wn_conv_launch<8, 2>(p, grid, x, up, bias, residual, gate, y, s);
-  else rc = wn_conv_launch<4, 2>(p, grid, x, up, bias, residual, gate, y, s);
-  if (rc == CSG_OK && p.ksplit > 1) {
-    launch_slab_reduce(workspace, p.slab, y_final, nullptr, 0, nullptr, p.ksplit, s);
-    rc = check_launch("csg_wino_conv(slab sum)");
-  }
-  return rc;
+  const WinoConvArgs a{x, packed, bias, residual, gate, gate_slope, y, workspace, workspace_bytes, (hipStream_t)stream};
+  return wino_conv_entry<WinoParams>(
+      "csg_wino_conv", "csg_wino_conv(slab sum)", d, WN_SPLIT, K_WINO_CONV, 9.0, a,
+      [&](WinoParams& p, size_t& shm) { return wn_plan(d, p, shm, "csg_wino_conv"); },
+      [&](const WinoParams& p, size_t, float* out) { return wn_conv_dispatch(p, a, out); });
 }
 
 }  // extern "C"
@@ -818,34 +768,18 @@ __global__ __launch_bounds__(256, 2) void k_wino_wgrad(WinoWgParams p, const flo
 static int wn_wg_tsx(int W) { return W >= 32 ? 16 : (W >= 16 ? 8 : 4); }
 
 static int wn_wg_plan(const csg_wino_desc* d, WinoWgParams& p, const char* who) {
-  CSG_REQUIRE(d != nullptr, CSG_E_BADSHAPE, "%s: null descriptor", who);
-  CSG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, CSG_E_BADSHAPE, "%s: non-positive dimension", who);
+  const int rc = wino_desc_check(d, who, 0, [](const csg_wino_desc& d) { return (int64_t)d.B * d.H * d.W + d.W + 1; });
+  if (rc) return rc;
   const int tsx = wn_wg_tsx(d->W), tsy = 16 / tsx;
   CSG_REQUIRE(d->W >= 8 && d->W % (2 * tsx) == 0 && d->H % (2 * tsy) == 0, CSG_E_UNSUPPORTED,
               "%s: H=%d, W=%d must be multiples of the %dx%d-tile stage", who, d->H, d->W, tsx, tsy);
-  CSG_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0 && d->x_cs % 4 == 0 && d->y_cs % 4 == 0 && d->x_cs >= d->Cin &&
-                  d->y_cs >= d->Cout,
-              CSG_E_UNSUPPORTED, "%s: channel counts and strides must be multiples of 4", who);
-  CSG_REQUIRE(((int64_t)d->B * d->H * d->W + d->W + 1) * (int64_t)(d->x_cs > d->y_cs ? d->x_cs : d->y_cs) * 4 < CSG_MAX_RECORDS,
-              CSG_E_UNSUPPORTED, "%s: tensor too large for 32-bit byte offsets", who);
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_cs = d->x_cs; p.Cout = d->Cout; p.y_cs = d->y_cs;
   p.RXn = d->W / (2 * tsx);
   p.RYn = d->H / (2 * tsy);
-  const int64_t nr = (int64_t)d->B * p.RXn * p.RYn;
-  CSG_REQUIRE(nr < (1ll << 30), CSG_E_UNSUPPORTED, "%s: too many regions", who);
-  p.nregions = (int)nr;
   p.cblocks = (d->Cout + 63) / 64;
   p.kblocks = (d->Cin + 31) / 32;
   // 2 blocks per CU are resident: aim at ~2 waves of blocks, at least 8 stages per block, at most 512 slabs
-  const int tiles2d = p.cblocks * p.kblocks;
-  int ns = (1024 + tiles2d - 1) / tiles2d;
-  const int max_ns = (int)((nr + 7) / 8);
-  if (ns > max_ns) ns = max_ns;
-  if (ns > 512) ns = 512;
-  if (ns < 1) ns = 1;
-  p.rps = (int)((nr + ns - 1) / ns);
-  p.nsplit = (int)((nr + p.rps - 1) / p.rps);
-  return CSG_OK;
+  return wino_wg_slice_plan(p, who, p.cblocks * p.kblocks, 1024, 8, 512);
 }
 
 // one tile shape's launch (TSX x 16/TSX tiles per region)
@@ -870,35 +804,23 @@ extern "C" {
 int64_t csg_wino_bwd_weight_workspace(const csg_wino_desc* d) {
   WinoWgParams p;
   if (wn_wg_plan(d, p, "csg_wino_bwd_weight_workspace")) return -1;
-  return (int64_t)p.nsplit * d->Cout * (9 * (int64_t)d->Cin + 1) * 4;
+  return wino_wg_workspace(d, p.nsplit);
 }
 
 int csg_wino_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                         int64_t workspace_bytes, void* stream) {
   WinoWgParams p;
-  int rc = wn_wg_plan(d, p, "csg_wino_bwd_weight");
+  const int rc = wn_wg_plan(d, p, "csg_wino_bwd_weight");
   if (rc) return rc;
-  const int64_t wsize = (int64_t)d->Cout * 9 * d->Cin;
-  const int64_t need = (int64_t)p.nsplit * (wsize + d->Cout) * 4;
-  CSG_REQUIRE(workspace != nullptr && workspace_bytes >= need, CSG_E_WORKSPACE, "csg_wino_bwd_weight: workspace %ld < %ld bytes",
-              (long)workspace_bytes, (long)need);
-  const int tsx = wn_wg_tsx(d->W);
   hipStream_t s = (hipStream_t)stream;
-  float* dbslabs = db != nullptr ? workspace + (int64_t)p.nsplit * wsize : nullptr;
-  if (p.nsplit == 1) {          // a single slice: the block results ARE the gradient
-    workspace = dw;
-    dbslabs = db;
-  }
-  if (tsx == 16) rc = wn_wg_launch<16>(p, x, dy, workspace, dbslabs, s);
-  else if (tsx == 8) rc = wn_wg_launch<8>(p, x, dy, workspace, dbslabs, s);
-  else rc = wn_wg_launch<4>(p, x, dy, workspace, dbslabs, s);
-  if (rc) return rc;
-  if (p.nsplit > 1) {
-    ProfScope ps(K_WGRAD_REDUCE, (double)(p.nsplit + 1) * wsize * 4, s);
-    launch_slab_reduce(workspace, wsize, dw, dbslabs, db != nullptr ? d->Cout : 0, db, p.nsplit, s);
-    rc = check_launch("csg_wino_bwd_weight(reduce)");
-  }
-  return rc;
+  // a single slice: the block results ARE the gradient
+  return wino_wg_run("csg_wino_bwd_weight", "csg_wino_bwd_weight(reduce)", d, p.nsplit, p.nsplit == 1, dw, db, workspace,
+                     workspace_bytes, s, [&](float* slabs, float* dbslabs) {
+                       const int tsx = wn_wg_tsx(d->W);
+                       if (tsx == 16) return wn_wg_launch<16>(p, x, dy, slabs, dbslabs, s);
+                       if (tsx == 8) return wn_wg_launch<8>(p, x, dy, slabs, dbslabs, s);
+                       return wn_wg_launch<4>(p, x, dy, slabs, dbslabs, s);
+                     });
 }
 
 }  // extern "C"

@@ -63,6 +63,7 @@
 #include "csg_common.h"
 #include "csg_pack.h"
 #include "csg_reduce.h"
+#include "csg_wino_host.h"
 
 using namespace csg;
 
@@ -933,8 +934,8 @@ constexpr size_t w4_lds = (size_t)(W4Geo<T>::OFFTAB + W4_THREADS * 4) * 4;
 
 // T = 4: F(4x4,3x3), pad 1, output = input size.  T = 3: F(3x3,4x4), pad 1 or 2, output = input + 2 pad - 3.
 static int w4_plan(const csg_wino_desc* d, int T, int pad, Wino4Params& p, size_t& shm, const char* who) {
-  CSG_REQUIRE(d != nullptr, CSG_E_BADSHAPE, "%s: null descriptor", who);
-  CSG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, CSG_E_BADSHAPE, "%s: non-positive dimension", who);
+  const int rc = wino_desc_check(d, who, 36, [](const csg_wino_desc& d) { return (int64_t)d.B * (d.H + 1) * (d.W + 1); });
+  if (rc) return rc;
   if (T == 4)
     CSG_REQUIRE(d->H % 4 == 0 && d->W % 4 == 0 && d->W >= 32 && d->H >= 16, CSG_E_UNSUPPORTED,
                 "%s: F(4x4,3x3) needs H=%d, W=%d multiples of 4, W >= 32, H >= 16", who, d->H, d->W);
@@ -942,13 +943,7 @@ static int w4_plan(const csg_wino_desc* d, int T, int pad, Wino4Params& p, size_
     CSG_REQUIRE((pad == 1 || pad == 2) && d->H + 2 * pad >= 4 && d->W + 2 * pad >= 4, CSG_E_UNSUPPORTED,
                 "%s: F(3x3,4x4) serves pad 1 or 2 (got %d) on maps of at least 4 - 2 pad pixels", who, pad);
   const int Ho = T == 4 ? d->H : d->H + 2 * pad - 3, Wo = T == 4 ? d->W : d->W + 2 * pad - 3;
-  CSG_REQUIRE(d->Cin % 8 == 0 && d->x_cs % 4 == 0 && d->x_cs >= d->Cin && d->Cout % 4 == 0 && d->y_cs % 4 == 0 &&
-                  d->y_cs >= d->Cout,
-              CSG_E_UNSUPPORTED, "%s: Cin must be a multiple of 8, the other channel counts and strides of 4", who);
-  CSG_REQUIRE((int64_t)d->B * (d->H + 1) * (d->W + 1) * (int64_t)(d->x_cs > d->y_cs ? d->x_cs : d->y_cs) * 4 < CSG_MAX_RECORDS,
-              CSG_E_UNSUPPORTED, "%s: tensor too large for 32-bit byte offsets", who);
-  CSG_REQUIRE((int64_t)36 * ((d->Cout + 31) / 32) * ((d->Cin + 7) / 8) * 1024 < CSG_MAX_RECORDS, CSG_E_UNSUPPORTED,
-              "%s: packed weights too large for 32-bit byte offsets", who);
+  CSG_REQUIRE(d->Cin % 8 == 0, CSG_E_UNSUPPORTED, "%s: Cin must be a multiple of 8 (one LDS stage)", who);
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_cs = d->x_cs; p.Cout = d->Cout; p.y_cs = d->y_cs;
   p.Ho = Ho; p.Wo = Wo; p.pad = pad;
   p.tbx = (Wo + T * W4_TW - 1) / (T * W4_TW);
@@ -992,10 +987,10 @@ static int w4_persistent_blocks(const Wino4Params& p, int64_t items) {
   return g;
 }
 
+// the launch of one tile size, persistent or not (inside the caller's ProfScope)
 template <int T>
-static int w4_launch(Wino4Params& p, size_t shm, int kid, double flops, const float* x, const float* packed,
-                     const float* bias, const float* residual, const float* gate, float* y, float* workspace,
-                     float* y_final, hipStream_t s, const char* who) {
+static int w4_launch(Wino4Params& p, size_t shm, const float* x, const float* packed, const float* bias,
+                     const float* residual, const float* gate, float* y, hipStream_t s, const char* who) {
   const int64_t grid = (int64_t)p.B * p.tby * p.tbx * p.nblocks * p.ksplit;
   CSG_REQUIRE(grid < (1ll << 31), CSG_E_UNSUPPORTED, "%s: grid too large", who);
   p.nitems = (int)grid;
@@ -1005,31 +1000,27 @@ static int w4_launch(Wino4Params& p, size_t shm, int kid, double flops, const fl
   int rc = pblocks ? lds_limit<k_wino4_conv_v<4, true>, w4_lds<4> + W4_THREADS * 16>(shm + W4_THREADS * 16, who)
                    : lds_limit<k_wino4_conv_v<T, false>, w4_lds<T>>(shm, who);
   if (rc) return rc;
-  ProfScope ps(kid, flops, s);
   if (pblocks)
     CSG_LAUNCH((k_wino4_conv_v<4, true>), dim3((unsigned)pblocks), dim3(W4_THREADS), shm + W4_THREADS * 16, s, p, x,
                (const float4*)packed, bias, residual, gate, y);
   else
     CSG_LAUNCH((k_wino4_conv_v<T, false>), dim3((unsigned)grid), dim3(W4_THREADS), shm, s, p, x, (const float4*)packed, bias,
                residual, gate, y);
-  rc = check_launch(who);
-  if (rc == CSG_OK && p.ksplit > 1) {
-    launch_slab_reduce(workspace, p.slab, y_final, nullptr, 0, nullptr, p.ksplit, s);
-    rc = check_launch("csg_wino4_conv(slab sum)");
-  }
-  return rc;
+  return check_launch(who);
 }
 
-// Split over the input channels when the tile grid alone cannot fill the chip (see wn_split_plan in wino.hip)
-static void w4_split_plan(Wino4Params& p, bool plain) {
-  if (!plain || p.y_cs != p.Cout) return;
-  const int64_t blocks = (int64_t)p.B * p.tby * p.tbx * p.nblocks;
-  if (blocks >= 384 || p.nstage < 32) return;
-  int ks = (int)((512 + blocks - 1) / blocks);
-  if (ks > p.nstage / 16) ks = p.nstage / 16;
-  if (ks < 2) return;
-  p.sps = (p.nstage + ks - 1) / ks;
-  p.ksplit = (p.nstage + p.sps - 1) / p.sps;
+// a split needs at least 32 stages of 8 channels and leaves at least 16 to a range (wino_split_plan): the channel counts of wino.hip
+#define W4_SPLIT 32, 16
+
+// csg_wino4_conv (T = 4, pad 1) and csg_wino34_conv (T = 3)
+template <int T>
+static int w4_conv(const char* who, const csg_wino_desc* d, int pad, const WinoConvArgs& a) {
+  return wino_conv_entry<Wino4Params>(
+      who, "csg_wino4_conv(slab sum)", d, W4_SPLIT, K_WINO4_CONV, T == 4 ? 9.0 : 16.0, a,
+      [&](Wino4Params& p, size_t& shm) { return w4_plan(d, T, pad, p, shm, who); },
+      [&](Wino4Params& p, size_t shm, float* y) {
+        return w4_launch<T>(p, shm, a.x, a.packed, a.bias, a.residual, a.gate, y, a.s, who);
+      });
 }
 
 extern "C" {
@@ -1101,39 +1092,18 @@ int32_t csg_wino4_persistent(int32_t on) {
   return prev;
 }
 
-int64_t csg_wino4_pack_bytes(int64_t N, int64_t K) {
-  if (N <= 0 || K <= 0) return -1;
-  return (int64_t)36 * cdiv(N, 32) * cdiv(K, 8) * 64 * 16;
-}
+int64_t csg_wino4_pack_bytes(int64_t N, int64_t K) { return wino_pack_bytes(36, N, K); }
 
 int csg_wino4_pack_weights(const float* w, int64_t s_o, int64_t s_i, int64_t s_h, int64_t s_w, int64_t Cout, int64_t Cin,
                            int32_t backward_data, const float* sigma, float* packed, void* stream) {
-  CSG_REQUIRE(w != nullptr && packed != nullptr && Cout > 0 && Cin > 0, CSG_E_BADSHAPE, "csg_wino4_pack_weights: bad arguments");
-  CSG_REQUIRE(((uintptr_t)packed % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino4_pack_weights: packed must be 16-byte aligned");
-  const int64_t N = backward_data ? Cin : Cout, K = backward_data ? Cout : Cin;
-  const int64_t s_n = backward_data ? s_i : s_o, s_k = backward_data ? s_o : s_i;
-  const int NT32 = (int)cdiv(N, 32), Q8 = (int)cdiv(K, 8);
-  const int64_t total = (int64_t)36 * NT32 * Q8 * 64;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(K_WINO_PACK, (double)Cout * Cin * 9 * 4 + (double)total * 16, s);
-  CSG_LAUNCH(k_wino4_pack<3>, dim3((unsigned)cdiv(Q8, 4), (unsigned)NT32), dim3(256), 0, s, w, s_n, s_k, s_h, s_w,
-                     backward_data ? 1 : 0, (int)N, (int)K, sigma, NT32, Q8, (float4*)packed);
-  return check_launch("csg_wino4_pack_weights");
+  return wino_pack_entry("csg_wino4_pack_weights", 36, 9, w, s_o, s_i, s_h, s_w, Cout, Cin, backward_data, sigma, packed, stream,
+                         [](dim3 grid, hipStream_t s, auto... a) { CSG_LAUNCH(k_wino4_pack<3>, grid, dim3(256), 0, s, a...); });
 }
 
 int csg_wino34_pack_weights(const float* w, int64_t s_o, int64_t s_i, int64_t s_h, int64_t s_w, int64_t Cout, int64_t Cin,
                             int32_t backward_data, const float* sigma, float* packed, void* stream) {
-  CSG_REQUIRE(w != nullptr && packed != nullptr && Cout > 0 && Cin > 0, CSG_E_BADSHAPE, "csg_wino34_pack_weights: bad arguments");
-  CSG_REQUIRE(((uintptr_t)packed % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino34_pack_weights: packed must be 16-byte aligned");
-  const int64_t N = backward_data ? Cin : Cout, K = backward_data ? Cout : Cin;
-  const int64_t s_n = backward_data ? s_i : s_o, s_k = backward_data ? s_o : s_i;
-  const int NT32 = (int)cdiv(N, 32), Q8 = (int)cdiv(K, 8);
-  const int64_t total = (int64_t)36 * NT32 * Q8 * 64;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(K_WINO_PACK, (double)Cout * Cin * 16 * 4 + (double)total * 16, s);
-  CSG_LAUNCH(k_wino4_pack<4>, dim3((unsigned)cdiv(Q8, 4), (unsigned)NT32), dim3(256), 0, s, w, s_n, s_k, s_h, s_w,
-                     backward_data ? 1 : 0, (int)N, (int)K, sigma, NT32, Q8, (float4*)packed);
-  return check_launch("csg_wino34_pack_weights");
+  return wino_pack_entry("csg_wino34_pack_weights", 36, 16, w, s_o, s_i, s_h, s_w, Cout, Cin, backward_data, sigma, packed, stream,
+                         [](dim3 grid, hipStream_t s, auto... a) { CSG_LAUNCH(k_wino4_pack<4>, grid, dim3(256), 0, s, a...); });
 }
 
 int32_t csg_wino34_supported(const csg_wino_desc* d, int32_t pad) {
@@ -1145,70 +1115,26 @@ int32_t csg_wino34_supported(const csg_wino_desc* d, int32_t pad) {
 }
 
 int64_t csg_wino34_conv_workspace(const csg_wino_desc* d, int32_t pad) {
-  Wino4Params p;
-  size_t shm = 0;
-  if (w4_plan(d, 3, pad, p, shm, "csg_wino34_conv_workspace")) return -1;
-  w4_split_plan(p, d->act == CSG_ACT_NONE);
-  return p.ksplit > 1 ? (int64_t)p.ksplit * p.slab * 4 : 0;
+  return wino_conv_workspace<Wino4Params>(
+      d, W4_SPLIT, [&](Wino4Params& p, size_t& shm) { return w4_plan(d, 3, pad, p, shm, "csg_wino34_conv_workspace"); });
 }
 
 int csg_wino34_conv(const csg_wino_desc* d, int32_t pad, const float* x, const float* packed, const float* bias,
                     const float* residual, const float* gate, float gate_slope, float* y, float* workspace,
                     int64_t workspace_bytes, void* stream) {
-  Wino4Params p;
-  size_t shm = 0;
-  int rc = w4_plan(d, 3, pad, p, shm, "csg_wino34_conv");
-  if (rc) return rc;
-  w4_split_plan(p, d->act == CSG_ACT_NONE && bias == nullptr && residual == nullptr && gate == nullptr);
-  p.gate_slope = gate_slope;
-  if (p.ksplit > 1 && (workspace == nullptr || workspace_bytes < (int64_t)p.ksplit * p.slab * 4)) {   // no slabs: unsplit
-    p.ksplit = 1;
-    p.sps = p.nstage;
-  }
-  float* const y_final = y;
-  if (p.ksplit > 1) {
-    CSG_REQUIRE(((uintptr_t)workspace % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino34_conv: workspace must be 16-byte aligned");
-    y = workspace;
-  }
-  CSG_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)packed % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
-                  (gate == nullptr || ((uintptr_t)gate % 16) == 0),
-              CSG_E_UNSUPPORTED, "csg_wino34_conv: pointers must be 16-byte aligned");
-  // algorithmic FLOPs of the DIRECT convolution this replaces (2 * M * 16*Cin * Cout)
-  return w4_launch<3>(p, shm, K_WINO4_CONV, 2.0 * p.B * p.Ho * p.Wo * 16.0 * p.Cin * p.Cout, x, packed, bias, residual, gate,
-                      y, workspace, y_final, (hipStream_t)stream, "csg_wino34_conv");
+  return w4_conv<3>("csg_wino34_conv", d, pad,
+                    {x, packed, bias, residual, gate, gate_slope, y, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 int64_t csg_wino4_conv_workspace(const csg_wino_desc* d) {
-  Wino4Params p;
-  size_t shm = 0;
-  if (w4_plan(d, 4, 1, p, shm, "csg_wino4_conv_workspace")) return -1;
-  w4_split_plan(p, d->act == CSG_ACT_NONE);
-  return p.ksplit > 1 ? (int64_t)p.ksplit * p.slab * 4 : 0;
+  return wino_conv_workspace<Wino4Params>(
+      d, W4_SPLIT, [&](Wino4Params& p, size_t& shm) { return w4_plan(d, 4, 1, p, shm, "csg_wino4_conv_workspace"); });
 }
 
 int csg_wino4_conv(const csg_wino_desc* d, const float* x, const float* packed, const float* bias, const float* residual,
                    const float* gate, float gate_slope, float* y, float* workspace, int64_t workspace_bytes, void* stream) {
-  Wino4Params p;
-  size_t shm = 0;
-  int rc = w4_plan(d, 4, 1, p, shm, "csg_wino4_conv");
-  if (rc) return rc;
-  w4_split_plan(p, d->act == CSG_ACT_NONE && bias == nullptr && residual == nullptr && gate == nullptr);
-  p.gate_slope = gate_slope;
-  CSG_REQUIRE(gate == nullptr || ((uintptr_t)gate % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino4_conv: gate must be 16-byte aligned");
-  if (p.ksplit > 1 && (workspace == nullptr || workspace_bytes < (int64_t)p.ksplit * p.slab * 4)) {   // no slabs: unsplit
-    p.ksplit = 1;
-    p.sps = p.nstage;
-  }
-  float* const y_final = y;
-  if (p.ksplit > 1) {
-    CSG_REQUIRE(((uintptr_t)workspace % 16) == 0, CSG_E_UNSUPPORTED, "csg_wino4_conv: workspace must be 16-byte aligned");
-    y = workspace;
-  }
-  CSG_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)packed % 16) == 0 && ((uintptr_t)y % 16) == 0, CSG_E_UNSUPPORTED,
-              "csg_wino4_conv: pointers must be 16-byte aligned");
-  // algorithmic FLOPs of the DIRECT convolution this replaces (2 * M * 9*Cin * Cout): what FlopCounterMode counts
-  return w4_launch<4>(p, shm, K_WINO4_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, x, packed, bias, residual, gate, y,
-                      workspace, y_final, (hipStream_t)stream, "csg_wino4_conv");
+  return w4_conv<4>("csg_wino4_conv", d, 1,
+                    {x, packed, bias, residual, gate, gate_slope, y, workspace, workspace_bytes, (hipStream_t)stream});
 }
 
 int csg_wino4_conv_part(const csg_wino_desc* d, const float* x, const float* packed, int64_t tile_off, int64_t tiles_total,
@@ -1238,8 +1164,9 @@ int csg_wino4_conv_part(const csg_wino_desc* d, const float* x, const float* pac
   CSG_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)packed % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
                   (bias == nullptr || ((uintptr_t)bias % 16) == 0),
               CSG_E_UNSUPPORTED, "csg_wino4_conv_part: pointers must be 16-byte aligned");
-  return w4_launch<4>(p, shm, K_WINO4_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, x, packed, bias, mod_x, mod_gamma, y,
-                      nullptr, y, (hipStream_t)stream, "csg_wino4_conv_part");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(K_WINO4_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
+  return w4_launch<4>(p, shm, x, packed, bias, mod_x, mod_gamma, y, s, "csg_wino4_conv_part");
 }
 
 // the joint launch exists in the persistent form only (w4_persistent_blocks: >= 2 items per CU, an even number of >= 4 stages)
@@ -1286,8 +1213,9 @@ int csg_wino4_conv_spade(const csg_wino_desc* d, const float* x, const float* pa
               CSG_E_UNSUPPORTED, "csg_wino4_conv_spade: pointers must be 16-byte aligned");
   p.g_cs = (int)gamma_cs; p.mod_slope = mod_slope; p.mod_mean = mod_mean; p.mod_invstd = mod_invstd;
   // algorithmic FLOPs of the direct gamma || beta convolution: 2C outputs
-  return w4_launch<4>(p, shm, K_WINO4_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * 2.0 * p.Cout, x, packed, bias, mod_x, gamma_out,
-                      y, nullptr, y, (hipStream_t)stream, "csg_wino4_conv_spade");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(K_WINO4_CONV, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * 2.0 * p.Cout, s);
+  return w4_launch<4>(p, shm, x, packed, bias, mod_x, gamma_out, y, s, "csg_wino4_conv_spade");
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@
 #include "csg_buffer.h"
 #include "csg_common.h"
 #include "csg_reduce.h"
+#include "csg_wino_host.h"
 
 using namespace csg;
 
@@ -453,75 +454,49 @@ __global__ __launch_bounds__(WW_THREADS, 2) void k_wino4_wgrad(Wino4WgParams p, 
 }
 
 static int ww_plan(const csg_wino_desc* d, Wino4WgParams& p, const char* who) {
-  CSG_REQUIRE(d != nullptr, CSG_E_BADSHAPE, "%s: null descriptor", who);
-  CSG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, CSG_E_BADSHAPE, "%s: non-positive dimension", who);
+  const int rc = wino_desc_check(d, who, 0, [](const csg_wino_desc& d) { return (int64_t)d.B * d.H * d.W + d.W + 1; });
+  if (rc) return rc;
   CSG_REQUIRE(d->W % 8 == 0 && d->H % 8 == 0, CSG_E_UNSUPPORTED, "%s: H=%d, W=%d must be multiples of the 8x8-pixel stage", who,
               d->H, d->W);
-  CSG_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0 && d->x_cs % 4 == 0 && d->y_cs % 4 == 0 && d->x_cs >= d->Cin &&
-                  d->y_cs >= d->Cout,
-              CSG_E_UNSUPPORTED, "%s: channel counts and strides must be multiples of 4", who);
-  CSG_REQUIRE(((int64_t)d->B * d->H * d->W + d->W + 1) * (int64_t)(d->x_cs > d->y_cs ? d->x_cs : d->y_cs) * 4 < CSG_MAX_RECORDS,
-              CSG_E_UNSUPPORTED, "%s: tensor too large for 32-bit byte offsets", who);
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.x_cs = d->x_cs; p.Cout = d->Cout; p.y_cs = d->y_cs;
   p.RXn = d->W / 8;
   p.RYn = d->H / 8;
-  const int64_t nr = (int64_t)d->B * p.RXn * p.RYn;
-  CSG_REQUIRE(nr < (1ll << 30), CSG_E_UNSUPPORTED, "%s: too many regions", who);
-  p.nregions = (int)nr;
   p.cblocks = (d->Cout + 63) / 64;
   p.kblocks = (d->Cin + 63) / 64;
   // one block per CU is resident: aim at ONE wave of blocks (256: every CU gets one block of equal length — measured 256 / 512 /
   // 768 / 1024: 4.92 / 5.00 / 5.13 / 5.24 ms over eight generator shapes, fewer slabs to sum and fewer epilogues), at least 16
   // stages per block, at most 256 slices
-  constexpr int target_blocks = 256;
-  const int tiles2d = p.cblocks * p.kblocks * 2;
-  int ns = (target_blocks + tiles2d - 1) / tiles2d;
-  const int max_ns = (int)((nr + 15) / 16);
-  if (ns > max_ns) ns = max_ns;
-  if (ns > 256) ns = 256;
-  if (ns < 1) ns = 1;
-  p.rps = (int)((nr + ns - 1) / ns);
-  p.nsplit = (int)((nr + p.rps - 1) / p.rps);
-  return CSG_OK;
+  return wino_wg_slice_plan(p, who, p.cblocks * p.kblocks * 2, 256, 16, 256);
+}
+
+static int ww_launch(const Wino4WgParams& p, const float* x, const float* dy, float* slabs, float* dbslabs, hipStream_t s) {
+  constexpr size_t ep_bytes = (size_t)2 * 18 * 32 * WW_EXR * 4;
+  constexpr size_t shm = (size_t)WW_LDS_FLOATS * 4 > ep_bytes ? (size_t)WW_LDS_FLOATS * 4 : ep_bytes;   // fixed: its own cap
+  const int rc = lds_limit<k_wino4_wgrad<false>, shm>(shm, "csg_wino4_bwd_weight");
+  if (rc) return rc;
+  ProfScope ps(K_WINO4_WGRAD, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
+  const dim3 grid((unsigned)(p.cblocks * p.kblocks * 2 * p.nsplit));
+  CSG_LAUNCH(k_wino4_wgrad<false>, grid, dim3(WW_THREADS), shm, s, p, x, dy, slabs, dbslabs);
+  return check_launch("csg_wino4_bwd_weight");
 }
 
 extern "C" {
 
+// two slabs per slice: one per half of the positions
 int64_t csg_wino4_bwd_weight_workspace(const csg_wino_desc* d) {
   Wino4WgParams p;
   if (ww_plan(d, p, "csg_wino4_bwd_weight_workspace")) return -1;
-  return (int64_t)p.nsplit * 2 * d->Cout * (9 * (int64_t)d->Cin + 1) * 4;
+  return wino_wg_workspace(d, p.nsplit * 2);
 }
 
 int csg_wino4_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                          int64_t workspace_bytes, void* stream) {
   Wino4WgParams p;
-  int rc = ww_plan(d, p, "csg_wino4_bwd_weight");
-  if (rc) return rc;
-  const int64_t wsize = (int64_t)d->Cout * 9 * d->Cin;
-  const int nslab = p.nsplit * 2;
-  const int64_t need = (int64_t)nslab * (wsize + d->Cout) * 4;
-  CSG_REQUIRE(workspace != nullptr && workspace_bytes >= need, CSG_E_WORKSPACE, "csg_wino4_bwd_weight: workspace %ld < %ld bytes",
-              (long)workspace_bytes, (long)need);
-  constexpr size_t ep_bytes = (size_t)2 * 18 * 32 * WW_EXR * 4;
-  constexpr size_t shm = (size_t)WW_LDS_FLOATS * 4 > ep_bytes ? (size_t)WW_LDS_FLOATS * 4 : ep_bytes;   // fixed: its own cap
-  rc = lds_limit<k_wino4_wgrad<false>, shm>(shm, "csg_wino4_bwd_weight");
+  const int rc = ww_plan(d, p, "csg_wino4_bwd_weight");
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  float* dbslabs = db != nullptr ? workspace + (int64_t)nslab * wsize : nullptr;
-  {
-    ProfScope ps(K_WINO4_WGRAD, 2.0 * p.B * p.H * p.W * 9.0 * p.Cin * p.Cout, s);
-    const dim3 grid((unsigned)(p.cblocks * p.kblocks * 2 * p.nsplit));
-    CSG_LAUNCH(k_wino4_wgrad<false>, grid, dim3(WW_THREADS), shm, s, p, x, dy, workspace, dbslabs);
-    rc = check_launch("csg_wino4_bwd_weight");
-    if (rc) return rc;
-  }
-  {
-    ProfScope ps(K_WGRAD_REDUCE, (double)(nslab + 1) * wsize * 4, s);
-    launch_slab_reduce(workspace, wsize, dw, dbslabs, db != nullptr ? d->Cout : 0, db, nslab, s);
-    rc = check_launch("csg_wino4_bwd_weight(reduce)");
-  }
-  return rc;
+  return wino_wg_run("csg_wino4_bwd_weight", "csg_wino4_bwd_weight(reduce)", d, p.nsplit * 2, false, dw, db, workspace,
+                     workspace_bytes, s, [&](float* slabs, float* dbslabs) { return ww_launch(p, x, dy, slabs, dbslabs, s); });
 }
 
 }  // extern "C"

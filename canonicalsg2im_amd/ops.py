@@ -198,12 +198,13 @@ def wino_variant(B, H, W, Cin, Cout, plain=False):
     F(4x4,3x3) works on (32 x 16 pixel region, 64 output channels) items, one per CU at a time: a launch with fewer than
     ~160 of them (small batches on the 32 x 32 / 64 x 64 maps: config C4's shard of 4 images) leaves half the chip idle and
     F(2x2,3x3) — 1.78x the multiplications in 4x the blocks — is 1.2-1.9x faster (profiles/archive/r05t_variant_ab.txt: 64-128 items;
-    at 192 the larger tile wins again).  `plain` (no bias / activation / residual / gate): such a launch is split over >= 256
-    input channels instead and stays on F(4x4,3x3)."""
-    if lib.csg_wino4_supported(_wino_desc(B, H, W, Cin, Cout)) != 1:
+    at 192 the larger tile wins again).  `plain` (no bias / activation / residual / gate): such a launch stays on F(4x4,3x3)
+    when the library's planner splits it over the input channels instead (from 256 of them: csrc/csg_wino_host.h)."""
+    d = _wino_desc(B, H, W, Cin, Cout)
+    if lib.csg_wino4_supported(d) != 1:
         return 2
     items = B * ((H + 15) // 16) * ((W + 31) // 32) * ((Cout + 63) // 64)
-    if items < WINO4_MIN_ITEMS and not (plain and Cin >= 256):
+    if items < WINO4_MIN_ITEMS and not (plain and lib.csg_wino4_conv_workspace(d) > 0):
         return 2
     return 4
 
@@ -221,6 +222,17 @@ def wino34_eligible(B, H, W, Cin, Cout, KH, KW, stride, pad, backward=False):
             and lib.csg_wino34_supported(_wino_desc(B, H, W, Cin, Cout), pad) == 1)
 
 
+# (pack_bytes, pack_weights, conv_workspace, conv) of the Winograd families 2: F(2x2,3x3), 4: F(4x4,3x3), 34: F(3x3,4x4) on 4x4
+# weights (its convolution calls take the padding behind the descriptor); by name: tests patch lib's attributes between calls
+_WINO_FAMILY = {2: ("csg_wino_pack_bytes", "csg_wino_pack_weights", "csg_wino_conv_workspace", "csg_wino_conv"),
+                4: ("csg_wino4_pack_bytes", "csg_wino4_pack_weights", "csg_wino4_conv_workspace", "csg_wino4_conv"),
+                34: ("csg_wino4_pack_bytes", "csg_wino34_pack_weights", "csg_wino34_conv_workspace", "csg_wino34_conv")}
+
+
+def _wino_family(variant):
+    return [getattr(lib, name) for name in _WINO_FAMILY[variant]]
+
+
 def wino_pack(weight, backward_data, sigma=None, variant=2):
     """Transformed weights U = G g G^T of a (Cout,Cin,3,3) weight in the MFMA operand order of k_wino_conv
     (variant 2: 16 positions) or k_wino4_conv (variant 4: 36 positions); variant 34: a (Cout,Cin,4,4) weight for
@@ -234,12 +246,11 @@ def wino_pack(weight, backward_data, sigma=None, variant=2):
         _note_pack_request(w, backward_data, variant)
     Cout, Cin = w.shape[0], w.shape[1]
     N, K = (Cin, Cout) if backward_data else (Cout, Cin)
-    nbytes = lib.csg_wino4_pack_bytes(N, K) if variant in (4, 34) else lib.csg_wino_pack_bytes(N, K)
-    packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    pack_bytes, pack_weights, _, _ = _wino_family(variant)
+    packed = torch.empty(pack_bytes(N, K) // 4, device=w.device, dtype=torch.float32)
     st = w.stride()
-    fn = {4: lib.csg_wino4_pack_weights, 34: lib.csg_wino34_pack_weights}.get(variant, lib.csg_wino_pack_weights)
-    check(fn(ptr(w), st[0], st[1], st[2], st[3], Cout, Cin, 1 if backward_data else 0, ptr(sigma), ptr(packed), stream()),
-          "wino_pack_weights")
+    check(pack_weights(ptr(w), st[0], st[1], st[2], st[3], Cout, Cin, 1 if backward_data else 0, ptr(sigma), ptr(packed),
+                       stream()), "wino_pack_weights")
     return packed
 
 
@@ -348,8 +359,7 @@ def prepack_weights(root):
             if backward_data and not grad:
                 continue
             N, K = (Cin, Cout) if backward_data else (Cout, Cin)
-            nbytes = lib.csg_wino4_pack_bytes(N, K) if variant == 4 else lib.csg_wino_pack_bytes(N, K)
-            packed = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+            packed = torch.empty(_wino_family(variant)[0](N, K) // 4, device=w.device, dtype=torch.float32)
             it = WinoPackItem()
             it.w, it.s_o, it.s_i, it.s_h, it.s_w = w.data_ptr(), st[0], st[1], st[2], st[3]
             it.Cout, it.Cin, it.backward_data, it.variant = Cout, Cin, 1 if backward_data else 0, variant
@@ -377,21 +387,23 @@ def _wino4_audit(kind, pixels, floats_per_pixel, packed):
         a[1] += 4.0 * pixels * floats_per_pixel + 4.0 * packed.numel()
 
 
-def _wino_launch(x, packed, bias, res, y, B, H, W, Cin, Cout, act, slope, what, gate=None, gate_slope=0.0, variant=2):
-    """Returns True when `gate` was folded into the launch (a launch split over the input channels has no epilogue:
-    the caller applies the gate in a separate pass then)."""
+def _wino_launch(x, packed, bias, res, y, B, H, W, Cin, Cout, act, slope, what, gate=None, gate_slope=0.0, variant=2, pad=1,
+                 may_split=True):
+    """One convolution of family `variant` (`pad`: F(3x3,4x4) only).  `may_split`: a launch without bias / activation /
+    residual asks the library for the slabs of a split over the input channels; a split launch has no epilogue, so `gate`
+    is left out of it.  Returns True when `gate` was folded into the launch (else the caller applies it in a separate pass)."""
     d = _wino_desc(B, H, W, Cin, Cout, act, slope)
     if variant == 4:
         _wino4_audit(what, B * H * W, Cin + Cout + (Cout if res is not None else 0) + (Cout if gate is not None else 0), packed)
-    ws_fn, conv_fn = (lib.csg_wino4_conv_workspace, lib.csg_wino4_conv) if variant == 4 else \
-        (lib.csg_wino_conv_workspace, lib.csg_wino_conv)
+    _, _, conv_workspace, conv = _wino_family(variant)
+    geom = (d, pad) if variant == 34 else (d,)
     ws, nws = None, 0
-    if bias is None and res is None and act == ACT_NONE:
-        nws = ws_fn(d)
+    if may_split and bias is None and res is None and act == ACT_NONE:
+        nws = conv_workspace(*geom)
         if nws > 0:
             ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32)
             gate = None
-    check(conv_fn(d, ptr(x), ptr(packed), ptr(bias), ptr(res), ptr(gate), gate_slope, ptr(y), ptr(ws), nws, stream()), what)
+    check(conv(*geom, ptr(x), ptr(packed), ptr(bias), ptr(res), ptr(gate), gate_slope, ptr(y), ptr(ws), nws, stream()), what)
     return gate is not None
 
 
@@ -586,8 +598,8 @@ def _conv_fwd(plan, x, w, b, res, packs):
             ut_pre = _take_dx_operand(plan, w)
         _wino_launch(x, up, b, res, y, B, IH, IW, Cin, Cout, act, slope, "wino_conv_fwd", variant=var)
     elif plan.fwd == "wino34":
-        check(lib.csg_wino34_conv(_wino_desc(B, IH, IW, Cin, Cout, act, slope), pad, ptr(x), ptr(wino_pack(w, False, None, 34)),
-                                  ptr(b), ptr(res), None, 0.0, ptr(y), None, 0, stream()), "wino34_conv_fwd")
+        _wino_launch(x, wino_pack(w, False, None, 34), b, res, y, B, IH, IW, Cin, Cout, act, slope, "wino34_conv_fwd",
+                     variant=34, pad=pad, may_split=False)                  # the forward pass never splits
     elif plan.fwd == "gemm":
         # a matrix product: rows = pixels (or the rows of a Linear), csrc/gemm.hip
         w2 = w.detach().reshape(Cout, Cin)
@@ -662,16 +674,11 @@ def _conv_bwd(plan, dy, x, w, y, need, packs, ut_pre):
         gated = _wino_launch(dpre, ut, None, None, dx, B, IH, IW, Cout, Cin, ACT_NONE, 0.0, "wino_conv_bwd_data", gate=gate,
                              gate_slope=gate_slope, variant=var) or in_act is None
     elif fam == "wino34":
-        # dX = conv4x4(dY, flipped W^T) with padding 3 - pad: the same F(3x3,4x4) kernel, channel counts swapped
+        # dX = conv4x4(dY, flipped W^T) with padding 3 - pad: the same F(3x3,4x4) kernel, channel counts swapped.  Without a
+        # gate a small tile grid is split over the input channels; a gated launch never asks for the slabs: its gate stays folded
         dx = empty_nhwc(B, Cin, IH, IW, dev)
-        d34 = _wino_desc(B, OH, OW, Cout, Cin)
-        ws, nws = None, 0
-        if in_act is None:                      # a small tile grid is split over the input channels (slabs + ordered sum)
-            nws = lib.csg_wino34_conv_workspace(d34, 3 - pad)
-            if nws > 0:
-                ws = torch.empty(nws // 4, device=dev, dtype=torch.float32)
-        check(lib.csg_wino34_conv(d34, 3 - pad, ptr(dpre), ptr(wino_pack(w, True, None, 34)), None, None, ptr(gate), gate_slope,
-                                  ptr(dx), ptr(ws), nws, stream()), "wino34_conv_bwd_data")
+        _wino_launch(dpre, wino_pack(w, True, None, 34), None, None, dx, B, OH, OW, Cout, Cin, ACT_NONE, 0.0,
+                     "wino34_conv_bwd_data", gate=gate, gate_slope=gate_slope, variant=34, pad=3 - pad, may_split=in_act is None)
         gated = True
     elif fam == "gemm":
         # dX (M, Cin) = dY (M, Cout) . W^T stored [Cin][Cout] (the reduction index contiguous), the producer's

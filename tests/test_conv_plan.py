@@ -177,6 +177,66 @@ def test_variant_follows_the_grid(built):
     assert ops.wino_variant(4, 16, 16, 512, 512) == 2             # below 32 pixels: never F(4x4,3x3)
 
 
+def test_winograd_split_and_slice_rules_hold_at_their_boundaries(built):
+    """The host rules csrc/csg_wino_host.h holds once, as the C ABI's size functions report them: the split over the input
+    channels (under 384 blocks, cut towards 512; F(2x2,3x3): from 16 stages of 16 channels, 8 per range; F(4x4,3x3) and
+    F(3x3,4x4): from 32 stages of 8 channels, 16 per range), the slices of the two weight gradients (1024 blocks, >= 8 regions,
+    <= 512 slices; 256 blocks, >= 16 regions, <= 256 slices, two slabs per slice) and the pack sizes (16 | 36 positions).  Every
+    expected value is the answer of the library before these rules were shared; each sits where one constant decides it."""
+    from canonicalsg2im_amd._lib import lib
+    ops = built
+
+    def d(B, H, W, Cin, Cout, act=NONE):
+        return ops._wino_desc(B, H, W, Cin, Cout, act, 0.2 if act else 0.0)
+
+    f2 = {(1, 32, 32, 2048, 128): 8388608,          # 2 blocks, 128 stages: 16 ranges of 8 stages
+          (1, 32, 32, 256, 128): 1048576,           # 16 stages: the fewest that split, 2 ranges
+          (1, 32, 32, 240, 128): 0,                 # 15 stages
+          (2, 64, 64, 256, 256): 16777216,          # 256 blocks: 2 ranges
+          (3, 64, 64, 256, 256): 0,                 # 384 blocks fill the chip
+          (1, 8, 8, 2048, 128): 524288,             # 4 x 4 tile regions
+          (383, 8, 8, 256, 64): 12550144,           # 383 blocks still split
+          (7, 8, 8, 9472, 64): 8486912,             # 7 blocks: ceil(512 / 7) = 74 ranges (511 would give 73)
+          (2, 64, 64, 640, 128): 16777216}          # 128 blocks: 512 / 128 = 4 ranges (513 would give 5)
+    for k, want in f2.items():
+        assert lib.csg_wino_conv_workspace(d(*k)) == want, k
+    assert lib.csg_wino_conv_workspace(d(1, 32, 32, 2048, 128, LEAKY)) == 0        # an epilogue: never split
+    f4 = {(1, 32, 64, 256, 64): 1048576,            # 32 stages: the fewest that split
+          (1, 32, 64, 248, 64): 0,                  # 31 stages
+          (1, 32, 64, 512, 64): 2097152,            # 64 stages: 4 ranges of 16
+          (1, 32, 64, 480, 64): 1572864,            # 60 stages: 3 ranges (15 per range would give 4)
+          (4, 64, 64, 512, 256): 67108864,          # 128 blocks: ceil(512 / 128) = 4 ranges
+          (6, 64, 64, 512, 256): 75497472,          # 192 blocks: 3 ranges
+          (1, 16, 16, 512, 64): -1}                 # narrower than 32 pixels: refused
+    for k, want in f4.items():
+        assert lib.csg_wino4_conv_workspace(d(*k)) == want, k
+    f34 = {(1, 31, 31, 512, 64): (921600, 1048576),          # 30 x 30 | 32 x 32 outputs, 64 stages: 4 ranges
+           (1, 31, 31, 256, 64): (460800, 524288),           # 32 stages
+           (1, 31, 31, 248, 64): (0, 0),                     # 31 stages
+           (2, 63, 63, 512, 512): (31490048, 33554432),
+           (16, 31, 31, 512, 512): (0, 0)}                   # 1152 blocks
+    for k, want in f34.items():
+        assert (lib.csg_wino34_conv_workspace(d(*k), 1), lib.csg_wino34_conv_workspace(d(*k), 2)) == want, k
+    wg = {(1, 8, 8, 64, 64): (147712, 295424),               # one slice: one slab | its two halves
+          (1, 32, 32, 128, 128): (1180672, 1180672),         # 16 regions: 2 slices of 8 | 1 slice of 16
+          (4, 64, 64, 256, 128): (37765120, 37765120),       # 256 regions: 32 slices of 8 | 16 slices of 16, x 2
+          (1, 12, 12, 64, 64): (-1, -1),                     # neither stage tiles the image
+          (1, 24, 40, 64, 64): (-1, 295424),                 # 8 x 8-pixel stages do, 16 x 2-tile stages do not
+          (31, 8, 8, 64, 64): (590848, 590848),              # 31 regions: 4 slices (7 per slice: 5) | 2 x 2 (15: 3)
+          (33, 8, 8, 64, 64): (738560, 886272),              # 33 regions: 5 slices (9 per slice: 4) | 3 x 2 (17: 2)
+          (16, 64, 64, 256, 128): (75530240, 37765120),      # the block targets decide: 1024 / 16 = 64 | 256 / 16 = 16, x 2
+          (4, 256, 256, 96, 64): (75732480, 28344320),       # ceil(1024 / 3) = 342 slices (1023: 341) | 256 / 4 = 64, x 2
+          (5, 256, 256, 32, 64): (37879808, 18939904)}       # at most 512 slices | 256 / 2 = 128, x 2
+    for k, want in wg.items():
+        assert (lib.csg_wino_bwd_weight_workspace(d(*k)), lib.csg_wino4_bwd_weight_workspace(d(*k))) == want, k
+    packs = {(1, 1): (16384, 36864), (33, 9): (65536, 147456), (128, 2048): (16777216, 37748736), (0, 8): (-1, -1)}
+    for k, want in packs.items():
+        assert (lib.csg_wino_pack_bytes(*k), lib.csg_wino4_pack_bytes(*k)) == want, k
+    # the variant rule asks that same planner: 128 items stay on F(4x4,3x3) from the 32 stages that split
+    assert ops.wino_variant(4, 64, 64, 248, 256, plain=True) == 2
+    assert ops.wino_variant(4, 64, 64, 256, 256, plain=True) == 4
+
+
 def test_default_rule_sends_the_narrow_shortcuts_to_the_gemm_kernels(built):
     """Mode "auto" (the default): N <= 256 <= K with at least 256 tiles — conv_s of the 64 x 64 and 128 x 128 residual blocks
     at batch 16; the graph encoder's wide linears and everything small stay on the implicit-GEMM kernel."""
