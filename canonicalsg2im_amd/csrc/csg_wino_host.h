@@ -26,6 +26,15 @@ static inline int wino_desc_check(const csg_wino_desc* d, const char* who, int p
   return CSG_OK;
 }
 
+// The convolution kernels load x a stage ahead of the channels they use, through a buffer descriptor that spans pixels * x_cs
+// floats from x: on a channel slice of a wider tensor that descriptor ends behind the tensor and the prefetch of the last
+// pixel would read there.  So the convolution entries take a dense x only; the weight gradients mask their loads at Cin
+// and keep x_cs.
+static inline int wino_conv_dense_x(const csg_wino_desc* d, const char* who) {
+  CSG_REQUIRE(d->x_cs == d->Cin, CSG_E_UNSUPPORTED, "%s: x must be dense (x_cs=%d, Cin=%d)", who, d->x_cs, d->Cin);
+  return CSG_OK;
+}
+
 // Split over the input channels when the tile grid alone cannot fill the chip (backward-data of the gamma/beta
 // convolutions: 128 output channels, 2048 input channels): only without an epilogue (bias / activation / residual / gate)
 // and with a dense output; the slabs are summed in a fixed order by k_slab_reduce.  A launch of fewer than 384 blocks is

@@ -415,7 +415,8 @@ constexpr size_t wn_conv_lds(int TW) {
 }
 
 static int wn_plan(const csg_wino_desc* d, WinoParams& p, size_t& shm, const char* who) {
-  const int rc = wino_desc_check(d, who, 16, [](const csg_wino_desc& d) { return (int64_t)d.B * d.H * d.W; });
+  int rc = wino_desc_check(d, who, 16, [](const csg_wino_desc& d) { return (int64_t)d.B * d.H * d.W; });
+  if (rc == CSG_OK) rc = wino_conv_dense_x(d, who);
   if (rc) return rc;
   CSG_REQUIRE(d->H % 2 == 0 && d->W % 2 == 0 && d->W >= 8, CSG_E_UNSUPPORTED, "%s: H=%d, W=%d must be even, W >= 8", who,
               d->H, d->W);

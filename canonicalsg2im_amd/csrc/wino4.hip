@@ -934,7 +934,8 @@ constexpr size_t w4_lds = (size_t)(W4Geo<T>::OFFTAB + W4_THREADS * 4) * 4;
 
 // T = 4: F(4x4,3x3), pad 1, output = input size.  T = 3: F(3x3,4x4), pad 1 or 2, output = input + 2 pad - 3.
 static int w4_plan(const csg_wino_desc* d, int T, int pad, Wino4Params& p, size_t& shm, const char* who) {
-  const int rc = wino_desc_check(d, who, 36, [](const csg_wino_desc& d) { return (int64_t)d.B * (d.H + 1) * (d.W + 1); });
+  int rc = wino_desc_check(d, who, 36, [](const csg_wino_desc& d) { return (int64_t)d.B * (d.H + 1) * (d.W + 1); });
+  if (rc == CSG_OK) rc = wino_conv_dense_x(d, who);
   if (rc) return rc;
   if (T == 4)
     CSG_REQUIRE(d->H % 4 == 0 && d->W % 4 == 0 && d->W >= 32 && d->H >= 16, CSG_E_UNSUPPORTED,

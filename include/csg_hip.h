@@ -238,7 +238,10 @@ int csg_conv_bwd_weight(const csg_conv_desc* d, const float* x, const float* dy,
 /* ---- K8w: 3x3 / stride 1 / pad 1 convolution by Winograd F(2x2,3x3) on fp32 MFMA (csrc/wino.hip) ----
  * The same nn.Conv2d call sites as above restricted to 3x3 kernels (generator.py:28; architecture.py:29-31;
  * normalization.py:89-94) and their backward-data passes: 16 instead of 36 multiplications per 2x2 output tile
- * and (cin,cout) pair, fp32 throughout.  x (B,H,W,Cin) NHWC with channel stride x_cs, y likewise with y_cs;
+ * and (cin,cout) pair, fp32 throughout.  x (B,H,W,Cin) NHWC, dense: every convolution entry of the Winograd families
+ * (csg_wino_conv, csg_wino4_conv, _conv_part, _conv_spade, csg_wino34_conv) refuses x_cs != Cin with CSG_E_UNSUPPORTED —
+ * the kernels load x a stage ahead through a descriptor of pixels * x_cs floats, which on a channel slice would end behind
+ * the tensor; the weight gradients below take x with channel stride x_cs.  y (and residual, gate) with channel stride y_cs;
  * H, W even; channel counts multiples of 4.  y = act(conv + bias) [+ residual] exactly as csg_conv_fwd.
  * `packed`: the transformed weights U = G g G^T in MFMA operand order, csg_wino_pack_bytes(N, K) bytes, produced by
  * csg_wino_pack_weights from the (Cout,Cin,3,3) weight with element strides (s_o,s_i,s_h,s_w) — contiguous or
@@ -269,8 +272,8 @@ int csg_wino_conv(const csg_wino_desc* d, const float* x, const float* packed, c
                   const float* residual, const float* gate, float gate_slope, float* y, float* workspace,
                   int64_t workspace_bytes, void* stream);
 /* Weight gradient of the same layers by Winograd F(3x3,2x2): dw [Cout][3][3][Cin] (the layout of
- * csg_conv_bwd_weight), db (Cout) or NULL; x (B,H,W,Cin) the layer's input, dy (B,H,W,Cout) the gradient of its
- * pre-activation output.  Deterministic: per-slice slabs in `workspace` + an ordered reduction.              */
+ * csg_conv_bwd_weight), db (Cout) or NULL; x (B,H,W,Cin) the layer's input with channel stride x_cs, dy (B,H,W,Cout) the
+ * gradient of its pre-activation output with channel stride y_cs.  Deterministic: per-slice slabs in `workspace` + an ordered reduction.              */
 int64_t csg_wino_bwd_weight_workspace(const csg_wino_desc* d);
 int csg_wino_bwd_weight(const csg_wino_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                         int64_t workspace_bytes, void* stream);
