@@ -180,6 +180,9 @@ SIGNATURES = {
     "csg_relation_agreement_workspace": (c_i64, [c_i64]),
     "csg_relation_agreement": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p,
                                        c_i64, c_p]),
+    "csg_layout_consistency": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "csg_graph_rows_select": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "csg_graph_rewrite": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i32, c_i32, c_f64, ctypes.c_uint64, c_p, c_p]),
     "csg_norm_apply_bwd_reduce": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64,
                                           c_i64, c_p]),
     "csg_norm_apply_bwd_dx": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_f64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_f32,

@@ -200,6 +200,115 @@ __global__ __launch_bounds__(64) void k_relation_agreement_fold(const int64_t* _
   }
 }
 
+// ---- layout consistency: two layouts of the same objects (the robustness run: graph A against its rewritten graph B) -----
+// Per counted object the IoU of the two clamped boxes (jaccard_one) and the L1 distance of their centres; per ordered pair
+// (i, j) of counted objects the six verdicts of agrees_one on either layout.  One block per sample; both layouts are
+// staged once in LDS (2 x O x 16 bytes, O <= 256: a thread stages one object and, as 16-byte rows read by consecutive
+// lanes, conflict-free) and the lanes are strided over the O (O - 1) ordered pairs.  The counts are 20 integers per
+// thread (a sample has at most 65 280 pairs): a shuffle tree per wave, then the waves in order through LDS; the four fp64
+// sums through block_sum_f64.  No atomics: the same bits on every run.
+constexpr int kConsThreads = 256;
+constexpr int kConsCounts = 20;                // {in_a, in_b, in_both} x 6, same_pairs, pairs
+
+__device__ __forceinline__ float4 clamp01_box(float4 v) { return make_float4(clamp01(v.x), clamp01(v.y), clamp01(v.z), clamp01(v.w)); }
+
+// the six verdicts of one ordered pair as bits 0..5 (a NaN in the pair: none)
+__device__ __forceinline__ unsigned verdicts(float4 sb, float4 ob) {
+  const float2 none = make_float2(0.f, 0.f);
+  unsigned m = 0u;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) m |= agrees_one(k, sb, ob, none, none, false) ? (1u << k) : 0u;
+  return m;
+}
+
+__global__ __launch_bounds__(kConsThreads) void k_layout_consistency(const float4* __restrict__ boxes_a,
+                                                                    const float4* __restrict__ boxes_b,
+                                                                    const uint8_t* __restrict__ counted, int O,
+                                                                    float* __restrict__ iou_ab, float* __restrict__ shift,
+                                                                    double* __restrict__ per_sample_f,
+                                                                    int64_t* __restrict__ per_sample_i) {
+  __shared__ float4 la[kConsThreads], lb[kConsThreads];
+  __shared__ uint8_t lc[kConsThreads];
+  __shared__ double fpart[kConsThreads / 64][4];
+  __shared__ unsigned ipart[kConsThreads / 64][kConsCounts];
+  const int b = blockIdx.x, o = threadIdx.x;
+  const int64_t obj = (int64_t)b * O;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (o < O) {                                   // O <= 256: one object per thread
+    const float4 pa = boxes_a[obj + o], pb = boxes_b[obj + o];
+    const bool on = counted[obj + o] != 0;
+    la[o] = pa, lb[o] = pb, lc[o] = on ? 1 : 0;
+    float v = 0.f, d = 0.f;
+    if (on) {
+      const float4 ca = clamp01_box(pa), cb = clamp01_box(pb);
+      v = jaccard_one(ca, cb);                   // its own clamp of the first box changes nothing
+      const float axc = __fadd_rn(ca.x, 0.5f * ca.z), ayc = __fadd_rn(ca.y, 0.5f * ca.w);
+      const float bxc = __fadd_rn(cb.x, 0.5f * cb.z), byc = __fadd_rn(cb.y, 0.5f * cb.w);
+      d = __fadd_rn(fabsf(__fsub_rn(axc, bxc)), fabsf(__fsub_rn(ayc, byc)));
+      acc[0] = (double)v;
+      acc[1] = v > 0.5f ? 1.0 : 0.0;
+      acc[2] = (double)d;
+      acc[3] = 1.0;
+    }
+    iou_ab[obj + o] = v;
+    shift[obj + o] = d;
+  }
+  __syncthreads();
+  unsigned cnt[kConsCounts];
+#pragma unroll
+  for (int q = 0; q < kConsCounts; ++q) cnt[q] = 0u;
+  const int npairs = O * (O - 1);
+  for (int q = threadIdx.x; q < npairs; q += kConsThreads) {
+    const int i = q / (O - 1), r = q - i * (O - 1), j = r + (r >= i ? 1 : 0);
+    if (lc[i] == 0 || lc[j] == 0) continue;
+    const unsigned ma = verdicts(la[i], la[j]), mb = verdicts(lb[i], lb[j]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      cnt[3 * k + 0] += (ma >> k) & 1u;
+      cnt[3 * k + 1] += (mb >> k) & 1u;
+      cnt[3 * k + 2] += ((ma & mb) >> k) & 1u;
+    }
+    cnt[18] += ma == mb ? 1u : 0u;
+    cnt[19] += 1u;
+  }
+#pragma unroll
+  for (int q = 0; q < kConsCounts; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt[q] += __shfl_down(cnt[q], off, 64);
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < kConsCounts; ++q) ipart[w][q] = cnt[q];
+  }
+  block_sum_f64<4, kConsThreads / 64>(acc, fpart);        // its barrier publishes ipart as well
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) per_sample_f[(int64_t)b * 4 + q] = acc[q];
+  }
+  if (threadIdx.x < kConsCounts) {
+    unsigned v = ipart[0][threadIdx.x];
+    for (int k = 1; k < kConsThreads / 64; ++k) v += ipart[k][threadIdx.x];
+    per_sample_i[(int64_t)b * kConsCounts + threadIdx.x] = (int64_t)v;
+  }
+}
+
+// totals += the samples, in ascending sample order: thread q < 4 owns one fp64 sum, thread 4 + q one integer count
+__global__ __launch_bounds__(64) void k_layout_consistency_fold(const double* __restrict__ per_sample_f,
+                                                                const int64_t* __restrict__ per_sample_i, int B,
+                                                                double* __restrict__ totals_f, int64_t* __restrict__ totals_i) {
+  const int q = threadIdx.x;
+  if (q < 4) {
+    double v = totals_f[q];
+    for (int b = 0; b < B; ++b) v += per_sample_f[(int64_t)b * 4 + q];
+    totals_f[q] = v;
+  } else if (q < 4 + kConsCounts) {
+    int64_t v = totals_i[q - 4];
+    for (int b = 0; b < B; ++b) v += per_sample_i[(int64_t)b * kConsCounts + q - 4];
+    totals_i[q - 4] = v;
+  }
+}
+
 }  // namespace csg
 
 using namespace csg;
@@ -275,6 +384,27 @@ int csg_relation_agreement(const float* boxes, const float* centers, const int64
              triplets, triplet_type, (int)O, (int)T, ids, tested, agrees, per_sample, (int64_t*)workspace);
   CSG_LAUNCH(k_relation_agreement_fold, dim3(kAgreeSlots), dim3(64), 0, s, (const int64_t*)workspace, (int)B, (int)P, ids, totals);
   return check_launch("csg_relation_agreement");
+}
+
+int csg_layout_consistency(const float* boxes_a, const float* boxes_b, const uint8_t* counted, int64_t B, int64_t O,
+                           float* iou_ab, float* shift, double* per_sample_f, int64_t* per_sample_i, double* totals_f,
+                           int64_t* totals_i, void* stream) {
+  CSG_REQUIRE(B > 0 && B <= 65535 && O > 0 && O <= kConsThreads, CSG_E_BADSHAPE,
+              "csg_layout_consistency: bad shape B=%ld O=%ld (B <= 65535, O <= %d)", (long)B, (long)O, kConsThreads);
+  CSG_REQUIRE(boxes_a != nullptr && boxes_b != nullptr && counted != nullptr && iou_ab != nullptr && shift != nullptr &&
+                  per_sample_f != nullptr && per_sample_i != nullptr && totals_f != nullptr && totals_i != nullptr,
+              CSG_E_BADSHAPE, "csg_layout_consistency: null operand");
+  CSG_REQUIRE(((uintptr_t)boxes_a | (uintptr_t)boxes_b) % 16 == 0 &&
+                  ((uintptr_t)per_sample_f | (uintptr_t)per_sample_i | (uintptr_t)totals_f | (uintptr_t)totals_i) % 8 == 0 &&
+                  ((uintptr_t)iou_ab | (uintptr_t)shift) % 4 == 0,
+              CSG_E_BADSHAPE,
+              "csg_layout_consistency: boxes must be 16-byte aligned, the fp64 and int64 outputs 8-byte, the fp32 outputs 4-byte");
+  hipStream_t s = (hipStream_t)stream;
+  CSG_LAUNCH(k_layout_consistency, dim3((unsigned)B), dim3(kConsThreads), 0, s, (const float4*)boxes_a, (const float4*)boxes_b,
+             counted, (int)O, iou_ab, shift, per_sample_f, per_sample_i);
+  CSG_LAUNCH(k_layout_consistency_fold, dim3(1), dim3(64), 0, s, (const double*)per_sample_f, (const int64_t*)per_sample_i, (int)B,
+             totals_f, totals_i);
+  return check_launch("csg_layout_consistency");
 }
 
 }  // extern "C"

@@ -2327,6 +2327,106 @@ def relation_agreement(boxes, triplets, triplet_type, vocab, totals, centers=Non
     return tested, agrees, per_sample
 
 
+REWRITE_MODES = {"one_sided": 0, "noise": 1}                              # CSG_REWRITE_* (include/csg_hip.h)
+REWRITE_DIRECTIONS = {"forward": 0, "backward": 1, "random": 2}
+
+
+def _location_ids(vocab, who):
+    p2i = vocab["pred_name_to_idx"]
+    missing = [n for n in PAIR_PREDICATES if n not in p2i]
+    if missing:
+        raise RuntimeError("%s: vocab lacks %s: the rows are those of the six location predicates" % (who, ", ".join(missing)))
+    return len(p2i), (ctypes.c_int32 * 8)(*[p2i[n] for n in PAIR_PREDICATES])
+
+
+def select_location_rows(triplets, triplet_type, vocab, num_objs=None):
+    """A batch's rows that are ORIGINAL and carry one of the six location predicates (csg_graph_rows_select): what the
+    robustness run rewrites.  triplets (B,T,3), triplet_type (B,T) int64 on the device.  Returns (rows (B,T,3) int64 — the
+    selected rows in input order, then [0, __padding__, 0]; counts (B,) int64 on the device).  `num_objs` = O: such a row
+    whose subject or object lies outside [0, O) is dropped and its sample's count is negative (-1 - the count); without
+    it only a negative index is.  Nothing is read back and nothing synchronises."""
+    if triplets.dtype != torch.int64 or triplets.dim() != 3 or triplets.shape[2] != 3:
+        raise RuntimeError("select_location_rows: triplets must be (B,T,3) int64 (collate contract)")
+    B, T, _ = triplets.shape
+    if triplet_type.dtype != torch.int64 or tuple(triplet_type.shape) != (B, T):
+        raise RuntimeError("select_location_rows: triplet_type must be (B,T) = %s int64, got %s" % (
+            (B, T), tuple(triplet_type.shape)))
+    O = (1 << 31) if num_objs is None else int(num_objs)
+    if not 1 <= O <= (1 << 31):
+        raise RuntimeError("select_location_rows: num_objs must be in [1, 2^31], got %r" % (num_objs,))
+    P, ids = _location_ids(vocab, "select_location_rows")
+    tr, tt = triplets.contiguous(), triplet_type.contiguous()
+    rows = torch.empty((B, T, 3), device=tr.device, dtype=torch.int64)
+    counts = torch.empty((B,), device=tr.device, dtype=torch.int64)
+    check(lib.csg_graph_rows_select(ptr(tr), ptr(tt), B, T, O, P, ids, ptr(rows), ptr(counts), stream()), "graph_rows_select")
+    return rows, counts
+
+
+def rewrite_rows(rows, counts, image_ids, vocab, mode, share, direction="random", seed=0):
+    """The first counts[b] rows of each sample rewritten into an equivalent (`mode` "one_sided") or a corrupted ("noise")
+    set of rows (csg_graph_rewrite; the hash and the rules: csrc/csg_rewrite.h, restated in tests/rewrite_cases.py).
+    rows (B,R,3), counts (B,), image_ids (B,) int64 on the device, as select_location_rows leaves the first two.  `share` in
+    [0, 1]: the probability that a row is rewritten; `direction` "forward" | "backward" | "random" (one_sided only):
+    the form a rewritten row takes; `seed`: an integer in [0, 2^64).  The result depends on (seed, image id, row) alone —
+    not on the batch a scene sits in, nor on the order of its rows.  Returns new rows (B,R,3); nothing is read back."""
+    if mode not in REWRITE_MODES:
+        raise RuntimeError("rewrite_rows: mode must be one of %s, got %r" % (" or ".join(repr(k) for k in REWRITE_MODES), mode))
+    if direction not in REWRITE_DIRECTIONS:
+        raise RuntimeError("rewrite_rows: direction must be one of %s, got %r" % (
+            " or ".join(repr(k) for k in REWRITE_DIRECTIONS), direction))
+    if isinstance(share, bool) or not isinstance(share, (int, float)) or not 0.0 <= float(share) <= 1.0:
+        raise RuntimeError("rewrite_rows: share must be a number in [0, 1], got %r" % (share,))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
+        raise RuntimeError("rewrite_rows: seed must be an integer in [0, 2^64), got %r" % (seed,))
+    if rows.dtype != torch.int64 or rows.dim() != 3 or rows.shape[2] != 3:
+        raise RuntimeError("rewrite_rows: rows must be (B,R,3) int64")
+    B, R, _ = rows.shape
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (B,):
+        raise RuntimeError("rewrite_rows: counts must be (B,) = (%d,) int64, got %s %s" % (B, tuple(counts.shape), counts.dtype))
+    if not torch.is_tensor(image_ids) or image_ids.dtype != torch.int64 or tuple(image_ids.shape) != (B,):
+        raise RuntimeError("rewrite_rows: image_ids must be a (B,) = (%d,) int64 tensor, got %s" % (
+            B, "%s %s" % (tuple(image_ids.shape), image_ids.dtype) if torch.is_tensor(image_ids) else type(image_ids).__name__))
+    P, ids = _location_ids(vocab, "rewrite_rows")
+    rw, cn, im = rows.contiguous(), counts.contiguous(), image_ids.contiguous()
+    out = torch.empty_like(rw)
+    check(lib.csg_graph_rewrite(ptr(rw), ptr(cn), ptr(im), B, R, P, ids, REWRITE_MODES[mode], REWRITE_DIRECTIONS[direction],
+                                float(share), seed, ptr(out), stream()), "graph_rewrite")
+    return out
+
+
+def layout_consistency(boxes_a, boxes_b, counted, totals_f, totals_i):
+    """Two layouts of the same objects compared (csg_layout_consistency): boxes_a, boxes_b (B,O,4) fp32 xywh, both clamped
+    to [0,1]; counted (B,O) uint8, the mask box_iou returns; O <= 256.  `totals_f` a dense float64 vector of 4 and
+    `totals_i` a dense int64 vector of 20 on the device, which the call ADDS to in place, the samples in ascending order.
+    Returns (iou_ab (B,O) fp32, shift (B,O) fp32 — the L1 distance of the box centres; both 0 where not counted;
+    per_sample_f (B,4) float64 = sum iou_ab, #(iou_ab > 0.5), sum shift, #counted; per_sample_i (B,20) int64 = {in_a,
+    in_b, in_both} for below, above, left of, right of, inside, surrounding — the ordered pairs of counted objects for
+    which the datasets' rule gives that relation in layout A, in B, in both — then same_pairs (all six verdicts equal)
+    and pairs).  Nothing is read back and nothing synchronises."""
+    if boxes_a.dim() != 3 or boxes_a.shape[2] != 4 or tuple(boxes_b.shape) != tuple(boxes_a.shape):
+        raise RuntimeError("layout_consistency: boxes_a and boxes_b must both be (B,O,4), got %s and %s" % (
+            tuple(boxes_a.shape), tuple(boxes_b.shape)))
+    B, O, _ = boxes_a.shape
+    if O > 256:
+        raise RuntimeError("layout_consistency: at most 256 objects per sample, got O = %d" % O)
+    if counted.dtype != torch.uint8 or tuple(counted.shape) != (B, O):
+        raise RuntimeError("layout_consistency: counted must be (B,O) = %s uint8, got %s %s" % (
+            (B, O), tuple(counted.shape), counted.dtype))
+    dev = counted.device
+    if totals_f.dtype != torch.float64 or totals_f.numel() != 4 or not totals_f.is_contiguous() or totals_f.device != dev:
+        raise RuntimeError("layout_consistency: totals_f must be a dense float64 vector of 4 on the batch's device")
+    if totals_i.dtype != torch.int64 or totals_i.numel() != 20 or not totals_i.is_contiguous() or totals_i.device != dev:
+        raise RuntimeError("layout_consistency: totals_i must be a dense int64 vector of 20 on the batch's device")
+    a, b, c = _f32(boxes_a.detach()).contiguous(), _f32(boxes_b.detach()).contiguous(), counted.contiguous()
+    iou_ab = torch.empty((B, O), device=dev, dtype=torch.float32)
+    shift = torch.empty((B, O), device=dev, dtype=torch.float32)
+    per_f = torch.empty((B, 4), device=dev, dtype=torch.float64)
+    per_i = torch.empty((B, 20), device=dev, dtype=torch.int64)
+    check(lib.csg_layout_consistency(ptr(a), ptr(b), ptr(c), B, O, ptr(iou_ab), ptr(shift), ptr(per_f), ptr(per_i),
+                                     ptr(totals_f), ptr(totals_i), stream()), "layout_consistency")
+    return iou_ab, shift, per_f, per_i
+
+
 def graph_csr(triplets, O):
     """(row_ptr (B,O+1) int32, col (B,2T) int32) — incident triplets per object, reference order."""
     B, T, _ = triplets.shape

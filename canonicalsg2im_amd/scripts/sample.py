@@ -55,6 +55,16 @@ model; on top of them:
                              triplets that the predicted layout obeys (ops.relation_agreement) by triplet type and by
                              predicate, and both by the number of objects in the graph.  --inception_weights FILE: the
                              Inception score of the predicted-layout pictures over 5 splits as well
+    --rewrite one_sided|noise    with --dataset packed_clevr_syn (refused with any other): the robustness run.  Every scene's
+                             minimal graph (A) is also rewritten on the device into graph B — one_sided: an EQUIVALENT
+                             graph, a share of the pairs stated in one direction only; noise: a share of the rows with a
+                             wrong location predicate — and both are laid out and drawn.  --rewrite_share S in [0, 1]
+                             (default 1), --rewrite_direction forward|backward|random (one_sided; default random),
+                             --rewrite_seed N (default 0).  The checkpoint's --learned_transitivity / --learned_converse
+                             are applied to both graphs.  Writes, besides the files above,
+                             generation/pred_box_pred_mask_rewritten/ and robustness.json: the IoU figures of both
+                             layouts, B's boxes against A's (IoU, centre shift), the pair relations both layouts share,
+                             B's agreement with the clean graph, and all of them by the number of objects
 
 The two modes without --split / --layouts deprocess with imagenet_deprocess whatever --img_deprocess says.
 
@@ -95,6 +105,13 @@ def build_parser():
                    help="--dataset packed_clevr_syn: a JSON file of scenes, read when it exists and written otherwise")
     p.add_argument('--inception_weights', default=None, type=str,
                    help="--dataset packed_clevr_syn: inception_v3_google-*.pth (or 'random', a stand-in)")
+    p.add_argument('--rewrite', default=None, choices=["one_sided", "noise"],
+                   help="--dataset packed_clevr_syn: the robustness run; every graph also rewritten into an equivalent "
+                        "(one_sided) or a corrupted (noise) one; writes robustness.json")
+    p.add_argument('--rewrite_share', default=1.0, type=float, help="--rewrite: the share of rows rewritten, in [0, 1]")
+    p.add_argument('--rewrite_direction', default="random", choices=["forward", "backward", "random"],
+                   help="--rewrite one_sided: the form a rewritten row takes")
+    p.add_argument('--rewrite_seed', default=0, type=int, help="--rewrite: the seed of the rows' hash and the converse draws")
     return p
 
 
@@ -121,6 +138,15 @@ def parse_args(argv=None):
     if len(given) > 1:
         raise SystemExit("%s exclude each other: a run draws a dataset split, a file of layouts or authored graphs" % (
             " and ".join(given)))
+    if args.rewrite is not None:
+        if args.dataset != SYN:
+            raise SystemExit("--rewrite %s goes with --dataset %s alone (got --dataset %s): the robustness run rewrites graphs "
+                             "whose every relation follows from the boxes; other datasets are out of its scope" % (
+                                 args.rewrite, SYN, args.dataset))
+        if not 0.0 <= args.rewrite_share <= 1.0:
+            raise SystemExit("--rewrite_share %r: a share in [0, 1] is needed" % (args.rewrite_share,))
+        if not 0 <= args.rewrite_seed < (1 << 32):
+            raise SystemExit("--rewrite_seed %r: an integer in [0, 2^32) is needed" % (args.rewrite_seed,))
     if args.dataset == SYN:
         if given:
             raise SystemExit("--dataset %s is a run of its own: %s does not go with it" % (SYN, given[0]))
@@ -225,20 +251,40 @@ def sample_generalisation(args, dev, dataset):
     print("data: %d scenes, %s" % (len(dataset), dataset.image_dir), flush=True)
     torch.manual_seed(0)
     sampler = Sampler(args, dev, ckpt)
-    builder = folder_builder(dataset, args, sampler, dev)
+    rewrite, builder_args = None, args
+    if args.rewrite is not None:
+        # the robustness run: the batches carry the plain minimal graph, so that a drawn edge is never taken for a source
+        # row; the checkpoint's learned_transitivity / learned_converse are applied to both graphs in generate_split
+        import argparse
+
+        from ..split import Rewrite, robustness_report
+        rewrite = Rewrite(args.rewrite, float(args.rewrite_share), args.rewrite_direction, int(args.rewrite_seed))
+        builder_args = argparse.Namespace(**dict(vars(args), learned_transitivity=0, learned_converse=0))
+    builder = folder_builder(dataset, builder_args, sampler, dev)
     tic = time.time()
     try:
         metrics, rows = generate_split(
             sampler, builder.batches(file_order_batches(len(dataset), args.batch_size)), args.output_dir,
             deprocess=args.img_deprocess, image_format=args.image_format, num_writers=args.num_writers,
-            max_pictures=args.max_pictures, split="synthetic", relations=True)
+            max_pictures=args.max_pictures, split="synthetic", relations=True,
+            **({} if rewrite is None else {"rewrite": rewrite}))
     finally:
         builder.close()
     torch.cuda.synchronize()
-    report = generalisation_report(
-        metrics, rows, dataset=SYN, checkpoint=args.checkpoint_name, seed=None if dataset.loaded else dataset.seed,
-        scenes=args.scenes, min_objects=min(len(s["objects"]) for s in dataset.scenes),
-        max_objects=max(len(s["objects"]) for s in dataset.scenes))
+    run = dict(dataset=SYN, checkpoint=args.checkpoint_name, seed=None if dataset.loaded else dataset.seed, scenes=args.scenes,
+               min_objects=min(len(s["objects"]) for s in dataset.scenes),
+               max_objects=max(len(s["objects"]) for s in dataset.scenes))
+    if rewrite is not None:
+        robust = robustness_report(metrics, rows, rewrite={"mode": rewrite.mode, "share": rewrite.share,
+                                                           "direction": rewrite.direction, "seed": rewrite.seed}, **run)
+        with open(os.path.join(args.output_dir, "robustness.json"), "w") as f:
+            json.dump(robust, f, indent=1)
+        c, r = robust["consistency"], robust["pair_relations"]
+        print("rewrite %s share %s: avg_iou %s -> %s; consistency avg_iou %s, avg_shift %s; same pairs %s of %s" % (
+            rewrite.mode, rewrite.share, robust["clean"]["avg_iou"], robust["rewritten"]["avg_iou"], c["avg_iou"], c["avg_shift"],
+            r["same_pairs"], r["pairs"]), flush=True)
+        metrics = {k: v for k, v in metrics.items() if k != "rewritten"}
+    report = generalisation_report(metrics, rows, **run)
     for k in ("avg_iou", "total_iou_05", "total_iou_03"):         # generate_clevr.py's three lines
         if k in metrics:
             print("%s: %s" % (k, metrics[k]), flush=True)

@@ -307,7 +307,7 @@ def clevr_triplets(objs, n_objs, vocab, rows, rows_host=None, use_transitivity=0
 
 def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transitivity=False, include_dummies=True,
                        learned_converse=False, converse_weights=None, uniforms=None, triplets=None, pairs=None,
-                       use_converse=False, pairs_host=None):
+                       use_converse=False, pairs_host=None, triplet_counts=None):
     """Batched `add_location_triplets` + `add_dummy_triplets` + `add_learnt_triplets` + collate padding.
 
     objs (B,O) or (B,O,A) int64 (attribute 0 is used, as `objs['shape']` in packed_clevr_dialog.py:207),
@@ -342,8 +342,29 @@ def canonical_triplets(objs, boxes, obj_centers, n_objs, vocab, learned_transiti
     all-pairs location relation is derived: ops.pair_relations gives every pair its predicate (`use_converse` as
     coco.py:404-421), the rows stay on the device (csg_canon_general_build_dev) and dummies, converse draws, transitive
     extras, order and padding follow as above.  The tensors may be on the host or the device; the host needs them
-    (refusals): `pairs_host` = their CPU copies spares the read-back of device tensors."""
+    (refusals): `pairs_host` = their CPU copies spares the read-back of device tensors.
+
+    `triplet_counts` (B,) int64 on the HOST, with `boxes=None` and `triplets` (B,R,3) int64 ON THE DEVICE: rows that never
+    were on the host (ops.select_location_rows, ops.rewrite_rows); a sample's first triplet_counts[b] rows are its rows, the
+    rest is ignored.  They go through csg_canon_general_build_dev as the sampled pairs do, and the graph is the one the same
+    rows would give as host `triplets`.  A negative count (a row the selection dropped) is refused."""
     p2i = vocab["pred_name_to_idx"]
+    if triplet_counts is not None:
+        if boxes is not None or obj_centers is not None or pairs is not None or not torch.is_tensor(triplets) \
+                or not triplets.is_cuda or any(name not in p2i for name in augmented_relations):
+            raise ValueError("canonical_triplets: triplet_counts goes with boxes=None, obj_centers=None, `triplets` on the "
+                             "device and a vocabulary that has the six location predicates")
+        counts_h = _host_int64(triplet_counts)
+        objs0 = (objs[..., 0] if objs.dim() == 3 else objs).contiguous()
+        if triplets.dtype != torch.int64 or triplets.dim() != 3 or triplets.shape[0] != objs0.shape[0] or triplets.shape[2] != 3 \
+                or tuple(counts_h.shape) != (objs0.shape[0],):
+            raise ValueError("canonical_triplets: triplets must be (B, R, 3) int64 and triplet_counts (B,); got %s and %s" % (
+                tuple(triplets.shape), tuple(counts_h.shape)))
+        _refuse_negative(counts_h, "canonical_triplets: triplet_counts[%d] is negative: a row of that sample named an object "
+                                   "outside the batch and was dropped when the rows were selected")
+        return _canonical_general(objs0, None, None, n_objs, vocab, _image_id(vocab), learned_transitivity, include_dummies,
+                                  learned_converse, converse_weights, uniforms, None, rel_dev=triplets.contiguous(),
+                                  rel_counts=counts_h)
     if boxes is None and obj_centers is None and triplets is not None and pairs is None \
             and any(name not in p2i for name in augmented_relations):
         # a vocabulary without the location predicates (the unpacked Visual Genome's): the rows alone, at most 64 per sample

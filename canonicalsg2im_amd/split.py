@@ -18,6 +18,9 @@ yields) through calls this package already has, in this order per batch and unde
     ops.relation_agreement        with relations=True only: whether the predicted layout obeys the batch's triplets, per image
                                   by triplet type and as running totals by type and predicate (`generalisation_report`
                                   makes the large-graph run's generalisation.json of them, on the host)
+    rewrite=Rewrite(...)          opt-in, the robustness walk: every graph also rewritten on the device into an equivalent or
+                                  a corrupted one (ops.select_location_rows, ops.rewrite_rows), laid out as well and compared
+                                  (ops.layout_consistency; `robustness_report` makes robustness.json) — see generate_split
 
 Nothing is read back inside the loop.  The uint8 pictures stay planar and leave, with the batch's ids, objects, boxes and
 IoU, in non-blocking copies to one of two pinned host buffers on a side stream (`PictureWriter`); a buffer whose copy has
@@ -32,6 +35,7 @@ gt_boxes, predicted_boxes, iou, over the rows `box_iou` counts — and `layouts.
 pictures from such rows with the generator alone: the scene-graph encoder is not run, so a generator-only checkpoint works.
 The rows carry boxes, not masks: a model that predicts masks draws its layouts from the boxes alone there.
 """
+import dataclasses
 import json
 import math
 import os
@@ -46,6 +50,32 @@ MAX_WRITER_THREADS = 16
 FORMATS = {"png": {}, "jpg": {"quality": 95}}
 SETS = ("gt", "generation/gt_box_gt_mask", "generation/pred_box_pred_mask", "layout/gt", "layout/pred")
 _BOX_KEYS = {"pred": "predicted_boxes", "gt": "gt_boxes"}
+REWRITTEN_SET = "generation/pred_box_pred_mask_rewritten"                   # generate_split(rewrite=...): the pictures of graph B
+LOCATION_RELATIONS = ("__below__", "__above__", "__left of__", "__right of__", "__inside__", "__surrounding__")   # slots 0..5
+
+
+@dataclasses.dataclass(frozen=True)
+class Rewrite:
+    """How generate_split rewrites every graph (ops.rewrite_rows): mode "one_sided" (an equivalent graph: a share of the
+    pairs stated in one direction only) or "noise" (a share of the rows with a wrong predicate), share in [0, 1],
+    direction "forward" | "backward" | "random" (one_sided), seed: of the rows' hash and of the converse draws."""
+    mode: str
+    share: float = 1.0
+    direction: str = "random"
+    seed: int = 0
+
+    def check(self):
+        from . import ops
+        if self.mode not in ops.REWRITE_MODES:
+            raise ValueError("rewrite: mode must be one of %s, got %r" % (" or ".join(repr(k) for k in ops.REWRITE_MODES), self.mode))
+        if self.direction not in ops.REWRITE_DIRECTIONS:
+            raise ValueError("rewrite: direction must be one of %s, got %r" % (
+                " or ".join(repr(k) for k in ops.REWRITE_DIRECTIONS), self.direction))
+        if isinstance(self.share, bool) or not isinstance(self.share, (int, float)) or not 0.0 <= self.share <= 1.0:
+            raise ValueError("rewrite: share must be a number in [0, 1], got %r" % (self.share,))
+        if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < (1 << 32):
+            raise ValueError("rewrite: seed must be an integer in [0, 2^32) (it seeds a numpy RandomState too), got %r" % (self.seed,))
+        return self
 
 
 def save_planar(array, path, **options):
@@ -281,9 +311,19 @@ class SplitRows:
             if "relations" in host:                     # generate_split(relations=True): {agreeing, tested} by triplet type
                 row["relation_agreement"] = {"agreeing": host["relations"][i, :, 0].tolist(),
                                              "tested": host["relations"][i, :, 1].tolist()}
+            if "rw_boxes_pred" in host:                 # generate_split(rewrite=...): the layout of the rewritten graph
+                pairs = host["rw_pairs"][i].tolist()
+                row["rewritten"] = {
+                    "boxes_pred": host["rw_boxes_pred"][i][keep].tolist(), "iou": host["rw_iou"][i][keep].tolist(),
+                    "consistency_iou": host["rw_cons_iou"][i][keep].tolist(), "shift": host["rw_shift"][i][keep].tolist(),
+                    "pair_relations": dict({name: {"in_a": pairs[3 * k], "in_b": pairs[3 * k + 1], "in_both": pairs[3 * k + 2]}
+                                            for k, name in enumerate(LOCATION_RELATIONS)},
+                                           same_pairs=pairs[18], pairs=pairs[19]),
+                    "relation_agreement": {"agreeing": host["rw_relations"][i, :, 0].tolist(),
+                                           "tested": host["rw_relations"][i, :, 1].tolist()}}
             self.rows.append(row)
             if self.paths is not None:
-                for name in SETS:
+                for name in SETS + (REWRITTEN_SET,):
                     if name in host:
                         self.files.submit(host[name][i], self.paths.of(name, image_id))
 
@@ -308,8 +348,86 @@ def _host_ids(batch):
     return ids
 
 
+_NOT_MINIMAL = ("generate_split(rewrite=...): the batch holds rows that are not ORIGINAL (transitive or converse edges): build "
+                "its batches with learned_transitivity = learned_converse = 0 at the dataset, so that a drawn edge is never "
+                "mistaken for a source row; the checkpoint's own settings are applied to both graphs here")
+
+
+class _RewriteWalk:
+    """The robustness half of generate_split: per batch graph A and graph B (`graphs`), then B's layout and the three
+    comparisons (`compare`); the running totals stay on the device until `summary`."""
+
+    def __init__(self, rewrite, sampler, vocab, dev):
+        import numpy as np
+        self.rewrite, self.sampler, self.vocab, self.dev = rewrite, sampler, vocab, dev
+        opt = sampler.opt
+        self.transitivity = bool(getattr(opt, "learned_transitivity", False))
+        self.converse = bool(getattr(opt, "learned_converse", False))
+        self.weights = None
+        if self.converse:
+            from .sg2im.model import get_conv_converse
+            self.weights = get_conv_converse(sampler.model).detach().cpu().numpy()
+        self.random = np.random.RandomState(rewrite.seed)           # the converse draws: never numpy's global stream
+        P = len(vocab["pred_name_to_idx"])
+        self.iou_totals = torch.zeros(4, device=dev, dtype=torch.float64)
+        self.rel_totals = torch.zeros((4, P, 2), device=dev, dtype=torch.int64)
+        self.cons_f = torch.zeros(4, device=dev, dtype=torch.float64)
+        self.cons_i = torch.zeros(20, device=dev, dtype=torch.int64)
+
+    def graphs(self, batch, image_ids):
+        """-> (triplets A, triplet_type A, (triplets B, triplet_type B))"""
+        from . import ops
+        from .sg2im.data.base_dataset import canonical_triplets
+        objs, triplets, triplet_type = batch[1], batch[3], batch[5]
+        host_objs = getattr(batch, "objs_host", None)
+        if host_objs is None or tuple(host_objs.shape) != tuple(objs.shape):
+            raise ValueError("generate_split(rewrite=...) needs batches that carry their object ids on the host as `objs_host` "
+                             "(sg2im.data.loader.HostBatch, what a BatchBuilder yields): the objects per sample are not read back")
+        n_objs = (host_objs[..., 0] != 0).sum(1).to(torch.int64) + 1          # the real objects and the `__image__` row
+        rows, counts = ops.select_location_rows(triplets, triplet_type, self.vocab, num_objs=objs.shape[1])
+        rows_b = ops.rewrite_rows(rows, counts, image_ids, self.vocab, self.rewrite.mode, self.rewrite.share,
+                                  self.rewrite.direction, self.rewrite.seed)
+        both = torch.cat([counts, (triplet_type != 0).any().to(torch.int64).view(1)]).cpu()     # the batch's one read-back
+        if int(both[-1]):
+            raise ValueError(_NOT_MINIMAL)
+        counts_h = both[:-1]
+        # a graph draws at most one number per original row, the dummies counted; both graphs see the same numbers
+        uniforms = self.random.random_sample(int(counts_h.clamp(min=0).sum()) + int(n_objs.sum())) if self.converse else None
+        made = [canonical_triplets(objs, None, None, n_objs, self.vocab, learned_transitivity=self.transitivity,
+                                   learned_converse=self.converse, converse_weights=self.weights, uniforms=uniforms,
+                                   triplets=r, triplet_counts=counts_h) for r in (rows, rows_b)]
+        return made[0][0], made[0][2], (made[1][0], made[1][2])
+
+    def compare(self, out, graph_b, objs, boxes, boxes_a, counted, triplets_a, triplet_type_a, image_id_obj, rescale, deprocess):
+        """B's layout against the ground truth, against the clean graph and against A's layout; -> B's pictures"""
+        from . import ops
+        u8, boxes_b, _ = self.sampler.generate(objs, graph_b[0], graph_b[1], rescale=rescale, deprocess=deprocess)
+        boxes_b = boxes_b.detach().float()
+        iou_b = ops.box_iou(boxes_b, boxes, objs, image_id_obj, self.iou_totals)[0]
+        agreement = ops.relation_agreement(boxes_b, triplets_a, triplet_type_a, self.vocab, self.rel_totals)[2]
+        cons_iou, shift, _, pairs = ops.layout_consistency(boxes_a.detach().float(), boxes_b, counted, self.cons_f, self.cons_i)
+        out.update({"rw_boxes_pred": boxes_b, "rw_iou": iou_b, "rw_cons_iou": cons_iou, "rw_shift": shift, "rw_pairs": pairs,
+                    "rw_relations": agreement})
+        return u8
+
+    def summary(self):
+        """The totals, read here once: what metrics["rewritten"] holds."""
+        t, f, i = self.iou_totals.cpu(), self.cons_f.cpu().tolist(), self.cons_i.cpu().tolist()
+        pair_relations = {name: {"in_a": i[3 * k], "in_b": i[3 * k + 1], "in_both": i[3 * k + 2],
+                                 "kept": (i[3 * k + 2] / i[3 * k]) if i[3 * k] else None}
+                          for k, name in enumerate(LOCATION_RELATIONS)}
+        pair_relations.update({"same_pairs": i[18], "pairs": i[19], "same_share": (i[18] / i[19]) if i[19] else None})
+        return {"avg_iou": float(t[0] / t[3]), "total_iou_05": float(t[1] / t[3]), "total_iou_03": float(t[2] / t[3]),
+                "num_boxes": float(t[3]),
+                "consistency": {"avg_iou": f[0] / f[3] if f[3] else None, "share_above_05": f[1] / f[3] if f[3] else None,
+                                "avg_shift": f[2] / f[3] if f[3] else None},
+                "pair_relations": pair_relations,
+                "relation_agreement": relation_summary(self.rel_totals.cpu().tolist(), self.vocab)}
+
+
 def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, draw_boxes=False, thickness=2,
-                   image_format="png", num_writers=8, max_pictures=0, split=None, draw_labels=False, relations=False):
+                   image_format="png", num_writers=8, max_pictures=0, split=None, draw_labels=False, relations=False,
+                   rewrite=None):
     """Walk `batches` (see the module docstring) -> (metrics, rows).  metrics: avg_iou, total_iou_05, total_iou_03 (the
     totals / counted boxes, float64, as Evaluator.check_model forms them) and num_boxes; empty for a model without a graph
     part.  With `out_dir` the pictures and layouts.json are written; without it only metrics and rows are made.
@@ -319,7 +437,18 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
     `relations` (opt-in; without it nothing below is made and every output is as before): whether the PREDICTED layout
     obeys the triplets it was made from (ops.relation_agreement on boxes_pred, box centres, in the loop and without a
     read-back): every row gets `relation_agreement` = {agreeing, tested} by triplet type, and metrics gets
-    `relation_agreement` (`relation_summary`) from one int64 (4,P,2) buffer of totals read once at the end."""
+    `relation_agreement` (`relation_summary`) from one int64 (4,P,2) buffer of totals read once at the end.
+    `rewrite` (a `Rewrite`; opt-in; without it every output is as before, key for key): the robustness walk.  The batches
+    must carry the plain minimal graph (the dataset's learned_transitivity and learned_converse off; a batch with a row
+    that is not ORIGINAL is refused) and their object ids on the host (`objs_host`).  Per batch the graph's location rows
+    are selected (ops.select_location_rows; the one read-back of the counts), graph A is built from them and graph B from
+    the rewritten rows (ops.rewrite_rows), both by canonical_triplets(boxes=None, ...) with the checkpoint's
+    learned_transitivity / learned_converse and the same converse draws, from a np.random.RandomState(seed).  Everything
+    above — pictures, boxes_pred, IoU, relations — is then made of graph A; graph B gets its own Sampler.generate,
+    ops.box_iou against the ground truth, ops.relation_agreement of its boxes against A's triplets (the clean graph) and
+    ops.layout_consistency(A, B).  Every row gains `rewritten` = {boxes_pred, iou, consistency_iou, shift, pair_relations,
+    relation_agreement}, metrics gains `rewritten` (its totals, read once at the end; `robustness_report` makes
+    robustness.json of both), and with `out_dir` B's pictures go to generation/pred_box_pred_mask_rewritten/."""
     from . import ops
     from .sample import NO_CPU
     from .sg2im.data.loader import HostBatch
@@ -337,6 +466,11 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
     relations = bool(relations) and model.has_graph
     rel_totals = torch.zeros((4, len(vocab["pred_name_to_idx"]), 2), device=dev, dtype=torch.int64) if relations else None
     palette = torch.tensor(authored.DEFAULT_PALETTE, dtype=torch.uint8).reshape(-1, 3).to(dev) if draw_boxes else None
+    rw = None
+    if rewrite is not None:
+        if not model.has_graph:
+            raise ValueError("generate_split(rewrite=...) needs a model with a graph part: it compares predicted layouts")
+        rw = _RewriteWalk(rewrite.check(), sampler, vocab, dev)
     taker = SplitRows(vocab, files, paths)
     rows, done = taker.rows, 0
     raising = True
@@ -352,6 +486,8 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                 if not objs.is_cuda:
                     raise RuntimeError(NO_CPU)
                 names = authored.labels_from_objs(_host_ids(batch), vocab) if draw_labels else None
+                if rw is not None:                      # graph A takes the batch's place; graph B is kept for below
+                    triplets, triplet_type, graph_b = rw.graphs(batch, torch.as_tensor(image_ids).to(dev).reshape(-1).to(torch.int64))
                 out = {}
                 u8 = sampler.generate(objs, triplets, triplet_type, boxes_gt=boxes, masks_gt=masks, rescale=rescale,
                                       deprocess=deprocess)[0]
@@ -384,6 +520,11 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                     if relations:
                         out["relations"] = ops.relation_agreement(boxes_pred.detach().float(), triplets, triplet_type, vocab,
                                                                   rel_totals)[2]
+                    if rw is not None:
+                        u8 = rw.compare(out, graph_b, objs, boxes, boxes_pred, counted, triplets, triplet_type, image_id_obj,
+                                        rescale, deprocess)
+                        if u8 is not None and paths is not None:
+                            out[REWRITTEN_SET] = u8
                 pictures.put(out, taker.take)
                 done += int(objs.shape[0])
                 if max_pictures and done >= max_pictures:
@@ -396,6 +537,8 @@ def generate_split(sampler, batches, out_dir=None, *, deprocess, rescale=True, d
                            "num_boxes": float(t[3])}
                 if relations:
                     metrics["relation_agreement"] = relation_summary(rel_totals.cpu().tolist(), vocab)
+                if rw is not None:
+                    metrics["rewritten"] = rw.summary()
         raising = False
     finally:
         if files is not None:
@@ -452,6 +595,62 @@ def generalisation_report(metrics, rows, **run):
     out = dict(run)
     out.update({"images": len(rows), "metrics": {k: v for k, v in metrics.items() if k != "relation_agreement"},
                 "relation_agreement": metrics.get("relation_agreement"), "by_num_objects": by_size})
+    return out
+
+
+def _iou_figures(ious):
+    n = len(ious)
+    if not n:
+        return {"num_boxes": 0}
+    return {"num_boxes": n, "avg_iou": sum(ious) / n, "total_iou_05": sum(v > 0.5 for v in ious) / n,
+            "total_iou_03": sum(v > 0.3 for v in ious) / n}
+
+
+def _pair_figures(per):
+    """[a row's rewritten.pair_relations] -> their sums, with kept = in_both / in_a and same_share = same_pairs / pairs"""
+    out = {}
+    for name in LOCATION_RELATIONS:
+        a, b, both = (sum(p[name][k] for p in per) for k in ("in_a", "in_b", "in_both"))
+        out[name] = {"in_a": a, "in_b": b, "in_both": both, "kept": (both / a) if a else None}
+    same, pairs = sum(p["same_pairs"] for p in per), sum(p["pairs"] for p in per)
+    out.update({"same_pairs": same, "pairs": pairs, "same_share": (same / pairs) if pairs else None})
+    return out
+
+
+def robustness_report(metrics, rows, **run):
+    """What the robustness run reports (robustness.json), on the host from `generate_split(rewrite=...)`'s two results.
+    `run`: what identifies the run — mode, share, direction, seed of the rewrite, checkpoint, scenes — recorded as given.
+    `clean` and `rewritten`: avg_iou, total_iou_05, total_iou_03 against the ground truth for the layout of graph A and of
+    graph B; `consistency` = {avg_iou, share_above_05, avg_shift} of B's boxes against A's; `pair_relations` = per location
+    predicate {in_a, in_b, in_both, kept = in_both / in_a} over the ordered pairs of objects, and same_pairs / pairs;
+    `relation_agreement`: of the rewritten layout with the CLEAN graph.  `by_num_objects`: every figure again by the number
+    of objects in the graph, summed from the per-image rows (the fp64 averages of a size are the host's sums of the rows'
+    fp32 values; the overall ones are the device's totals)."""
+    rewritten = metrics.get("rewritten")
+    if rewritten is None or any("rewritten" not in row for row in rows):
+        raise ValueError("robustness_report: metrics and rows of generate_split(rewrite=...) are needed")
+    sizes = {}
+    for row in rows:
+        sizes.setdefault(len(row["objects"]), []).append(row)
+    by_size = {}
+    for n in sorted(sizes):
+        group = [row["rewritten"] for row in sizes[n]]
+        cons, shift = [v for r in group for v in r["consistency_iou"]], [v for r in group for v in r["shift"]]
+        by_type = {EDGE_TYPES[k]: _rate(sum(r["relation_agreement"]["agreeing"][k] for r in group),
+                                        sum(r["relation_agreement"]["tested"][k] for r in group)) for k in range(4)}
+        by_size[str(n)] = {
+            "images": len(group), "clean": _iou_figures([v for row in sizes[n] for v in row["iou"]]),
+            "rewritten": _iou_figures([v for r in group for v in r["iou"]]),
+            "consistency": {"avg_iou": sum(cons) / len(cons), "share_above_05": sum(v > 0.5 for v in cons) / len(cons),
+                            "avg_shift": sum(shift) / len(shift)} if cons else None,
+            "pair_relations": _pair_figures([r["pair_relations"] for r in group]),
+            "relation_agreement": dict(_rate(sum(v["agreeing"] for v in by_type.values()),
+                                             sum(v["tested"] for v in by_type.values())), by_type=by_type)}
+    iou_keys = ("avg_iou", "total_iou_05", "total_iou_03", "num_boxes")
+    out = dict(run)
+    out.update({"images": len(rows), "clean": {k: metrics[k] for k in iou_keys}, "rewritten": {k: rewritten[k] for k in iou_keys},
+                "consistency": rewritten["consistency"], "pair_relations": rewritten["pair_relations"],
+                "relation_agreement": rewritten["relation_agreement"], "by_num_objects": by_size})
     return out
 
 

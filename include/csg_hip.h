@@ -725,6 +725,57 @@ int csg_relation_agreement(const float* boxes, const float* centers, const int64
                            int64_t P, const int32_t* pred_ids, uint8_t* tested, uint8_t* agrees, int64_t* per_sample,
                            int64_t* totals, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- layout metric: consistency of two layouts of the same objects (csrc/metrics.hip) ----------------
+ * The robustness run's metric: layout A from a graph, layout B from its rewritten graph.  (Added after revision 122 without
+ * a new revision number, as the three entries below: callers detect them by their symbols.)
+ * boxes_a, boxes_b (B,O,4) fp32 xywh, 16-byte aligned, BOTH clamped to [0,1] as xywh (a NaN stays NaN); counted (B,O) uint8,
+ * the mask csg_box_iou writes.  Per counted object: iou_ab = csg_box_iou's jaccard of the two clamped boxes, the same
+ * correctly rounded fp32 operations in the same order; shift = |axc - bxc| + |ayc - byc| with xc = x0 + 0.5f * w, every
+ * step one fp32 operation; both (B,O) fp32, 0 where not counted.  Per ORDERED pair (i, j), i != j, of counted objects and
+ * per location relation (slots below 0, above 1, left of 2, right of 3, inside 4, surrounding 5): the verdict of
+ * csg_relation_agreement's rule with box centres on layout A and on layout B; a NaN in a pair makes all of that
+ * layout's verdicts false.
+ * per_sample_f (B,4) fp64 = {sum iou_ab, #(iou_ab > 0.5), sum shift, #counted}: thread o holds object o, a shuffle tree
+ * (offsets 32 .. 1) per wave of 64, then waves 1, 2, 3 added to wave 0 in order.  per_sample_i (B,20) int64 = {in_a, in_b,
+ * in_both} per slot, then same_pairs (the six verdicts identical in A and B) and pairs.  totals_f[4] fp64 and totals_i[20]
+ * int64 += the samples in ascending sample order (running buffers the caller zeroes once).  No atomics: bit-reproducible.
+ * Two launches (one block per sample; the fold), stream ordered and capturable; nothing is read back.
+ * LIMITS: 1 <= B <= 65535, 1 <= O <= 256 (CSG_E_BADSHAPE otherwise, before the first launch).                         */
+int csg_layout_consistency(const float* boxes_a, const float* boxes_b, const uint8_t* counted, int64_t B, int64_t O,
+                           float* iou_ab, float* shift, double* per_sample_f, int64_t* per_sample_i, double* totals_f,
+                           int64_t* totals_i, void* stream);
+
+/* ---- graph rewriting for the robustness run (csrc/rewrite.hip; the hash and the row rules: csrc/csg_rewrite.h) ---------
+ * csg_graph_rows_select: a sample's rows that are of type 0 (ORIGINAL) and carry one of the six location predicates, in
+ * input order.  triplets (B,T,3), triplet_type (B,T) int64; pred_ids as csg_relation_agreement takes them.  rows (B,T,3)
+ * int64 (not triplets): the selected rows, then [0, __padding__, 0]; counts (B,) int64: their number.  Such a row whose
+ * subject or object lies outside [0, O) is dropped and the count is then NEGATIVE (-1 - the count), the convention of
+ * csg_canon_general_build_dev.  One block per sample, an in-block prefix sum; one launch.
+ * LIMITS: 1 <= B <= 65535, 0 <= T <= 2^20, 1 <= O <= 2^31, 1 <= P <= 4096.
+ *
+ * csg_graph_rewrite: out (B,R,3) = rows (B,R,3), the first counts[b] rows of each sample rewritten (a negative count:
+ * none); out may be rows.  The row count never changes; duplicates may appear.  image_id (B,) int64 on the device.
+ * h = the splitmix64-finaliser chain of csg_rewrite.h over (seed, image_id[b], a << 32 | b, slot); a row is selected when
+ * (h >> 32) < floor(share * 2^32 + 0.5).
+ * mode CSG_REWRITE_ONE_SIDED (0): the key is the row's forward form (a, b, slot_f) — a row of below, right of or
+ * surrounding has subject and object swapped and its slot ^ 1.  A selected row becomes the forward form (direction 0), the
+ * backward form (b, a, slot_f ^ 1) (1), or the one a coin of one more round names (2): both mirrored rows of a pair land
+ * on the same form.  mode CSG_REWRITE_NOISE (1): the key is the row as given; a selected row's predicate becomes one of
+ * the other five location predicates, uniformly, by ascending slot.  Integers only: the host restates every row exactly.
+ * Refused before any launch (CSG_E_BADSHAPE): share outside [0, 1] or NaN, an unknown mode or direction, predicate ids
+ * outside [0, P) or not distinct, a null operand, 1 <= B <= 65535, 0 <= R <= 2^20, 1 <= P <= 4096.  One launch.
+ * Both entries are stream ordered and capturable, use no atomics and read nothing back.                              */
+#define CSG_REWRITE_ONE_SIDED 0
+#define CSG_REWRITE_NOISE 1
+#define CSG_REWRITE_FORWARD 0
+#define CSG_REWRITE_BACKWARD 1
+#define CSG_REWRITE_RANDOM 2
+int csg_graph_rows_select(const int64_t* triplets, const int64_t* triplet_type, int64_t B, int64_t T, int64_t O, int64_t P,
+                          const int32_t* pred_ids, int64_t* rows, int64_t* counts, void* stream);
+int csg_graph_rewrite(const int64_t* rows, const int64_t* counts, const int64_t* image_id, int64_t B, int64_t R, int64_t P,
+                      const int32_t* pred_ids, int mode, int direction, double share, uint64_t seed, int64_t* out,
+                      void* stream);
+
 /* ---- K7 / pooling ------------------------------------------------------------------------------
  * nearest 2x upsample (generator.py:48,102-121) and its adjoint */
 /* F.interpolate(x, size=(OH, OW), mode='nearest') of an NHWC map (B,IH,IW,C), C a multiple of 4 — the resize of the
