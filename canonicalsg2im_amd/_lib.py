@@ -243,6 +243,11 @@ SIGNATURES = {
     "csg_softmax_rows": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p]),
     "csg_inception_score_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "csg_inception_score": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
+    "csg_crop_windows": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p]),
+    "csg_crop_resize_bilinear": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_f32, c_i32, c_p, c_p]),
+    "csg_kid_sums_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "csg_kid_sums": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_f64, c_f64, c_i32, c_p, c_i64, c_p, c_p]),
+    "csg_feat_class_sums": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
 }
 
 

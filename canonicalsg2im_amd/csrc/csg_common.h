@@ -81,6 +81,10 @@ enum KernelId {
   K_INCEPTION_SCORE,
   K_DRAW_LABELS,
   K_DRAW_GRAPH,
+  K_CROP_WINDOWS,
+  K_CROP_RESIZE_BILINEAR,
+  K_KID_SUMS,
+  K_FEAT_CLASS_SUMS,
   K_COUNT
 };
 

@@ -23,6 +23,7 @@ __all__ = [
     "norm_act_pair", "graph_csr", "gather_concat", "segment_avg", "layout_pyramid", "layout_paint", "disc_input", "crop_objects", "maxpool2", "avgpool2", "l1_mean",
     "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "preprocess_images", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
     "conv2d_forward", "pool3", "spatial_mean", "resize_bilinear", "feat_stats", "feat_stats_finalize", "softmax_rows", "inception_score", "POOL_MAX", "POOL_AVG9", "POOL_AVG_INSIDE",
+    "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums",
 ]
 
 
@@ -2871,3 +2872,94 @@ def inception_score(probs, splits):
     out = torch.empty((2 + splits,), device=probs.device, dtype=torch.float64)
     check(lib.csg_inception_score(ptr(probs), N, K, splits, ptr(ws), nbytes, ptr(out), stream()), "inception_score")
     return out
+
+
+# ------------------------------------------------------------------------------------ KID, object crops (csrc/quality.hip)
+def _dense_dev(t, dtype, what, name):
+    if not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a dense %s tensor" % (what, name, str(dtype).replace("torch.", "")))
+    ptr(t)                                                    # refuses a CPU tensor: no CPU path
+    return t
+
+
+def crop_windows(boxes, H, W):
+    """boxes (N,4) fp32 [x, y, w, h] in units of the picture -> int32 (N,4) pixel windows [X0, Y0, X1, Y1) of an H x W picture
+    (csg_crop_windows; the fp32 rule and the guarded conversion: include/csg_hip.h).  Every row, NaN and +-inf included, gives
+    a window inside the picture with at least one pixel."""
+    _f32(boxes)
+    _dense_dev(boxes, torch.float32, "crop_windows", "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.shape[0] < 1:
+        raise RuntimeError("crop_windows: boxes must be (N,4) with N >= 1, got %s" % (tuple(boxes.shape),))
+    win = torch.empty((boxes.shape[0], 4), device=boxes.device, dtype=torch.int32)
+    check(lib.csg_crop_windows(ptr(boxes.detach()), boxes.shape[0], int(H), int(W), ptr(win), stream()), "crop_windows")
+    return win
+
+
+def crop_resize_bilinear(pictures, windows, image_index, size, a=1.0, b=0.0, reverse=False):
+    """Cut window n out of picture image_index[n] and resize_bilinear it to `size` = (OH, OW), all crops in one launch
+    (csg_crop_resize_bilinear): pictures uint8 (B,H,W,3), windows int32 (N,4) as crop_windows gives them, image_index int32 (N).
+    Returns logical (N,4,OH,OW) with NHWC memory, channel 3 zero — bit for bit resize_bilinear of the window uploaded alone."""
+    OH, OW = int(size[0]), int(size[1])
+    _dense_dev(pictures, torch.uint8, "crop_resize_bilinear", "pictures")
+    if pictures.dim() != 4 or pictures.shape[3] != 3:
+        raise RuntimeError("crop_resize_bilinear: pictures must be a dense uint8 (B,H,W,3) tensor, got %s" % (tuple(pictures.shape),))
+    _dense_dev(windows, torch.int32, "crop_resize_bilinear", "windows")
+    _dense_dev(image_index, torch.int32, "crop_resize_bilinear", "image_index")
+    N = windows.shape[0]
+    if windows.dim() != 2 or windows.shape[1] != 4 or N < 1 or tuple(image_index.shape) != (N,):
+        raise RuntimeError("crop_resize_bilinear: windows must be (N,4) and image_index (N,) with N >= 1, got %s and %s" % (
+            tuple(windows.shape), tuple(image_index.shape)))
+    if windows.device != pictures.device or image_index.device != pictures.device:
+        raise RuntimeError("crop_resize_bilinear: windows and image_index must be on the pictures' device")
+    B, H, W = pictures.shape[0], pictures.shape[1], pictures.shape[2]
+    out = empty_nhwc(N, 4, OH, OW, pictures.device)
+    check(lib.csg_crop_resize_bilinear(ptr(pictures), B, H, W, ptr(windows), ptr(image_index), N, OH, OW, float(a), float(b),
+                                       int(bool(reverse)), ptr(out), stream()), "crop_resize_bilinear")
+    return out
+
+
+def kid_sums(fx, fy, ix, iy, gamma, coef0=1.0, degree=3):
+    """The three kernel sums of KID for S subsets at once (csg_kid_sums): fx (nx,D), fy (ny,D) fp32, D a multiple of 64;
+    ix, iy (S,m) int32 row indices.  -> (S,3) float64 on the device: sum_{i != j} k(x_i,x_j), sum_{i != j} k(y_i,y_j),
+    sum_{i,j} k(x_i,y_j) with k(u,v) = (gamma u.v + coef0)^degree.  Fixed summation order: the same bits on every run."""
+    for t, name in ((fx, "fx"), (fy, "fy")):
+        _f32(t)
+        _dense_dev(t, torch.float32, "kid_sums", name)
+        _no_grad_only("kid_sums", t)
+    for t, name in ((ix, "ix"), (iy, "iy")):
+        _dense_dev(t, torch.int32, "kid_sums", name)
+    if fx.dim() != 2 or fy.dim() != 2 or fx.shape[1] != fy.shape[1] or fx.shape[0] < 1 or fy.shape[0] < 1:
+        raise RuntimeError("kid_sums: features must be (nx,D) and (ny,D), got %s and %s" % (tuple(fx.shape), tuple(fy.shape)))
+    if ix.dim() != 2 or ix.shape != iy.shape or ix.shape[0] < 1:
+        raise RuntimeError("kid_sums: ix and iy must both be (S,m), got %s and %s" % (tuple(ix.shape), tuple(iy.shape)))
+    if any(t.device != fx.device for t in (fy, ix, iy)):
+        raise RuntimeError("kid_sums: every operand must be on one device")
+    S, m = ix.shape
+    D = fx.shape[1]
+    nbytes = max(int(lib.csg_kid_sums_workspace_bytes(S, m)), 8)       # -1 (m < 2, ...): the library's refusal follows
+    ws = torch.empty(nbytes // 8, device=fx.device, dtype=torch.float64)
+    out = torch.empty((S, 3), device=fx.device, dtype=torch.float64)
+    check(lib.csg_kid_sums(ptr(fx.detach()), fx.shape[0], ptr(fy.detach()), fy.shape[0], D, ptr(ix), ptr(iy), S, m, float(gamma),
+                           float(coef0), int(degree), ptr(ws), nbytes, ptr(out), stream()), "kid_sums")
+    return out
+
+
+def feat_class_sums(x, class_ids, sums, counts):
+    """sums (C,D) float64 += the rows of x (n,D) fp32 by class, rows in order; counts (C) int64 += their number
+    (csg_feat_class_sums).  class_ids (n) int32; an id outside [0, C) is skipped."""
+    _f32(x)
+    _dense_dev(x, torch.float32, "feat_class_sums", "features")
+    _dense_dev(class_ids, torch.int32, "feat_class_sums", "class_ids")
+    _dense_dev(sums, torch.float64, "feat_class_sums", "sums")
+    _dense_dev(counts, torch.int64, "feat_class_sums", "counts")
+    if x.dim() != 2 or tuple(class_ids.shape) != (x.shape[0],):
+        raise RuntimeError("feat_class_sums: features must be (n,D) and class_ids (n,), got %s and %s" % (
+            tuple(x.shape), tuple(class_ids.shape)))
+    n, D = x.shape
+    if sums.dim() != 2 or sums.shape[1] != D or tuple(counts.shape) != (sums.shape[0],):
+        raise RuntimeError("feat_class_sums: the accumulators must be (C,D) and (C,), got %s and %s" % (
+            tuple(sums.shape), tuple(counts.shape)))
+    if any(t.device != x.device for t in (class_ids, sums, counts)):
+        raise RuntimeError("feat_class_sums: every operand must be on the features' device")
+    check(lib.csg_feat_class_sums(ptr(x.detach()), ptr(class_ids), n, D, sums.shape[0], ptr(sums), ptr(counts), stream()),
+          "feat_class_sums")

@@ -6,6 +6,12 @@ reference's `calculate_frechet_distance` (evaluation/fid/fid_score.py:136-190) o
 `InceptionScore(net)` keeps the fp32 softmax rows of every picture as float64 on the device and computes the reference's
 `compute_score` (evaluation/inception.py:35-49) there.
 
+Opt-in companions (csrc/quality.hip): `KID(net)` keeps the fp32 features and gives the unbiased kernel distance
+over seeded subsets (`ops.kid_sums`, fp64, one fixed summation order); `ObjectFID(net)` is FID over the crops of every object's
+box (SceneFID; `ops.crop_windows`, `ops.crop_resize_bilinear`) with per-class feature means (`ops.feat_class_sums`,
+`class_mean_distance`: the reference's evaluation/fid.py:77-93); `crops_from_layouts` reads the boxes of a layouts.json.
+Equality of these numbers with any other KID or SceneFID implementation is unchecked: the rules are this project's own.
+
 LOADING THE REAL WEIGHT FILES AND THE NUMBERS THEY GIVE ARE UNCHECKED HERE (see inception.py): with `weights="random"` the
 network is a seeded stand-in and `stand_in` is True on both classes — every output built on it says so.
 """
@@ -128,3 +134,240 @@ class InceptionScore:
     def compute(self, splits=1):
         out = ops.inception_score(self.probabilities(), splits).cpu()
         return float(out[0]), float(out[1])
+
+
+# ------------------------------------------------------------------------------------------------ KID
+def kid_from_features(fx, fy, subsets=100, subset_size=1000, seed=0, degree=3, gamma=None, coef0=1.0):
+    """KID (Binkowski et al. 2018) of two sets of feature rows, fp32 (n0,D) and (n1,D) on the device: the mean and the
+    population std (np.std, ddof 0) over `subsets` subsets of the unbiased MMD^2 with k(u,v) = (gamma u.v + coef0)^degree,
+    gamma = 1 / D unless given.  m = min(subset_size, n0, n1) rows per subset (a cap is printed and reported as
+    `subset_size`); rng = np.random.RandomState(seed), per subset rng.choice(n0, m, replace=False) and then
+    rng.choice(n1, m, replace=False).  One `ops.kid_sums` call, one read of its (S,3) sums; per subset
+    MMD^2 = s0 / (m (m - 1)) + s1 / (m (m - 1)) - 2 s2 / m^2 in numpy fp64."""
+    n0, n1 = int(fx.shape[0]), int(fy.shape[0])
+    if n0 < 2 or n1 < 2:
+        raise ValueError("KID needs at least 2 rows per side, got %d and %d" % (n0, n1))
+    subsets, subset_size = int(subsets), int(subset_size)
+    if subsets < 1 or subset_size < 2:
+        raise ValueError("KID: subsets must be >= 1 and subset_size >= 2, got %d and %d" % (subsets, subset_size))
+    m = min(subset_size, n0, n1)
+    if m < subset_size:
+        print("KID: subset_size %d capped to %d, the smaller side" % (subset_size, m))
+    gamma = 1.0 / int(fx.shape[1]) if gamma is None else float(gamma)
+    rng = np.random.RandomState(seed)
+    ix, iy = np.empty((subsets, m), np.int32), np.empty((subsets, m), np.int32)
+    for s in range(subsets):
+        ix[s] = rng.choice(n0, m, replace=False)
+        iy[s] = rng.choice(n1, m, replace=False)
+    sums = ops.kid_sums(fx.contiguous(), fy.contiguous(), torch.from_numpy(ix).to(fx.device), torch.from_numpy(iy).to(fx.device),
+                        gamma, coef0, degree).cpu().numpy()
+    mmd2 = sums[:, 0] / (m * (m - 1)) + sums[:, 1] / (m * (m - 1)) - 2 * sums[:, 2] / (m * m)
+    return {"mean": float(np.mean(mmd2)), "std": float(np.std(mmd2)), "subsets": subsets, "subset_size": m, "n": [n0, n1]}
+
+
+class KID:
+    """KID of two sets of pictures over the features FID uses: `update(images, which)` (which 0 or 1; uint8 (B,H,W,3)
+    pictures or fp32 (B,3,H,W) images, prepared as for FID) or `update_features(feats, which)` keep the fp32 features on
+    the device; `compute()` -> {"mean", "std", "subsets", "subset_size", "n": [n0, n1], "stand_in"} (kid_from_features)."""
+
+    def __init__(self, net, dims=2048, channel_order="rgb", size=(299, 299), subsets=100, subset_size=1000, seed=0, degree=3,
+                 gamma=None, coef0=1.0):
+        if net.variant != "fid":
+            raise ValueError("KID needs InceptionV3('fid', ...), got the %r variant" % net.variant)
+        if dims not in inception.DIMS:
+            raise ValueError("KID: dims must be among %s" % (inception.DIMS,))
+        self.net, self.dims, self.channel_order, self.size = net, dims, channel_order, size
+        self.subsets, self.subset_size, self.seed = subsets, subset_size, seed
+        self.degree, self.gamma, self.coef0 = degree, gamma, coef0
+        self.stand_in = net.stand_in
+        self.clean()
+
+    def clean(self):
+        self._feats = ([], [])
+
+    @staticmethod
+    def _which(which):
+        if which not in (0, 1):
+            raise ValueError("KID: which must be 0 or 1, got %r" % (which,))
+        return which
+
+    def update(self, images, which):
+        self._which(which)
+        images = _to_device_images(images, None)
+        self.update_features(self.net(inception.prepare(images, "fid", self.size, self.channel_order), dims=self.dims), which)
+
+    def update_features(self, feats, which):
+        if feats.dim() != 2 or feats.shape[1] != self.dims or feats.dtype != torch.float32:
+            raise ValueError("KID: features must be fp32 (n, %d), got %s %s" % (self.dims, feats.dtype, tuple(feats.shape)))
+        self._feats[self._which(which)].append(feats.detach())
+
+    @property
+    def n(self):
+        return [sum(int(f.shape[0]) for f in side) for side in self._feats]
+
+    def compute(self):
+        n0, n1 = self.n
+        if n0 < 2 or n1 < 2:
+            raise ValueError("KID needs at least 2 pictures per side, got %d and %d" % (n0, n1))
+        fx, fy = (torch.cat(side) for side in self._feats)
+        out = kid_from_features(fx, fy, self.subsets, self.subset_size, self.seed, self.degree,
+                                1.0 / self.dims if self.gamma is None else self.gamma, self.coef0)
+        out["stand_in"] = bool(self.stand_in)
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ object-level FID
+def _host_rows(what, values, dtype, width):
+    a = np.asarray(values, dtype=dtype)
+    if a.ndim != (2 if width else 1) or (width and a.shape[1] != width):
+        raise ValueError("ObjectFID: %s must be %s, got an array of shape %s" % (
+            what, "(N,%d)" % width if width else "(N,)", a.shape))
+    return a
+
+
+class ObjectFID(FID):
+    """SceneFID (Sylvain et al. 2021): FID over the crops of every object's box.  `update(pictures_u8, boxes, image_index,
+    class_ids=None)`: uint8 (B,H,W,3) pictures on the device, boxes (N,4) [x, y, w, h] in units of the picture, image_index
+    (N) — host arrays (checked: finite values, index in range, ValueError naming the row) or device tensors.  `batch_size`
+    crops at a time, the remainder batch included: ops.crop_windows, ops.crop_resize_bilinear with the "fid" affine (2, -1),
+    the network, ops.feat_stats and, with class_ids (integers into `classes`), ops.feat_class_sums.  `statistics()` as
+    FID's; `class_means()` -> (means (C,dims) float64, NaN for a class without crops; counts (C) int64)."""
+
+    def __init__(self, net, dims=2048, channel_order="rgb", size=(299, 299), batch_size=50, classes=None):
+        super().__init__(net, dims=dims, channel_order=channel_order, size=size)
+        if int(batch_size) < 1:
+            raise ValueError("ObjectFID: batch_size must be positive")
+        self.batch_size = int(batch_size)
+        self.classes = None if classes is None else list(classes)
+
+    def clean(self):
+        super().clean()
+        self._class_sums, self._class_counts = None, None
+
+    def _operands(self, pictures, boxes, image_index, class_ids):
+        pictures = _to_device_images(pictures, None)
+        if pictures.dtype != torch.uint8 or pictures.dim() != 4 or pictures.shape[3] != 3:
+            raise ValueError("ObjectFID: pictures must be uint8 (B,H,W,3), got %s %s" % (pictures.dtype, tuple(pictures.shape)))
+        dev, B = pictures.device, int(pictures.shape[0])
+        if not torch.is_tensor(boxes):
+            host = _host_rows("boxes", boxes, np.float32, 4)
+            bad = np.flatnonzero(~np.isfinite(host).all(axis=1))
+            if bad.size:
+                raise ValueError("ObjectFID: boxes row %d is not finite: %s" % (int(bad[0]), host[bad[0]].tolist()))
+            boxes = torch.from_numpy(np.ascontiguousarray(host))
+        if not torch.is_tensor(image_index):
+            host = _host_rows("image_index", image_index, np.int64, 0)
+            bad = np.flatnonzero((host < 0) | (host >= B))
+            if bad.size:
+                raise ValueError("ObjectFID: image_index row %d is %d, outside the %d pictures" % (
+                    int(bad[0]), int(host[bad[0]]), B))
+            image_index = torch.from_numpy(host)
+        boxes = boxes.to(device=dev, dtype=torch.float32).contiguous()
+        image_index = image_index.to(device=dev, dtype=torch.int32).contiguous()
+        N = int(boxes.shape[0])
+        if boxes.dim() != 2 or boxes.shape[1] != 4 or N < 1 or tuple(image_index.shape) != (N,):
+            raise ValueError("ObjectFID: boxes must be (N,4) and image_index (N,) with N >= 1, got %s and %s" % (
+                tuple(boxes.shape), tuple(image_index.shape)))
+        if class_ids is not None:
+            if self.classes is None:
+                raise ValueError("ObjectFID: class_ids need ObjectFID(classes=[...]): the ids index that list")
+            if not torch.is_tensor(class_ids):
+                class_ids = torch.from_numpy(_host_rows("class_ids", class_ids, np.int64, 0))
+            class_ids = class_ids.to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(class_ids.shape) != (N,):
+                raise ValueError("ObjectFID: class_ids must be (N,) = (%d,), got %s" % (N, tuple(class_ids.shape)))
+        return pictures.contiguous(), boxes, image_index, class_ids
+
+    def _batches(self, pictures, boxes, image_index):
+        """(first crop, features) of every batch of `batch_size` crops, the remainder batch included."""
+        reverse = self.channel_order == "bgr"
+        windows = ops.crop_windows(boxes, pictures.shape[1], pictures.shape[2])
+        for i in range(0, int(boxes.shape[0]), self.batch_size):
+            j = i + self.batch_size
+            x = ops.crop_resize_bilinear(pictures, windows[i:j], image_index[i:j], self.size, 2.0, -1.0, reverse=reverse)
+            yield i, self.net(x, dims=self.dims)
+
+    def features(self, pictures, boxes, image_index):
+        """(N, dims) fp32 on the device: the features of the crops, in row order."""
+        pictures, boxes, image_index, _ = self._operands(pictures, boxes, image_index, None)
+        return torch.cat([f for _, f in self._batches(pictures, boxes, image_index)])
+
+    def update(self, pictures, boxes, image_index, class_ids=None):
+        """-> the (N, dims) features it accumulated (for `KID` on crops)."""
+        pictures, boxes, image_index, class_ids = self._operands(pictures, boxes, image_index, class_ids)
+        kept = []
+        for i, feats in self._batches(pictures, boxes, image_index):
+            self.update_features(feats, None if class_ids is None else class_ids[i:i + self.batch_size])
+            kept.append(feats)
+        return torch.cat(kept)
+
+    def update_features(self, feats, class_ids=None):
+        super().update_features(feats)
+        if class_ids is None:
+            return
+        if self._class_sums is None:
+            C = len(self.classes)
+            self._class_sums = torch.zeros(C, self.dims, device=feats.device, dtype=torch.float64)
+            self._class_counts = torch.zeros(C, device=feats.device, dtype=torch.int64)
+        ops.feat_class_sums(feats.contiguous(), class_ids.contiguous(), self._class_sums, self._class_counts)
+
+    def class_means(self):
+        if self._class_sums is None:
+            raise RuntimeError("ObjectFID.class_means: no crop with a class was given")
+        sums, counts = self._class_sums.cpu().numpy(), self._class_counts.cpu().numpy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return sums / counts[:, None].astype(np.float64), counts
+
+
+def class_mean_distance(means_a, counts_a, means_b, counts_b, min_crops=1):
+    """Per class with at least `min_crops` crops on both sides, |mu_b - mu_a|^2 of the class's feature means, and the mean of
+    those distances: the reference's per-class `get_fid` (evaluation/fid.py:77-93).  A class that has `min_crops` crops on
+    one side only is listed under "missing" and not averaged.  -> {"mean", "per_class": {class index: distance}, "missing"}."""
+    means_a, means_b = np.asarray(means_a, np.float64), np.asarray(means_b, np.float64)
+    counts_a, counts_b = np.asarray(counts_a), np.asarray(counts_b)
+    if means_a.shape != means_b.shape or counts_a.shape != counts_b.shape or counts_a.shape != means_a.shape[:1]:
+        raise ValueError("class_mean_distance: the two sides must have the same (C,dims) means and (C,) counts")
+    need = max(int(min_crops), 1)
+    per_class, missing = {}, []
+    for c in range(means_a.shape[0]):
+        in_a, in_b = counts_a[c] >= need, counts_b[c] >= need
+        if in_a and in_b:
+            diff = means_b[c] - means_a[c]
+            per_class[c] = float(diff.dot(diff))
+        elif in_a or in_b:
+            missing.append(c)
+    mean = float(np.mean(list(per_class.values()))) if per_class else float("nan")
+    return {"mean": mean, "per_class": per_class, "missing": missing}
+
+
+def crops_from_layouts(doc, which="gt", min_object_size=0.0):
+    """Host only.  `doc`: the dict of a layouts.json (scripts.sample --split).  -> {image id: (boxes [n][4], class keys [n])}
+    of the rows kept: `gt_boxes`, or `predicted_boxes` with which="pred".  The class key is the row's `objects` entry, or
+    json.dumps(entry, sort_keys=True) when it is not a string.  A row whose w * h < min_object_size, or whose box is not
+    finite, is left out."""
+    import json
+    if which not in ("gt", "pred"):
+        raise ValueError("crops_from_layouts: which must be 'gt' or 'pred', got %r" % (which,))
+    if not isinstance(doc, dict) or not isinstance(doc.get("images"), list):
+        raise ValueError("crops_from_layouts: the document has no 'images' list")
+    key = "gt_boxes" if which == "gt" else "predicted_boxes"
+    out = {}
+    for index, row in enumerate(doc["images"]):
+        for need in ("image_id", "objects", key):
+            if need not in row:
+                raise ValueError("crops_from_layouts: images[%d] has no %r%s" % (
+                    index, need, " (which='pred' needs the rows of a run that predicted boxes)" if need == "predicted_boxes" else ""))
+        names, boxes = row["objects"], row[key]
+        if len(names) != len(boxes):
+            raise ValueError("crops_from_layouts: images[%d] has %d objects and %d %s" % (index, len(names), len(boxes), key))
+        kept_boxes, kept_keys = [], []
+        for name, box in zip(names, boxes):
+            box = [float(v) for v in box]
+            if len(box) != 4 or not all(np.isfinite(box)) or box[2] * box[3] < min_object_size:
+                continue
+            kept_boxes.append(box)
+            kept_keys.append(name if isinstance(name, str) else json.dumps(name, sort_keys=True))
+        if row["image_id"] in out:
+            raise ValueError("crops_from_layouts: image id %r a second time" % (row["image_id"],))
+        out[row["image_id"]] = (kept_boxes, kept_keys)
+    return out

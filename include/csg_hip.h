@@ -1147,6 +1147,45 @@ int64_t csg_inception_score_workspace(int64_t N, int64_t K, int64_t splits);
 int csg_inception_score(const double* probs, int64_t N, int64_t K, int64_t splits, double* workspace, int64_t workspace_bytes,
                         double* out, void* stream);
 
+/* ---- KID and the object-level FID (SceneFID): the crop stage and the sums behind them (csrc/quality.hip) -------------
+ * (Added after revision 122 without a new revision number: callers detect the entries by their symbols.)  As above: stream
+ * ordered and capturable, no atomics, every sum in one fixed order, nothing read back.
+ *
+ * csg_crop_windows: boxes (N,4) fp32 [x, y, w, h] in units of the picture, 16-byte aligned -> windows (N,4) int32
+ * [X0, Y0, X1, Y1), 16-byte aligned.  In fp32, one operation each: fx0 = x * W, fx1 = (x + w) * W;
+ * X0 = clamp(floor(fx0), 0, W - 1), X1 = clamp(ceil(fx1), X0 + 1, W); likewise for y with H.  The conversion to int is
+ * guarded: a value that is not >= 0 becomes 0 and a value above the side becomes the side, before the cast — every bit
+ * pattern (NaN, +-inf) gives a window inside the picture with at least one pixel.  H and W in 1..16384.               */
+int csg_crop_windows(const float* boxes, int64_t N, int64_t H, int64_t W, int32_t* windows, void* stream);
+/* "Cut the window out, then csg_resize_bilinear it", one launch over all N crops: pictures uint8 (B,H,W,3), windows as
+ * csg_crop_windows writes them, image_index (N) int32 -> out fp32 (N,OH,OW,4), the fourth channel 0.  Per crop the arithmetic
+ * of csg_resize_bilinear on uint8 with the window as the whole picture, operation for operation: sy = (float)(Y1 - Y0) /
+ * (float)OH, fy = max((oy + 0.5f) * sy - 0.5f, 0), the taps clamped to the window and offset by (Y0, X0), bytes / 255, the
+ * same four products and three sums, a * v + b; reverse as there.  The kernel clamps the window to the picture (at least
+ * one pixel) and image_index to [0, B) in integers before it forms an address: it reads inside `pictures` whatever the
+ * two arrays hold.                                                                                                     */
+int csg_crop_resize_bilinear(const uint8_t* pictures, int64_t B, int64_t H, int64_t W, const int32_t* windows,
+                             const int32_t* image_index, int64_t N, int64_t OH, int64_t OW, float a, float b, int32_t reverse,
+                             float* out, void* stream);
+/* The three kernel sums of KID (Binkowski et al. 2018) for S subsets at once, no Gram matrix in memory.  fx (nx,D), fy (ny,D)
+ * fp32, D a multiple of 64 (at most 8192); ix, iy (S,m) int32 row indices into them (clamped to the table before use).  With
+ * k(u,v) = (gamma u.v + coef0)^degree, degree in {1,2,3}, over the subset's rows:
+ *   out[s,0] = sum_{i != j} k(x_i,x_j)   out[s,1] = sum_{i != j} k(y_i,y_j)   out[s,2] = sum_{i,j} k(x_i,y_j)    (S,3) fp64.
+ * A block owns a 64 x 64 tile of one matrix of one subset (xx and yy: the upper triangle, off-diagonal tiles doubled,
+ * i = j skipped), a thread 4 x 4 dot products in fp64 registers, columns in order; a tile's 256 partial sums are added by
+ * a fixed tree into the workspace, a second launch adds a matrix's tiles in index order.  Rows past m in the last tile
+ * are masked, never read.  LIMITS: 2 <= m <= 65536 (CSG_E_BADSHAPE otherwise), 1 <= S <= 65535;
+ * csg_kid_sums_workspace_bytes(S, m) bytes of workspace (-1 outside the limits), 8-byte aligned.                       */
+int64_t csg_kid_sums_workspace_bytes(int64_t S, int64_t m);
+int csg_kid_sums(const float* fx, int64_t nx, const float* fy, int64_t ny, int64_t D, const int32_t* ix, const int32_t* iy,
+                 int64_t S, int64_t m, double gamma, double coef0, int32_t degree, void* workspace, int64_t workspace_bytes,
+                 double* out, void* stream);
+/* sums (C,D) fp64 += the rows of x (n,D) fp32 whose class_ids (n) int32 entry is the class, rows in order; counts (C) int64 +=
+ * their number (running buffers the caller zeroes once).  One block per (class, 64-column slab); an id outside [0, C) is
+ * skipped.  D a multiple of 64, at most 8192; C <= 65535.                                                             */
+int csg_feat_class_sums(const float* x, const int32_t* class_ids, int64_t n, int64_t D, int64_t C, double* sums, int64_t* counts,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
