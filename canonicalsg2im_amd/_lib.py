@@ -248,6 +248,11 @@ SIGNATURES = {
     "csg_kid_sums_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "csg_kid_sums": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_f64, c_f64, c_i32, c_p, c_i64, c_p, c_p]),
     "csg_feat_class_sums": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
+    "csg_manifold_column_chunks": (c_i64, [c_i64, c_i64]),
+    "csg_knn_radii_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "csg_knn_radii": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
+    "csg_ball_counts_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "csg_ball_counts": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p]),
 }
 
 

@@ -85,6 +85,8 @@ enum KernelId {
   K_CROP_RESIZE_BILINEAR,
   K_KID_SUMS,
   K_FEAT_CLASS_SUMS,
+  K_KNN_RADII,
+  K_BALL_COUNTS,
   K_COUNT
 };
 

@@ -23,7 +23,7 @@ __all__ = [
     "norm_act_pair", "graph_csr", "gather_concat", "segment_avg", "layout_pyramid", "layout_paint", "disc_input", "crop_objects", "maxpool2", "avgpool2", "l1_mean",
     "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "preprocess_images", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
     "conv2d_forward", "pool3", "spatial_mean", "resize_bilinear", "feat_stats", "feat_stats_finalize", "softmax_rows", "inception_score", "POOL_MAX", "POOL_AVG9", "POOL_AVG_INSIDE",
-    "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums",
+    "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums", "knn_radii", "ball_counts",
 ]
 
 
@@ -2874,7 +2874,7 @@ def inception_score(probs, splits):
     return out
 
 
-# ------------------------------------------------------------------------------------ KID, object crops (csrc/quality.hip)
+# ------------------------------------------------- KID, object crops (csrc/quality.hip), k-NN manifolds (csrc/manifold.hip)
 def _dense_dev(t, dtype, what, name):
     if not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous():
         raise RuntimeError("%s: %s must be a dense %s tensor" % (what, name, str(dtype).replace("torch.", "")))
@@ -2942,6 +2942,49 @@ def kid_sums(fx, fy, ix, iy, gamma, coef0=1.0, degree=3):
     check(lib.csg_kid_sums(ptr(fx.detach()), fx.shape[0], ptr(fy.detach()), fy.shape[0], D, ptr(ix), ptr(iy), S, m, float(gamma),
                            float(coef0), int(degree), ptr(ws), nbytes, ptr(out), stream()), "kid_sums")
     return out
+
+
+def knn_radii(f, k):
+    """r2 (n,) float64 on the device: r2[i] = the k-th smallest squared distance from row i of f (n,D) fp32 to the OTHER rows
+    (csg_knn_radii; the distance, the tie rule and self-exclusion by index: include/csg_hip.h).  1 <= k <= 16, k <= n - 1,
+    D a multiple of 64.  The same bits on every run."""
+    _f32(f)
+    _dense_dev(f, torch.float32, "knn_radii", "f")
+    _no_grad_only("knn_radii", f)
+    if f.dim() != 2 or f.shape[0] < 1:
+        raise RuntimeError("knn_radii: features must be (n,D), got %s" % (tuple(f.shape),))
+    n, D = f.shape
+    k = int(k)
+    nbytes = max(int(lib.csg_knn_radii_workspace_bytes(n, k)), 8)       # -1 (k > n - 1, ...): the library's refusal follows
+    ws = torch.empty(nbytes // 8, device=f.device, dtype=torch.float64)
+    r2 = torch.empty((n,), device=f.device, dtype=torch.float64)
+    check(lib.csg_knn_radii(ptr(f.detach()), n, D, k, ptr(ws), nbytes, ptr(r2), stream()), "knn_radii")
+    return r2
+
+
+def ball_counts(q, f, r2):
+    """Queries q (m,D) and centres f (n,D) fp32, r2 (n,) float64 -> (inside (m,), holds (n,)) int32 on the device:
+    inside[j] = #{i : d2(q_j, f_i) <= r2[i]}, holds[i] = #{j : d2(q_j, f_i) <= r2[i]} (csg_ball_counts; one pass over the
+    pairs, no m x n array).  The same bits on every run."""
+    for t, name in ((q, "q"), (f, "f")):
+        _f32(t)
+        _dense_dev(t, torch.float32, "ball_counts", name)
+        _no_grad_only("ball_counts", t)
+    _dense_dev(r2, torch.float64, "ball_counts", "r2")
+    if q.dim() != 2 or f.dim() != 2 or q.shape[1] != f.shape[1] or q.shape[0] < 1 or f.shape[0] < 1:
+        raise RuntimeError("ball_counts: queries and centres must be (m,D) and (n,D), got %s and %s" % (tuple(q.shape), tuple(f.shape)))
+    if tuple(r2.shape) != (f.shape[0],):
+        raise RuntimeError("ball_counts: r2 must be (n,) = (%d,), got %s" % (f.shape[0], tuple(r2.shape)))
+    if f.device != q.device or r2.device != q.device:
+        raise RuntimeError("ball_counts: every operand must be on one device")
+    (m, D), n = q.shape, f.shape[0]
+    nbytes = max(int(lib.csg_ball_counts_workspace_bytes(m, n)), 4)
+    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.int32)
+    inside = torch.empty((m,), device=q.device, dtype=torch.int32)
+    holds = torch.empty((n,), device=q.device, dtype=torch.int32)
+    check(lib.csg_ball_counts(ptr(q.detach()), m, ptr(f.detach()), n, D, ptr(r2), ptr(ws), nbytes, ptr(inside), ptr(holds), stream()),
+          "ball_counts")
+    return inside, holds
 
 
 def feat_class_sums(x, class_ids, sums, counts):

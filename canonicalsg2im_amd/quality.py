@@ -10,7 +10,10 @@ Opt-in companions (csrc/quality.hip): `KID(net)` keeps the fp32 fe
 over seeded subsets (`ops.kid_sums`, fp64, one fixed summation order); `ObjectFID(net)` is FID over the crops of every object's
 box (SceneFID; `ops.crop_windows`, `ops.crop_resize_bilinear`) with per-class feature means (`ops.feat_class_sums`,
 `class_mean_distance`: the reference's evaluation/fid.py:77-93); `crops_from_layouts` reads the boxes of a layouts.json.
-Equality of these numbers with any other KID or SceneFID implementation is unchecked: the rules are this project's own.
+`PRDC(net)` keeps the same features and gives improved precision / recall and density / coverage over k-nearest-neighbour
+balls (csrc/manifold.hip: `ops.knn_radii`, `ops.ball_counts`, fp64 distances, integer counts, a stated tie rule).
+Equality of these numbers with any other KID, SceneFID or precision / recall implementation is unchecked: the rules are this
+project's own.
 
 LOADING THE REAL WEIGHT FILES AND THE NUMBERS THEY GIVE ARE UNCHECKED HERE (see inception.py): with `weights="random"` the
 network is a seeded stand-in and `stand_in` is True on both classes — every output built on it says so.
@@ -212,6 +215,93 @@ class KID:
         fx, fy = (torch.cat(side) for side in self._feats)
         out = kid_from_features(fx, fy, self.subsets, self.subset_size, self.seed, self.degree,
                                 1.0 / self.dims if self.gamma is None else self.gamma, self.coef0)
+        out["stand_in"] = bool(self.stand_in)
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ precision / recall, density / coverage
+def prdc_from_features(real, gen, k=5):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of two sets of
+    feature rows, fp32 (n_real,D) and (n_gen,D) on the device, over k-nearest-neighbour balls: the radius of
+    a row is the distance to its k-th nearest OTHER row of its own set (`ops.knn_radii`), and with
+    inside = ops.ball_counts(gen, real, r_real)[0], holds = ...[1] and inside_r = ops.ball_counts(real, gen, r_gen)[0]
+
+        precision = mean(inside > 0)      density  = sum(inside) / (k n_gen)
+        recall    = mean(inside_r > 0)    coverage = mean(holds > 0)
+
+    The four integer sums are formed on the device and read once; the divisions happen on the host.  k = 5 is the default
+    of the `prdc` package, which reports all four with one k; the improved precision and recall paper uses k = 3.
+    Non-finite features and k >= min(n_real, n_gen) are refused.
+    -> {"precision", "recall", "density", "coverage", "k", "n": [n_real, n_gen]}"""
+    for t, name in ((real, "real"), (gen, "generated")):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError("PRDC: the %s features must be an fp32 (n,D) tensor" % name)
+    if real.shape[1] != gen.shape[1]:
+        raise ValueError("PRDC: the two sides differ in width: %d and %d" % (real.shape[1], gen.shape[1]))
+    n_real, n_gen, k = int(real.shape[0]), int(gen.shape[0]), int(k)
+    if k < 1 or k >= min(n_real, n_gen):
+        raise ValueError("PRDC: k = %d needs 1 <= k < min(n_real, n_gen) = %d rows: a row's radius is the distance to its "
+                         "k-th nearest other row" % (k, min(n_real, n_gen)))
+    real, gen = real.detach().contiguous(), gen.detach().contiguous()
+    _to_device_images(real, None), _to_device_images(gen, None)
+    # a side's largest and smallest entry (torch's max and min hand a NaN on): no temporary the size of the features
+    ends = torch.isfinite(torch.stack([real.amax(), real.amin(), gen.amax(), gen.amin()])).cpu().tolist()
+    for ok, name in zip((ends[0] and ends[1], ends[2] and ends[3]), ("real", "generated")):
+        if not ok:
+            raise ValueError("PRDC: the %s features hold a NaN or an infinity: a ball around such a row means nothing" % name)
+    inside, holds = ops.ball_counts(gen, real, ops.knn_radii(real, k))
+    inside_r, _ = ops.ball_counts(real, gen, ops.knn_radii(gen, k))
+    sums = torch.stack([(inside > 0).sum(), (inside_r > 0).sum(), inside.sum(dtype=torch.int64), (holds > 0).sum()]).cpu().tolist()
+    return {"precision": sums[0] / n_gen, "recall": sums[1] / n_real, "density": sums[2] / (k * n_gen),
+            "coverage": sums[3] / n_real, "k": k, "n": [n_real, n_gen]}
+
+
+class PRDC:
+    """Precision, recall, density and coverage of two sets of pictures over the features FID uses: `update(images, which)`
+    (which 0 = real, 1 = generated; uint8 (B,H,W,3) pictures or fp32 (B,3,H,W) images, prepared as for FID) or
+    `update_features(feats, which)` keep the fp32 features on the device; `compute()` -> prdc_from_features's dict with
+    "stand_in"."""
+
+    def __init__(self, net, dims=2048, channel_order="rgb", size=(299, 299), k=5):
+        if net.variant != "fid":
+            raise ValueError("PRDC needs InceptionV3('fid', ...), got the %r variant" % net.variant)
+        if dims not in inception.DIMS:
+            raise ValueError("PRDC: dims must be among %s" % (inception.DIMS,))
+        if int(k) < 1:
+            raise ValueError("PRDC: k must be at least 1, got %r" % (k,))
+        self.net, self.dims, self.channel_order, self.size, self.k = net, dims, channel_order, size, int(k)
+        self.stand_in = net.stand_in
+        self.clean()
+
+    def clean(self):
+        self._feats = ([], [])
+
+    @staticmethod
+    def _which(which):
+        if which not in (0, 1):
+            raise ValueError("PRDC: which must be 0 (real) or 1 (generated), got %r" % (which,))
+        return which
+
+    def update(self, images, which):
+        self._which(which)
+        images = _to_device_images(images, None)
+        self.update_features(self.net(inception.prepare(images, "fid", self.size, self.channel_order), dims=self.dims), which)
+
+    def update_features(self, feats, which):
+        if feats.dim() != 2 or feats.shape[1] != self.dims or feats.dtype != torch.float32:
+            raise ValueError("PRDC: features must be fp32 (n, %d), got %s %s" % (self.dims, feats.dtype, tuple(feats.shape)))
+        self._feats[self._which(which)].append(feats.detach())
+
+    @property
+    def n(self):
+        return [sum(int(f.shape[0]) for f in side) for side in self._feats]
+
+    def compute(self):
+        n0, n1 = self.n
+        if self.k >= min(n0, n1):
+            raise ValueError("PRDC: k = %d needs more than k pictures per side, got %d and %d" % (self.k, n0, n1))
+        real, gen = (torch.cat(side) for side in self._feats)
+        out = prdc_from_features(real, gen, self.k)
         out["stand_in"] = bool(self.stand_in)
         return out
 

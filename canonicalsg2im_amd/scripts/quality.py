@@ -4,6 +4,7 @@ evaluation/fid/fid_score.py with its behaviours kept.
     python -m canonicalsg2im_amd.scripts.quality A B --fid_weights FILE [--dims 2048] [--batch-size 50]
         [--inception_weights FILE --splits 5] [--channel_order bgr|rgb] [--output_dir DIR]
         [--kid [--kid_subsets 100 --kid_subset_size 1000 --kid_seed 0]]
+        [--prdc [--prdc_k 5] [--prdc_real A|B]]
         [--object_crops LAYOUTS.json [--layout_boxes gt|pred] [--min_object_size 0.0] [--class_min_crops 1]]
 
 A and B are folders of *.jpg / *.png, or .npz statistics with `mu` and `sigma` (fid_score.py:218-229).  Prints `FID:`; with
@@ -12,10 +13,13 @@ DIR/stats_A.npz / stats_B.npz.  PIL decodes on the host; everything after the de
 
 Opt-in, for two folders (an .npz holds no pictures: the flags are refused for it):
   --kid           `KID: mean +- std` over the pictures FID used (quality.KID; the remainder rule applies to them too)
+  --prdc          `Precision:`, `Recall:`, `Density:`, `Coverage:` over the pictures FID used (quality.PRDC, k-nearest-neighbour
+                  balls with --prdc_k neighbours; the remainder rule applies); --prdc_real names the folder taken as the real
+                  pictures (default A: the ground-truth folder comes first)
   --object_crops  the layouts.json of `scripts.sample --split`: pictures are matched to its rows by file stem = image id;
                   prints `SceneFID:` (FID over the crops of every object's box, all of them: no remainder is dropped), the
                   crops per side and `class_mean_distance:` (per class |mu_B - mu_A|^2, averaged); with --kid also
-                  `SceneKID:`.  Writes stats_A_objects.npz / stats_B_objects.npz and "objects" into quality.json.
+                  `SceneKID:` and with --prdc `ScenePrecision:` ... `SceneCoverage:` over the crops' features.  Writes stats_A_objects.npz / stats_B_objects.npz and "objects" into quality.json.
 """
 import argparse
 import glob
@@ -52,6 +56,9 @@ def build_parser():
     p.add_argument("--kid_subsets", type=int, default=100)
     p.add_argument("--kid_subset_size", type=int, default=1000)
     p.add_argument("--kid_seed", type=int, default=0)
+    p.add_argument("--prdc", action="store_true", help="also precision / recall / density / coverage over the pictures FID used")
+    p.add_argument("--prdc_k", type=int, default=5, help="neighbours of a ball (5: the prdc package; 3: the improved P&R paper)")
+    p.add_argument("--prdc_real", choices=["A", "B"], default="A", help="the folder taken as the real pictures")
     p.add_argument("--object_crops", default=None, metavar="LAYOUTS.json",
                    help="SceneFID over the crops of the boxes of this layouts.json (scripts.sample --split)")
     p.add_argument("--layout_boxes", choices=["gt", "pred"], default="gt")
@@ -61,8 +68,9 @@ def build_parser():
 
 
 def refuse_statistics_files(args):
-    """--kid and --object_crops work on pictures: an .npz of (mu, sigma) holds none."""
-    asked = [flag for flag, on in (("--kid", args.kid), ("--object_crops", args.object_crops is not None)) if on]
+    """--kid, --object_crops and --prdc work on pictures: an .npz of (mu, sigma) holds none."""
+    asked = [flag for flag, on in (("--kid", args.kid), ("--object_crops", args.object_crops is not None),
+                                   ("--prdc", args.prdc)) if on]
     for path in (args.A, args.B):
         if asked and path.endswith(".npz"):
             raise SystemExit("%s need%s pictures: %s holds statistics (mu, sigma) only; give the folder"
@@ -136,8 +144,28 @@ def batches(files, batch_size, dev):
         yield torch.from_numpy(np.stack(pics)).to(dev)
 
 
+def print_prdc(out, real, label, prefix=""):
+    for name in ("precision", "recall", "density", "coverage"):
+        print("%s%s: %s%s" % (prefix, name.capitalize(), out[name], label))
+    print("%sPRDC: k = %d, real = folder %s (%d rows), generated = the other (%d rows)%s" % (
+        prefix, out["k"], real, out["n"][0], out["n"][1], label))
+
+
+def prdc_of(quality, net, args, feats_a, feats_b):
+    """--prdc over the two folders' feature rows, --prdc_real naming the real side -> the "prdc" of quality.json."""
+    real, gen = (feats_a, feats_b) if args.prdc_real == "A" else (feats_b, feats_a)
+    try:
+        out = quality.prdc_from_features(real, gen, args.prdc_k)
+    except ValueError as e:
+        raise SystemExit("--prdc: %s" % e)
+    out["real"] = args.prdc_real
+    out["stand_in"] = bool(net.stand_in)
+    return out
+
+
 def objects(quality, net, args, plan, dev, label):
-    """--object_crops: SceneFID, the per-class mean distance and, with --kid, SceneKID -> the "objects" of quality.json."""
+    """--object_crops: SceneFID, the per-class mean distance and, with --kid, SceneKID, with --prdc the four over the crops
+    -> the "objects" of quality.json."""
     crops, classes, matched = plan
     sides = []
     for tag, files in zip("AB", matched):
@@ -160,6 +188,9 @@ def objects(quality, net, args, plan, dev, label):
         out["kid"] = quality.kid_from_features(feats_a, feats_b, args.kid_subsets, args.kid_subset_size, args.kid_seed)
         out["kid"]["stand_in"] = bool(net.stand_in)
         print("SceneKID: %s +- %s%s" % (out["kid"]["mean"], out["kid"]["std"], label))
+    if args.prdc:
+        out["prdc"] = prdc_of(quality, net, args, feats_a, feats_b)
+        print_prdc(out["prdc"], args.prdc_real, label, prefix="Scene")
     return out
 
 
@@ -201,6 +232,7 @@ def main(argv=None):
     stats, counts, score = [], [], None
     kid = quality.KID(net, dims=args.dims, channel_order=args.channel_order, subsets=args.kid_subsets,
                       subset_size=args.kid_subset_size, seed=args.kid_seed) if args.kid else None
+    kept = ([], []) if args.prdc else None          # --prdc: the features of both sides, fp32 on the device
     for side, (tag, path) in enumerate(zip("AB", args.path)):
         if path.endswith(".npz"):
             stats.append(quality.load_statistics(path))
@@ -209,12 +241,15 @@ def main(argv=None):
         fid = quality.FID(net, dims=args.dims, channel_order=args.channel_order)
         scorer = quality.InceptionScore(score_net, channel_order=args.channel_order) if (score_net is not None and tag == "A") else None
         for pics in batches(list_files(path), args.batch_size, dev):
-            if kid is None:
+            if kid is None and kept is None:
                 fid.update(pics)
             else:                                   # the same features, kept
                 feats = fid.features(pics)
                 fid.update_features(feats)
-                kid.update_features(feats, side)
+                if kid is not None:
+                    kid.update_features(feats, side)
+                if kept is not None:
+                    kept[side].append(feats.detach())
             if scorer is not None:
                 scorer.update(pics)
         stats.append(fid.statistics())
@@ -232,6 +267,9 @@ def main(argv=None):
     if kid is not None:
         result["kid"] = kid.compute()
         print("KID: %s +- %s%s" % (result["kid"]["mean"], result["kid"]["std"], label))
+    if kept is not None:
+        result["prdc"] = prdc_of(quality, net, args, torch.cat(kept[0]), torch.cat(kept[1]))
+        print_prdc(result["prdc"], args.prdc_real, label)
     if plan is not None:
         result["objects"] = objects(quality, net, args, plan, dev, label)
     with open(os.path.join(args.output_dir, "quality.json"), "w") as f:

@@ -1186,6 +1186,44 @@ int csg_kid_sums(const float* fx, int64_t nx, const float* fy, int64_t ny, int64
 int csg_feat_class_sums(const float* x, const int32_t* class_ids, int64_t n, int64_t D, int64_t C, double* sums, int64_t* counts,
                         void* stream);
 
+/* ---- k-nearest-neighbour manifolds: precision / recall, density / coverage (csrc/manifold.hip) -----------------------
+ * (Added after revision 122 without a new revision number: callers detect the entries by their symbols.)  As above: stream
+ * ordered and capturable, no atomics, nothing read back, the same bits on every run.  No n x m array exists in memory.
+ *
+ * THE DISTANCE, the only one both entries use: d2(u, v) = sum_c t_c * t_c with t_c = (double)u_c - (double)v_c, the columns
+ * in ascending order, accumulated in fp64 with ONE FUSED multiply-add per column, acc = fma(t_c, t_c, acc).  It is the
+ * difference form, not |u|^2 + |v|^2 - 2 u.v: identical rows are at exactly 0, d2(u, v) and d2(v, u) are the same bits, and
+ * integer-valued features give the exact integer.  A NaN distance ranks as +inf; a NaN or +inf distance is "<=" nothing.
+ *
+ * csg_knn_radii: f (n,D) fp32, 16-byte aligned -> r2 (n) fp64: r2[i] = the k-th smallest of { d2(f_i, f_j) : j != i }.
+ * Self is excluded by index, not by value: a duplicate row at another index counts, with distance 0; equal values count as
+ * often as they occur.  With fewer than k finite distances r2[i] = +inf.  A block owns a 64 x 64 tile at a time (4 x 4 fp64
+ * accumulators per thread), each row keeps its k smallest so far, one lane per row inserts a tile's candidates; when the
+ * column tiles are cut into chunks, a second launch merges the chunks' k-lists in chunk order.
+ * LIMITS (CSG_E_BADSHAPE otherwise): 1 <= k <= 16, k <= n - 1, n <= 2^20, D a multiple of 64, at most 8192.
+ * csg_knn_radii_workspace_bytes(n, k) = chunks n k 8 bytes (-1 outside the limits), 8-byte aligned.
+ *
+ * csg_ball_counts: queries q (m,D), centres f (n,D), r2 (n) fp64 -> inside (m) int32, holds (n) int32:
+ *   inside[j] = #{ i : d2(q_j, f_i) <= r2[i] }     holds[i] = #{ j : d2(q_j, f_i) <= r2[i] }
+ * with "<=": a query on the sphere is inside.  A pair whose distance is NaN or +inf, or whose radius is NaN, is not counted
+ * (so a centre with r2 = +inf holds every query at a finite distance and no other).  Both vectors come out of ONE pass over
+ * the m x n pairs: the query tiles are cut into min(64, ceil(m / 64)) row groups and the centres into
+ * csg_manifold_column_chunks(min(m, 4096), n) chunks, a block owns a (group, chunk) pair and is the only writer of its
+ * partial counts; a second launch adds the groups and the chunks in index order.  Rows past m or n are masked, never read.
+ * LIMITS: 1 <= m, n <= 2^20, D as above.  csg_ball_counts_workspace_bytes(m, n) = (m chunks + n groups) 4 bytes (-1
+ * outside the limits), 4-byte aligned.
+ *
+ * csg_manifold_column_chunks(rows, cols), host only, no device needed: THE SPLIT RULE.  With ceil(rows / 64) blocks side by
+ * side, the ceil(cols / 64) column tiles are cut into min(64, ceil(tiles / 2), ceil(8192 / blocks)) chunks, chunk c =
+ * tiles [c tiles / chunks, (c + 1) tiles / chunks).  -1 unless 1 <= rows, cols <= 2^20.  csg_knn_radii uses (n, n).      */
+int64_t csg_manifold_column_chunks(int64_t rows, int64_t cols);
+int64_t csg_knn_radii_workspace_bytes(int64_t n, int64_t k);
+int csg_knn_radii(const float* f, int64_t n, int64_t D, int64_t k, void* workspace, int64_t workspace_bytes, double* r2,
+                  void* stream);
+int64_t csg_ball_counts_workspace_bytes(int64_t m, int64_t n);
+int csg_ball_counts(const float* q, int64_t m, const float* f, int64_t n, int64_t D, const double* r2, void* workspace,
+                    int64_t workspace_bytes, int32_t* inside, int32_t* holds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
