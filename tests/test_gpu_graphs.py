@@ -109,8 +109,9 @@ def test_graph_step_vs_oracle(cuda):
 
 
 def test_new_shape_runs_eagerly_in_process(cuda):
-    """A batch with another batch size (a new key) runs eagerly, the captured key keeps replaying afterwards, and the
-    gradients the optimisers read are the right buffers on both sides of the switch."""
+    """A batch with another batch size (a new key) runs eagerly and the captured key keeps replaying afterwards.  That the
+    gradients the optimisers read are the right buffers on both sides of the switch is asserted in
+    tests/test_gpu_update_rule.py::test_replayed_gradients_are_this_steps (against an eager twin, step by step)."""
     vocab, tr = _make(cuda, ["--use_img_disc", "0"], graphs=True)
     a = _batches(vocab, cuda, 2, B=4)
     b = _batches(vocab, cuda, 1, B=2)
