@@ -72,6 +72,11 @@ class NormEvalItem(ctypes.Structure):
     _fields_ = [("running_mean", c_p), ("running_var", c_p), ("C", c_i64), ("offset", c_i64)]
 
 
+class EmaItem(ctypes.Structure):
+    """Mirror of `csg_ema_item` (include/csg_hip.h)."""
+    _fields_ = [("src", c_p), ("dst", c_p), ("numel", c_i64), ("chunk0", c_i64), ("kind", c_i32), ("reserved", c_i32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/csg_hip.h
 class GemmDesc(ctypes.Structure):
     """csg_gemm_desc (include/csg_hip.h)."""
@@ -253,6 +258,8 @@ SIGNATURES = {
     "csg_knn_radii": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
     "csg_ball_counts_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "csg_ball_counts": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p]),
+    "csg_ema_table_plan": (c_i64, [ctypes.POINTER(EmaItem), c_i64]),
+    "csg_ema_apply": (c_i32, [c_p, c_i64, c_i64, c_i32, c_f32, c_f32, c_p]),
 }
 
 

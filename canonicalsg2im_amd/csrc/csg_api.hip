@@ -131,7 +131,8 @@ static const char* kNames[K_COUNT] = {
     "resize_bilinear", "pool3", "spatial_mean", "bias_act", "feat_stats", "inception_score",
     "draw_labels_u8", "draw_graph_u8",
     "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums",
-    "knn_radii", "ball_counts"};
+    "knn_radii", "ball_counts",
+    "ema"};
 
 }  // namespace csg
 

@@ -87,6 +87,7 @@ enum KernelId {
   K_FEAT_CLASS_SUMS,
   K_KNN_RADII,
   K_BALL_COUNTS,
+  K_EMA,
   K_COUNT
 };
 

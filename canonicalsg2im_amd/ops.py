@@ -430,7 +430,7 @@ def invalidate_weight_caches():
     """Call after editing parameters in place OUTSIDE an optimiser step through `.data` (a broadcast, an EMA swap,
     weight clipping): such edits bump neither `_version` nor the optimiser hook, so tensors derived from the weights
     (Winograd operands, the PatchGAN's permuted first-layer weight) would otherwise stay stale until the next step.
-    `dist.broadcast_module` and `Trainer.load_checkpoint` call it.  Parked Winograd operands are dropped as well (they
+    `dist.broadcast_module`, `Trainer.load_checkpoint` and `ema.WeightEMA.swapped` (on both sides) call it.  Parked Winograd operands are dropped as well (they
     would be refused by their epoch tag anyway; dropping them frees their memory now)."""
     _bump_weight_epoch()
     _PREPACKED.clear()
@@ -3006,3 +3006,140 @@ def feat_class_sums(x, class_ids, sums, counts):
         raise RuntimeError("feat_class_sums: every operand must be on the features' device")
     check(lib.csg_feat_class_sums(ptr(x.detach()), ptr(class_ids), n, D, sums.shape[0], ptr(sums), ptr(counts), stream()),
           "feat_class_sums")
+
+
+# ---- EMA of the weights (csrc/ema.hip; the formula, the table and the modes: include/csg_hip.h) ----------------------------
+EMA_CHUNK = 4096                     # CSG_EMA_CHUNK: floats per chunk; a chunk never spans two items
+EMA_AVERAGE, EMA_COPY = 0, 1         # item kinds: e' = fmaf(d, e, omd * p) | e' = p
+EMA_UPDATE, EMA_SWAP, EMA_FILL = 0, 1, 2
+
+
+def ema_scalars(decay):
+    """(d, omd) as the kernel receives them: d = (float)D, omd = (float)(1.0 - (double)D), each a Python float holding the
+    fp32 value.  0 <= D <= 1, anything else (NaN included) is refused."""
+    D = float(decay)
+    if not 0.0 <= D <= 1.0:
+        raise RuntimeError("ema_update: decay must lie in [0, 1], got %r" % (decay,))
+    return ctypes.c_float(D).value, ctypes.c_float(1.0 - D).value
+
+
+def ema_layout(numels):
+    """Slot offsets (in floats) of tensors of `numels` elements in the flat shadow, and the floats the slots take: every
+    slot starts at a multiple of 4 floats (16 bytes); an empty tensor takes no room."""
+    offsets, at = [], 0
+    for n in numels:
+        n = int(n)
+        if n < 0:
+            raise RuntimeError("ema_layout: a tensor of %d elements" % n)
+        offsets.append(at)
+        at += (n + 3) // 4 * 4
+    return offsets, at
+
+
+def _ema_source(t, i, device):
+    """A source is one dense run of fp32 on the device, 16-byte aligned: contiguous in torch's sense for its own memory
+    format (row-major, or channels-last as the convolution weights are kept).  Anything else is refused, not served slowly."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise RuntimeError("EmaTable: source %d must be an fp32 tensor, got %s" % (
+            i, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    ptr(t)                                                    # refuses a CPU tensor: no CPU path
+    if t.device != device:
+        raise RuntimeError("EmaTable: source %d is on %s, the shadow on %s" % (i, t.device, device))
+    if not (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+        raise RuntimeError("EmaTable: source %d (shape %s, strides %s) is not contiguous: a source must be one dense run of "
+                           "floats" % (i, tuple(t.shape), tuple(t.stride())))
+    if t.numel() and t.data_ptr() % 16:
+        raise RuntimeError("EmaTable: source %d starts at an address that is not 16-byte aligned (a view at an offset?); "
+                           "there is no unaligned path" % i)
+
+
+class EmaTable:
+    """The device-resident item table of one shadow: built from `sources` (fp32 device tensors, each one dense 16-byte aligned
+    run) with `kinds` (EMA_AVERAGE | EMA_COPY) over `shadow` (flat fp32; allocated and zeroed when None) and uploaded.  A
+    source that is not fp32, not contiguous or not aligned is refused here, before anything is launched.  Attributes: `shadow`,
+    `offsets` / `numels` / `kinds` per item, `chunks`.  Holds the sources: the addresses in the table stay valid while it lives."""
+
+    def __init__(self, sources, kinds, shadow=None):
+        sources, kinds = list(sources), [int(k) for k in kinds]
+        if not sources or len(sources) != len(kinds):
+            raise RuntimeError("EmaTable: %d sources and %d kinds; at least one item" % (len(sources), len(kinds)))
+        if any(k not in (EMA_AVERAGE, EMA_COPY) for k in kinds):
+            raise RuntimeError("EmaTable: kinds are EMA_AVERAGE (0) or EMA_COPY (1), got %s" % sorted(set(kinds)))
+        device = shadow.device if shadow is not None else (sources[0].device if torch.is_tensor(sources[0]) else None)
+        for i, t in enumerate(sources):
+            _ema_source(t, i, device)
+        self.numels = [t.numel() for t in sources]
+        self.offsets, self.floats = ema_layout(self.numels)
+        if shadow is None:
+            shadow = torch.zeros(max(self.floats, 4), device=device, dtype=torch.float32)
+        _dense_dev(shadow, torch.float32, "EmaTable", "shadow")
+        if shadow.dim() != 1 or shadow.numel() < self.floats or shadow.data_ptr() % 16:
+            raise RuntimeError("EmaTable: the shadow must be a flat, 16-byte aligned fp32 tensor of at least %d floats, got "
+                               "shape %s" % (self.floats, tuple(shadow.shape)))
+        self.sources, self.kinds, self.shadow = sources, kinds, shadow
+        self.n = len(sources)
+        self.items = None                 # the table on the device (uint8)
+        self._ptrs = None
+        self._upload()
+
+    def _upload(self):
+        arr = (_lib.EmaItem * self.n)()
+        base = self.shadow.data_ptr()
+        for i, t in enumerate(self.sources):
+            arr[i].src, arr[i].dst = t.data_ptr() or None, base + 4 * self.offsets[i]
+            arr[i].numel, arr[i].kind = self.numels[i], self.kinds[i]
+        chunks = int(lib.csg_ema_table_plan(arr, self.n))
+        if chunks < 0:
+            check(chunks, "ema_table_plan")
+        self.chunks = chunks
+        host = torch.frombuffer(arr, dtype=torch.uint8).clone()
+        if self.items is None:
+            self.items = host.to(self.shadow.device)
+        else:
+            self.items.copy_(host)                             # stream ordered behind the launches that read the old table
+        self._ptrs = [t.data_ptr() for t in self.sources]
+
+    def refresh(self):
+        """Before every launch: a source whose storage was replaced since the upload (the SPADE layers join their gamma / beta
+        parameters into one allocation at their first call; `module.to`) is checked again and the table uploaded again — the
+        kernel never follows a stale address.  The common case is a comparison of addresses on the host."""
+        ptrs = self._ptrs
+        for i, t in enumerate(self.sources):
+            if t.data_ptr() != ptrs[i]:
+                for j, s in enumerate(self.sources):
+                    if s.numel() != self.numels[j]:
+                        raise RuntimeError("EmaTable: source %d changed its size from %d to %d elements" % (
+                            j, self.numels[j], s.numel()))
+                    _ema_source(s, j, self.shadow.device)
+                self._upload()
+                return True
+        return False
+
+    def slot(self, i):
+        """The floats of item i in the shadow (a view)."""
+        return self.shadow[self.offsets[i]:self.offsets[i] + self.numels[i]]
+
+
+def _ema_apply(table, mode, d, omd, what):
+    if not isinstance(table, EmaTable):
+        raise RuntimeError("%s: expected an ops.EmaTable, got %s" % (what, type(table).__name__))
+    table.refresh()
+    check(lib.csg_ema_apply(ptr(table.items), table.n, table.chunks, mode, d, omd, stream()), what)
+
+
+def ema_update(table, decay):
+    """One launch: e' = fmaf(d, e, omd * p) for the AVERAGE items, e' = p for the COPY items ((d, omd) = ema_scalars(decay);
+    a decay of exactly 1 leaves the AVERAGE items bit-identical)."""
+    d, omd = ema_scalars(decay)
+    _ema_apply(table, EMA_UPDATE, d, omd, "ema_update")
+
+
+def ema_swap(table):
+    """One launch: every source and its slot exchanged, bit for bit.  Twice is the identity.  The caller invalidates what is
+    derived from the weights (`invalidate_weight_caches`)."""
+    _ema_apply(table, EMA_SWAP, 0.0, 0.0, "ema_swap")
+
+
+def ema_fill(table):
+    """One launch: every slot = its source, bit for bit, whatever the kind."""
+    _ema_apply(table, EMA_FILL, 0.0, 0.0, "ema_fill")

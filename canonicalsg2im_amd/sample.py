@@ -29,13 +29,22 @@ from .spectral_norm import HipSpectralNorm
 NO_CPU = "canonicalsg2im_amd.sample needs a HIP device: there is no CPU path"
 
 
-def model_state_of(ckpt):
+NO_EMA = ("checkpoint has no 'model_ema_state': it was written without an EMA of the weights — train with --ema_decay D "
+          "(0 < D <= 1) to have one saved, or sample the raw weights (use_ema=False, --use_ema 0)")
+
+
+def model_state_of(ckpt, use_ema=False):
     """`model_state` of a checkpoint dictionary written by `Trainer.save_checkpoint` or by the reference
     (scripts/train.py:488-520; its `gans_model_state` — DataParallel's `module.` keys — and the discriminator / optimiser
-    entries are not needed here and not read).  A generator saved from inside a DataParallel wrapper loses its `module.`."""
-    if "model_state" not in ckpt:
+    entries are not needed here and not read).  A generator saved from inside a DataParallel wrapper loses its `module.`.
+    `use_ema`: `model_ema_state` instead, the averaged weights a run with --ema_decay saves under the same keys (ema.py);
+    a checkpoint without it is refused."""
+    key = "model_ema_state" if use_ema else "model_state"
+    if use_ema and key not in ckpt:
+        raise KeyError(NO_EMA)
+    if key not in ckpt:
         raise KeyError("checkpoint has no 'model_state' (keys: %s)" % sorted(ckpt))
-    sd = ckpt["model_state"]
+    sd = ckpt[key]
     if sd and all(k.startswith("module.") for k in sd):
         sd = {k[len("module."):]: v for k, v in sd.items()}
     return sd
@@ -64,12 +73,15 @@ class _Replay:
 
 
 class Sampler:
-    def __init__(self, opt, device, checkpoint=None, model=None):
-        """`model`: a MetaGeneratorModel to ADOPT instead of constructing one (the evaluator walks the trainer's own module:
+    def __init__(self, opt, device, checkpoint=None, model=None, use_ema=False):
+        """`use_ema`: load the checkpoint's `model_ema_state` (the EMA of the weights, ema.py) instead of `model_state`.
+        `model`: a MetaGeneratorModel to ADOPT instead of constructing one (the evaluator walks the trainer's own module:
         one copy of the weights).  Its mode is left alone here; `generate` puts it in eval mode and leaves it there.  Whoever
         trains an adopted model calls `invalidate()` before the next walk: a fused optimiser step and a replayed training
         step write parameters and running statistics without touching the `_version` counters `_signature` reads."""
         self.opt, self.device = opt, torch.device(device)
+        if use_ema and checkpoint is None:
+            raise ValueError("Sampler(use_ema=True) needs a checkpoint: the averaged weights are read from it")
         if model is None:
             model = MetaGeneratorModel(opt, self.device)
             model.eval()
@@ -78,14 +90,15 @@ class Sampler:
         self._replays, self._seen = {}, {}
         self.replays = self.eager_calls = 0
         if checkpoint is not None:
-            self.load(checkpoint)
+            self.load(checkpoint, use_ema=use_ema)
 
     # ------------------------------------------------------------------ weights
-    def load(self, ckpt):
-        """Strict load of `model_state` from a checkpoint dictionary or a path to one; drops every preparation and graph."""
+    def load(self, ckpt, use_ema=False):
+        """Strict load of `model_state` (`use_ema`: of `model_ema_state`) from a checkpoint dictionary or a path to one;
+        drops every preparation and graph."""
         if not isinstance(ckpt, dict):
             ckpt = torch.load(ckpt, map_location=self.device)
-        self.model.load_state_dict(model_state_of(ckpt), strict=True)
+        self.model.load_state_dict(model_state_of(ckpt, use_ema), strict=True)
         self.model.eval()
         self.invalidate()
 

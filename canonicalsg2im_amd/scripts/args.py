@@ -16,6 +16,13 @@ def bool_flag(s):
     raise ValueError('Invalid value "%s" for bool flag (should be 0 or 1)' % s)
 
 
+def ema_decay_flag(s):
+    d = float(s)
+    if not 0.0 <= d <= 1.0:              # (a NaN fails both comparisons)
+        raise ValueError('Invalid value "%s" for --ema_decay (0 = off, else 0 < D <= 1)' % s)
+    return d
+
+
 _OFF_PATH_FLAGS = {
     # data
     'img_deprocess': ('decode_img', 'str'), 'num_train_samples': (None, 'int'), 'num_val_samples': (1024, 'int'),
@@ -135,6 +142,10 @@ def build_parser():
     p.add_argument('--print_every', default=10, type=int)
     p.add_argument('--min_objects', type=int)
     p.add_argument('--max_objects', type=int)
+    # EMA of the generator's weights (ema.py; not a flag of the reference): 0 = off, else 0 < D <= 1.  --ema_warmup 1 uses
+    # min(D, (1 + n) / (10 + n)) at update n.  The trainer reads both with getattr: older namespaces lack them
+    p.add_argument('--ema_decay', default=0.0, type=ema_decay_flag)
+    p.add_argument('--ema_warmup', default=1, type=int, choices=(0, 1))
     # every other flag of the reference's command line (data loading, logging, checkpointing, evaluation, unused SPADE
     # options): accepted with the reference's defaults so that its recipes parse unchanged; none is read on the hot path
     for name, (default, kind) in _OFF_PATH_FLAGS.items():

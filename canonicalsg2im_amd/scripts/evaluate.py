@@ -11,6 +11,9 @@ validation set is seeded synthetic batches of the chosen dataset's shape.  The r
 of them:
 
     --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (required)
+    --use_ema 0|1            1: validate the checkpoint's `model_ema_state`, the exponential moving average of the weights a run
+                             with --ema_decay saves (canonicalsg2im_amd/ema.py); the lines then read `EMA GT VAL` / `EMA VAL`.
+                             A checkpoint without the entry is refused (default 0: `model_state`)
     --output_dir DIR         where <pass>_<key>_%03d.png, metrics.json and table.json go (default: nothing is written)
     --num_val_samples N      images to validate (default 1024, the reference's), in batches of --batch_size
     --inception_weights FILE torchvision's inception_v3_google-*.pth: both passes also report `inception_mean` /
@@ -44,6 +47,7 @@ def build_parser():
     from .args import build_parser as train_parser
     p = train_parser()
     p.add_argument("--inception_weights", default=None)
+    p.add_argument("--use_ema", default=0, type=int, choices=[0, 1])
     return p
 
 
@@ -102,15 +106,16 @@ def log_results(losses, t, prefix):
     print(head + ("  " + rest if rest else ""), flush=True)
 
 
-def validate(args, evaluator, dev, t, world=1, val_set=None, inception=None):
-    """The two passes of scripts/train.py:410-424 -> (gt_val_losses, val_losses, val_samples, val_table)."""
+def validate(args, evaluator, dev, t, world=1, val_set=None, inception=None, prefix=""):
+    """The two passes of scripts/train.py:410-424 -> (gt_val_losses, val_losses, val_samples, val_table).  `prefix` goes in
+    front of the passes' names on the printed lines ("EMA ": the averaged weights are being validated)."""
     tr = evaluator.trainer
     extra = {} if inception is None else {"inception": inception}
     gt_losses, _, _ = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=True, **extra)
-    log_results(gt_losses, t, "GT VAL")
+    log_results(gt_losses, t, prefix + "GT VAL")
     use_gt = bool(args.skip_graph_model)                                          # :419
     losses, samples, table = evaluator.check_model(validation_batches(args, tr, dev, world, val_set), use_gt=use_gt, **extra)
-    log_results(losses, t, "VAL")
+    log_results(losses, t, prefix + "VAL")
     return gt_losses, losses, samples, table
 
 
@@ -148,12 +153,24 @@ def main(argv=None):
     init_args(args)
     torch.manual_seed(0)
     trainer = T.Trainer(args, dev)
-    t, _ = trainer.load_checkpoint(args.checkpoint_name)
+    ckpt = torch.load(args.checkpoint_name, map_location=dev)
+    t, _ = trainer.load_checkpoint(ckpt)
+    use_ema = bool(getattr(args, "use_ema", 0))
+    if use_ema:                          # the averaged weights over the raw ones, through the sampler's strict path
+        from .. import ops
+        from ..sample import model_state_of
+        try:
+            trainer.model.load_state_dict(model_state_of(ckpt, use_ema=True), strict=True)
+        except KeyError as e:
+            raise SystemExit("--use_ema 1: %s" % (e.args[0],))
+        ops.invalidate_weight_caches()
+    del ckpt
     net = None
     if getattr(args, "inception_weights", None):
         from ..inception import InceptionV3
         net = InceptionV3("torchvision", args.inception_weights).to(dev)
-    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t, val_set=val_set, inception=net)
+    gt_losses, losses, samples, table = validate(args, Evaluator(trainer), dev, t, val_set=val_set, inception=net,
+                                                 prefix="EMA " if use_ema else "")
     if args.output_dir:
         write_outputs(args.output_dir, gt_losses, losses, samples, table)
     torch.cuda.synchronize()

@@ -10,6 +10,9 @@ model; on top of them:
 
     --checkpoint_name PATH   a checkpoint of `Trainer.save_checkpoint` or of the reference (default: none — the freshly
                              initialised weights, which is only good for timing)
+    --use_ema 0|1            1: draw from the checkpoint's `model_ema_state`, the exponential moving average of the weights a
+                             run with --ema_decay saves (canonicalsg2im_amd/ema.py), in every mode below; needs
+                             --checkpoint_name, and a checkpoint without the entry is refused (default 0: `model_state`)
     --output_dir DIR         where img_%06d.png go (default: nothing is written)
     --num_samples N          pictures to generate (default 16), in batches of --batch_size
     --scene_graphs FILE      authored scene graphs (JSON), drawn in batches of --batch_size; the vocabulary is the one the
@@ -87,6 +90,8 @@ def build_parser():
     from .args import build_parser as train_parser
     p = train_parser()
     p.add_argument('--num_samples', default=16, type=int)
+    p.add_argument('--use_ema', default=0, type=int, choices=[0, 1],
+                   help="1: sample the checkpoint's model_ema_state (written by a run with --ema_decay), not model_state")
     p.add_argument('--scene_graphs', default=None, type=str)
     p.add_argument('--draw_boxes', default=1, type=int)
     p.add_argument('--draw_labels', default=0, type=int)
@@ -125,6 +130,9 @@ def parse_args(argv=None):
         raise SystemExit("--num_samples and --batch_size must be positive")
     if args.checkpoint_name != _NO_CHECKPOINT and not os.path.isfile(args.checkpoint_name):
         raise SystemExit("--checkpoint_name %s: no such file" % args.checkpoint_name)
+    if args.use_ema and args.checkpoint_name == _NO_CHECKPOINT:
+        raise SystemExit("--use_ema 1 needs --checkpoint_name: the averaged weights are read from a checkpoint written with "
+                         "--ema_decay")
     if args.draw_labels and not args.draw_boxes:
         raise SystemExit("--draw_labels 1 needs --draw_boxes 1: the names go on the layout pictures, which --draw_boxes 0 "
                          "leaves out")
@@ -208,7 +216,7 @@ def sample_split(args, dev, dataset):
     init_args(args)
     print("data: %d pictures of %s" % (len(dataset), dataset.image_dir), flush=True)
     torch.manual_seed(0)
-    sampler = Sampler(args, dev, ckpt)
+    sampler = Sampler(args, dev, ckpt, use_ema=bool(args.use_ema))
     # a Visual Genome builder samples objects: a stream seeded anew, so every run sees the same ones (scripts/evaluate.py)
     builder = folder_builder(dataset, args, sampler, dev, rng=random.Random(0))
     tic = time.time()
@@ -250,7 +258,7 @@ def sample_generalisation(args, dev, dataset):
     init_args(args)
     print("data: %d scenes, %s" % (len(dataset), dataset.image_dir), flush=True)
     torch.manual_seed(0)
-    sampler = Sampler(args, dev, ckpt)
+    sampler = Sampler(args, dev, ckpt, use_ema=bool(args.use_ema))
     rewrite, builder_args = None, args
     if args.rewrite is not None:
         # the robustness run: the batches carry the plain minimal graph, so that a drawn edge is never taken for a source
@@ -330,7 +338,7 @@ def sample_layouts(args, dev):
     except ValueError as e:
         raise SystemExit("--layouts %s: %s" % (args.layouts, e))
     torch.manual_seed(0)
-    sampler = Sampler(args, dev, ckpt)
+    sampler = Sampler(args, dev, ckpt, use_ema=bool(args.use_ema))
     tic = time.time()
     done = generate_layouts(sampler, rows, args.layout_boxes, args.output_dir, deprocess=args.img_deprocess,
                             batch_size=args.batch_size, image_format=args.image_format, num_writers=args.num_writers,
@@ -359,7 +367,7 @@ def sample_scene_graphs(args, dev):
     except ValueError as e:
         raise SystemExit("--scene_graphs %s: %s" % (args.scene_graphs, e))
     torch.manual_seed(0)
-    sampler = Sampler(args, dev, ckpt)
+    sampler = Sampler(args, dev, ckpt, use_ema=bool(args.use_ema))
     Image = None
     if args.output_dir:
         from PIL import Image
@@ -416,7 +424,8 @@ def main(argv=None):
     args.vocab = make_vocab(_vocab_kind(args.dataset))
     init_args(args)
     torch.manual_seed(0)
-    sampler = Sampler(args, dev, None if args.checkpoint_name == _NO_CHECKPOINT else args.checkpoint_name)
+    sampler = Sampler(args, dev, None if args.checkpoint_name == _NO_CHECKPOINT else args.checkpoint_name,
+                      use_ema=bool(args.use_ema))
     packed = args.dataset.startswith("packed")
     cfg = synth_config(args, args.batch_size)
     Image = None

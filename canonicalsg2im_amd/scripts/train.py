@@ -43,7 +43,14 @@ ones among the vocabulary's non-location predicates) that join the graph as in s
 every N iterations on the validation set of scripts/evaluate.py: the first `--num_val_samples` pictures of the val split
 when its directory exists, seeded synthetic batches (seeds disjoint from the training seeds) otherwise.  With N > 1 ranks
 every rank validates the SAME batches and rank 0 prints: the passes advance the discriminators' spectral-norm vectors and
-BatchNorm statistics (evaluate.py), which must stay identical across ranks, and no collective is issued."""
+BatchNorm statistics (evaluate.py), which must stay identical across ranks, and no collective is issued.
+
+`--ema_decay D` (default 0: off; 0 < D <= 1) keeps an exponential moving average of the whole generator model's weights
+(canonicalsg2im_amd/ema.py): one launch per iteration after the optimiser steps, `--ema_warmup 1` (default) with the decay
+min(D, (1 + n) / (10 + n)) at update n.  Checkpoints then carry `model_ema_state` and `ema` besides today's keys, and a
+restored run continues the average (a checkpoint without them starts it from the restored weights).  `--val_ema 1` (default
+0; needs --ema_decay) runs the validation passes of --val_every on the averaged weights, swapped in for the passes and out
+again; their lines read `EMA GT VAL` and `EMA VAL`."""
 import os
 import sys
 import time
@@ -106,10 +113,28 @@ def synth_config(args, batch_size):
     return BatchConfig(batch_size, args.image_size[0], lo, hi, graph, mask_size=args.mask_size)
 
 
+def validate_in_training(args, trainer, evaluator, dev, t, world=1, val_set=None):
+    """The validation passes of --val_every.  With --val_ema 1 they run on the averaged weights: inside
+    `trainer.ema.swapped()` (one swap launch and a cache invalidation on each side), with the evaluator's sampler — which
+    adopted the trainer's model and keeps W / sigma and packed operands of its own — invalidated on both sides as well."""
+    from . import evaluate as val_cli
+    if not getattr(args, "val_ema", 0):
+        return val_cli.validate(args, evaluator, dev, t, world, val_set)
+    if trainer.ema is None:
+        raise RuntimeError("--val_ema 1 needs a trainer with --ema_decay")
+    with trainer.ema.swapped():
+        evaluator.sampler.invalidate()
+        try:
+            return val_cli.validate(args, evaluator, dev, t, world, val_set, prefix="EMA ")
+        finally:
+            evaluator.sampler.invalidate()
+
+
 def build_parser():
     from .args import build_parser as base_parser
     p = base_parser()
     p.add_argument('--val_every', default=0, type=int)
+    p.add_argument('--val_ema', default=0, type=int, choices=[0, 1])
     return p
 
 
@@ -129,6 +154,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.val_every < 0:
         raise SystemExit("--val_every must be >= 0 (0: no validation)")
+    if args.val_ema and not args.ema_decay:
+        raise SystemExit("--val_ema 1 needs --ema_decay D (0 < D <= 1): there are no averaged weights to validate")
     if args.dataset == "packed_clevr_syn":
         from ..sg2im.data.packed_clevr_syn import NO_TRAINING
         raise SystemExit(NO_TRAINING)
@@ -202,7 +229,7 @@ def main(argv=None):
             import contextlib
             vargs = argparse_copy(args, batch_size=per_rank)
             with (contextlib.nullcontext() if rank == 0 else contextlib.redirect_stdout(open(os.devnull, "w"))):
-                val_cli.validate(vargs, evaluator, dev, t, world, val_set)
+                validate_in_training(vargs, trainer, evaluator, dev, t, world, val_set)
             tic = time.time()
         if args.output_dir and t % args.checkpoint_every == 0:
             os.makedirs(args.output_dir, exist_ok=True)

@@ -66,6 +66,13 @@ class Trainer:
         self.graphs = csg_graphs.StepGraphs(self) if use_graphs else None
         self.bucket_generation = ()            # (N > 1) generations of the gradient buckets, refreshed at the top of every step
         self.use_graphs = True                 # False: run eagerly without dropping the captured graphs (bench.py's event legs)
+        # EMA of the whole MetaGeneratorModel's weights (ema.py), opt-in: `--ema_decay D`, 0 = off.  Read with getattr:
+        # namespaces made before the flags existed (old run_args.json files, hand-built ones) have neither attribute.
+        self.ema = None
+        ema_decay = getattr(opt, "ema_decay", 0) or 0
+        if ema_decay:
+            from .ema import WeightEMA
+            self.ema = WeightEMA(self.model, ema_decay, warmup=bool(getattr(opt, "ema_warmup", 1)))
 
     def freeze_weights(self, module):
         """`--freeze 1 --freeze_options generation` (scripts/train.py:104-117, 337-338): the layout-to-image model and
@@ -109,7 +116,19 @@ class Trainer:
 
     def step(self, batch):
         """One training iteration.  Shape keys that repeat are replayed from captured HIP graphs (graphs.py); anything
-        else — a new shape, N > 1 ranks, masks, `--learned_converse` — runs the eager path below, in this process."""
+        else — a new shape, N > 1 ranks, masks, `--learned_converse` — runs the eager path below, in this process.
+        With `--ema_decay` the shadow weights are updated once per iteration, on either path, in one eager launch on the
+        current stream AFTER the iteration's optimiser steps: the eager path issues every step on the current stream (the
+        generator's Adam step and `_converse_step` included); the replayed path runs the generator's Adam step on a side
+        stream beside S3 and joins that stream to the current one before it returns (`main.wait_stream(self.side)` at the
+        end of graphs.StepGraphs._run), so no further event is needed.  The update is outside every captured graph: its
+        per-step decay (the warm-up) stays a plain kernel argument."""
+        out = self._step_once(batch)
+        if self.ema is not None:
+            self.ema.update()
+        return out
+
+    def _step_once(self, batch):
         if csg_dist.active():
             # a late-gradient flag of the previous iteration re-agrees the bucket set HERE, on every rank and on either path
             # (dist.GradBuckets.resolve): a rebuild re-allocates the flats that captured graphs address
@@ -215,6 +234,9 @@ class Trainer:
             out.update({'d_obj_state': d.obj_discriminator.state_dict(), 'd_mask_state': d.mask_discriminator.state_dict(),
                         'd_obj_optim_state': d.optimizer_d_obj.state_dict(),
                         'd_mask_optim_state': d.optimizer_d_mask.state_dict()})
+        if self.ema is not None:                 # (EMA off: exactly the keys above)
+            out['model_ema_state'] = self.ema.state_dict()
+            out['ema'] = self.ema.meta()
         return out
 
     def save_checkpoint(self, path, t=0, epoch=0):
@@ -244,6 +266,16 @@ class Trainer:
                     _load_optimizer(d.optimizer_d_mask, ckpt['d_mask_optim_state'])
         from . import ops
         ops.invalidate_weight_caches()
+        if self.ema is not None:
+            # this run's --ema_decay / --ema_warmup hold; the checkpoint gives the shadow and the counter
+            if 'model_ema_state' in ckpt and 'ema' in ckpt:
+                self.ema.load_state_dict(ckpt['model_ema_state'], ckpt['ema'].get('num_updates', 0))
+            else:
+                # a reference checkpoint, or a run that turns the EMA on late
+                self.ema.fill_from_model()
+                if csg_dist.rank() == 0:
+                    print("ema: the checkpoint has no 'model_ema_state': shadow filled from 'model_state', num_updates = 0",
+                          flush=True)
         if self.graphs is not None:
             # optimizer.load_state_dict REPLACES the moment tensors the captured Adam step updates in place: the graphs
             # would keep stepping the old ones.  Drop them; the next repeated shape is captured afresh.

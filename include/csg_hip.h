@@ -1224,6 +1224,55 @@ int64_t csg_ball_counts_workspace_bytes(int64_t m, int64_t n);
 int csg_ball_counts(const float* q, int64_t m, const float* f, int64_t n, int64_t D, const double* r2, void* workspace,
                     int64_t workspace_bytes, int32_t* inside, int32_t* holds, void* stream);
 
+/* ---- EMA of the weights: update, swap and fill of a flat fp32 shadow, one launch per call (csrc/ema.hip) --------------
+ * (Added after revision 122 without a new revision number, as the entries above: callers detect them by their symbols.)
+ * Stream ordered and capturable; no atomics, no host synchronisation, nothing read back; the same bits on every run.
+ *
+ * The work is an ITEM TABLE: item i pairs `numel` floats at `src` (a parameter or a floating buffer of the model) with
+ * `numel` floats at `dst` (its slot in the shadow).  The shadow is ONE flat fp32 allocation; every slot starts at a
+ * multiple of 4 floats, so src and dst are both 16-byte aligned (anything else is refused: there is no slow path), and
+ * both are dense runs of numel floats.  numel = 0 is a legal item.
+ *
+ * WHERE THE TABLE LIVES: IN DEVICE MEMORY, built once when the shadow is made, because the storage of a model's tensors
+ * stays where it is.  The multi-tensor entries above whose items change per call carry them in the kernel's arguments
+ * and need one launch per 24-32 items; here one call is ONE launch for any number of items (at most CSG_EMA_MAX_ITEMS).
+ * The host fills src / dst / numel / kind of a host copy, the planning entry below checks it and fills chunk0 (host only,
+ * no device needed; returns the total number of chunks, or a negative code), the caller uploads the array (8-byte
+ * aligned) and keeps it, and the tensors it names, alive while calls are in flight.
+ *
+ * WORK SPLIT: an item is cut into ceil(numel / CSG_EMA_CHUNK) chunks of CSG_EMA_CHUNK floats; a chunk never spans two
+ * items; chunk0 is the number of chunks of the items before it.  A block takes a chunk at a time, finds its item by
+ * bisection over chunk0, and moves 16 bytes per lane and stream; an item's last numel % 4 floats go one by one.
+ *
+ * MODES
+ *   CSG_EMA_UPDATE  kind CSG_EMA_AVERAGE (parameters):  e' = fmaf(d, e, omd * p)  in fp32 — the product omd * p rounded,
+ *                   then ONE fused multiply-add; this operation sequence is the contract (the tests' bound, two roundings,
+ *                   is derived from it).  d = (float)D and omd = (float)(1.0 - (double)D) are made on the host, both in
+ *                   [0, 1].  omd == 0 (D = 1) leaves AVERAGE items untouched, bit for bit.  D = 0 follows the formula,
+ *                   fmaf(0, e, 1 * p): e = inf gives NaN.
+ *                   kind CSG_EMA_COPY (running statistics, spectral-norm u / v):  e' = p, bit for bit.
+ *   CSG_EMA_SWAP    p and e exchanged for every item, bit for bit (NaN payloads, signed zeros); twice is the identity.
+ *   CSG_EMA_FILL    e = p for every kind (initialisation), bit for bit.  d and omd are ignored by SWAP and FILL.
+ * Floats of the shadow outside the slots (the padding up to the next multiple of 4, anything behind the last slot) are
+ * never read or written.                                                                                              */
+#define CSG_EMA_AVERAGE 0
+#define CSG_EMA_COPY 1
+#define CSG_EMA_UPDATE 0
+#define CSG_EMA_SWAP 1
+#define CSG_EMA_FILL 2
+#define CSG_EMA_CHUNK 4096
+#define CSG_EMA_MAX_ITEMS 65536
+typedef struct csg_ema_item {
+  float* src;      /* the live tensor (written by SWAP only) */
+  float* dst;      /* its slot in the shadow */
+  int64_t numel;
+  int64_t chunk0;  /* filled by the planning entry */
+  int32_t kind;    /* CSG_EMA_AVERAGE | CSG_EMA_COPY */
+  int32_t reserved;
+} csg_ema_item;
+int64_t csg_ema_table_plan(csg_ema_item* host_items, int64_t n);
+int csg_ema_apply(const csg_ema_item* items, int64_t n, int64_t chunks, int32_t mode, float d, float omd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
