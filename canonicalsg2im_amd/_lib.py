@@ -260,6 +260,11 @@ SIGNATURES = {
     "csg_ball_counts": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p]),
     "csg_ema_table_plan": (c_i64, [ctypes.POINTER(EmaItem), c_i64]),
     "csg_ema_apply": (c_i32, [c_p, c_i64, c_i64, c_i32, c_f32, c_f32, c_p]),
+    "csg_augment_table": (c_i32, [ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
+    "csg_augment_table_host": (c_i32, [ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
+    "csg_augment_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "csg_augment_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
+    "csg_augment_bwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
 }
 
 

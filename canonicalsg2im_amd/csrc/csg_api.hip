@@ -132,7 +132,7 @@ static const char* kNames[K_COUNT] = {
     "draw_labels_u8", "draw_graph_u8",
     "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums",
     "knn_radii", "ball_counts",
-    "ema"};
+    "ema", "augment"};
 
 }  // namespace csg
 

@@ -88,6 +88,7 @@ enum KernelId {
   K_KNN_RADII,
   K_BALL_COUNTS,
   K_EMA,
+  K_AUGMENT,
   K_COUNT
 };
 

@@ -24,6 +24,7 @@ __all__ = [
     "invalidate_weight_caches", "pack_conv_weight", "wino_pack", "prepack_weights", "wino_eligible", "wino_variant", "plan_conv", "spectral_weight", "spectral_weights", "spade_infer", "norm_eval_stats", "deprocess_u8", "preprocess_images", "pack_frozen_forward", "ACT_NONE", "ACT_LEAKY", "ACT_TANH",
     "conv2d_forward", "pool3", "spatial_mean", "resize_bilinear", "feat_stats", "feat_stats_finalize", "softmax_rows", "inception_score", "POOL_MAX", "POOL_AVG9", "POOL_AVG_INSIDE",
     "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums", "knn_radii", "ball_counts",
+    "augment_table", "augment_table_host", "d_augment",
 ]
 
 
@@ -3143,3 +3144,95 @@ def ema_swap(table):
 def ema_fill(table):
     """One launch: every slot = its source, bit for bit, whatever the kind."""
     _ema_apply(table, EMA_FILL, 0.0, 0.0, "ema_fill")
+
+
+# ---- DiffAugment of the discriminators' inputs (csrc/augment.hip; the transform and the table: include/csg_hip.h) ----------
+AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
+AUG_CHUNK = 256                      # CSG_AUG_CHUNK: pixels per partial of the per-sample sums
+
+
+def _aug_key(what, seed, iteration, pass_id, rank, rows, H):
+    for name, v, hi in (("seed", seed, 1 << 64), ("iteration", iteration, 1 << 63), ("pass_id", pass_id, 1 << 31),
+                        ("rank", rank, 1 << 31), ("rows", rows, 1 << 31)):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < hi:
+            raise RuntimeError("%s: %s must be an integer in [0, 2^%d), got %r" % (what, name, hi.bit_length() - 1, v))
+    if not isinstance(H, int) or H < 2:
+        raise RuntimeError("%s: H must be an integer >= 2, got %r" % (what, H))
+
+
+def augment_table_host(seed, iteration, pass_id, rows, H, rank=0):
+    """(rows, 8) int32 on the HOST: the words the device entry writes, from the host half of csrc/csg_augment.h."""
+    _aug_key("augment_table_host", seed, iteration, pass_id, rank, rows, H)
+    out = torch.zeros((rows, 8), dtype=torch.int32)
+    check(lib.csg_augment_table_host(seed, iteration, pass_id, rank, rows, H, ctypes.c_void_p(out.data_ptr())), "augment_table_host")
+    return out
+
+
+def augment_table(seed, iteration, pass_id, rows, H, rank=0, out=None, device=None):
+    """One launch: the parameter rows (b, s, c | tx, ty, y0, x0, size) of `rows` samples of an H x H map, an int32 (rows, 8)
+    device tensor (`out`, or a fresh one on `device`), from the counter-based hash over (seed, iteration, pass_id,
+    rank << 32 | row): no RNG state anywhere."""
+    _aug_key("augment_table", seed, iteration, pass_id, rank, rows, H)
+    if out is None:
+        out = torch.empty((rows, 8), dtype=torch.int32, device=device if device is not None else "cuda")
+    _aug_table_operand("augment_table", out, rows)
+    check(lib.csg_augment_table(seed, iteration, pass_id, rank, rows, H, ptr(out), stream()), "augment_table")
+    return out
+
+
+def _aug_table_operand(what, table, N):
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise RuntimeError("%s: the table must be a contiguous int32 (rows, 8) tensor, got %s" % (
+            what, (table.dtype, tuple(table.shape)) if torch.is_tensor(table) else type(table).__name__))
+    if table.shape[0] < N:
+        raise RuntimeError("%s: the table has %d rows, fewer than N = %d" % (what, table.shape[0], N))
+
+
+def _aug_launch(fn, what, x, table, c0, policy):
+    N, Ct, H, W = x.shape
+    out = empty_nhwc(N, Ct, H, W, x.device)
+    ws, nws = None, 0
+    if policy & AUG_COLOR and N:
+        nws = int(lib.csg_augment_workspace_bytes(N, H))
+        ws = torch.empty(max(nws, 8) // 8, dtype=torch.float64, device=x.device)
+    check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, policy, ptr(ws), nws, stream()), what)
+    return out
+
+
+class _DAugment(torch.autograd.Function):
+    """The transform of csrc/augment.hip and its adjoint.  Linear in x: the backward needs the table alone."""
+
+    @staticmethod
+    def forward(ctx, x, table, c0, policy):
+        ctx.save_for_backward(table)
+        ctx.meta = (c0, policy)
+        return _aug_launch(lib.csg_augment_fwd, "augment_fwd", nhwc(x), table, c0, policy)
+
+    @staticmethod
+    def backward(ctx, g):
+        (table,) = ctx.saved_tensors
+        c0, policy = ctx.meta
+        return _aug_launch(lib.csg_augment_bwd, "augment_bwd", nhwc(_f32(g)), table, c0, policy), None, None, None
+
+
+def d_augment(x, table, c0, policy):
+    """DiffAugment of x, a logical (N, Ct, H, H) tensor with NHWC memory and Ct % 4 == 0 (what `disc_input` and
+    `crop_objects` return): colour on channels [c0, c0 + 3), translation and cutout on all of them, as the mask `policy`
+    (a sum of AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT; the flag's names: d_augment.policy_mask) selects; sample n reads row n
+    of `table` (`augment_table`).  Returns the same kind of tensor; differentiable in x."""
+    if not isinstance(policy, int) or isinstance(policy, bool) or not 0 <= policy <= 7:
+        raise RuntimeError("d_augment: policy must be a mask in [0, 7] (1 = color, 2 = translation, 4 = cutout), got %r" % (policy,))
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise RuntimeError("d_augment: x must be a (N, Ct, H, H) tensor, got %s" % (
+            tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    _f32(x)
+    N, Ct, H, _ = x.shape
+    c0 = int(c0)
+    if Ct % 4:
+        raise RuntimeError("d_augment: Ct = %d must be a multiple of 4 (Ct %% 4 != 0)" % Ct)
+    if c0 < 0 or c0 + 3 > Ct:
+        raise RuntimeError("d_augment: colour channels [%d, %d) do not fit Ct = %d (c0 + 3 > Ct)" % (c0, c0 + 3, Ct))
+    if H < 2:
+        raise RuntimeError("d_augment: H = %d (H < 2)" % H)
+    _aug_table_operand("d_augment", table, N)
+    return _DAugment.apply(x, table, c0, policy)

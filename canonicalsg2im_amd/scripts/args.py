@@ -23,6 +23,21 @@ def ema_decay_flag(s):
     return d
 
 
+def d_augment_flag(s):
+    from ..d_augment import policy_mask, policy_names
+    try:
+        return policy_names(policy_mask(s))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def d_augment_seed_flag(s):
+    n = int(s)
+    if not 0 <= n < 1 << 64:
+        raise argparse.ArgumentTypeError("--d_augment_seed must be an integer in [0, 2^64), got %s" % s)
+    return n
+
+
 _OFF_PATH_FLAGS = {
     # data
     'img_deprocess': ('decode_img', 'str'), 'num_train_samples': (None, 'int'), 'num_val_samples': (1024, 'int'),
@@ -146,6 +161,13 @@ def build_parser():
     # min(D, (1 + n) / (10 + n)) at update n.  The trainer reads both with getattr: older namespaces lack them
     p.add_argument('--ema_decay', default=0.0, type=ema_decay_flag)
     p.add_argument('--ema_warmup', default=1, type=int, choices=(0, 1))
+    # DiffAugment of what the discriminators see (d_augment.py; not a flag of the reference): a comma list out of
+    # color,translation,cutout; empty = off.  The seed keys the counter-based hash the transforms' parameters come from.
+    p.add_argument('--d_augment', default='', type=d_augment_flag, metavar='POLICIES',
+                   help="differentiable augmentation of the discriminators' inputs: a comma list out of "
+                        "color,translation,cutout (default: empty = off)")
+    p.add_argument('--d_augment_seed', default=0, type=d_augment_seed_flag, metavar='N',
+                   help="seed of the augmentation's parameter stream (default 0)")
     # every other flag of the reference's command line (data loading, logging, checkpointing, evaluation, unused SPADE
     # options): accepted with the reference's defaults so that its recipes parse unchanged; none is read on the hot path
     for name, (default, kind) in _OFF_PATH_FLAGS.items():

@@ -50,7 +50,13 @@ BatchNorm statistics (evaluate.py), which must stay identical across ranks, and 
 min(D, (1 + n) / (10 + n)) at update n.  Checkpoints then carry `model_ema_state` and `ema` besides today's keys, and a
 restored run continues the average (a checkpoint without them starts it from the restored weights).  `--val_ema 1` (default
 0; needs --ema_decay) runs the validation passes of --val_every on the averaged weights, swapped in for the passes and out
-again; their lines read `EMA GT VAL` and `EMA VAL`."""
+again; their lines read `EMA GT VAL` and `EMA VAL`.
+
+`--d_augment POLICIES` (default empty: off) transforms everything the PatchGAN and the object-crop discriminator see during
+training with DiffAugment (canonicalsg2im_amd/d_augment.py): a comma list out of color,translation,cutout, anything else is
+refused.  `--d_augment_seed N` (default 0) keys the counter-based hash the transforms' parameters come from; there is no RNG
+state.  Both flags are part of the run's argument namespace; checkpoints then carry `d_augment` = {seed, iteration, policies}
+and a restored run continues the parameter stream.  Validation and sampling see raw inputs."""
 import os
 import sys
 import time
@@ -207,6 +213,8 @@ def main(argv=None):
     if rank == 0:
         print("data: %s" % ("%d pictures of %s, %d loader threads" % (len(train_set), train_set.image_dir, builder.num_workers)
                             if train_set is not None else "seeded synthetic batches (%s shapes)" % args.dataset), flush=True)
+        if trainer.d_augment is not None:
+            print("d_augment: %s" % trainer.d_augment.meta(), flush=True)
     tic = time.time()
     for t in range(t0 + 1, args.num_iterations + 1):
         if real is not None:

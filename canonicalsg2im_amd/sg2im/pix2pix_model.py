@@ -91,7 +91,8 @@ class Pix2PixModel(torch.nn.Module):
     def generator_image_terms(self, imgs, objs, boxes, masks, imgs_pred):
         """GAN_Img, GAN_Feat, VGG (reference :94-113): two passes of the (frozen) image discriminator."""
         opt, out = self.opt, {}
-        d_args = dict(layout_masks=masks, gt_train=True, fool=False)
+        # (--d_augment: both passes read table 0 — feature matching compares them, so they see ONE transform)
+        d_args = dict(layout_masks=masks, gt_train=True, fool=False, aug_pass=0)
         fake = self.netD_img(imgs_pred, objs, boxes, **d_args)
         out['GAN_Img'] = self._fool(fake, opt.discriminator_img_loss_weight)
         if not opt.no_ganFeat_loss:
@@ -103,7 +104,7 @@ class Pix2PixModel(torch.nn.Module):
     def generator_object_terms(self, imgs_pred, objs, boxes, masks, masks_pred):
         """GAN_Obj, GAN_Ac (:115-121) and the mask discriminator's terms (:124-138)."""
         opt, out = self.opt, {}
-        crop_scores, ac_loss, _ = self.netD_obj(imgs_pred, objs, boxes)
+        crop_scores, ac_loss, _ = self.netD_obj(imgs_pred, objs, boxes, aug_pass=3)
         out['GAN_Obj'] = self._fool(crop_scores, opt.discriminator_obj_loss_weight)
         out['GAN_Ac'] = ac_loss * opt.ac_loss_weight
         if self.netD_mask is not None and opt.mask_size > 0 and masks_pred is not None:
@@ -142,20 +143,22 @@ class Pix2PixModel(torch.nn.Module):
         spectral-norm vectors, so it is replayed — without autograd."""
         opt, crit = self.opt, self.criterionGAN
         d_args = dict(layout_masks=masks, gt_train=True)
-        out = {"D_img_fake": crit(self.netD_img(fake_img, objs, boxes, fool=False, **d_args), False, for_discriminator=True),
-               "D_img_real": crit(self.netD_img(imgs, objs, boxes, fool=False, **d_args), True, for_discriminator=True)}
+        out = {"D_img_fake": crit(self.netD_img(fake_img, objs, boxes, fool=False, aug_pass=1, **d_args), False,
+                                  for_discriminator=True),
+               "D_img_real": crit(self.netD_img(imgs, objs, boxes, fool=False, aug_pass=2, **d_args), True,
+                                  for_discriminator=True)}
         out["total_img_loss"] = _total(out)
         if not opt.use_img_disc:
             with torch.no_grad():
-                wrong = self.netD_img(imgs, objs, boxes, fool=True, **d_args)
+                wrong = self.netD_img(imgs, objs, boxes, fool=True, aug_pass=2, **d_args)
                 out["D_img_wrong"] = crit(wrong, False, for_discriminator=True) * (1 / 2) * (.5)
         return out
 
     def discriminator_object_terms(self, imgs, objs, boxes, masks, fake_img, masks_pred):
         """D_ac_real, D_ac_fake, D_obj, total_obj_loss (:178-185) and the mask discriminator's terms (:188-196)."""
         opt, crit, out = self.opt, self.criterionGAN, {}
-        s_real, out["D_ac_real"], self.d_real_crops = self.netD_obj(imgs, objs, boxes)
-        s_fake, out["D_ac_fake"], self.d_fake_crops = self.netD_obj(fake_img, objs, boxes)
+        s_real, out["D_ac_real"], self.d_real_crops = self.netD_obj(imgs, objs, boxes, aug_pass=5)
+        s_fake, out["D_ac_fake"], self.d_fake_crops = self.netD_obj(fake_img, objs, boxes, aug_pass=4)
         out["D_obj"] = self.gan_d_loss(s_real, s_fake) * 0.5
         out["total_obj_loss"] = out["D_obj"] + out["D_ac_real"] + out["D_ac_fake"]
         if opt.mask_size > 0 and masks_pred is not None:

@@ -84,6 +84,8 @@ def _side_stream(device):
 
 
 class MultiscaleDiscriminator(BaseNetwork):
+    d_augment = None                 # a d_augment.DAugment while the trainer runs with --d_augment (train.Trainer sets it)
+
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
@@ -102,13 +104,16 @@ class MultiscaleDiscriminator(BaseNetwork):
     def downsample(self, input):
         return ops.avgpool3s2(input)
 
-    def forward(self, img, objs, layout_boxes, layout_masks=None, gt_train=True, fool=False):
-        """`fool` is accepted and ignored, as in the reference."""
+    def forward(self, img, objs, layout_boxes, layout_masks=None, gt_train=True, fool=False, aug_pass=None):
+        """`fool` is accepted and ignored, as in the reference.  `aug_pass`: which parameter table of
+        `--d_augment` the packed input is transformed with (d_augment.py); raw outside a training step and without the flag."""
         csg_spectral_norm.prepare(self)              # the spectrally normalised weights of every scale, one launch per stage
         obj_vecs = self.attribute_embedding(objs)
         valid = real_object_mask(objs, self.opt.vocab)
         S = obj_vecs.size(-1)
         x = ops.disc_input(img, obj_vecs, layout_boxes, valid, self.opt.image_size[0], masks=layout_masks)
+        if self.d_augment is not None:               # picture and layout together: they stay aligned
+            x = self.d_augment.apply(x, aug_pass, S)
         # Who reads d(input)?  In the generator pass only the image (the discriminator is frozen), in the
         # discriminator passes only the layout (through D's own embedding): the first conv's backward-data
         # is restricted to those channels.
@@ -179,6 +184,7 @@ class AcDiscriminator(nn.Module):
 
 class AcCropDiscriminator(nn.Module):
     """reference discriminator.py:240-261: bilinear crops of every real object, then AcDiscriminator."""
+    d_augment = None                 # as MultiscaleDiscriminator.d_augment
 
     def __init__(self, vocab, arch, normalization='none', activation='relu', object_size=64, padding='same',
                  pooling='avg'):
@@ -222,13 +228,14 @@ class AcCropDiscriminator(nn.Module):
         nz = real_object_mask(objs, self.vocab).nonzero()   # (N,2) [image, object]; synchronises
         return nz[:, 0].contiguous(), nz[:, 1].contiguous()
 
-    def forward(self, imgs, objs, boxes):
+    def forward(self, imgs, objs, boxes, aug_pass=None):
         img_idx, obj_idx = self._object_index(objs)
         flat_boxes = boxes[img_idx, obj_idx]
         labels = objs[img_idx, obj_idx, 0]
         crops = ops.crop_objects(imgs, flat_boxes, img_idx, self.object_size)
-        real_scores, ac_loss = self.discriminator(crops, labels)
-        return real_scores, ac_loss, crops[:, :imgs.size(1)]
+        seen = crops if self.d_augment is None else self.d_augment.apply(crops, aug_pass, 0)
+        real_scores, ac_loss = self.discriminator(seen, labels)
+        return real_scores, ac_loss, crops[:, :imgs.size(1)]      # the crops kept for display are the raw ones
 
 
 class NLayerMaskDiscriminator2(NLayerDiscriminator):

@@ -73,6 +73,24 @@ class Trainer:
         if ema_decay:
             from .ema import WeightEMA
             self.ema = WeightEMA(self.model, ema_decay, warmup=bool(getattr(opt, "ema_warmup", 1)))
+        # DiffAugment of what the discriminators see (d_augment.py), opt-in: `--d_augment color,translation,cutout`, empty =
+        # off.  Read with getattr, as the EMA flags.  The two discriminators reach the object through a class-level attribute
+        # that is None without the flag: nothing on their path changes then.
+        self.d_augment = None
+        if getattr(opt, "d_augment", "") and opt.skip_generation:
+            if csg_dist.rank() == 0:
+                print("d_augment: --skip_generation runs no discriminator: --d_augment '%s' has nothing to act on" % opt.d_augment,
+                      flush=True)
+        elif getattr(opt, "d_augment", ""):
+            from .d_augment import DAugment
+            if opt.use_img_disc and csg_dist.rank() == 0:
+                print("d_augment: --use_img_disc 1 trains no object-crop discriminator: only the PatchGAN's input is augmented",
+                      flush=True)
+            self.d_augment = DAugment(opt.d_augment, getattr(opt, "d_augment_seed", 0), device, opt.batch_size,
+                                      opt.image_size[0], rank=csg_dist.rank())
+            self.discriminator.img_discriminator.d_augment = self.d_augment
+            if not opt.use_img_disc:
+                self.discriminator.obj_discriminator.d_augment = self.d_augment
 
     def freeze_weights(self, module):
         """`--freeze 1 --freeze_options generation` (scripts/train.py:104-117, 337-338): the layout-to-image model and
@@ -123,7 +141,16 @@ class Trainer:
         stream beside S3 and joins that stream to the current one before it returns (`main.wait_stream(self.side)` at the
         end of graphs.StepGraphs._run), so no further event is needed.  The update is outside every captured graph: its
         per-step decay (the warm-up) stays a plain kernel argument."""
-        out = self._step_once(batch)
+        if self.d_augment is None:
+            out = self._step_once(batch)
+        else:
+            # the counter advances and the PatchGAN passes' tables are refilled HERE, by eager launches on the current stream,
+            # before either path runs: the captured graphs only read the tables.  Active for the step alone.
+            self.d_augment.begin_step()
+            try:
+                out = self._step_once(batch)
+            finally:
+                self.d_augment.end_step()
         if self.ema is not None:
             self.ema.update()
         return out
@@ -237,6 +264,8 @@ class Trainer:
         if self.ema is not None:                 # (EMA off: exactly the keys above)
             out['model_ema_state'] = self.ema.state_dict()
             out['ema'] = self.ema.meta()
+        if self.d_augment is not None:           # (off: exactly the keys above)
+            out['d_augment'] = self.d_augment.meta()
         return out
 
     def save_checkpoint(self, path, t=0, epoch=0):
@@ -276,6 +305,10 @@ class Trainer:
                 if csg_dist.rank() == 0:
                     print("ema: the checkpoint has no 'model_ema_state': shadow filled from 'model_state', num_updates = 0",
                           flush=True)
+        if self.d_augment is not None:
+            # this run's --d_augment / --d_augment_seed hold; the checkpoint gives the iteration the parameter stream is at
+            self.d_augment.load_meta(ckpt.get('d_augment'), say=(lambda s: print(s, flush=True)) if csg_dist.rank() == 0
+                                     else (lambda s: None))
         if self.graphs is not None:
             # optimizer.load_state_dict REPLACES the moment tensors the captured Adam step updates in place: the graphs
             # would keep stepping the old ones.  Drop them; the next repeated shape is captured afresh.

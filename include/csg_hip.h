@@ -1273,6 +1273,42 @@ typedef struct csg_ema_item {
 int64_t csg_ema_table_plan(csg_ema_item* host_items, int64_t n);
 int csg_ema_apply(const csg_ema_item* items, int64_t n, int64_t chunks, int32_t mode, float d, float omd, void* stream);
 
+/* ---- DiffAugment of the discriminators' inputs: colour, translation, cutout; forward and adjoint (csrc/augment.hip) ---
+ * (Added after revision 122 without a new revision number, as the entries above: callers detect them by their symbols.)
+ * Stream ordered and capturable; no atomics, no host synchronisation, nothing read back; the same bits on every run.
+ *
+ * in / out: N samples of (H, H, Ct) floats, NHWC, dense, Ct a multiple of 4 (16-byte pixel rows), 16-byte aligned, not the
+ * same buffer.  Colour channels are [c0, c0 + 3); c0 need not be a multiple of 4.  policy is a sum of CSG_AUG_COLOR,
+ * CSG_AUG_TRANSLATION and CSG_AUG_CUTOUT; a policy that is off is skipped (policy 0 copies).  The transform, its order
+ * (colour, translation, cutout), the zero fill and the exact fp32 operation sequence of the colour map: csrc/augment.hip.
+ *
+ * THE TABLE: one row of eight 32-bit words per sample, in device memory, 16-byte aligned: the fp32 bits of b, s, c, then
+ * tx, ty, y0, x0, size as int32 (out[y, x] = in[y - ty, x - tx]; rows [y0, y0 + size) and columns [x0, x0 + size) are cut).
+ * The transform entries read their parameters ONLY from it — nothing that varies per step is a kernel argument — and take
+ * any values: every index is checked against the map.  The table entry fills `rows` rows from the counter-based hash of
+ * csrc/csg_augment.h over (seed, iteration, pass, rank << 32 | row) with the ranges of the DiffAugment paper for maps of
+ * H x H; its _host twin writes the same words to host memory (no device needed).
+ *
+ * The backward entry is the adjoint: `in` is the gradient at the transform's output, `out` the gradient at its input.
+ * workspace: needed with CSG_AUG_COLOR only (8-byte aligned, the size the workspace entry returns): the per-sample sums
+ * are a fixed fp64 tree over chunks of CSG_AUG_CHUNK pixels, so the bits do not depend on the grid.
+ * Refused with a message (CSG_E_BADSHAPE): c0 + 3 > Ct, Ct % 4 != 0, H < 2 or H > CSG_AUG_MAX_H, table_rows < N,
+ * N H H Ct >= 2^31, misaligned or null pointers, in == out, a workspace too small.                                      */
+#define CSG_AUG_COLOR 1
+#define CSG_AUG_TRANSLATION 2
+#define CSG_AUG_CUTOUT 4
+#define CSG_AUG_CHUNK 256
+#define CSG_AUG_MAX_H 16384
+int csg_augment_table(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H, uint32_t* table,
+                      void* stream);
+int csg_augment_table_host(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H,
+                           uint32_t* table);
+int64_t csg_augment_workspace_bytes(int64_t N, int64_t H);
+int csg_augment_fwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
+                    int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, void* stream);
+int csg_augment_bwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
+                    int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""The measurements of DiffAugment (profiles/d_augment.txt).  Not a test; no figure is fixed in advance.
+
+  python tools/augment_bench.py kernel [--out FILE]
+      Forward (`ops.d_augment`) and backward (the adjoint launch of its autograd Function), all three policies on, (a) on the C3 packed PatchGAN input
+      (16 x 256 x 256 x 40 fp32, c0 = 32) and (b) on 128 crops (128 x 32 x 32 x 4, c0 = 0), against the yardstick: a
+      `copy_` of the same buffer, timed in the same process, window by window in turn.  With colour on the forward reads
+      its input twice (the per-sample sum, then the map) and writes once, so it cannot beat the copy: the ratio is
+      recorded, not promised.  Also the two policies that move no colour (translation,cutout): one read, one write.
+
+  python tools/augment_bench.py steps [--out FILE]
+      ms per training step of the C3 trainer, replayed from HIP graphs, with `--d_augment color,translation,cutout` against
+      off: ONE trainer switched between the two (same allocations; each leg replays its own captured graph set), same
+      process, same build, windows in turn.  The difference is recorded in ms.
+
+Timing: HIP events around a window of calls after untimed warm-up calls, several windows, the median and all values
+reported.  Seeded inputs; the kernels' work does not depend on the values.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def window(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def median(v):
+    s = sorted(v)
+    return s[len(s) // 2]
+
+
+def fmt(v):
+    return "%.4f ms  [%s]" % (median(v), " ".join("%.4f" % x for x in v))
+
+
+def kernel(args, dev):
+    from canonicalsg2im_amd import ops
+    from canonicalsg2im_amd._lib import lib
+    lines = ["device: %s; HIP events, %d calls per window after %d warm-up calls, %d windows in turn; median [all windows]" % (
+        torch.cuda.get_device_name(0), args.iters, args.warmup, args.windows)]
+    for name, (N, H, Ct, c0) in (("C3 packed PatchGAN input", (16, 256, 40, 32)), ("128 crops", (128, 32, 4, 0))):
+        torch.manual_seed(0)
+        x = ops.empty_nhwc(N, Ct, H, H, dev).normal_()
+        g = ops.empty_nhwc(N, Ct, H, H, dev).normal_()
+        dst = torch.empty_like(x)
+        table = ops.augment_table(0, 1, 0, N, H, device=dev)
+        nbytes = x.numel() * 4
+        runs = {}
+        for label, policy in (("color,translation,cutout", 7), ("translation,cutout", 6)):
+            runs[label + " forward"] = lambda policy=policy: ops.d_augment(x, table, c0, policy)
+            # the adjoint as the Function's backward issues it (ops._aug_launch on a gradient that is already there): timed
+            # through autograd the call is bound by the host, 0.07-0.08 ms whatever the size
+            runs[label + " backward"] = lambda policy=policy: ops._aug_launch(lib.csg_augment_bwd, "augment_bwd", g, table, c0, policy)
+        runs["copy_ of the same buffer"] = lambda: dst.copy_(x)
+        for fn in runs.values():
+            for _ in range(args.warmup):
+                fn()
+        times = {k: [] for k in runs}
+        for _ in range(args.windows):
+            for k, fn in runs.items():
+                times[k].append(window(fn, args.iters))
+        copy = median(times["copy_ of the same buffer"])
+        lines.append("%s: %d x %d x %d x %d fp32 = %.1f MB, c0 = %d" % (name, N, H, H, Ct, nbytes / 1e6, c0))
+        for k, v in times.items():
+            lines.append("    %-42s %s per call = %.2f x the copy, %.2f TB/s of (one read + one write)" % (
+                k, fmt(v), median(v) / copy, 2 * nbytes / (median(v) * 1e-3) / 1e12))
+    return lines
+
+
+def c3_trainer(T, synth, dev, policies):
+    base = synth.BASELINE_CONFIGS["C3"]
+    vocab = synth.make_vocab(base["vocab"])
+    opt = T.make_opt(vocab, ["--image_size", "256,256", "--no_vgg_loss", "--batch_size", "16", "--d_augment", policies])
+    torch.manual_seed(0)
+    tr = T.Trainer(opt, dev)
+    cfg = base["cfg"]
+    bs = [[None if t is None else t.to(dev) for t in
+           synth.make_batch(vocab, synth.BatchConfig(16, 256, cfg.min_objects, cfg.max_objects, cfg.graph), seed=i)] for i in range(4)]
+    return tr, bs
+
+
+def steps(args, dev):
+    from canonicalsg2im_amd import synth, train as T
+    tr, bs = c3_trainer(T, synth, dev, "color,translation,cutout")
+    aug, it = tr.d_augment, [0]
+
+    def switch(on):
+        # ONE trainer, so that both legs run on the same allocations: off = the DAugment object taken away, which is what a
+        # trainer without the flag holds (None); the policy is part of the graph key, so each leg has its own captured set
+        obj = aug if on else None
+        tr.d_augment = tr.discriminator.img_discriminator.d_augment = tr.discriminator.obj_discriminator.d_augment = obj
+
+    def step():
+        tr.step(bs[it[0] % 4])
+        it[0] += 1
+
+    for on in (False, True):
+        switch(on)
+        for _ in range(10):                  # eager, the set's capture, the encoder buckets' captures, replays
+            step()
+    times = {False: [], True: []}
+    for _ in range(args.windows):
+        for on in (False, True):
+            switch(on)
+            times[on].append(window(step, args.iters))
+    return ["device: %s; C3 trainer (256 x 256, 16 images, --no_vgg_loss), replayed path, ONE trainer switched between the legs" %
+            torch.cuda.get_device_name(0),
+            "HIP events, %d steps per window, %d windows in turn; median [all windows]; %d replays, %d eager steps, %d graph sets" % (
+                args.iters, args.windows, tr.graphs.replays, tr._eager_steps, len(tr.graphs.sets)),
+            "augmentation off:                      %s per step" % fmt(times[False]),
+            "color,translation,cutout:              %s per step" % fmt(times[True]),
+            "difference: %+.3f ms per step" % (median(times[True]) - median(times[False]))]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["kernel", "steps"])
+    ap.add_argument("--iters", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    if args.iters is None:
+        args.iters = 2000 if args.what == "kernel" else 10        # kernel windows of 0.04-0.2 s
+    sys.path.insert(0, HERE)
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/augment_bench.py measures on the device: no HIP device here, nothing measured")
+    dev = torch.device("cuda", 0)
+    lines = kernel(args, dev) if args.what == "kernel" else steps(args, dev)
+    text = "\n".join(["$ python tools/augment_bench.py " + " ".join(sys.argv[1:] if argv is None else argv)] + lines) + "\n"
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
