@@ -265,6 +265,13 @@ SIGNATURES = {
     "csg_augment_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "csg_augment_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
     "csg_augment_bwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
+    "csg_augment_gate": (c_i32, [ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
+    "csg_augment_gate_host": (c_i32, [ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
+    "csg_augment_fwd_gated": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i64, c_p, c_p]),
+    "csg_augment_bwd_gated": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i64, c_p, c_p]),
+    "csg_ada_accumulate": (c_i32, [ctypes.POINTER(HingeItem), c_i32, c_p, c_p]),
+    "csg_ada_update": (c_i32, [c_p, c_i64, c_i64, c_p]),
+    "csg_ada_update_host": (c_i32, [c_p, c_i64, c_i64]),
 }
 
 

@@ -38,6 +38,14 @@
 // whose float4 holds a colour channel fetches the pixel's colour triple again (one or two more 16-byte loads that hit L1 /
 // L2).  Nothing that varies per step is a kernel argument: the parameters come from the table, which is what lets a
 // captured graph replay the pass.
+//
+// ADAPTIVE STRENGTH (StyleGAN2-ADA; the arithmetic: csg_augment.h).  The _gated entries take one int32 mask per sample beside
+// the table: sample n runs policy & gate[n], so "off for this sample" is the same skip as "off for the launch" — bit copies.
+// The ungated entries pass a null gate and instantiate the kernels without it: their code is what it was.  k_aug_gate fills
+// the masks from the hash and from p24, which it reads from the controller record in device memory; k_ada_accumulate adds
+// the signs and the count of the real pass's prediction maps to that record (integer sums, integer atomics: order-free);
+// k_ada_update, one thread, moves p24 by one step towards the target and restarts the counts.  None of them takes p as an
+// argument or reads anything back, so the gate fills can run eagerly before a replayed step and the accumulation inside it.
 #include "csg_common.h"
 #include "csg_augment.h"
 #include "csg_reduce.h"
@@ -126,20 +134,23 @@ __device__ __forceinline__ void aug_colour_bwd(float& r, float& g, float& b, con
 }
 
 // stage 1 of the per-sample sum: one partial per chunk of 256 pixels (forward: of x; backward: of the shifted, masked g)
-template <bool BWD>
+// GATED: sample n runs policy & gate[n].  A sample whose colour bit is off needs no mean: its chunks read nothing and write
+// 0.0 partials (the block still walks them: the tree and the barriers are per chunk).  Without GATED the code is what it was.
+template <bool BWD, bool GATED>
 __global__ __launch_bounds__(kAugThreads) void k_aug_sum(const float* __restrict__ in, const uint32_t* __restrict__ table,
-                                                         double* __restrict__ partials, int N, int H, int Ct, int c0, int policy,
-                                                         int chunks) {
+                                                         const int32_t* __restrict__ gate, double* __restrict__ partials, int N,
+                                                         int H, int Ct, int c0, int policy, int chunks) {
   __shared__ double part[kAugThreads / 64][1];
   const int total = N * chunks, HH = H * H;
   for (int gc = blockIdx.x; gc < total; gc += gridDim.x) {
     const int n = gc / chunks, pix = (gc - n * chunks) * CSG_AUG_CHUNK + (int)threadIdx.x;
+    const int pol = GATED ? policy & gate[n] : policy;
     double v[1] = {0.0};
-    if (pix < HH) {
+    if (pix < HH && (!GATED || (pol & CSG_AUG_COLOR))) {
       const int y = pix / H, x = pix - y * H;
       int sy = y, sx = x;
       bool live = true;
-      if (BWD) live = aug_source<true>(aug_load(table, n, H), policy, H, y, x, sy, sx);
+      if (BWD) live = aug_source<true>(aug_load(table, n, H), pol, H, y, x, sy, sx);
       if (live) {
         float r, g, b;
         aug_colour3(in + (((size_t)n * H + sy) * H + sx) * Ct, c0, r, g, b);
@@ -173,10 +184,13 @@ __device__ __forceinline__ float aug_pick(float keep, int ch, float r, float g, 
   return ch == 0 ? r : ch == 1 ? g : ch == 2 ? b : keep;
 }
 
-template <bool BWD, bool COLOR>
+// GATED: sample n runs policy & gate[n] — a per-lane value, since a block's float4 may belong to several samples.  A lane of a
+// sample whose colour bit is off takes the copy path of a colour-free launch: no second load, no arithmetic on its value.
+template <bool BWD, bool COLOR, bool GATED>
 __global__ __launch_bounds__(kAugThreads) void k_aug_apply(const float* __restrict__ in, float* __restrict__ out,
-                                                           const uint32_t* __restrict__ table, const float* __restrict__ mean, int H,
-                                                           int Ct, int c0, int policy, unsigned total) {
+                                                           const uint32_t* __restrict__ table, const int32_t* __restrict__ gate,
+                                                           const float* __restrict__ mean, int H, int Ct, int c0, int policy,
+                                                           unsigned total) {
   const unsigned G = (unsigned)Ct >> 2, HH = (unsigned)(H * H);
   const unsigned base = blockIdx.x * (unsigned)(kAugThreads * kAugUnroll) + threadIdx.x;
   float4 v[kAugUnroll];
@@ -196,10 +210,11 @@ __global__ __launch_bounds__(kAugThreads) void k_aug_apply(const float* __restri
       const unsigned n = q / HH, rem = q - n * HH;
       const int y = (int)(rem / (unsigned)H), x = (int)(rem - (unsigned)y * (unsigned)H);
       prm[k] = aug_load(table, (int)n, H);
+      const int pol = GATED ? policy & gate[n] : policy;
       int sy, sx;
-      const bool live = aug_source<BWD>(prm[k], policy, H, y, x, sy, sx);
+      const bool live = aug_source<BWD>(prm[k], pol, H, y, x, sy, sx);
       const float* px = in + (((size_t)n * H + sy) * H + sx) * Ct;
-      const bool colour = COLOR && (int)(4 * grp) < c0 + 3 && (int)(4 * grp) + 4 > c0;
+      const bool colour = COLOR && (!GATED || (pol & CSG_AUG_COLOR)) && (int)(4 * grp) < c0 + 3 && (int)(4 * grp) + 4 > c0;
       if (colour) {
         rel[k] = (int)(4 * grp) - c0;
         mu[k] = mean[n];
@@ -238,6 +253,70 @@ __global__ __launch_bounds__(kAugThreads) void k_aug_table(uint64_t seed, uint64
   *(uint4*)(table + 8 * (size_t)n + 4) = make_uint4(r.w[4], r.w[5], r.w[6], r.w[7]);
 }
 
+__global__ __launch_bounds__(kAugThreads) void k_aug_gate(uint64_t seed, uint64_t iteration, uint64_t pass, uint64_t rank, int rows,
+                                                          const int64_t* __restrict__ ctrl, int32_t* __restrict__ gate) {
+  const int n = blockIdx.x * kAugThreads + threadIdx.x;
+  if (n >= rows) return;
+  gate[n] = (int32_t)aug_gate(seed, iteration, pass, rank, (uint64_t)n, (uint32_t)ada_clamp_p(ctrl[0]));
+}
+
+// The overfitting figure of StyleGAN2-ADA, r_t = E[sign(D(real))], as two integers: S += sum of sign(x), C += the number of
+// elements, over every element of up to four prediction maps (the item form of csg_hinge_mean_fwd).  sign: +1 for x > 0, -1
+// for x < 0, else 0 (both zeros, NaN).  Integer sums do not depend on their order: a lane strides over the flat element
+// index, a block adds its lanes (shuffles, then the four waves), and lane 0 adds the block's pair to the record with two
+// 64-bit integer atomics — the same words whatever the grid.
+constexpr int kAdaMaxGrid = 256;
+
+struct AdaItems {
+  const float* x[4];
+  int64_t sb[4], sh[4], sw[4];
+  int64_t first[5];               // map m holds elements [first[m], first[m + 1]) of the launch; an absent map none
+  int H[4], W[4];
+  int n;
+};
+
+__global__ __launch_bounds__(kAugThreads) void k_ada_accumulate(AdaItems it, int64_t* __restrict__ ctrl) {
+  __shared__ long long part[kAugThreads / 64][2];
+  long long sum = 0, cnt = 0;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {                       // (constant indices: the items stay in the kernel's arguments)
+    const int64_t count = it.first[m + 1] - it.first[m], hw = (int64_t)it.H[m] * it.W[m];
+    for (int64_t e = (int64_t)blockIdx.x * kAugThreads + threadIdx.x; e < count; e += (int64_t)gridDim.x * kAugThreads) {
+      const int64_t b = e / hw, r = e - b * hw;
+      const int64_t y = r / it.W[m], x = r - y * it.W[m];
+      const float v = it.x[m][b * it.sb[m] + y * it.sh[m] + x * it.sw[m]];
+      sum += (v > 0.0f) ? 1 : (v < 0.0f) ? -1 : 0;
+      cnt += 1;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_down(sum, o, 64);
+    cnt += __shfl_down(cnt, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    part[wave][0] = sum;
+    part[wave][1] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long S = 0, C = 0;
+    for (int w = 0; w < kAugThreads / 64; ++w) {
+      S += part[w][0];
+      C += part[w][1];
+    }
+    if (C) {
+      atomicAdd((unsigned long long*)(ctrl + 1), (unsigned long long)S);
+      atomicAdd((unsigned long long*)(ctrl + 2), (unsigned long long)C);
+    }
+  }
+}
+
+__global__ void k_ada_update(int64_t* __restrict__ ctrl, int64_t T24, int64_t step24) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ada_update_words(ctrl, T24, step24);
+}
+
 static int64_t aug_chunks(int64_t H) { return cdiv(H * H, (int64_t)CSG_AUG_CHUNK); }
 
 static int aug_check_table(const char* who, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H) {
@@ -249,9 +328,18 @@ static int aug_check_table(const char* who, int64_t iteration, int64_t pass, int
   return CSG_OK;
 }
 
+static int aug_check_gate(const char* who, int64_t iteration, int64_t pass, int64_t rank, int64_t rows) {
+  CSG_REQUIRE(iteration >= 0 && pass >= 0 && pass <= 0x7fffffff && rank >= 0 && rank <= 0x7fffffff, CSG_E_BADSHAPE,
+              "%s: iteration %ld, pass %ld and rank %ld must be non-negative (pass and rank below 2^31)", who, (long)iteration,
+              (long)pass, (long)rank);
+  CSG_REQUIRE(rows >= 0 && rows <= 0x7fffffff, CSG_E_BADSHAPE, "%s: %ld rows (0 .. 2^31 - 1)", who, (long)rows);
+  return CSG_OK;
+}
+
 template <bool BWD>
 static int aug_apply(const char* who, const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H,
-                     int64_t Ct, int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, void* stream) {
+                     int64_t Ct, int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, bool gated,
+                     const int32_t* gate, void* stream) {
   CSG_REQUIRE(policy >= 0 && policy <= (CSG_AUG_COLOR | CSG_AUG_TRANSLATION | CSG_AUG_CUTOUT), CSG_E_BADSHAPE,
               "%s: policy %d (a sum of 1 = colour, 2 = translation, 4 = cutout)", who, (int)policy);
   CSG_REQUIRE(H >= 2 && H <= CSG_AUG_MAX_H, CSG_E_BADSHAPE, "%s: H = %ld (2 .. %d)", who, (long)H, CSG_AUG_MAX_H);
@@ -268,6 +356,9 @@ static int aug_apply(const char* who, const float* in, float* out, const uint32_
   CSG_REQUIRE((((uintptr_t)in | (uintptr_t)out | (uintptr_t)table) & 15) == 0, CSG_E_BADSHAPE,
               "%s: in, out and the table must be 16-byte aligned", who);
   CSG_REQUIRE((const void*)in != (const void*)out, CSG_E_BADSHAPE, "%s: not in place (a translated pixel reads another one)", who);
+  if (gated)
+    CSG_REQUIRE(gate != nullptr && ((uintptr_t)gate & 3) == 0, CSG_E_BADSHAPE,
+                "%s: the gate must be a 4-byte aligned array of N int32 (null pointer or misaligned)", who);
   const bool colour = (policy & CSG_AUG_COLOR) != 0;
   const int64_t chunks = aug_chunks(H);
   if (colour)
@@ -281,19 +372,25 @@ static int aug_apply(const char* who, const float* in, float* out, const uint32_
   if (colour) {
     const int64_t total = N * chunks;
     const unsigned grid = (unsigned)(total < kAugMaxGrid ? total : kAugMaxGrid);
-    CSG_LAUNCH(k_aug_sum<BWD>, dim3(grid), dim3(kAugThreads), 0, s, in, table, partials, (int)N, (int)H, (int)Ct, (int)c0,
-               (int)policy, (int)chunks);
+    if (gated)
+      CSG_LAUNCH((k_aug_sum<BWD, true>), dim3(grid), dim3(kAugThreads), 0, s, in, table, gate, partials, (int)N, (int)H, (int)Ct,
+                 (int)c0, (int)policy, (int)chunks);
+    else
+      CSG_LAUNCH((k_aug_sum<BWD, false>), dim3(grid), dim3(kAugThreads), 0, s, in, table, gate, partials, (int)N, (int)H, (int)Ct,
+                 (int)c0, (int)policy, (int)chunks);
     CSG_LAUNCH(k_aug_mean<BWD>, dim3((unsigned)N), dim3(kAugThreads), 0, s, (const double*)partials, table, mean, (int)chunks,
                3.0 * (double)H * (double)H);
   }
   const unsigned total4 = (unsigned)(N * H * H * (Ct / 4));
   const unsigned grid = (unsigned)cdiv((int64_t)total4, (int64_t)kAugThreads * kAugUnroll);
-  if (colour)
-    CSG_LAUNCH((k_aug_apply<BWD, true>), dim3(grid), dim3(kAugThreads), 0, s, in, out, table, (const float*)mean, (int)H, (int)Ct,
-               (int)c0, (int)policy, total4);
-  else
-    CSG_LAUNCH((k_aug_apply<BWD, false>), dim3(grid), dim3(kAugThreads), 0, s, in, out, table, (const float*)mean, (int)H, (int)Ct,
-               (int)c0, (int)policy, total4);
+#define CSG_AUG_APPLY(COLOR, GATED)                                                                                          \
+  CSG_LAUNCH((k_aug_apply<BWD, COLOR, GATED>), dim3(grid), dim3(kAugThreads), 0, s, in, out, table, gate, (const float*)mean, \
+             (int)H, (int)Ct, (int)c0, (int)policy, total4)
+  if (colour && gated) CSG_AUG_APPLY(true, true);
+  else if (colour) CSG_AUG_APPLY(true, false);
+  else if (gated) CSG_AUG_APPLY(false, true);
+  else CSG_AUG_APPLY(false, false);
+#undef CSG_AUG_APPLY
   return check_launch(who);
 }
 
@@ -331,12 +428,100 @@ int64_t csg_augment_workspace_bytes(int64_t N, int64_t H) {
 
 int csg_augment_fwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
                     int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, void* stream) {
-  return aug_apply<false>("csg_augment_fwd", in, out, table, table_rows, N, H, Ct, c0, policy, workspace, workspace_bytes, stream);
+  return aug_apply<false>("csg_augment_fwd", in, out, table, table_rows, N, H, Ct, c0, policy, workspace, workspace_bytes, false,
+                          nullptr, stream);
 }
 
 int csg_augment_bwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
                     int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, void* stream) {
-  return aug_apply<true>("csg_augment_bwd", in, out, table, table_rows, N, H, Ct, c0, policy, workspace, workspace_bytes, stream);
+  return aug_apply<true>("csg_augment_bwd", in, out, table, table_rows, N, H, Ct, c0, policy, workspace, workspace_bytes, false,
+                         nullptr, stream);
+}
+
+int csg_augment_fwd_gated(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
+                          int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, const int32_t* gate, void* stream) {
+  return aug_apply<false>("csg_augment_fwd_gated", in, out, table, table_rows, N, H, Ct, c0, policy, workspace, workspace_bytes,
+                          true, gate, stream);
+}
+
+int csg_augment_bwd_gated(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
+                          int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, const int32_t* gate, void* stream) {
+  return aug_apply<true>("csg_augment_bwd_gated", in, out, table, table_rows, N, H, Ct, c0, policy, workspace, workspace_bytes,
+                         true, gate, stream);
+}
+
+int csg_augment_gate_host(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t p24, int32_t* gate) {
+  if (int rc = aug_check_gate("csg_augment_gate_host", iteration, pass, rank, rows)) return rc;
+  CSG_REQUIRE(p24 >= 0 && p24 <= CSG_ADA_ONE, CSG_E_BADSHAPE, "csg_augment_gate_host: p24 = %ld (0 .. 2^24)", (long)p24);
+  CSG_REQUIRE(rows == 0 || gate != nullptr, CSG_E_BADSHAPE, "csg_augment_gate_host: null pointer");
+  for (int64_t n = 0; n < rows; ++n)
+    gate[n] = (int32_t)aug_gate(seed, (uint64_t)iteration, (uint64_t)pass, (uint64_t)rank, (uint64_t)n, (uint32_t)p24);
+  return CSG_OK;
+}
+
+int csg_augment_gate(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, const int64_t* ctrl, int32_t* gate,
+                     void* stream) {
+  if (int rc = aug_check_gate("csg_augment_gate", iteration, pass, rank, rows)) return rc;
+  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
+              "csg_augment_gate: the controller must be 8-byte aligned (null pointer or misaligned)");
+  if (rows == 0) return CSG_OK;
+  CSG_REQUIRE(gate != nullptr && ((uintptr_t)gate & 3) == 0, CSG_E_BADSHAPE,
+              "csg_augment_gate: the gate must be 4-byte aligned (null pointer or misaligned)");
+  hipStream_t s = (hipStream_t)stream;
+  CSG_LAUNCH(k_aug_gate, dim3((unsigned)cdiv(rows, (int64_t)kAugThreads)), dim3(kAugThreads), 0, s, seed, (uint64_t)iteration,
+             (uint64_t)pass, (uint64_t)rank, (int)rows, ctrl, gate);
+  return check_launch("csg_augment_gate");
+}
+
+int csg_ada_accumulate(const csg_hinge_item* items, int32_t n_items, int64_t* ctrl, void* stream) {
+  CSG_REQUIRE(items != nullptr && n_items >= 1 && n_items <= 4, CSG_E_BADSHAPE, "csg_ada_accumulate: 1..4 maps (got %d)",
+              (int)n_items);
+  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
+              "csg_ada_accumulate: the controller must be 8-byte aligned (null pointer or misaligned)");
+  AdaItems it;
+  it.n = n_items;
+  int64_t total = 0;
+  for (int i = 0; i < 4; ++i) {
+    const csg_hinge_item& d = items[i < n_items ? i : 0];
+    CSG_REQUIRE(d.x != nullptr && ((uintptr_t)d.x & 3) == 0 && d.B > 0 && d.H > 0 && d.W > 0 && d.B * d.H * d.W < (1ll << 30),
+                CSG_E_BADSHAPE, "csg_ada_accumulate: bad map %d (null pointer, misaligned, or not 1 .. 2^30 - 1 elements)", i);
+    it.x[i] = d.x; it.sb[i] = d.sb; it.sh[i] = d.sh; it.sw[i] = d.sw;
+    it.H[i] = (int)d.H; it.W[i] = (int)d.W;
+    it.first[i] = total;
+    if (i < n_items) total += d.B * d.H * d.W;
+  }
+  it.first[4] = total;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t blocks = cdiv(total, (int64_t)kAugThreads * 4);
+  ProfScope p(K_AUGMENT, (double)total * 4.0, s);
+  CSG_LAUNCH(k_ada_accumulate, dim3((unsigned)(blocks < kAdaMaxGrid ? blocks : kAdaMaxGrid)), dim3(kAugThreads), 0, s, it, ctrl);
+  return check_launch("csg_ada_accumulate");
+}
+
+static int ada_check_update(const char* who, const int64_t* ctrl, int64_t T24, int64_t step24) {
+  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
+              "%s: the controller must be 8-byte aligned (null pointer or misaligned)", who);
+  CSG_REQUIRE(T24 >= 0 && T24 <= CSG_ADA_ONE, CSG_E_BADSHAPE, "%s: T24 = %ld (0 .. 2^24)", who, (long)T24);
+  CSG_REQUIRE(step24 >= 1, CSG_E_BADSHAPE, "%s: step24 = %ld (step24 < 1)", who, (long)step24);
+  return CSG_OK;
+}
+
+int csg_ada_update_host(int64_t* ctrl, int64_t T24, int64_t step24) {
+  if (int rc = ada_check_update("csg_ada_update_host", ctrl, T24, step24)) return rc;
+  CSG_REQUIRE(ctrl[0] >= 0 && ctrl[0] <= CSG_ADA_ONE, CSG_E_BADSHAPE, "csg_ada_update_host: p24 = %ld (0 .. 2^24)", (long)ctrl[0]);
+  CSG_REQUIRE(ctrl[2] >= 0 && ctrl[2] < CSG_ADA_MAX_COUNT, CSG_E_BADSHAPE,
+              "csg_ada_update_host: C = %ld elements (0 .. 2^38 - 1: S * 2^24 must fit int64)", (long)ctrl[2]);
+  ada_update_words(ctrl, T24, step24);
+  return CSG_OK;
+}
+
+// The device twin cannot read the words before the launch: a p24 outside [0, 2^24] is clamped and a count outside
+// [0, 2^38) leaves p24 alone (csg_augment.h), where the host entry refuses.
+int csg_ada_update(int64_t* ctrl, int64_t T24, int64_t step24, void* stream) {
+  if (int rc = ada_check_update("csg_ada_update", ctrl, T24, step24)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  CSG_LAUNCH(k_ada_update, dim3(1), dim3(1), 0, s, ctrl, T24, step24);
+  return check_launch("csg_ada_update");
 }
 
 }  // extern "C"

@@ -19,6 +19,16 @@
 //   y0 = cy - size / 2, x0 = cx - size / 2
 //
 // A row is eight 32-bit words: the bits of b, s, c, then tx, ty, y0, x0, size as int32.
+//
+// THE GATE (adaptive strength, StyleGAN2-ADA's p): policy j = 0, 1, 2 (colour, translation, cutout) is on for the sample iff
+//   aug_u24(step(h, 8 + j)) < p24,   p24 an integer in [0, 2^24] (p = p24 * 2^-24).
+// Draws 8, 9, 10 are the gate's alone: draws 1..7 and every row are what they were.  p24 = 2^24 turns every policy on (a 24-bit
+// draw is below 2^24), p24 = 0 turns every policy off.
+//
+// THE CONTROLLER is eight int64 words, [p24, S, C, updates, S_last, C_last, 0, 0]: S the sum of sign(D(real)) over the
+// elements counted since the last update, C their number.  One update moves p24 by a fixed step towards the target:
+//   d = S * 2^24 - T24 * C  (int64; the sign of S / C - T),   p24' = clamp(p24 + sgn(d) * step24, 0, 2^24);
+// C = 0 or d = 0 leaves p24 alone.  |S| <= C < 2^38 keeps both products below 2^62; words outside that leave p24 alone too.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -76,6 +86,40 @@ CSG_AUG_HD AugRow aug_row(uint64_t seed, uint64_t iteration, uint64_t pass, uint
   r.w[6] = (uint32_t)(aug_int(rw_step(h, 7ull), centres) - size / 2);
   r.w[7] = (uint32_t)size;
   return r;
+}
+
+#define CSG_ADA_ONE (1ll << 24)
+#define CSG_ADA_MAX_COUNT (1ll << 38)
+
+// p24 in [0, 2^24]: the caller has clamped or refused everything else
+CSG_AUG_HD uint32_t aug_gate(uint64_t seed, uint64_t iteration, uint64_t pass, uint64_t rank, uint64_t n, uint32_t p24) {
+  const uint64_t h = aug_key(seed, iteration, pass, rank, n);
+  uint32_t m = 0;
+  for (uint32_t j = 0; j < 3; ++j)
+    if (aug_u24(rw_step(h, 8ull + j)) < p24) m |= 1u << j;
+  return m;
+}
+
+CSG_AUG_HD int64_t ada_clamp_p(int64_t p24) { return p24 < 0 ? 0 : p24 > CSG_ADA_ONE ? CSG_ADA_ONE : p24; }
+
+CSG_AUG_HD int64_t ada_next_p(int64_t p24, int64_t S, int64_t C, int64_t T24, int64_t step24) {
+  if (C <= 0 || C >= CSG_ADA_MAX_COUNT || S > C || S < -C) return p24;
+  const int64_t d = S * CSG_ADA_ONE - T24 * C;
+  if (d == 0) return p24;
+  // step24 may be anything >= 1: saturate before the addition
+  if (d > 0) return step24 >= CSG_ADA_ONE - p24 ? CSG_ADA_ONE : p24 + step24;
+  return step24 >= p24 ? 0 : p24 - step24;
+}
+
+// one update of the record: p24 moves, (S, C) go to the _last words and start again from 0
+CSG_AUG_HD void ada_update_words(int64_t* ctrl, int64_t T24, int64_t step24) {
+  const int64_t S = ctrl[1], C = ctrl[2];
+  ctrl[0] = ada_next_p(ada_clamp_p(ctrl[0]), S, C, T24, step24);
+  ctrl[4] = S;
+  ctrl[5] = C;
+  ctrl[1] = 0;
+  ctrl[2] = 0;
+  ctrl[3] += 1;
 }
 
 }  // namespace csg

@@ -92,7 +92,9 @@ def drain_watchdog(timeout_s=10.0):
 
 # ---- communication audit (bench.py's "comm" object, tests): what was exchanged since the last comm_reset()
 _COMM = {"grad_allreduce_calls": 0, "grad_allreduce_bytes": 0, "syncbn_allreduce_calls": 0, "syncbn_allreduce_bytes": 0,
-         "allgather_calls": 0, "allgather_bytes": 0, "grad_copy_bytes": 0, "wait_events": []}
+         "allgather_calls": 0, "allgather_bytes": 0, "ada_allreduce_calls": 0, "ada_allreduce_bytes": 0,
+         "grad_copy_bytes": 0, "wait_events": []}
+#       (ada_allreduce: the (S, C) sum of --d_augment_target, d_augment.DAugment._reduce_counts: 16 bytes every K-th step)
 _AUDIT = [False]        # counters and wait events are recorded only between comm_reset() and comm_report(): a training run of
 #                         a million iterations must not accumulate six timing events per step
 

@@ -336,10 +336,12 @@ class StepGraphs:
         imgs, objs, masks = batch[0], batch[1], batch[6]
         if masks is not None or not imgs.is_cuda:
             return None
-        # (the policy set of --d_augment is a launch constant of the captured transform kernels: part of the key)
+        # (the policy set of --d_augment is a launch constant of the captured transform kernels: part of the key; so is whether
+        #  the kernels are the gated ones and whether S3 holds the sign accumulation.  p itself is device data.)
         aug = getattr(self.tr, "d_augment", None)
         return (tuple(imgs.shape), int(objs.shape[0]), _pad_objects(objs.shape[1]), int(objs.shape[2])) + (
-            () if aug is None else (aug.policy,))
+            () if aug is None else (aug.policy,)) + (
+            () if aug is None or not aug.gated else ("adaptive" if aug.adaptive else "gated",))
 
     def invalidate(self):
         """Drop every captured graph: needed whenever a tensor a graph reads or writes by ADDRESS is replaced — parameters

@@ -25,6 +25,7 @@ __all__ = [
     "conv2d_forward", "pool3", "spatial_mean", "resize_bilinear", "feat_stats", "feat_stats_finalize", "softmax_rows", "inception_score", "POOL_MAX", "POOL_AVG9", "POOL_AVG_INSIDE",
     "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums", "knn_radii", "ball_counts",
     "augment_table", "augment_table_host", "d_augment",
+    "augment_gate", "augment_gate_host", "ada_accumulate", "ada_update", "ada_update_host",
 ]
 
 
@@ -3149,6 +3150,8 @@ def ema_fill(table):
 # ---- DiffAugment of the discriminators' inputs (csrc/augment.hip; the transform and the table: include/csg_hip.h) ----------
 AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
 AUG_CHUNK = 256                      # CSG_AUG_CHUNK: pixels per partial of the per-sample sums
+ADA_ONE = 1 << 24                    # p = p24 / ADA_ONE (adaptive strength: the gate and the controller, csrc/csg_augment.h)
+ADA_WORDS = 8                        # the controller record: [p24, S, C, updates, S_last, C_last, 0, 0], int64
 
 
 def _aug_key(what, seed, iteration, pass_id, rank, rows, H):
@@ -3188,14 +3191,17 @@ def _aug_table_operand(what, table, N):
         raise RuntimeError("%s: the table has %d rows, fewer than N = %d" % (what, table.shape[0], N))
 
 
-def _aug_launch(fn, what, x, table, c0, policy):
+def _aug_launch(fn, what, x, table, c0, policy, gate=None):
     N, Ct, H, W = x.shape
     out = empty_nhwc(N, Ct, H, W, x.device)
     ws, nws = None, 0
     if policy & AUG_COLOR and N:
         nws = int(lib.csg_augment_workspace_bytes(N, H))
         ws = torch.empty(max(nws, 8) // 8, dtype=torch.float64, device=x.device)
-    check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, policy, ptr(ws), nws, stream()), what)
+    if gate is None:
+        check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, policy, ptr(ws), nws, stream()), what)
+    else:
+        check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, policy, ptr(ws), nws, ptr(gate), stream()), what)
     return out
 
 
@@ -3215,11 +3221,107 @@ class _DAugment(torch.autograd.Function):
         return _aug_launch(lib.csg_augment_bwd, "augment_bwd", nhwc(_f32(g)), table, c0, policy), None, None, None
 
 
-def d_augment(x, table, c0, policy):
+class _DAugmentGated(torch.autograd.Function):
+    """_DAugment with a per-sample gate (csg_augment_fwd_gated / _bwd_gated): sample n runs policy & gate[n]."""
+
+    @staticmethod
+    def forward(ctx, x, table, c0, policy, gate):
+        ctx.save_for_backward(table, gate)
+        ctx.meta = (c0, policy)
+        return _aug_launch(lib.csg_augment_fwd_gated, "augment_fwd_gated", nhwc(x), table, c0, policy, gate)
+
+    @staticmethod
+    def backward(ctx, g):
+        table, gate = ctx.saved_tensors
+        c0, policy = ctx.meta
+        return _aug_launch(lib.csg_augment_bwd_gated, "augment_bwd_gated", nhwc(_f32(g)), table, c0, policy, gate), None, None, \
+            None, None
+
+
+def _aug_gate_operand(what, gate, N):
+    if not torch.is_tensor(gate) or gate.dtype != torch.int32 or gate.dim() != 1 or not gate.is_contiguous():
+        raise RuntimeError("%s: the gate must be a contiguous int32 (rows,) tensor, got %s" % (
+            what, (gate.dtype, tuple(gate.shape)) if torch.is_tensor(gate) else type(gate).__name__))
+    if gate.shape[0] < N:
+        raise RuntimeError("%s: the gate has %d rows, fewer than N = %d" % (what, gate.shape[0], N))
+
+
+def _ada_ctrl_operand(what, ctrl, cuda=True):
+    if not torch.is_tensor(ctrl) or ctrl.dtype != torch.int64 or ctrl.dim() != 1 or ctrl.shape[0] != ADA_WORDS \
+            or not ctrl.is_contiguous() or ctrl.is_cuda != cuda:
+        raise RuntimeError("%s: the controller must be a contiguous int64 (%d,) tensor %s, got %s" % (
+            what, ADA_WORDS, "on the device" if cuda else "on the host",
+            (ctrl.dtype, tuple(ctrl.shape), str(ctrl.device)) if torch.is_tensor(ctrl) else type(ctrl).__name__))
+
+
+def _aug_gate_key(what, seed, iteration, pass_id, rank, rows):
+    _aug_key(what, seed, iteration, pass_id, rank, rows, 2)
+
+
+def augment_gate_host(seed, iteration, pass_id, rows, p24, rank=0):
+    """(rows,) int32 on the HOST: the masks the device entry writes when the controller holds p24 (csrc/csg_augment.h)."""
+    _aug_gate_key("augment_gate_host", seed, iteration, pass_id, rank, rows)
+    if not isinstance(p24, int) or isinstance(p24, bool) or not 0 <= p24 <= ADA_ONE:
+        raise RuntimeError("augment_gate_host: p24 must be an integer in [0, 2^24], got %r" % (p24,))
+    out = torch.zeros((rows,), dtype=torch.int32)
+    check(lib.csg_augment_gate_host(seed, iteration, pass_id, rank, rows, p24, ctypes.c_void_p(out.data_ptr())), "augment_gate_host")
+    return out
+
+
+def augment_gate(seed, iteration, pass_id, rows, ctrl, rank=0, out=None):
+    """One launch: gate[n] = the mask of the policies that are on for sample n (policy j iff draw 8 + j of the sample's key,
+    24 bits, is below p24), an int32 (rows,) device tensor (`out`, or a fresh one).  p24 is read from ctrl[0] ON THE DEVICE:
+    nothing is read back and the launch's arguments do not depend on p."""
+    _aug_gate_key("augment_gate", seed, iteration, pass_id, rank, rows)
+    _ada_ctrl_operand("augment_gate", ctrl)
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.int32, device=ctrl.device)
+    _aug_gate_operand("augment_gate", out, rows)
+    check(lib.csg_augment_gate(seed, iteration, pass_id, rank, rows, ptr(ctrl), ptr(out), stream()), "augment_gate")
+    return out
+
+
+def ada_accumulate(preds, ctrl):
+    """One launch: ctrl[1] += the sum of sign(x), ctrl[2] += the number of elements, over every element of 1..4 prediction
+    maps (B, 1, h, w) of any strides (what `hinge_mean` takes).  sign(+-0) = sign(NaN) = 0.  Integer sums: order-free."""
+    _ada_ctrl_operand("ada_accumulate", ctrl)
+    if not 1 <= len(preds) <= 4:
+        raise RuntimeError("ada_accumulate: 1..4 maps, got %d" % len(preds))
+    for p in preds:
+        if not torch.is_tensor(p) or not p.is_cuda or p.dim() != 4 or p.shape[1] != 1 or p.dtype != torch.float32:
+            raise RuntimeError("ada_accumulate: a map must be a float32 (B, 1, h, w) device tensor, got %s" % (
+                (p.dtype, tuple(p.shape)) if torch.is_tensor(p) else type(p).__name__,))
+    preds = [p.detach() for p in preds]
+    check(lib.csg_ada_accumulate(_HingeMean._items(preds), len(preds), ptr(ctrl), stream()), "ada_accumulate")
+
+
+def _ada_update_args(what, T24, step24):
+    for name, v, lo, hi in (("T24", T24, 0, ADA_ONE), ("step24", step24, 1, 1 << 62)):
+        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+            raise RuntimeError("%s: %s must be an integer in [%d, %d], got %r" % (what, name, lo, hi, v))
+
+
+def ada_update(ctrl, T24, step24):
+    """One launch of one thread: p24 <- clamp(p24 + sgn(S 2^24 - T24 C) step24, 0, 2^24) (unchanged when C = 0 or the
+    difference is 0), then S_last = S, C_last = C, S = C = 0, updates += 1."""
+    _ada_ctrl_operand("ada_update", ctrl)
+    _ada_update_args("ada_update", T24, step24)
+    check(lib.csg_ada_update(ptr(ctrl), T24, step24, stream()), "ada_update")
+
+
+def ada_update_host(ctrl, T24, step24):
+    """`ada_update` on an int64 (8,) HOST tensor, in place, by the host half of csrc/csg_augment.h."""
+    _ada_ctrl_operand("ada_update_host", ctrl, cuda=False)
+    _ada_update_args("ada_update_host", T24, step24)
+    check(lib.csg_ada_update_host(ctypes.c_void_p(ctrl.data_ptr()), T24, step24), "ada_update_host")
+
+
+def d_augment(x, table, c0, policy, gate=None):
     """DiffAugment of x, a logical (N, Ct, H, H) tensor with NHWC memory and Ct % 4 == 0 (what `disc_input` and
     `crop_objects` return): colour on channels [c0, c0 + 3), translation and cutout on all of them, as the mask `policy`
     (a sum of AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT; the flag's names: d_augment.policy_mask) selects; sample n reads row n
-    of `table` (`augment_table`).  Returns the same kind of tensor; differentiable in x."""
+    of `table` (`augment_table`).  With `gate` (`augment_gate`: int32, one mask per sample) sample n runs policy & gate[n];
+    without it the call is what it was.  Returns the same kind of tensor; differentiable in x."""
     if not isinstance(policy, int) or isinstance(policy, bool) or not 0 <= policy <= 7:
         raise RuntimeError("d_augment: policy must be a mask in [0, 7] (1 = color, 2 = translation, 4 = cutout), got %r" % (policy,))
     if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] != x.shape[3]:
@@ -3235,4 +3337,9 @@ def d_augment(x, table, c0, policy):
     if H < 2:
         raise RuntimeError("d_augment: H = %d (H < 2)" % H)
     _aug_table_operand("d_augment", table, N)
+    if gate is not None:
+        _aug_gate_operand("d_augment", gate, N)
+        if gate.device != x.device:
+            raise RuntimeError("d_augment: the gate is on %s, x on %s" % (gate.device, x.device))
+        return _DAugmentGated.apply(x, table, c0, policy, gate)
     return _DAugment.apply(x, table, c0, policy)

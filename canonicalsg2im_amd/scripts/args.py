@@ -38,6 +38,47 @@ def d_augment_seed_flag(s):
     return n
 
 
+def d_augment_p_flag(s):
+    p = float(s)
+    if not 0.0 <= p <= 1.0:              # (a NaN fails both comparisons)
+        raise argparse.ArgumentTypeError("--d_augment_p must be in [0, 1], got %s" % s)
+    return p
+
+
+def d_augment_target_flag(s):
+    t = float(s)
+    if not (t == 0.0 or 0.0 < t < 1.0):
+        raise argparse.ArgumentTypeError("--d_augment_target must be 0 (a fixed p) or in (0, 1), got %s" % s)
+    return t
+
+
+def d_augment_interval_flag(s):
+    k = int(s)
+    if k < 1:
+        raise argparse.ArgumentTypeError("--d_augment_interval must be an integer >= 1, got %s" % s)
+    return k
+
+
+def d_augment_kimg_flag(s):
+    m = float(s)
+    if not 0.0 < m < float("inf"):
+        raise argparse.ArgumentTypeError("--d_augment_kimg must be a positive number, got %s" % s)
+    return m
+
+
+class _Parser(argparse.ArgumentParser):
+    """argparse checks one flag at a time; the strength flags of --d_augment are also checked TOGETHER, after the parse."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        from ..d_augment import ada_settings_of
+        try:
+            ada_settings_of(ns)
+        except ValueError as e:
+            self.error(str(e))
+        return ns, rest
+
+
 _OFF_PATH_FLAGS = {
     # data
     'img_deprocess': ('decode_img', 'str'), 'num_train_samples': (None, 'int'), 'num_val_samples': (1024, 'int'),
@@ -85,7 +126,7 @@ _OFF_PATH_FLAGS = {
 
 
 def build_parser():
-    p = argparse.ArgumentParser()
+    p = _Parser()
     p.add_argument('--dataset', default='coco',
                    choices=['vg', 'clevr', 'coco', 'synthetic', 'packed_coco', 'packed_vg', 'packed_clevr', 'packed_clevr_syn'])
     # optimisation
@@ -168,6 +209,17 @@ def build_parser():
                         "color,translation,cutout (default: empty = off)")
     p.add_argument('--d_augment_seed', default=0, type=d_augment_seed_flag, metavar='N',
                    help="seed of the augmentation's parameter stream (default 0)")
+    # Adaptive strength (StyleGAN2-ADA): every policy is applied to a sample with probability p.  All four default to None =
+    # not given: without any of them the run is ungated, exactly DiffAugment; d_augment.ada_settings fills the defaults
+    # (target 0 = a fixed p, interval 4, kimg 500; p: 1 with a fixed p, 0 when adaptive) and refuses them without policies.
+    p.add_argument('--d_augment_p', default=None, type=d_augment_p_flag, metavar='P',
+                   help="probability in [0, 1] that a policy is applied to a sample; with --d_augment_target the start value")
+    p.add_argument('--d_augment_target', default=None, type=d_augment_target_flag, metavar='T',
+                   help="0 (default): p is fixed; 0 < T < 1: p is steered so that E[sign(D(real))] stays at T (ADA's paper: 0.6)")
+    p.add_argument('--d_augment_interval', default=None, type=d_augment_interval_flag, metavar='K',
+                   help="iterations between two updates of p (default 4)")
+    p.add_argument('--d_augment_kimg', default=None, type=d_augment_kimg_flag, metavar='M',
+                   help="thousands of pictures over which p can move from 0 to 1 (default 500)")
     # every other flag of the reference's command line (data loading, logging, checkpointing, evaluation, unused SPADE
     # options): accepted with the reference's defaults so that its recipes parse unchanged; none is read on the hot path
     for name, (default, kind) in _OFF_PATH_FLAGS.items():

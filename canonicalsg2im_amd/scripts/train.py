@@ -56,7 +56,14 @@ again; their lines read `EMA GT VAL` and `EMA VAL`.
 training with DiffAugment (canonicalsg2im_amd/d_augment.py): a comma list out of color,translation,cutout, anything else is
 refused.  `--d_augment_seed N` (default 0) keys the counter-based hash the transforms' parameters come from; there is no RNG
 state.  Both flags are part of the run's argument namespace; checkpoints then carry `d_augment` = {seed, iteration, policies}
-and a restored run continues the parameter stream.  Validation and sampling see raw inputs."""
+and a restored run continues the parameter stream.  Validation and sampling see raw inputs.
+
+`--d_augment_p P`, `--d_augment_target T`, `--d_augment_interval K` (default 4), `--d_augment_kimg M` (default 500) gate the
+policies per sample with probability p (StyleGAN2-ADA): T = 0 (default) keeps p = P (default 1); 0 < T < 1 (the paper uses
+0.6) steers p, starting from P (default 0), so that r_t = E[sign(D(real))] — taken per PatchGAN output element, over all
+scales — stays at T: every K iterations p moves by B K / (1000 M) towards it, B the pictures of one iteration over all ranks.  Any of the four without
+--d_augment policies is refused.  The controller lives on the device and is read back here only: every --print_every a line
+`d_augment: p %.4f r_t %.4f` follows the loss line.  Checkpoints carry its eight words and the four settings in `d_augment`."""
 import os
 import sys
 import time
@@ -179,6 +186,9 @@ def main(argv=None):
     per_rank = args.batch_size // max(world, 1)
     torch.manual_seed(0)
     trainer = T.Trainer(args, dev)
+    if trainer.d_augment is not None:
+        # --batch_size is the GLOBAL batch here: the strength controller's step counts it once, not once per rank
+        trainer.d_augment.set_pictures_per_iteration(per_rank * max(world, 1))
     t0 = epoch = 0
     if args.restore_checkpoint:
         # scripts/train.py:29-60: `--checkpoint_name` is the PATH of the checkpoint file; a failed restore raises
@@ -233,6 +243,9 @@ def main(argv=None):
             tic = time.time()
             terms = " ".join("%s %.4f" % (k, float(v.detach())) for k, v in list(G.items()) + list(D.items()) if v.numel() == 1)
             print("t = %d / %d  [%.1f img/s]  %s" % (t, args.num_iterations, rate, terms), flush=True)
+            if trainer.d_augment is not None and trainer.d_augment.gated:
+                c = trainer.d_augment.read()                 # the only read-back of the controller outside checkpoints
+                print("d_augment: p %.4f r_t %.4f" % (c["p"], c["r_t"]), flush=True)
         if evaluator is not None and t % args.val_every == 0:
             import contextlib
             vargs = argparse_copy(args, batch_size=per_rank)

@@ -143,10 +143,14 @@ class Pix2PixModel(torch.nn.Module):
         spectral-norm vectors, so it is replayed — without autograd."""
         opt, crit = self.opt, self.criterionGAN
         d_args = dict(layout_masks=masks, gt_train=True)
-        out = {"D_img_fake": crit(self.netD_img(fake_img, objs, boxes, fool=False, aug_pass=1, **d_args), False,
-                                  for_discriminator=True),
-               "D_img_real": crit(self.netD_img(imgs, objs, boxes, fool=False, aug_pass=2, **d_args), True,
-                                  for_discriminator=True)}
+        d_fake = crit(self.netD_img(fake_img, objs, boxes, fool=False, aug_pass=1, **d_args), False, for_discriminator=True)
+        real = self.netD_img(imgs, objs, boxes, fool=False, aug_pass=2, **d_args)
+        aug = getattr(self.netD_img, "d_augment", None)
+        if aug is not None:
+            # (--d_augment_target: the signs of this pass's prediction maps feed the strength controller — one launch, captured
+            #  with the pass on a replayed step; nothing without the flag, nothing outside a training step)
+            aug.observe_real(real)
+        out = {"D_img_fake": d_fake, "D_img_real": crit(real, True, for_discriminator=True)}
         out["total_img_loss"] = _total(out)
         if not opt.use_img_disc:
             with torch.no_grad():

@@ -77,17 +77,22 @@ class Trainer:
         # off.  Read with getattr, as the EMA flags.  The two discriminators reach the object through a class-level attribute
         # that is None without the flag: nothing on their path changes then.
         self.d_augment = None
+        from .d_augment import ada_settings_of
+        ada = ada_settings_of(opt)               # the four strength flags (refused without policies); None: the ungated run
         if getattr(opt, "d_augment", "") and opt.skip_generation:
             if csg_dist.rank() == 0:
                 print("d_augment: --skip_generation runs no discriminator: --d_augment '%s' has nothing to act on" % opt.d_augment,
                       flush=True)
         elif getattr(opt, "d_augment", ""):
             from .d_augment import DAugment
+            if ada is not None and ada["adaptive"] and opt.num_D > 4:
+                raise ValueError("d_augment: --d_augment_target takes the signs of at most 4 PatchGAN scales in one launch "
+                                 "(ops.ada_accumulate), --num_D is %d" % opt.num_D)
             if opt.use_img_disc and csg_dist.rank() == 0:
                 print("d_augment: --use_img_disc 1 trains no object-crop discriminator: only the PatchGAN's input is augmented",
                       flush=True)
             self.d_augment = DAugment(opt.d_augment, getattr(opt, "d_augment_seed", 0), device, opt.batch_size,
-                                      opt.image_size[0], rank=csg_dist.rank())
+                                      opt.image_size[0], rank=csg_dist.rank(), ada=ada, world_size=csg_dist.world_size())
             self.discriminator.img_discriminator.d_augment = self.d_augment
             if not opt.use_img_disc:
                 self.discriminator.obj_discriminator.d_augment = self.d_augment

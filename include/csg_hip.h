@@ -1309,6 +1309,42 @@ int csg_augment_fwd(const float* in, float* out, const uint32_t* table, int64_t 
 int csg_augment_bwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
                     int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Adaptive strength of the augmentation (StyleGAN2-ADA, Karras et al., NeurIPS 2020): a per-sample gate, the
+ * discriminator's overfitting figure and the controller of p, all on the device (csrc/augment.hip, csrc/csg_augment.h) ---
+ * (Added after revision 122 without a new revision number: callers detect the entries by their symbols.)
+ *
+ * THE CONTROLLER RECORD: eight int64 words in device memory, 8-byte aligned, at an address that never changes:
+ *     [p24, S, C, updates, S_last, C_last, 0, 0]
+ * p = p24 * 2^-24 with p24 in [0, 2^24]; S = the sum of sign(x) and C = the number of elements x of the real pass's
+ * prediction maps since the last update (sign: +1 for x > 0, -1 for x < 0, 0 for both zeros and NaN), so r_t = S / C.
+ *
+ * THE GATE: gate[n] is the mask (CSG_AUG_COLOR | _TRANSLATION | _CUTOUT) of the policies that are on for sample n: policy j is
+ * on iff the 24-bit draw 8 + j of the sample's key is below p24.  The gate entry reads p24 from ctrl[0] ON THE DEVICE (a value
+ * outside [0, 2^24] is clamped); its _host twin takes p24 as an argument.  The _gated transform entries are the ungated ones
+ * plus `gate` (N int32, 4-byte aligned): sample n runs policy & gate[n]; a policy that is off for a sample is skipped for it
+ * (colour off: the colour channels are bit copies; everything off: the sample is a bit copy, forward and backward).  The
+ * ungated entries compute what they always did.
+ *
+ * csg_ada_accumulate adds to ctrl[1] and ctrl[2] over every element of 1..4 maps in the item form of csg_hinge_mean_fwd
+ * (`dx` unused); the sums are integers (64-bit integer atomics, one pair per block): the same words whatever the grid.
+ * csg_ada_update (one thread) applies   d = S 2^24 - T24 C;  p24 <- clamp(p24 + sgn(d) step24, 0, 2^24)   (C = 0 or d = 0:
+ * unchanged), then S_last = S, C_last = C, S = C = 0, updates += 1; its _host twin does the same on host memory.
+ * Refused with a message (CSG_E_BADSHAPE) before any launch: null or misaligned pointers, T24 outside [0, 2^24],
+ * step24 < 1, and in the host entries p24 outside [0, 2^24] and C >= 2^38 (S 2^24 would leave int64; the device entry
+ * leaves p24 alone there).                                                                                              */
+int csg_augment_gate(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, const int64_t* ctrl,
+                     int32_t* gate, void* stream);
+int csg_augment_gate_host(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t p24, int32_t* gate);
+int csg_augment_fwd_gated(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H,
+                          int64_t Ct, int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, const int32_t* gate,
+                          void* stream);
+int csg_augment_bwd_gated(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H,
+                          int64_t Ct, int64_t c0, int32_t policy, void* workspace, int64_t workspace_bytes, const int32_t* gate,
+                          void* stream);
+int csg_ada_accumulate(const csg_hinge_item* items, int32_t n_items, int64_t* ctrl, void* stream);
+int csg_ada_update(int64_t* ctrl, int64_t T24, int64_t step24, void* stream);
+int csg_ada_update_host(int64_t* ctrl, int64_t T24, int64_t step24);
+
 #ifdef __cplusplus
 }
 #endif

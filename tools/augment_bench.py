@@ -13,6 +13,13 @@
       off: ONE trainer switched between the two (same allocations; each leg replays its own captured graph set), same
       process, same build, windows in turn.  The difference is recorded in ms.
 
+  python tools/augment_bench.py ada [--out FILE]
+      The adaptive strength (profiles/d_augment_ada.txt).  (a) The GATED forward and backward on the C3 packed input, all
+      three policies, with the gate filled on the device at p24 = 2^24 (every sample on) and at 2^23 (each policy on half
+      of the samples), against the UNGATED kernels of the same build, windows in turn; the spread of the ungated figure
+      over the windows is reported beside the difference.  (b) What an adaptive run adds to a step: `ada_accumulate` over
+      the C3 recipe's two prediction maps, plus one `ada_update` and the three gate fills of `begin_step`.
+
 Timing: HIP events around a window of calls after untimed warm-up calls, several windows, the median and all values
 reported.  Seeded inputs; the kernels' work does not depend on the values.
 """
@@ -79,6 +86,51 @@ def kernel(args, dev):
     return lines
 
 
+def ada(args, dev):
+    from canonicalsg2im_amd import ops
+    from canonicalsg2im_amd._lib import lib
+    lines = ["device: %s; HIP events, %d calls per window after %d warm-up calls, %d windows in turn; median [all windows]" % (
+        torch.cuda.get_device_name(0), args.iters, args.warmup, args.windows)]
+    N, H, Ct, c0 = 16, 256, 40, 32
+    torch.manual_seed(0)
+    x = ops.empty_nhwc(N, Ct, H, H, dev).normal_()
+    g = ops.empty_nhwc(N, Ct, H, H, dev).normal_()
+    table = ops.augment_table(0, 1, 0, N, H, device=dev)
+    gates = {}
+    for label, p24 in (("p24 = 2^24", 1 << 24), ("p24 = 2^23", 1 << 23)):
+        ctrl = torch.tensor([p24, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+        gates[label] = ops.augment_gate(0, 1, 0, N, ctrl)
+    runs = {"ungated forward": lambda: ops.d_augment(x, table, c0, 7),
+            "ungated backward": lambda: ops._aug_launch(lib.csg_augment_bwd, "augment_bwd", g, table, c0, 7)}
+    for label, gate in gates.items():
+        runs["gated forward,  " + label] = lambda gate=gate: ops.d_augment(x, table, c0, 7, gate=gate)
+        runs["gated backward, " + label] = lambda gate=gate: ops._aug_launch(lib.csg_augment_bwd_gated, "augment_bwd_gated", g, table,
+                                                                             c0, 7, gate)
+    # the C3 recipe's PatchGAN: two scales, 16 pictures, prediction maps of 35 x 35 and 19 x 19 (4 x 4 convolutions, three
+    # of stride 2, on 256 and 128 pixels)
+    preds = [torch.randn(16, 1, 35, 35, device=dev), torch.randn(16, 1, 19, 19, device=dev)]
+    ctrl = torch.zeros(8, dtype=torch.int64, device=dev)
+    three = torch.zeros((3, N), dtype=torch.int32, device=dev)
+    runs["ada_accumulate, 2 maps of 16 pictures"] = lambda: ops.ada_accumulate(preds, ctrl)
+    runs["ada_update"] = lambda: ops.ada_update(ctrl, 10066330, 537)
+    runs["three gate fills of 16 rows"] = lambda: [ops.augment_gate(0, 1, p, N, ctrl, out=three[p]) for p in range(3)]
+    for fn in runs.values():
+        for _ in range(args.warmup):
+            fn()
+    times = {k: [] for k in runs}
+    for _ in range(args.windows):
+        for k, fn in runs.items():
+            times[k].append(window(fn, args.iters))
+    lines.append("C3 packed PatchGAN input: %d x %d x %d x %d fp32 = %.1f MB, c0 = %d, color,translation,cutout; gate masks at 2^23: %s" % (
+        N, H, H, Ct, x.numel() * 4 / 1e6, c0, gates["p24 = 2^23"].tolist()))
+    for k, v in times.items():
+        base = times.get("ungated " + ("forward" if "forward" in k else "backward")) if k.startswith("gated") else None
+        tail = "" if base is None else "  = %+.4f ms against ungated (ungated windows span %.4f ms)" % (
+            median(v) - median(base), max(base) - min(base))
+        lines.append("    %-42s %s per call%s" % (k, fmt(v), tail))
+    return lines
+
+
 def c3_trainer(T, synth, dev, policies):
     base = synth.BASELINE_CONFIGS["C3"]
     vocab = synth.make_vocab(base["vocab"])
@@ -126,19 +178,19 @@ def steps(args, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernel", "steps"])
+    ap.add_argument("what", choices=["kernel", "steps", "ada"])
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.iters is None:
-        args.iters = 2000 if args.what == "kernel" else 10        # kernel windows of 0.04-0.2 s
+        args.iters = 10 if args.what == "steps" else 2000        # kernel windows of 0.04-0.2 s
     sys.path.insert(0, HERE)
     if not torch.cuda.is_available():
         raise SystemExit("tools/augment_bench.py measures on the device: no HIP device here, nothing measured")
     dev = torch.device("cuda", 0)
-    lines = kernel(args, dev) if args.what == "kernel" else steps(args, dev)
+    lines = {"kernel": kernel, "steps": steps, "ada": ada}[args.what](args, dev)
     text = "\n".join(["$ python tools/augment_bench.py " + " ".join(sys.argv[1:] if argv is None else argv)] + lines) + "\n"
     print(text, flush=True)
     if args.out:
