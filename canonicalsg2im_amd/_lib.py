@@ -272,6 +272,10 @@ SIGNATURES = {
     "csg_ada_accumulate": (c_i32, [ctypes.POINTER(HingeItem), c_i32, c_p, c_p]),
     "csg_ada_update": (c_i32, [c_p, c_i64, c_i64, c_p]),
     "csg_ada_update_host": (c_i32, [c_p, c_i64, c_i64]),
+    "csg_ada_pipeline_table": (c_i32, [ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p, c_p]),
+    "csg_ada_pipeline_table_host": (c_i32, [ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_p]),
+    "csg_ada_pipeline_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
+    "csg_ada_pipeline_bwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
 }
 
 

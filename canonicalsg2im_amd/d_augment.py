@@ -36,25 +36,42 @@ when r_t > T (the discriminator is too sure of the real pictures), down when r_t
 step: `read()` (the trainer script's print line, checkpoints) is the only read-back.  Without the four flags there is no
 record, no gate, no extra launch: the run is what it was.
 
+THE ADA PIPELINE (StyleGAN2-ADA's own transforms, appendix B of the paper), opt-in by three more policy names:
+`ada_blit` (x-flip, rot90, integer translation), `ada_geom` (isotropic scale, pre-rotation, anisotropic scale, post-rotation,
+fractional translation) and `ada_color` (brightness, contrast, luma flip, hue rotation, saturation).  Every single transform
+is on for a sample with probability p (each of the two rotations with 1 - sqrt(1 - p)), so these names need a strength:
+`--d_augment_p` or a non-zero `--d_augment_target` — at p = 1 such transforms leak into the generator, and the flags refuse a
+run that would apply them always by default.  The stage is ONE launch (ops.ada_pipeline: an affine resampling with four
+bilinear taps and zero fill, then a 3 x 4 colour matrix) that runs BEFORE the DiffAugment kernel when both families are named.
+Its parameters are rows of 32 words (csrc/csg_ada_pipeline.h) in one more persistent (3, rows, 32) allocation for passes 0-2,
+filled in `begin_step()` after the controller update and beside the gate fills by launches that read p24 on the device; the
+crops of passes 3-5 get fresh tables.  The draws are those of the same per-sample key, from index 16 on: naming an `ada_*`
+group moves no draw of DiffAugment's rows (1-7) or gates (8-10).  Checkpoints carry the names in `d_augment.policies`,
+nothing else.  Deviations from the authors' pipeline (bilinear taps for the wavelet filters, zero fill for reflection, a
+bounded normal, clamped scales) are stated in csrc/ada_pipeline.hip; no quality figure is claimed.
+
 This module imports nothing at its top: scripts/args.py checks the flags with `policy_mask` and `ada_settings` without
 loading the library.
 """
-POLICY_BITS = {"color": 1, "translation": 2, "cutout": 4}
+POLICY_BITS = {"color": 1, "translation": 2, "cutout": 4, "ada_blit": 8, "ada_geom": 16, "ada_color": 32}
+DIFF_BITS, ADA_BITS = 7, 56
+POLICY_LIST = "color,translation,cutout,ada_blit,ada_geom,ada_color"
 PASS_G_IMG, PASS_D_IMG_FAKE, PASS_D_IMG_REAL, PASS_G_OBJ, PASS_D_OBJ_FAKE, PASS_D_OBJ_REAL = range(6)
 IMG_PASSES = 3
 
 
 def policy_mask(policies):
-    """The mask (ops.AUG_COLOR | AUG_TRANSLATION | AUG_CUTOUT) of the flag's value: a comma list out of
-    color,translation,cutout.  '' and None are 0: off.  Anything else is refused with a message."""
+    """The mask (ops.AUG_COLOR | AUG_TRANSLATION | AUG_CUTOUT | AUG_ADA_BLIT | AUG_ADA_GEOM | AUG_ADA_COLOR) of the flag's value:
+    a comma list out of color,translation,cutout,ada_blit,ada_geom,ada_color.  '' and None are 0: off.  Anything else is
+    refused with a message."""
     if policies is None or policies == "":
         return 0
     if not isinstance(policies, str):
-        raise ValueError("d_augment: the policies are a comma list out of color,translation,cutout, got %r" % (policies,))
+        raise ValueError("d_augment: the policies are a comma list out of %s, got %r" % (POLICY_LIST, policies))
     mask = 0
     for p in (p.strip() for p in policies.split(",")):
         if p not in POLICY_BITS:
-            raise ValueError("d_augment: unknown policy %r (a comma list out of color,translation,cutout)" % (p,))
+            raise ValueError("d_augment: unknown policy %r (a comma list out of %s)" % (p, POLICY_LIST))
         mask |= POLICY_BITS[p]
     return mask
 
@@ -83,11 +100,16 @@ def ada_settings(p=None, target=None, interval=None, kimg=None, policies=""):
     import math
     given = {"--d_augment_p": p, "--d_augment_target": target, "--d_augment_interval": interval, "--d_augment_kimg": kimg}
     given = {k: v for k, v in given.items() if v is not None}
+    mask = policy_mask(policies)
+    if mask & ADA_BITS and "--d_augment_p" not in given and not (target is not None and float(target) != 0.0):
+        raise ValueError("d_augment: the policies %s need a strength: give --d_augment_p P or a non-zero --d_augment_target "
+                         "(every ADA transform is applied with probability p; at p = 1 these transforms leak into the "
+                         "generator, so there is no default)" % policy_names(mask & ADA_BITS))
     if not given:
         return None
     if not policy_mask(policies):
         raise ValueError("d_augment: %s without --d_augment policies: there is nothing to gate (give --d_augment a comma list "
-                         "out of color,translation,cutout)" % ", ".join(sorted(given)))
+                         "out of %s)" % (", ".join(sorted(given)), POLICY_LIST))
     target = ADA_DEFAULTS["d_augment_target"] if target is None else float(target)
     if not (target == 0.0 or 0.0 < target < 1.0):
         raise ValueError("d_augment: --d_augment_target must be 0 (a fixed p) or in (0, 1), got %r" % (target,))
@@ -136,12 +158,17 @@ class DAugment:
         self.ada = None if ada is None else dict(ada)
         self.gated = ada is not None
         self.adaptive = bool(self.gated and ada["adaptive"])
-        self.ctrl = self.gates = None
+        self.ctrl = self.gates = self.ada_tables = None
+        self.diff_policy, self.ada_policy = self.policy & DIFF_BITS, self.policy & ADA_BITS
+        if self.ada_policy and not self.gated:
+            raise ValueError("DAugment: the policies %s need the strength settings (`ada_settings`)" % policy_names(self.ada_policy))
         if self.gated:
             self.set_pictures_per_iteration(max(int(batch_size), 1) * max(int(world_size), 1))
             self.ctrl = torch.zeros(8, dtype=torch.int64, device=device)        # persistent: captured graphs add to it
             self.ctrl[0] = ada["p24"]
             self.gates = torch.zeros((IMG_PASSES, self.rows), dtype=torch.int32, device=device)
+            if self.ada_policy:                  # ONE more allocation: the ADA pipeline's rows of the three PatchGAN passes
+                self.ada_tables = torch.zeros((IMG_PASSES, self.rows, 32), dtype=torch.int32, device=device)
 
     def set_pictures_per_iteration(self, n):
         """step24 for n pictures per iteration over ALL ranks: p can then cross [0, 1] in `kimg` thousand pictures."""
@@ -161,6 +188,9 @@ class DAugment:
             ops.augment_table(self.seed, self.iteration, p, self.rows, self.image_size, rank=self.rank, out=self.tables[p])
             if self.gated:
                 ops.augment_gate(self.seed, self.iteration, p, self.rows, self.ctrl, rank=self.rank, out=self.gates[p])
+            if self.ada_policy:
+                ops.ada_pipeline_table(self.seed, self.iteration, p, self.rows, self.image_size, self.ada_policy, self.ctrl,
+                                       rank=self.rank, out=self.ada_tables[p])
         self.active = True
 
     def _reduce_counts(self):
@@ -188,6 +218,17 @@ class DAugment:
         if not IMG_PASSES <= pass_id < 6:
             raise ValueError("DAugment.crop_table: pass %r (3, 4 or 5)" % (pass_id,))
         return ops.augment_table(self.seed, self.iteration, pass_id, n, size, rank=self.rank, device=self.device)
+
+    def ada_table(self, pass_id, n, size):
+        """The ADA pipeline's rows of pass `pass_id`: the persistent ones of PatchGAN pass 0, 1 or 2, or a fresh table of n
+        rows for crops of size x size (pass 3, 4 or 5; one eager launch on the current stream)."""
+        from . import ops
+        if pass_id < IMG_PASSES:
+            self.image_table(pass_id, n)         # (the checks)
+            return self.ada_tables[pass_id]
+        if not pass_id < 6:
+            raise ValueError("DAugment.ada_table: pass %r (0 .. 5)" % (pass_id,))
+        return ops.ada_pipeline_table(self.seed, self.iteration, pass_id, n, size, self.ada_policy, self.ctrl, rank=self.rank)
 
     def image_gate(self, pass_id):
         """The persistent gate of PatchGAN pass 0, 1 or 2; None on an ungated run."""
@@ -220,11 +261,15 @@ class DAugment:
         if not self.active or pass_id is None or x.shape[0] == 0:
             return x
         n = x.shape[0]
+        if self.ada_policy:                      # the ADA stage first, one launch; DiffAugment then runs on its output
+            x = ops.ada_pipeline(x, self.ada_table(pass_id, n, x.shape[2]), c0)
+            if not self.diff_policy:
+                return x
         table = self.image_table(pass_id, n) if pass_id < IMG_PASSES else self.crop_table(pass_id, n, x.shape[2])
         if not self.gated:
-            return ops.d_augment(x, table, c0, self.policy)
+            return ops.d_augment(x, table, c0, self.diff_policy)
         gate = self.image_gate(pass_id) if pass_id < IMG_PASSES else self.crop_gate(pass_id, n)
-        return ops.d_augment(x, table, c0, self.policy, gate=gate)
+        return ops.d_augment(x, table, c0, self.diff_policy, gate=gate)
 
     # ------------------------------------------------------------------ checkpoints
     def meta(self):

@@ -26,6 +26,7 @@ __all__ = [
     "crop_windows", "crop_resize_bilinear", "kid_sums", "feat_class_sums", "knn_radii", "ball_counts",
     "augment_table", "augment_table_host", "d_augment",
     "augment_gate", "augment_gate_host", "ada_accumulate", "ada_update", "ada_update_host",
+    "ada_pipeline_table", "ada_pipeline_table_host", "ada_pipeline",
 ]
 
 
@@ -3343,3 +3344,99 @@ def d_augment(x, table, c0, policy, gate=None):
             raise RuntimeError("d_augment: the gate is on %s, x on %s" % (gate.device, x.device))
         return _DAugmentGated.apply(x, table, c0, policy, gate)
     return _DAugment.apply(x, table, c0, policy)
+
+
+# ---- The ADA augmentation pipeline (csrc/ada_pipeline.hip; the row and its draws: csrc/csg_ada_pipeline.h) ----------------
+AUG_ADA_BLIT, AUG_ADA_GEOM, AUG_ADA_COLOR = 8, 16, 32
+ADA_ROW_WORDS = 32                   # CSG_ADA_ROW_WORDS: M (6), G (6), margin, flags, ex, ey, C (12), a b c d
+ADA_MAX_BOX = 16                     # CSG_ADA_MAX_BOX: the longest side of the adjoint's search box
+ADA_GEOM_ID, ADA_GEOM_INT, ADA_COLOR_ID = 1, 2, 4
+
+
+def _ada_policy(what, policy):
+    if not isinstance(policy, int) or isinstance(policy, bool) or not 0 <= policy < 64:
+        raise RuntimeError("%s: policy must be a mask in [0, 63] (8 = ada_blit, 16 = ada_geom, 32 = ada_color), got %r" % (
+            what, policy))
+
+
+def _ada_table_operand(what, table, N):
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != ADA_ROW_WORDS \
+            or not table.is_contiguous():
+        raise RuntimeError("%s: the table must be a contiguous int32 (rows, %d) tensor, got %s" % (
+            what, ADA_ROW_WORDS, (table.dtype, tuple(table.shape)) if torch.is_tensor(table) else type(table).__name__))
+    if table.shape[0] < N:
+        raise RuntimeError("%s: the table has %d rows, fewer than N = %d" % (what, table.shape[0], N))
+
+
+def ada_pipeline_table_host(seed, iteration, pass_id, rows, H, policy, p24, rank=0):
+    """(rows, 32) int32 on the HOST: the words the device entry writes when the controller holds p24, from the host half of
+    csrc/csg_ada_pipeline.h."""
+    _aug_key("ada_pipeline_table_host", seed, iteration, pass_id, rank, rows, H)
+    _ada_policy("ada_pipeline_table_host", policy)
+    if not isinstance(p24, int) or isinstance(p24, bool) or not 0 <= p24 <= ADA_ONE:
+        raise RuntimeError("ada_pipeline_table_host: p24 must be an integer in [0, 2^24], got %r" % (p24,))
+    out = torch.zeros((rows, ADA_ROW_WORDS), dtype=torch.int32)
+    check(lib.csg_ada_pipeline_table_host(seed, iteration, pass_id, rank, rows, H, policy, p24, ctypes.c_void_p(out.data_ptr())),
+          "ada_pipeline_table_host")
+    return out
+
+
+def ada_pipeline_table(seed, iteration, pass_id, rows, H, policy, ctrl, rank=0, out=None):
+    """One launch: the rows (M | G | margin, flags, ex, ey | C | a b c d) of `rows` samples of an H x H map, an int32
+    (rows, 32) device tensor (`out`, or a fresh one), from the counter-based hash over (seed, iteration, pass_id,
+    rank << 32 | row).  p24 is read from ctrl[0] ON THE DEVICE: nothing is read back."""
+    _aug_key("ada_pipeline_table", seed, iteration, pass_id, rank, rows, H)
+    _ada_policy("ada_pipeline_table", policy)
+    _ada_ctrl_operand("ada_pipeline_table", ctrl)
+    if out is None:
+        out = torch.empty((rows, ADA_ROW_WORDS), dtype=torch.int32, device=ctrl.device)
+    _ada_table_operand("ada_pipeline_table", out, rows)
+    check(lib.csg_ada_pipeline_table(seed, iteration, pass_id, rank, rows, H, policy, ptr(ctrl), ptr(out), stream()),
+          "ada_pipeline_table")
+    return out
+
+
+def _ada_launch(fn, what, x, table, c0):
+    N, Ct, H, W = x.shape
+    out = empty_nhwc(N, Ct, H, W, x.device)
+    check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, stream()), what)
+    return out
+
+
+class _AdaPipeline(torch.autograd.Function):
+    """The resampling and colour matrix of csrc/ada_pipeline.hip and their adjoint.  Linear in x: the backward needs the table
+    alone."""
+
+    @staticmethod
+    def forward(ctx, x, table, c0):
+        ctx.save_for_backward(table)
+        ctx.c0 = c0
+        return _ada_launch(lib.csg_ada_pipeline_fwd, "ada_pipeline_fwd", nhwc(x), table, c0)
+
+    @staticmethod
+    def backward(ctx, g):
+        (table,) = ctx.saved_tensors
+        return _ada_launch(lib.csg_ada_pipeline_bwd, "ada_pipeline_bwd", nhwc(_f32(g)), table, ctx.c0), None, None
+
+
+def ada_pipeline(x, table, c0):
+    """The ADA pipeline of x, a logical (N, Ct, H, H) tensor with NHWC memory and Ct % 4 == 0: sample n is resampled by the
+    affine map of row n of `table` (`ada_pipeline_table`) with four bilinear taps and zero fill — or copied where the row says
+    the geometry is the identity or an integer map —, then the row's 3 x 4 colour matrix acts on channels [c0, c0 + 3).
+    Returns the same kind of tensor; differentiable in x (the exact adjoint)."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise RuntimeError("ada_pipeline: x must be a (N, Ct, H, H) tensor, got %s" % (
+            tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    _f32(x)
+    N, Ct, H, _ = x.shape
+    c0 = int(c0)
+    if Ct % 4:
+        raise RuntimeError("ada_pipeline: Ct = %d must be a multiple of 4 (Ct %% 4 != 0)" % Ct)
+    if c0 < 0 or c0 + 3 > Ct:
+        raise RuntimeError("ada_pipeline: colour channels [%d, %d) do not fit Ct = %d (c0 + 3 > Ct)" % (c0, c0 + 3, Ct))
+    if H < 2:
+        raise RuntimeError("ada_pipeline: H = %d (H < 2)" % H)
+    _ada_table_operand("ada_pipeline", table, N)
+    if table.device != x.device:
+        raise RuntimeError("ada_pipeline: the table is on %s, x on %s" % (table.device, x.device))
+    return _AdaPipeline.apply(x, table, c0)

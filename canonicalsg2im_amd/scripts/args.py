@@ -206,7 +206,9 @@ def build_parser():
     # color,translation,cutout; empty = off.  The seed keys the counter-based hash the transforms' parameters come from.
     p.add_argument('--d_augment', default='', type=d_augment_flag, metavar='POLICIES',
                    help="differentiable augmentation of the discriminators' inputs: a comma list out of "
-                        "color,translation,cutout (default: empty = off)")
+                        "color,translation,cutout,ada_blit,ada_geom,ada_color (default: empty = off); the ada_* names are "
+                        "StyleGAN2-ADA's blitting, geometric and colour transforms and need --d_augment_p or a non-zero "
+                        "--d_augment_target")
     p.add_argument('--d_augment_seed', default=0, type=d_augment_seed_flag, metavar='N',
                    help="seed of the augmentation's parameter stream (default 0)")
     # Adaptive strength (StyleGAN2-ADA): every policy is applied to a sample with probability p.  All four default to None =

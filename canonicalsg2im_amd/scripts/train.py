@@ -63,7 +63,13 @@ policies per sample with probability p (StyleGAN2-ADA): T = 0 (default) keeps p 
 0.6) steers p, starting from P (default 0), so that r_t = E[sign(D(real))] — taken per PatchGAN output element, over all
 scales — stays at T: every K iterations p moves by B K / (1000 M) towards it, B the pictures of one iteration over all ranks.  Any of the four without
 --d_augment policies is refused.  The controller lives on the device and is read back here only: every --print_every a line
-`d_augment: p %.4f r_t %.4f` follows the loss line.  Checkpoints carry its eight words and the four settings in `d_augment`."""
+`d_augment: p %.4f r_t %.4f` follows the loss line.  Checkpoints carry its eight words and the four settings in `d_augment`.
+
+`--d_augment` also takes `ada_blit` (x-flip, rot90, integer translation), `ada_geom` (isotropic scale, rotation, anisotropic
+scale, rotation, fractional translation) and `ada_color` (brightness, contrast, luma flip, hue, saturation): StyleGAN2-ADA's
+own pipeline, one more launch in front of the DiffAugment kernel.  Each transform is applied with probability p, so these names
+are refused without `--d_augment_p` or a non-zero `--d_augment_target` (at p = 1 they leak into the generator).  Checkpoints
+carry the names in `d_augment.policies`."""
 import os
 import sys
 import time

@@ -1345,6 +1345,38 @@ int csg_ada_accumulate(const csg_hinge_item* items, int32_t n_items, int64_t* ct
 int csg_ada_update(int64_t* ctrl, int64_t T24, int64_t step24, void* stream);
 int csg_ada_update_host(int64_t* ctrl, int64_t T24, int64_t step24);
 
+/* ---- The ADA augmentation pipeline: pixel blitting, general geometry and linear colour transforms as ONE per-sample
+ * affine resampling with a 3 x 4 colour matrix, forward and exact adjoint (csrc/ada_pipeline.hip, csrc/csg_ada_pipeline.h) ---
+ * (Added after revision 122 without a new revision number: callers detect the entries by their symbols.)
+ * Stream ordered and capturable; no atomics, no host synchronisation, nothing read back; the same bits on every run.
+ *
+ * THE TABLE: one row of CSG_ADA_ROW_WORDS = 32 words of 32 bits per sample, in device memory, 16-byte aligned (the layout, the
+ * draws, the fp64 composition and the polynomials: csrc/csg_ada_pipeline.h): the inverse map M (6 fp32), the forward map G
+ * (6 fp32), the adjoint's search margin, a flag word, the integer map's offsets, the colour matrix (12 fp32) and the integer
+ * map's signed permutation.  csg_ada_pipeline_table fills `rows` rows for H x H maps from the hash of (seed, iteration, pass,
+ * rank << 32 | row) and from p24, which it reads from ctrl[0] ON THE DEVICE (clamped to [0, 2^24]); policy is a sum of
+ * CSG_AUG_ADA_BLIT, CSG_AUG_ADA_GEOM and CSG_AUG_ADA_COLOR (the DiffAugment bits count for nothing here).  The _host twin
+ * takes p24 as an argument and writes the same words to host memory (no device needed).
+ *
+ * in / out: N samples of (H, H, Ct) floats, NHWC, dense, Ct a multiple of 4, 16-byte aligned, not the same buffer.  Colour
+ * channels are [c0, c0 + 3).  The transform entries read their parameters ONLY from the table and take any values: a
+ * non-finite map or a coordinate of 2^23 or more gives zeros, every index is checked against the map, the adjoint's walk is
+ * clamped to the map and to CSG_ADA_MAX_BOX pixels a side.  The operation sequences: csrc/ada_pipeline.hip.
+ * Refused with a message (CSG_E_BADSHAPE) before any launch: c0 + 3 > Ct, Ct % 4 != 0, H < 2 or H > CSG_AUG_MAX_H,
+ * table_rows < N, N H H Ct >= 2^31, misaligned or null pointers, in == out, policy outside the three bits, p24 outside
+ * [0, 2^24] (host entry).                                                                                               */
+#define CSG_AUG_ADA_BLIT 8
+#define CSG_AUG_ADA_GEOM 16
+#define CSG_AUG_ADA_COLOR 32
+int csg_ada_pipeline_table(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H, int32_t policy,
+                           const int64_t* ctrl, uint32_t* table, void* stream);
+int csg_ada_pipeline_table_host(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H,
+                                int32_t policy, int64_t p24, uint32_t* table);
+int csg_ada_pipeline_fwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
+                         int64_t c0, void* stream);
+int csg_ada_pipeline_bwd(const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H, int64_t Ct,
+                         int64_t c0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

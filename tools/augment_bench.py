@@ -20,6 +20,12 @@
       over the windows is reported beside the difference.  (b) What an adaptive run adds to a step: `ada_accumulate` over
       the C3 recipe's two prediction maps, plus one `ada_update` and the three gate fills of `begin_step`.
 
+  python tools/augment_bench.py pipeline [--out FILE]
+      The ADA pipeline (profiles/ada_pipeline.txt): forward (`ops.ada_pipeline`'s launch) and backward (its adjoint) on the C3
+      packed input with rows filled on the device at p = 1 for all three groups, for blitting alone (the copy path), and for
+      the row with the largest search box among 10^4 generated keys (every sample given that row); beside them, windows in
+      turn, a `copy_` of the same buffer and DiffAugment's forward and backward; and the three table fills of `begin_step`.
+
 Timing: HIP events around a window of calls after untimed warm-up calls, several windows, the median and all values
 reported.  Seeded inputs; the kernels' work does not depend on the values.
 """
@@ -131,6 +137,48 @@ def ada(args, dev):
     return lines
 
 
+def pipeline(args, dev):
+    from canonicalsg2im_amd import ops
+    from canonicalsg2im_amd._lib import lib
+    lines = ["device: %s; HIP events, %d calls per window after %d warm-up calls, %d windows in turn; median [all windows]" % (
+        torch.cuda.get_device_name(0), args.iters, args.warmup, args.windows)]
+    N, H, Ct, c0 = 16, 256, 40, 32
+    torch.manual_seed(0)
+    x = ops.empty_nhwc(N, Ct, H, H, dev).normal_()
+    g = ops.empty_nhwc(N, Ct, H, H, dev).normal_()
+    dst = torch.empty_like(x)
+    ctrl = torch.tensor([1 << 24, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+    tables = {"blit,geom,color at p = 1": ops.ada_pipeline_table(0, 1, 0, N, H, 56, ctrl),
+              "blit alone at p = 1 (copies)": ops.ada_pipeline_table(0, 1, 0, N, H, 8, ctrl)}
+    host = ops.ada_pipeline_table_host(0, 1, 0, 10000, H, 56, 1 << 24)
+    G = host[:, 6:12].view(torch.float32).abs().double()
+    half = torch.maximum(G[:, 0] + G[:, 1], G[:, 3] + G[:, 4])
+    worst = int(half.argmax())
+    tables["largest box of 10^4 keys (row %d, half side %.3f)" % (worst, float(half[worst]))] = host[worst:worst + 1].repeat(N, 1).to(dev)
+    old = ops.augment_table(0, 1, 0, N, H, device=dev)
+    three = torch.zeros((3, N, 32), dtype=torch.int32, device=dev)
+    runs = {}
+    for label, t in tables.items():
+        runs[label + ": forward"] = lambda t=t: ops._ada_launch(lib.csg_ada_pipeline_fwd, "ada_pipeline_fwd", x, t, c0)
+        runs[label + ": backward"] = lambda t=t: ops._ada_launch(lib.csg_ada_pipeline_bwd, "ada_pipeline_bwd", g, t, c0)
+    runs["copy_ of the same buffer"] = lambda: dst.copy_(x)
+    runs["d_augment color,translation,cutout: forward"] = lambda: ops.d_augment(x, old, c0, 7)
+    runs["d_augment color,translation,cutout: backward"] = lambda: ops._aug_launch(lib.csg_augment_bwd, "augment_bwd", g, old, c0, 7)
+    runs["three table fills of 16 rows"] = lambda: [ops.ada_pipeline_table(0, 1, p, N, H, 56, ctrl, out=three[p]) for p in range(3)]
+    for fn in runs.values():
+        for _ in range(args.warmup):
+            fn()
+    times = {k: [] for k in runs}
+    for _ in range(args.windows):
+        for k, fn in runs.items():
+            times[k].append(window(fn, args.iters))
+    copy = median(times["copy_ of the same buffer"])
+    lines.append("C3 packed PatchGAN input: %d x %d x %d x %d fp32 = %.1f MB, c0 = %d" % (N, H, H, Ct, x.numel() * 4 / 1e6, c0))
+    for k, v in times.items():
+        lines.append("    %-62s %s per call = %.2f x the copy" % (k, fmt(v), median(v) / copy))
+    return lines
+
+
 def c3_trainer(T, synth, dev, policies):
     base = synth.BASELINE_CONFIGS["C3"]
     vocab = synth.make_vocab(base["vocab"])
@@ -178,19 +226,19 @@ def steps(args, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernel", "steps", "ada"])
+    ap.add_argument("what", choices=["kernel", "steps", "ada", "pipeline"])
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.iters is None:
-        args.iters = 10 if args.what == "steps" else 2000        # kernel windows of 0.04-0.2 s
+        args.iters = 10 if args.what == "steps" else 200 if args.what == "pipeline" else 2000        # kernel windows of 0.04-0.2 s
     sys.path.insert(0, HERE)
     if not torch.cuda.is_available():
         raise SystemExit("tools/augment_bench.py measures on the device: no HIP device here, nothing measured")
     dev = torch.device("cuda", 0)
-    lines = {"kernel": kernel, "steps": steps, "ada": ada}[args.what](args, dev)
+    lines = {"kernel": kernel, "steps": steps, "ada": ada, "pipeline": pipeline}[args.what](args, dev)
     text = "\n".join(["$ python tools/augment_bench.py " + " ".join(sys.argv[1:] if argv is None else argv)] + lines) + "\n"
     print(text, flush=True)
     if args.out:
