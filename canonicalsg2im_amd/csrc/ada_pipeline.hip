@@ -43,6 +43,7 @@
 // kernel argument: the parameters come from the table, which is what lets a captured graph replay the pass.
 #include "csg_common.h"
 #include "csg_ada_pipeline.h"
+#include "csg_augment_host.h"
 #include "csg_vec4.h"
 
 namespace csg {
@@ -307,11 +308,8 @@ __global__ __launch_bounds__(kAdaThreads) void k_ada_pipeline_table(uint64_t see
 }
 
 static int ada_check_table(const char* who, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H, int32_t policy) {
-  CSG_REQUIRE(iteration >= 0 && pass >= 0 && pass <= 0x7fffffff && rank >= 0 && rank <= 0x7fffffff, CSG_E_BADSHAPE,
-              "%s: iteration %ld, pass %ld and rank %ld must be non-negative (pass and rank below 2^31)", who, (long)iteration,
-              (long)pass, (long)rank);
-  CSG_REQUIRE(rows >= 0 && rows <= 0x7fffffff / CSG_ADA_ROW_WORDS, CSG_E_BADSHAPE, "%s: %ld rows (0 .. 2^26 - 1)", who, (long)rows);
-  CSG_REQUIRE(H >= 2 && H <= CSG_AUG_MAX_H, CSG_E_BADSHAPE, "%s: H = %ld (2 .. %d)", who, (long)H, CSG_AUG_MAX_H);
+  if (int rc = aug_check_key(who, iteration, pass, rank, rows, 0x7fffffff / CSG_ADA_ROW_WORDS, "0 .. 2^26 - 1")) return rc;
+  if (int rc = aug_check_h(who, H)) return rc;
   CSG_REQUIRE(policy >= 0 && policy < 64, CSG_E_BADSHAPE,
               "%s: policy %d (a sum of 8 = ada_blit, 16 = ada_geom, 32 = ada_color; the bits below count for nothing)", who,
               (int)policy);
@@ -321,20 +319,9 @@ static int ada_check_table(const char* who, int64_t iteration, int64_t pass, int
 template <bool BWD>
 static int ada_apply(const char* who, const float* in, float* out, const uint32_t* table, int64_t table_rows, int64_t N, int64_t H,
                      int64_t Ct, int64_t c0, void* stream) {
-  CSG_REQUIRE(H >= 2 && H <= CSG_AUG_MAX_H, CSG_E_BADSHAPE, "%s: H = %ld (2 .. %d)", who, (long)H, CSG_AUG_MAX_H);
-  CSG_REQUIRE(Ct >= 4 && Ct % 4 == 0, CSG_E_BADSHAPE, "%s: Ct = %ld must be a positive multiple of 4 (16-byte pixel rows)", who,
-              (long)Ct);
-  CSG_REQUIRE(c0 >= 0 && c0 + 3 <= Ct, CSG_E_BADSHAPE, "%s: colour channels [%ld, %ld) do not fit Ct = %ld (c0 + 3 > Ct)", who,
-              (long)c0, (long)c0 + 3, (long)Ct);
-  CSG_REQUIRE(N >= 0 && N <= 0x7fffffff && (double)N * (double)H * (double)H * (double)Ct < 2147483648.0, CSG_E_BADSHAPE,
-              "%s: N = %ld samples of %ld x %ld x %ld floats (fewer than 2^31 floats in all)", who, (long)N, (long)H, (long)H,
-              (long)Ct);
-  CSG_REQUIRE(table_rows >= N, CSG_E_BADSHAPE, "%s: the table has %ld rows, fewer than N = %ld", who, (long)table_rows, (long)N);
-  if (N == 0) return CSG_OK;
-  CSG_REQUIRE(in != nullptr && out != nullptr && table != nullptr, CSG_E_BADSHAPE, "%s: null pointer", who);
-  CSG_REQUIRE((((uintptr_t)in | (uintptr_t)out | (uintptr_t)table) & 15) == 0, CSG_E_BADSHAPE,
-              "%s: in, out and the table must be 16-byte aligned", who);
-  CSG_REQUIRE((const void*)in != (const void*)out, CSG_E_BADSHAPE, "%s: not in place (a resampled pixel reads other ones)", who);
+  bool empty;
+  if (int rc = aug_check_map(who, in, out, table, table_rows, N, H, Ct, c0, "a resampled pixel reads other ones", empty)) return rc;
+  if (empty) return CSG_OK;
   hipStream_t s = (hipStream_t)stream;
   const unsigned total4 = (unsigned)(N * H * H * (Ct / 4));
   const unsigned grid = (unsigned)cdiv((int64_t)total4, (int64_t)kAdaThreads);
@@ -353,7 +340,7 @@ extern "C" {
 int csg_ada_pipeline_table_host(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H,
                                 int32_t policy, int64_t p24, uint32_t* table) {
   if (int rc = ada_check_table("csg_ada_pipeline_table_host", iteration, pass, rank, rows, H, policy)) return rc;
-  CSG_REQUIRE(p24 >= 0 && p24 <= CSG_ADA_ONE, CSG_E_BADSHAPE, "csg_ada_pipeline_table_host: p24 = %ld (0 .. 2^24)", (long)p24);
+  if (int rc = aug_check_p24("csg_ada_pipeline_table_host", p24)) return rc;
   CSG_REQUIRE(rows == 0 || table != nullptr, CSG_E_BADSHAPE, "csg_ada_pipeline_table_host: null table");
   for (int64_t n = 0; n < rows; ++n) {
     const AdaRow r = ada_row(seed, (uint64_t)iteration, (uint64_t)pass, (uint64_t)rank, (uint64_t)n, (int32_t)H, policy, (uint32_t)p24);
@@ -365,8 +352,7 @@ int csg_ada_pipeline_table_host(uint64_t seed, int64_t iteration, int64_t pass, 
 int csg_ada_pipeline_table(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H, int32_t policy,
                            const int64_t* ctrl, uint32_t* table, void* stream) {
   if (int rc = ada_check_table("csg_ada_pipeline_table", iteration, pass, rank, rows, H, policy)) return rc;
-  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
-              "csg_ada_pipeline_table: the controller must be 8-byte aligned (null pointer or misaligned)");
+  if (int rc = aug_check_ctrl("csg_ada_pipeline_table", ctrl)) return rc;
   if (rows == 0) return CSG_OK;
   CSG_REQUIRE(table != nullptr && ((uintptr_t)table & 15) == 0, CSG_E_BADSHAPE,
               "csg_ada_pipeline_table: the table must be 16-byte aligned (null pointer or misaligned)");

@@ -47,7 +47,7 @@
 // k_ada_update, one thread, moves p24 by one step towards the target and restarts the counts.  None of them takes p as an
 // argument or reads anything back, so the gate fills can run eagerly before a replayed step and the accumulation inside it.
 #include "csg_common.h"
-#include "csg_augment.h"
+#include "csg_augment_host.h"
 #include "csg_reduce.h"
 #include "csg_vec4.h"
 
@@ -320,20 +320,8 @@ __global__ void k_ada_update(int64_t* __restrict__ ctrl, int64_t T24, int64_t st
 static int64_t aug_chunks(int64_t H) { return cdiv(H * H, (int64_t)CSG_AUG_CHUNK); }
 
 static int aug_check_table(const char* who, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t H) {
-  CSG_REQUIRE(iteration >= 0 && pass >= 0 && pass <= 0x7fffffff && rank >= 0 && rank <= 0x7fffffff, CSG_E_BADSHAPE,
-              "%s: iteration %ld, pass %ld and rank %ld must be non-negative (pass and rank below 2^31)", who, (long)iteration,
-              (long)pass, (long)rank);
-  CSG_REQUIRE(rows >= 0 && rows <= 0x7fffffff, CSG_E_BADSHAPE, "%s: %ld rows (0 .. 2^31 - 1)", who, (long)rows);
-  CSG_REQUIRE(H >= 2 && H <= CSG_AUG_MAX_H, CSG_E_BADSHAPE, "%s: H = %ld (2 .. %d)", who, (long)H, CSG_AUG_MAX_H);
-  return CSG_OK;
-}
-
-static int aug_check_gate(const char* who, int64_t iteration, int64_t pass, int64_t rank, int64_t rows) {
-  CSG_REQUIRE(iteration >= 0 && pass >= 0 && pass <= 0x7fffffff && rank >= 0 && rank <= 0x7fffffff, CSG_E_BADSHAPE,
-              "%s: iteration %ld, pass %ld and rank %ld must be non-negative (pass and rank below 2^31)", who, (long)iteration,
-              (long)pass, (long)rank);
-  CSG_REQUIRE(rows >= 0 && rows <= 0x7fffffff, CSG_E_BADSHAPE, "%s: %ld rows (0 .. 2^31 - 1)", who, (long)rows);
-  return CSG_OK;
+  if (int rc = aug_check_key(who, iteration, pass, rank, rows, 0x7fffffff, "0 .. 2^31 - 1")) return rc;
+  return aug_check_h(who, H);
 }
 
 template <bool BWD>
@@ -342,20 +330,9 @@ static int aug_apply(const char* who, const float* in, float* out, const uint32_
                      const int32_t* gate, void* stream) {
   CSG_REQUIRE(policy >= 0 && policy <= (CSG_AUG_COLOR | CSG_AUG_TRANSLATION | CSG_AUG_CUTOUT), CSG_E_BADSHAPE,
               "%s: policy %d (a sum of 1 = colour, 2 = translation, 4 = cutout)", who, (int)policy);
-  CSG_REQUIRE(H >= 2 && H <= CSG_AUG_MAX_H, CSG_E_BADSHAPE, "%s: H = %ld (2 .. %d)", who, (long)H, CSG_AUG_MAX_H);
-  CSG_REQUIRE(Ct >= 4 && Ct % 4 == 0, CSG_E_BADSHAPE, "%s: Ct = %ld must be a positive multiple of 4 (16-byte pixel rows)", who,
-              (long)Ct);
-  CSG_REQUIRE(c0 >= 0 && c0 + 3 <= Ct, CSG_E_BADSHAPE, "%s: colour channels [%ld, %ld) do not fit Ct = %ld (c0 + 3 > Ct)", who,
-              (long)c0, (long)c0 + 3, (long)Ct);
-  CSG_REQUIRE(N >= 0 && N <= 0x7fffffff && (double)N * (double)H * (double)H * (double)Ct < 2147483648.0, CSG_E_BADSHAPE,
-              "%s: N = %ld samples of %ld x %ld x %ld floats (fewer than 2^31 floats in all)", who, (long)N, (long)H, (long)H,
-              (long)Ct);
-  CSG_REQUIRE(table_rows >= N, CSG_E_BADSHAPE, "%s: the table has %ld rows, fewer than N = %ld", who, (long)table_rows, (long)N);
-  if (N == 0) return CSG_OK;
-  CSG_REQUIRE(in != nullptr && out != nullptr && table != nullptr, CSG_E_BADSHAPE, "%s: null pointer", who);
-  CSG_REQUIRE((((uintptr_t)in | (uintptr_t)out | (uintptr_t)table) & 15) == 0, CSG_E_BADSHAPE,
-              "%s: in, out and the table must be 16-byte aligned", who);
-  CSG_REQUIRE((const void*)in != (const void*)out, CSG_E_BADSHAPE, "%s: not in place (a translated pixel reads another one)", who);
+  bool empty;
+  if (int rc = aug_check_map(who, in, out, table, table_rows, N, H, Ct, c0, "a translated pixel reads another one", empty)) return rc;
+  if (empty) return CSG_OK;
   if (gated)
     CSG_REQUIRE(gate != nullptr && ((uintptr_t)gate & 3) == 0, CSG_E_BADSHAPE,
                 "%s: the gate must be a 4-byte aligned array of N int32 (null pointer or misaligned)", who);
@@ -451,8 +428,8 @@ int csg_augment_bwd_gated(const float* in, float* out, const uint32_t* table, in
 }
 
 int csg_augment_gate_host(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, int64_t p24, int32_t* gate) {
-  if (int rc = aug_check_gate("csg_augment_gate_host", iteration, pass, rank, rows)) return rc;
-  CSG_REQUIRE(p24 >= 0 && p24 <= CSG_ADA_ONE, CSG_E_BADSHAPE, "csg_augment_gate_host: p24 = %ld (0 .. 2^24)", (long)p24);
+  if (int rc = aug_check_key("csg_augment_gate_host", iteration, pass, rank, rows, 0x7fffffff, "0 .. 2^31 - 1")) return rc;
+  if (int rc = aug_check_p24("csg_augment_gate_host", p24)) return rc;
   CSG_REQUIRE(rows == 0 || gate != nullptr, CSG_E_BADSHAPE, "csg_augment_gate_host: null pointer");
   for (int64_t n = 0; n < rows; ++n)
     gate[n] = (int32_t)aug_gate(seed, (uint64_t)iteration, (uint64_t)pass, (uint64_t)rank, (uint64_t)n, (uint32_t)p24);
@@ -461,9 +438,8 @@ int csg_augment_gate_host(uint64_t seed, int64_t iteration, int64_t pass, int64_
 
 int csg_augment_gate(uint64_t seed, int64_t iteration, int64_t pass, int64_t rank, int64_t rows, const int64_t* ctrl, int32_t* gate,
                      void* stream) {
-  if (int rc = aug_check_gate("csg_augment_gate", iteration, pass, rank, rows)) return rc;
-  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
-              "csg_augment_gate: the controller must be 8-byte aligned (null pointer or misaligned)");
+  if (int rc = aug_check_key("csg_augment_gate", iteration, pass, rank, rows, 0x7fffffff, "0 .. 2^31 - 1")) return rc;
+  if (int rc = aug_check_ctrl("csg_augment_gate", ctrl)) return rc;
   if (rows == 0) return CSG_OK;
   CSG_REQUIRE(gate != nullptr && ((uintptr_t)gate & 3) == 0, CSG_E_BADSHAPE,
               "csg_augment_gate: the gate must be 4-byte aligned (null pointer or misaligned)");
@@ -476,8 +452,7 @@ int csg_augment_gate(uint64_t seed, int64_t iteration, int64_t pass, int64_t ran
 int csg_ada_accumulate(const csg_hinge_item* items, int32_t n_items, int64_t* ctrl, void* stream) {
   CSG_REQUIRE(items != nullptr && n_items >= 1 && n_items <= 4, CSG_E_BADSHAPE, "csg_ada_accumulate: 1..4 maps (got %d)",
               (int)n_items);
-  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
-              "csg_ada_accumulate: the controller must be 8-byte aligned (null pointer or misaligned)");
+  if (int rc = aug_check_ctrl("csg_ada_accumulate", ctrl)) return rc;
   AdaItems it;
   it.n = n_items;
   int64_t total = 0;
@@ -499,8 +474,7 @@ int csg_ada_accumulate(const csg_hinge_item* items, int32_t n_items, int64_t* ct
 }
 
 static int ada_check_update(const char* who, const int64_t* ctrl, int64_t T24, int64_t step24) {
-  CSG_REQUIRE(ctrl != nullptr && ((uintptr_t)ctrl & 7) == 0, CSG_E_BADSHAPE,
-              "%s: the controller must be 8-byte aligned (null pointer or misaligned)", who);
+  if (int rc = aug_check_ctrl(who, ctrl)) return rc;
   CSG_REQUIRE(T24 >= 0 && T24 <= CSG_ADA_ONE, CSG_E_BADSHAPE, "%s: T24 = %ld (0 .. 2^24)", who, (long)T24);
   CSG_REQUIRE(step24 >= 1, CSG_E_BADSHAPE, "%s: step24 = %ld (step24 < 1)", who, (long)step24);
   return CSG_OK;
@@ -508,7 +482,7 @@ static int ada_check_update(const char* who, const int64_t* ctrl, int64_t T24, i
 
 int csg_ada_update_host(int64_t* ctrl, int64_t T24, int64_t step24) {
   if (int rc = ada_check_update("csg_ada_update_host", ctrl, T24, step24)) return rc;
-  CSG_REQUIRE(ctrl[0] >= 0 && ctrl[0] <= CSG_ADA_ONE, CSG_E_BADSHAPE, "csg_ada_update_host: p24 = %ld (0 .. 2^24)", (long)ctrl[0]);
+  if (int rc = aug_check_p24("csg_ada_update_host", ctrl[0])) return rc;
   CSG_REQUIRE(ctrl[2] >= 0 && ctrl[2] < CSG_ADA_MAX_COUNT, CSG_E_BADSHAPE,
               "csg_ada_update_host: C = %ld elements (0 .. 2^38 - 1: S * 2^24 must fit int64)", (long)ctrl[2]);
   ada_update_words(ctrl, T24, step24);

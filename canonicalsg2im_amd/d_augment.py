@@ -204,35 +204,32 @@ class DAugment:
     def end_step(self):
         self.active = False
 
-    def image_table(self, pass_id, n):
-        """The persistent table of PatchGAN pass 0, 1 or 2 (all its rows: the kernel reads the first n)."""
-        if not 0 <= pass_id < IMG_PASSES:
-            raise ValueError("DAugment.image_table: pass %r (0, 1 or 2)" % (pass_id,))
-        if n > self.rows:
-            raise RuntimeError("DAugment: a batch of %d pictures, the tables were made for --batch_size %d" % (n, self.rows))
-        return self.tables[pass_id]
+    def operands(self, pass_id, n, size):
+        """(table, gate, ada_table) of pass `pass_id` for n samples of size x size; what the run does not use is None.
+        PatchGAN pass 0, 1 or 2: the persistent ones (all their rows: the kernels read the first n).  Crop pass 3, 4 or 5:
+        fresh ones of n rows, one eager launch each on the current stream."""
+        from . import ops
+        if not 0 <= pass_id < 6:
+            raise ValueError("DAugment.operands: pass %r (0 .. 5)" % (pass_id,))
+        if pass_id < IMG_PASSES:
+            if n > self.rows:
+                raise RuntimeError("DAugment: a batch of %d pictures, the tables were made for --batch_size %d" % (n, self.rows))
+            return (self.tables[pass_id] if self.diff_policy else None,
+                    self.gates[pass_id] if self.diff_policy and self.gated else None,
+                    self.ada_tables[pass_id] if self.ada_policy else None)
+        ada_table = table = gate = None
+        if self.ada_policy:
+            ada_table = ops.ada_pipeline_table(self.seed, self.iteration, pass_id, n, size, self.ada_policy, self.ctrl,
+                                               rank=self.rank)
+        if self.diff_policy:
+            table = self.crop_table(pass_id, n, size)
+            gate = self.crop_gate(pass_id, n) if self.gated else None
+        return table, gate, ada_table
 
     def crop_table(self, pass_id, n, size):
         """A fresh table of n rows for crops of size x size (pass 3, 4 or 5): one eager launch on the current stream."""
         from . import ops
-        if not IMG_PASSES <= pass_id < 6:
-            raise ValueError("DAugment.crop_table: pass %r (3, 4 or 5)" % (pass_id,))
         return ops.augment_table(self.seed, self.iteration, pass_id, n, size, rank=self.rank, device=self.device)
-
-    def ada_table(self, pass_id, n, size):
-        """The ADA pipeline's rows of pass `pass_id`: the persistent ones of PatchGAN pass 0, 1 or 2, or a fresh table of n
-        rows for crops of size x size (pass 3, 4 or 5; one eager launch on the current stream)."""
-        from . import ops
-        if pass_id < IMG_PASSES:
-            self.image_table(pass_id, n)         # (the checks)
-            return self.ada_tables[pass_id]
-        if not pass_id < 6:
-            raise ValueError("DAugment.ada_table: pass %r (0 .. 5)" % (pass_id,))
-        return ops.ada_pipeline_table(self.seed, self.iteration, pass_id, n, size, self.ada_policy, self.ctrl, rank=self.rank)
-
-    def image_gate(self, pass_id):
-        """The persistent gate of PatchGAN pass 0, 1 or 2; None on an ungated run."""
-        return None if not self.gated else self.gates[pass_id]
 
     def crop_gate(self, pass_id, n):
         """A fresh gate of n rows for the crops of pass 3, 4 or 5 (gated runs): one eager launch beside the crop table's."""
@@ -260,24 +257,22 @@ class DAugment:
         from . import ops
         if not self.active or pass_id is None or x.shape[0] == 0:
             return x
-        n = x.shape[0]
+        table, gate, ada_table = self.operands(pass_id, x.shape[0], x.shape[2])
         if self.ada_policy:                      # the ADA stage first, one launch; DiffAugment then runs on its output
-            x = ops.ada_pipeline(x, self.ada_table(pass_id, n, x.shape[2]), c0)
-            if not self.diff_policy:
-                return x
-        table = self.image_table(pass_id, n) if pass_id < IMG_PASSES else self.crop_table(pass_id, n, x.shape[2])
-        if not self.gated:
-            return ops.d_augment(x, table, c0, self.diff_policy)
-        gate = self.image_gate(pass_id) if pass_id < IMG_PASSES else self.crop_gate(pass_id, n)
-        return ops.d_augment(x, table, c0, self.diff_policy, gate=gate)
+            x = ops.ada_pipeline(x, ada_table, c0)
+        if self.diff_policy:
+            x = ops.d_augment(x, table, c0, self.diff_policy, gate=gate)
+        return x
 
     # ------------------------------------------------------------------ checkpoints
+    def _ada_meta(self):
+        return {k: self.ada[k] for k in ("p24", "T24", "interval", "kimg")}
+
     def meta(self):
         out = {"seed": self.seed, "iteration": self.iteration, "policies": policy_names(self.policy)}
         if self.gated:                           # (ungated: exactly the keys above)
             out["ctrl"] = [int(v) for v in self.ctrl.tolist()]
-            out["ada"] = {"p24": self.ada["p24"], "T24": self.ada["T24"], "interval": self.ada["interval"],
-                          "kimg": self.ada["kimg"]}
+            out["ada"] = self._ada_meta()
         return out
 
     def load_meta(self, meta, say=print):
@@ -301,7 +296,7 @@ class DAugment:
                 words[1] = words[2] = 0
             self.ctrl.copy_(torch.tensor([int(v) for v in words], dtype=torch.int64))
             theirs_ada = (meta or {}).get("ada")
-            mine = {"p24": self.ada["p24"], "T24": self.ada["T24"], "interval": self.ada["interval"], "kimg": self.ada["kimg"]}
+            mine = self._ada_meta()
             if theirs_ada is not None and theirs_ada != mine:
                 say("d_augment: the checkpoint was written with the settings %s; this run's hold: %s (p24 = %d continues)" % (
                     theirs_ada, mine, int(words[0])))

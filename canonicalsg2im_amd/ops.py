@@ -3179,72 +3179,82 @@ def augment_table(seed, iteration, pass_id, rows, H, rank=0, out=None, device=No
     _aug_key("augment_table", seed, iteration, pass_id, rank, rows, H)
     if out is None:
         out = torch.empty((rows, 8), dtype=torch.int32, device=device if device is not None else "cuda")
-    _aug_table_operand("augment_table", out, rows)
+    _aug_rows_operand("augment_table", "table", out, rows, 8)
     check(lib.csg_augment_table(seed, iteration, pass_id, rank, rows, H, ptr(out), stream()), "augment_table")
     return out
 
 
-def _aug_table_operand(what, table, N):
-    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
-        raise RuntimeError("%s: the table must be a contiguous int32 (rows, 8) tensor, got %s" % (
-            what, (table.dtype, tuple(table.shape)) if torch.is_tensor(table) else type(table).__name__))
-    if table.shape[0] < N:
-        raise RuntimeError("%s: the table has %d rows, fewer than N = %d" % (what, table.shape[0], N))
+def _aug_rows_operand(what, name, t, N, width):
+    """One row per sample: a (rows, width) table, or the (rows,) gate with width None."""
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_contiguous() \
+            or (t.dim() != 1 if width is None else t.dim() != 2 or t.shape[1] != width):
+        raise RuntimeError("%s: the %s must be a contiguous int32 (rows,%s) tensor, got %s" % (
+            what, name, "" if width is None else " %d" % width,
+            (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    if t.shape[0] < N:
+        raise RuntimeError("%s: the %s has %d rows, fewer than N = %d" % (what, name, t.shape[0], N))
 
 
-def _aug_launch(fn, what, x, table, c0, policy, gate=None):
+def _aug_map_operand(what, x, c0):
+    """x as what the transforms run on -> (N, Ct, H, c0)."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise RuntimeError("%s: x must be a (N, Ct, H, H) tensor, got %s" % (
+            what, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    _f32(x)
+    N, Ct, H, _ = x.shape
+    c0 = int(c0)
+    if Ct % 4:
+        raise RuntimeError("%s: Ct = %d must be a multiple of 4 (Ct %% 4 != 0)" % (what, Ct))
+    if c0 < 0 or c0 + 3 > Ct:
+        raise RuntimeError("%s: colour channels [%d, %d) do not fit Ct = %d (c0 + 3 > Ct)" % (what, c0, c0 + 3, Ct))
+    if H < 2:
+        raise RuntimeError("%s: H = %d (H < 2)" % (what, H))
+    return N, Ct, H, c0
+
+
+# kind -> (forward entry, adjoint entry, name): DiffAugment, DiffAugment with a per-sample gate (sample n runs
+# policy & gate[n]), the ADA pipeline
+_AUG_KINDS = {"diff": (lib.csg_augment_fwd, lib.csg_augment_bwd, "augment_%s"),
+              "gated": (lib.csg_augment_fwd_gated, lib.csg_augment_bwd_gated, "augment_%s_gated"),
+              "ada": (lib.csg_ada_pipeline_fwd, lib.csg_ada_pipeline_bwd, "ada_pipeline_%s")}
+
+
+def _aug_launch(kind, bwd, x, table, c0, policy=0, gate=None):
+    """The kind's forward or adjoint entry on x (NHWC float32) into a fresh tensor of its shape."""
+    fwd, adjoint, name = _AUG_KINDS[kind]
     N, Ct, H, W = x.shape
     out = empty_nhwc(N, Ct, H, W, x.device)
-    ws, nws = None, 0
-    if policy & AUG_COLOR and N:
-        nws = int(lib.csg_augment_workspace_bytes(N, H))
-        ws = torch.empty(max(nws, 8) // 8, dtype=torch.float64, device=x.device)
-    if gate is None:
-        check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, policy, ptr(ws), nws, stream()), what)
-    else:
-        check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, policy, ptr(ws), nws, ptr(gate), stream()), what)
+    args = (ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0)
+    if kind != "ada":
+        ws, nws = None, 0
+        if policy & AUG_COLOR and N:
+            nws = int(lib.csg_augment_workspace_bytes(N, H))
+            ws = torch.empty(max(nws, 8) // 8, dtype=torch.float64, device=x.device)
+        args += (policy, ptr(ws), nws) if gate is None else (policy, ptr(ws), nws, ptr(gate))
+    check((adjoint if bwd else fwd)(*args, stream()), name % ("bwd" if bwd else "fwd"))
     return out
 
 
-class _DAugment(torch.autograd.Function):
-    """The transform of csrc/augment.hip and its adjoint.  Linear in x: the backward needs the table alone."""
+class _Augment(torch.autograd.Function):
+    """A transform of csrc/augment.hip or csrc/ada_pipeline.hip and its adjoint.  Linear in x: the backward needs the table
+    (and the gate) alone."""
 
     @staticmethod
-    def forward(ctx, x, table, c0, policy):
-        ctx.save_for_backward(table)
-        ctx.meta = (c0, policy)
-        return _aug_launch(lib.csg_augment_fwd, "augment_fwd", nhwc(x), table, c0, policy)
-
-    @staticmethod
-    def backward(ctx, g):
-        (table,) = ctx.saved_tensors
-        c0, policy = ctx.meta
-        return _aug_launch(lib.csg_augment_bwd, "augment_bwd", nhwc(_f32(g)), table, c0, policy), None, None, None
-
-
-class _DAugmentGated(torch.autograd.Function):
-    """_DAugment with a per-sample gate (csg_augment_fwd_gated / _bwd_gated): sample n runs policy & gate[n]."""
-
-    @staticmethod
-    def forward(ctx, x, table, c0, policy, gate):
-        ctx.save_for_backward(table, gate)
-        ctx.meta = (c0, policy)
-        return _aug_launch(lib.csg_augment_fwd_gated, "augment_fwd_gated", nhwc(x), table, c0, policy, gate)
+    def forward(ctx, x, kind, table, c0, policy, gate):
+        ctx.save_for_backward(*((table,) if gate is None else (table, gate)))
+        ctx.meta = (kind, c0, policy)
+        return _aug_launch(kind, False, nhwc(x), table, c0, policy, gate)
 
     @staticmethod
     def backward(ctx, g):
-        table, gate = ctx.saved_tensors
-        c0, policy = ctx.meta
-        return _aug_launch(lib.csg_augment_bwd_gated, "augment_bwd_gated", nhwc(_f32(g)), table, c0, policy, gate), None, None, \
-            None, None
+        table, gate = (ctx.saved_tensors + (None,))[:2]
+        kind, c0, policy = ctx.meta
+        return _aug_launch(kind, True, nhwc(_f32(g)), table, c0, policy, gate), None, None, None, None, None
 
 
-def _aug_gate_operand(what, gate, N):
-    if not torch.is_tensor(gate) or gate.dtype != torch.int32 or gate.dim() != 1 or not gate.is_contiguous():
-        raise RuntimeError("%s: the gate must be a contiguous int32 (rows,) tensor, got %s" % (
-            what, (gate.dtype, tuple(gate.shape)) if torch.is_tensor(gate) else type(gate).__name__))
-    if gate.shape[0] < N:
-        raise RuntimeError("%s: the gate has %d rows, fewer than N = %d" % (what, gate.shape[0], N))
+def _ada_p24(what, p24):
+    if not isinstance(p24, int) or isinstance(p24, bool) or not 0 <= p24 <= ADA_ONE:
+        raise RuntimeError("%s: p24 must be an integer in [0, 2^24], got %r" % (what, p24))
 
 
 def _ada_ctrl_operand(what, ctrl, cuda=True):
@@ -3262,8 +3272,7 @@ def _aug_gate_key(what, seed, iteration, pass_id, rank, rows):
 def augment_gate_host(seed, iteration, pass_id, rows, p24, rank=0):
     """(rows,) int32 on the HOST: the masks the device entry writes when the controller holds p24 (csrc/csg_augment.h)."""
     _aug_gate_key("augment_gate_host", seed, iteration, pass_id, rank, rows)
-    if not isinstance(p24, int) or isinstance(p24, bool) or not 0 <= p24 <= ADA_ONE:
-        raise RuntimeError("augment_gate_host: p24 must be an integer in [0, 2^24], got %r" % (p24,))
+    _ada_p24("augment_gate_host", p24)
     out = torch.zeros((rows,), dtype=torch.int32)
     check(lib.csg_augment_gate_host(seed, iteration, pass_id, rank, rows, p24, ctypes.c_void_p(out.data_ptr())), "augment_gate_host")
     return out
@@ -3277,7 +3286,7 @@ def augment_gate(seed, iteration, pass_id, rows, ctrl, rank=0, out=None):
     _ada_ctrl_operand("augment_gate", ctrl)
     if out is None:
         out = torch.empty((rows,), dtype=torch.int32, device=ctrl.device)
-    _aug_gate_operand("augment_gate", out, rows)
+    _aug_rows_operand("augment_gate", "gate", out, rows, None)
     check(lib.csg_augment_gate(seed, iteration, pass_id, rank, rows, ptr(ctrl), ptr(out), stream()), "augment_gate")
     return out
 
@@ -3325,25 +3334,13 @@ def d_augment(x, table, c0, policy, gate=None):
     without it the call is what it was.  Returns the same kind of tensor; differentiable in x."""
     if not isinstance(policy, int) or isinstance(policy, bool) or not 0 <= policy <= 7:
         raise RuntimeError("d_augment: policy must be a mask in [0, 7] (1 = color, 2 = translation, 4 = cutout), got %r" % (policy,))
-    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] != x.shape[3]:
-        raise RuntimeError("d_augment: x must be a (N, Ct, H, H) tensor, got %s" % (
-            tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
-    _f32(x)
-    N, Ct, H, _ = x.shape
-    c0 = int(c0)
-    if Ct % 4:
-        raise RuntimeError("d_augment: Ct = %d must be a multiple of 4 (Ct %% 4 != 0)" % Ct)
-    if c0 < 0 or c0 + 3 > Ct:
-        raise RuntimeError("d_augment: colour channels [%d, %d) do not fit Ct = %d (c0 + 3 > Ct)" % (c0, c0 + 3, Ct))
-    if H < 2:
-        raise RuntimeError("d_augment: H = %d (H < 2)" % H)
-    _aug_table_operand("d_augment", table, N)
+    N, _, _, c0 = _aug_map_operand("d_augment", x, c0)
+    _aug_rows_operand("d_augment", "table", table, N, 8)
     if gate is not None:
-        _aug_gate_operand("d_augment", gate, N)
+        _aug_rows_operand("d_augment", "gate", gate, N, None)
         if gate.device != x.device:
             raise RuntimeError("d_augment: the gate is on %s, x on %s" % (gate.device, x.device))
-        return _DAugmentGated.apply(x, table, c0, policy, gate)
-    return _DAugment.apply(x, table, c0, policy)
+    return _Augment.apply(x, "diff" if gate is None else "gated", table, c0, policy, gate)
 
 
 # ---- The ADA augmentation pipeline (csrc/ada_pipeline.hip; the row and its draws: csrc/csg_ada_pipeline.h) ----------------
@@ -3359,22 +3356,12 @@ def _ada_policy(what, policy):
             what, policy))
 
 
-def _ada_table_operand(what, table, N):
-    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != ADA_ROW_WORDS \
-            or not table.is_contiguous():
-        raise RuntimeError("%s: the table must be a contiguous int32 (rows, %d) tensor, got %s" % (
-            what, ADA_ROW_WORDS, (table.dtype, tuple(table.shape)) if torch.is_tensor(table) else type(table).__name__))
-    if table.shape[0] < N:
-        raise RuntimeError("%s: the table has %d rows, fewer than N = %d" % (what, table.shape[0], N))
-
-
 def ada_pipeline_table_host(seed, iteration, pass_id, rows, H, policy, p24, rank=0):
     """(rows, 32) int32 on the HOST: the words the device entry writes when the controller holds p24, from the host half of
     csrc/csg_ada_pipeline.h."""
     _aug_key("ada_pipeline_table_host", seed, iteration, pass_id, rank, rows, H)
     _ada_policy("ada_pipeline_table_host", policy)
-    if not isinstance(p24, int) or isinstance(p24, bool) or not 0 <= p24 <= ADA_ONE:
-        raise RuntimeError("ada_pipeline_table_host: p24 must be an integer in [0, 2^24], got %r" % (p24,))
+    _ada_p24("ada_pipeline_table_host", p24)
     out = torch.zeros((rows, ADA_ROW_WORDS), dtype=torch.int32)
     check(lib.csg_ada_pipeline_table_host(seed, iteration, pass_id, rank, rows, H, policy, p24, ctypes.c_void_p(out.data_ptr())),
           "ada_pipeline_table_host")
@@ -3390,33 +3377,10 @@ def ada_pipeline_table(seed, iteration, pass_id, rows, H, policy, ctrl, rank=0, 
     _ada_ctrl_operand("ada_pipeline_table", ctrl)
     if out is None:
         out = torch.empty((rows, ADA_ROW_WORDS), dtype=torch.int32, device=ctrl.device)
-    _ada_table_operand("ada_pipeline_table", out, rows)
+    _aug_rows_operand("ada_pipeline_table", "table", out, rows, ADA_ROW_WORDS)
     check(lib.csg_ada_pipeline_table(seed, iteration, pass_id, rank, rows, H, policy, ptr(ctrl), ptr(out), stream()),
           "ada_pipeline_table")
     return out
-
-
-def _ada_launch(fn, what, x, table, c0):
-    N, Ct, H, W = x.shape
-    out = empty_nhwc(N, Ct, H, W, x.device)
-    check(fn(ptr(x), ptr(out), ptr(table), table.shape[0], N, H, Ct, c0, stream()), what)
-    return out
-
-
-class _AdaPipeline(torch.autograd.Function):
-    """The resampling and colour matrix of csrc/ada_pipeline.hip and their adjoint.  Linear in x: the backward needs the table
-    alone."""
-
-    @staticmethod
-    def forward(ctx, x, table, c0):
-        ctx.save_for_backward(table)
-        ctx.c0 = c0
-        return _ada_launch(lib.csg_ada_pipeline_fwd, "ada_pipeline_fwd", nhwc(x), table, c0)
-
-    @staticmethod
-    def backward(ctx, g):
-        (table,) = ctx.saved_tensors
-        return _ada_launch(lib.csg_ada_pipeline_bwd, "ada_pipeline_bwd", nhwc(_f32(g)), table, ctx.c0), None, None
 
 
 def ada_pipeline(x, table, c0):
@@ -3424,19 +3388,8 @@ def ada_pipeline(x, table, c0):
     affine map of row n of `table` (`ada_pipeline_table`) with four bilinear taps and zero fill — or copied where the row says
     the geometry is the identity or an integer map —, then the row's 3 x 4 colour matrix acts on channels [c0, c0 + 3).
     Returns the same kind of tensor; differentiable in x (the exact adjoint)."""
-    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[2] != x.shape[3]:
-        raise RuntimeError("ada_pipeline: x must be a (N, Ct, H, H) tensor, got %s" % (
-            tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
-    _f32(x)
-    N, Ct, H, _ = x.shape
-    c0 = int(c0)
-    if Ct % 4:
-        raise RuntimeError("ada_pipeline: Ct = %d must be a multiple of 4 (Ct %% 4 != 0)" % Ct)
-    if c0 < 0 or c0 + 3 > Ct:
-        raise RuntimeError("ada_pipeline: colour channels [%d, %d) do not fit Ct = %d (c0 + 3 > Ct)" % (c0, c0 + 3, Ct))
-    if H < 2:
-        raise RuntimeError("ada_pipeline: H = %d (H < 2)" % H)
-    _ada_table_operand("ada_pipeline", table, N)
+    N, _, _, c0 = _aug_map_operand("ada_pipeline", x, c0)
+    _aug_rows_operand("ada_pipeline", "table", table, N, ADA_ROW_WORDS)
     if table.device != x.device:
         raise RuntimeError("ada_pipeline: the table is on %s, x on %s" % (table.device, x.device))
-    return _AdaPipeline.apply(x, table, c0)
+    return _Augment.apply(x, "ada", table, c0, 0, None)

@@ -171,6 +171,45 @@ def test_autograd_through_ops(cuda):
         assert wf <= 1.0 and wb <= 1.0
 
 
+def test_autograd_runs_each_kinds_own_adjoint(cuda):
+    """DiffAugment, gated DiffAugment and the ADA pipeline go through one autograd Function: for each kind the gradient that
+    autograd returns is, bit for bit, what the kind's own _bwd entry gives on the same upstream gradient with the operands
+    the forward was called with.  N = 3, Ct = 8, H = 5, c0 = 4: an odd side (the translation wraps, the cutout clips), 25
+    pixels (a partial chunk), colour channels in the second float4.  Tables of seed 1, passes 0, 1 and 2 (one per kind, so a
+    kind that saved another's table shows), gate and ADA rows at p24 = 2^23, ADA policy 56.  ITERATION 2, not 1: at
+    iteration 1 the gate of pass 1 is [3, 4, 3], no row fully off; at iteration 2 it is [0, 1, 4] (asserted below)."""
+    from canonicalsg2im_amd import ops
+    from canonicalsg2im_amd._lib import check, lib, ptr, stream
+    N, Ct, H, c0, seed, it, p24 = 3, 8, 5, 4, 1, 2, 1 << 23
+    gate_h = ops.augment_gate_host(seed, it, 1, N, p24)
+    ada_h = ops.ada_pipeline_table_host(seed, it, 2, N, H, 56, p24)
+    assert bool((gate_h == 0).any()) and bool((gate_h != 0).any()), gate_h.tolist()
+    identity = ops.ADA_GEOM_ID | ops.ADA_COLOR_ID
+    assert bool(((ada_h[:, 13] & identity) != identity).any()), ada_h[:, 13].tolist()
+    tables = [ops.augment_table_host(seed, it, p, N, H).to(cuda) for p in (0, 1)]
+    gate, ada_table = gate_h.to(cuda), ada_h.to(cuda)
+    torch.manual_seed(31)
+    x = ops.empty_nhwc(N, Ct, H, H, cuda).normal_().requires_grad_(True)
+    g = ops.empty_nhwc(N, Ct, H, H, cuda).normal_()
+    nws = int(lib.csg_augment_workspace_bytes(N, H))
+    ws = torch.empty(nws // 8 + 1, dtype=torch.float64, device=cuda)
+    head = lambda out, table: (ptr(g), ptr(out), ptr(table), N, N, H, Ct, c0)
+    kinds = (("d_augment", lambda: ops.d_augment(x, tables[0], c0, 7),
+              lambda out: lib.csg_augment_bwd(*head(out, tables[0]), 7, ptr(ws), nws, stream())),
+             ("d_augment, gated", lambda: ops.d_augment(x, tables[1], c0, 7, gate=gate),
+              lambda out: lib.csg_augment_bwd_gated(*head(out, tables[1]), 7, ptr(ws), nws, ptr(gate), stream())),
+             ("ada_pipeline", lambda: ops.ada_pipeline(x, ada_table, c0),
+              lambda out: lib.csg_ada_pipeline_bwd(*head(out, ada_table), stream())))
+    grads = []
+    for name, forward, adjoint in kinds:
+        (gx,) = torch.autograd.grad(forward(), x, g)
+        want = ops.empty_nhwc(N, Ct, H, H, cuda)
+        check(adjoint(want), name)
+        assert gx.shape == x.shape and _same_bits(gx, want), name
+        grads.append(gx)
+    assert not _same_bits(grads[0], grads[1]) and not _same_bits(grads[0], grads[2]) and not _same_bits(grads[1], grads[2])
+
+
 def test_library_refusals(cuda):
     from canonicalsg2im_amd._lib import last_error, lib, ptr, stream
     x = torch.zeros(2 * 4 * 4 * 8, device=cuda)

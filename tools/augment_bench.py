@@ -60,7 +60,6 @@ def fmt(v):
 
 def kernel(args, dev):
     from canonicalsg2im_amd import ops
-    from canonicalsg2im_amd._lib import lib
     lines = ["device: %s; HIP events, %d calls per window after %d warm-up calls, %d windows in turn; median [all windows]" % (
         torch.cuda.get_device_name(0), args.iters, args.warmup, args.windows)]
     for name, (N, H, Ct, c0) in (("C3 packed PatchGAN input", (16, 256, 40, 32)), ("128 crops", (128, 32, 4, 0))):
@@ -75,7 +74,7 @@ def kernel(args, dev):
             runs[label + " forward"] = lambda policy=policy: ops.d_augment(x, table, c0, policy)
             # the adjoint as the Function's backward issues it (ops._aug_launch on a gradient that is already there): timed
             # through autograd the call is bound by the host, 0.07-0.08 ms whatever the size
-            runs[label + " backward"] = lambda policy=policy: ops._aug_launch(lib.csg_augment_bwd, "augment_bwd", g, table, c0, policy)
+            runs[label + " backward"] = lambda policy=policy: ops._aug_launch("diff", True, g, table, c0, policy)
         runs["copy_ of the same buffer"] = lambda: dst.copy_(x)
         for fn in runs.values():
             for _ in range(args.warmup):
@@ -94,7 +93,6 @@ def kernel(args, dev):
 
 def ada(args, dev):
     from canonicalsg2im_amd import ops
-    from canonicalsg2im_amd._lib import lib
     lines = ["device: %s; HIP events, %d calls per window after %d warm-up calls, %d windows in turn; median [all windows]" % (
         torch.cuda.get_device_name(0), args.iters, args.warmup, args.windows)]
     N, H, Ct, c0 = 16, 256, 40, 32
@@ -107,11 +105,10 @@ def ada(args, dev):
         ctrl = torch.tensor([p24, 0, 0, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
         gates[label] = ops.augment_gate(0, 1, 0, N, ctrl)
     runs = {"ungated forward": lambda: ops.d_augment(x, table, c0, 7),
-            "ungated backward": lambda: ops._aug_launch(lib.csg_augment_bwd, "augment_bwd", g, table, c0, 7)}
+            "ungated backward": lambda: ops._aug_launch("diff", True, g, table, c0, 7)}
     for label, gate in gates.items():
         runs["gated forward,  " + label] = lambda gate=gate: ops.d_augment(x, table, c0, 7, gate=gate)
-        runs["gated backward, " + label] = lambda gate=gate: ops._aug_launch(lib.csg_augment_bwd_gated, "augment_bwd_gated", g, table,
-                                                                             c0, 7, gate)
+        runs["gated backward, " + label] = lambda gate=gate: ops._aug_launch("gated", True, g, table, c0, 7, gate)
     # the C3 recipe's PatchGAN: two scales, 16 pictures, prediction maps of 35 x 35 and 19 x 19 (4 x 4 convolutions, three
     # of stride 2, on 256 and 128 pixels)
     preds = [torch.randn(16, 1, 35, 35, device=dev), torch.randn(16, 1, 19, 19, device=dev)]
@@ -139,7 +136,6 @@ def ada(args, dev):
 
 def pipeline(args, dev):
     from canonicalsg2im_amd import ops
-    from canonicalsg2im_amd._lib import lib
     lines = ["device: %s; HIP events, %d calls per window after %d warm-up calls, %d windows in turn; median [all windows]" % (
         torch.cuda.get_device_name(0), args.iters, args.warmup, args.windows)]
     N, H, Ct, c0 = 16, 256, 40, 32
@@ -159,11 +155,11 @@ def pipeline(args, dev):
     three = torch.zeros((3, N, 32), dtype=torch.int32, device=dev)
     runs = {}
     for label, t in tables.items():
-        runs[label + ": forward"] = lambda t=t: ops._ada_launch(lib.csg_ada_pipeline_fwd, "ada_pipeline_fwd", x, t, c0)
-        runs[label + ": backward"] = lambda t=t: ops._ada_launch(lib.csg_ada_pipeline_bwd, "ada_pipeline_bwd", g, t, c0)
+        runs[label + ": forward"] = lambda t=t: ops._aug_launch("ada", False, x, t, c0)
+        runs[label + ": backward"] = lambda t=t: ops._aug_launch("ada", True, g, t, c0)
     runs["copy_ of the same buffer"] = lambda: dst.copy_(x)
     runs["d_augment color,translation,cutout: forward"] = lambda: ops.d_augment(x, old, c0, 7)
-    runs["d_augment color,translation,cutout: backward"] = lambda: ops._aug_launch(lib.csg_augment_bwd, "augment_bwd", g, old, c0, 7)
+    runs["d_augment color,translation,cutout: backward"] = lambda: ops._aug_launch("diff", True, g, old, c0, 7)
     runs["three table fills of 16 rows"] = lambda: [ops.ada_pipeline_table(0, 1, p, N, H, 56, ctrl, out=three[p]) for p in range(3)]
     for fn in runs.values():
         for _ in range(args.warmup):
